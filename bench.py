@@ -4,7 +4,10 @@ STARTC (CWINDOW=32, MATCH10, static tree), whole job, plus the compression ratio
 
 --gpus 1 (default).  Headline = BASELINE configs[1]: 2^20 x 2 KiB synthetic blocks (families 1..4 of
   test_deflate.py:38-66, every block distinct, 2 GiB >> 256 MB Infinity Cache), resident in HBM before the
-  timed region; a "step" = one hdlz_compress_batch launch over all blocks.  The same JSON line carries a
+  timed region; a "step" = one hdlz_compress_batch launch over all blocks.  A plain run does only that: set-up,
+  W warm-up steps, the K timed steps, the line.  --dump-outputs DIR writes what the last timed step returned
+  (dump_outputs).  Everything else below -- roofline, cpu_baseline, archive, end_to_end, the zlib spot check, the
+  detail file -- is measured with --full, whose JSON line also carries a
   "secondary" array with the other single-GPU configurations of BASELINE.json, each with its own roofline:
     * configs[4] shape on one GPU: the WHOLE 8 GiB job of 131 072 x 64 KiB blocks, CWINDOW=32 (north_star's
       target shape; its ms_per_step is T(1) of the strong-scaling curve below)
@@ -17,7 +20,7 @@ STARTC (CWINDOW=32, MATCH10, static tree), whole job, plus the compression ratio
   the rank's hdlz_compress_batch launch + the RCCL all-gather of the uint32[B/N] output lengths
   (SURVEY 8(e)); STRONG scaling: total work is fixed, value = 8 GiB / max-over-ranks step time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0; with --full (N=1) it carries two extra objects:
   roofline     -- dominant kernel: algorithmic bytes per launch (N_in + N_out + 4 per block) /
                   average launch duration measured with HIP events on the launch stream, against the 8 TB/s
                   HBM3E peak
@@ -164,8 +167,35 @@ def zlib_spot_check(torch, d_in, d_out, ol, count):
         assert zlib.decompress(ho[k, :hl[k]].tobytes()) == hi[k].tobytes(), "zlib round trip failed"
 
 
-def run_compress(torch, eng, d_in, cwindow, maxmatch, steps, warmup, verify, d_out=None):
-    """single-GPU compress measurement of one workload -> dict (wall step time, kernel durations, sizes)"""
+DUMP_BYTES = 60 << 20       # --dump-outputs: the arrays in all (below 64 MB with the .npy headers)
+DUMP_ROWS = 4096            # compressed rows in the sample, fewer when they would not fit
+
+
+def dump_outputs(torch, path, out, ol, st):
+    """--dump-outputs: what one hdlz_compress_batch call returned, as .npy files that two builds can be compared by --
+    out_len.npy / status.npy (float64): every block's length and status, or, when the blocks are too many, those of a sample;
+    out_rows_sample.npy (float32 [S, out_pitch]): a sample of the compressed rows, the bytes past each row's length set to 0 (they
+    are not part of the result).  The samples are rows of a seeded permutation (seed 0, sorted): the same for the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    B, pitch = out.shape
+    g = torch.Generator(device="cpu")
+    g.manual_seed(0)
+    perm = torch.randperm(B, generator=g)
+    nb = min(B, DUMP_BYTES // 2 // 16)                      # lengths + statuses: at most half of the budget
+    bidx = None if nb == B else perm[:nb].sort().values.to(out.device)
+    nrow = min(B, DUMP_ROWS, (DUMP_BYTES - 16 * nb) // (4 * pitch))
+    ridx = perm[:nrow].sort().values.to(out.device)
+    rows = out[ridx]
+    rows.masked_fill_(torch.arange(pitch, device=out.device).unsqueeze(0) >= ol[ridx].unsqueeze(1).to(torch.int64), 0)
+    for name, t in (("out_len", ol if bidx is None else ol[bidx]), ("status", st if bidx is None else st[bidx])):
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(path, "out_rows_sample.npy"), rows.to(torch.float32).cpu().numpy())
+
+
+def run_compress(torch, eng, d_in, cwindow, maxmatch, steps, warmup, verify, d_out=None, launches=True, dump=None):
+    """single-GPU compress measurement of one workload -> dict (wall step time, kernel durations, sizes).  launches=False: no
+    separately timed launches after the timed steps (k_ms is then empty); dump: directory for dump_outputs"""
     from hdl_deflate_amd.constants import pitch_for
     B, n = d_in.shape
     pitch = pitch_for(n)
@@ -176,7 +206,9 @@ def run_compress(torch, eng, d_in, cwindow, maxmatch, steps, warmup, verify, d_o
         return eng.compress_batch(d_in, cwindow=cwindow, maxmatch=maxmatch, out=d_out, out_pitch=pitch)
 
     dt, (out, ol, st) = time_steps(torch, None, step, steps, warmup, 1, None)
-    k_ms = kernel_ms(torch, step, max(10, steps))
+    if dump:                                    # before any other launch writes into d_out
+        dump_outputs(torch, dump, out, ol, st)
+    k_ms = kernel_ms(torch, step, max(10, steps)) if launches else []
     assert int((st != 0).sum().item()) == 0, "blocks failed"
     out_bytes = int(ol.to(torch.int64).sum().item())
     if verify:
@@ -257,7 +289,7 @@ def compress_entry(name, workload, r, cwindow, maxmatch, steps, warmup, traffic_
 
 # ------------------------------------------------------------------------------------------------ the ONE line
 LINE_MAX = 12288            # the driver keeps only the tail of stdout: a line beyond ~16 KB was not parsed (BENCH_r05.parsed == None)
-DETAIL_DEFAULT = os.path.join("profiles", "r06_bench_detail.json")
+DETAIL_DEFAULT = "bench_detail.json"        # (untracked: a run must not rewrite the recorded profiles/r06_bench_detail.json)
 ROOF_KEEP = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "algorithmic_bytes_per_launch",
              "kernel_ms_avg", "kernel_ms_median", "kernel_ms_min", "launches_timed", "device_copy_GBps", "frac_of_device_copy")
 ISSUE_KEEP = ("frac", "valu_insts_per_launch", "valu_insts_per_byte", "source")
@@ -368,6 +400,28 @@ def emit(res, a=None):
 
 
 # ------------------------------------------------------------------------------------------------ N = 1
+def headline_roofline(torch, a, d_in, r):
+    """--full: the headline's `roofline` (from the launches run_compress timed after the timed steps), beside the achievable HBM
+    ceiling on this box: a plain device copy of the same input (read + write)"""
+    B, n = d_in.shape
+    cp = torch.empty_like(d_in)
+    cp.copy_(d_in)
+    torch.cuda.synchronize()
+    c_ms = kernel_ms(torch, lambda: cp.copy_(d_in), 5)
+    copy_gbs = 2.0 * d_in.numel() / (sum(c_ms) / len(c_ms) * 1e-3) / 1e9
+    del cp
+
+    algo = r["in_bytes"] + r["out_bytes"] + 4 * B
+    kname = kname_for(a.cwindow, n)
+    rl = roofline(kname, algo, r["k_ms"], "k_compress<%d>|blocks=%d|block=%d|data=%s" % (1 if a.cwindow <= 32 else 2 if a.cwindow <= 64 else 8, B, n, a.data),
+                  {"device_copy_GBps": round(copy_gbs, 1),
+                   "note": "bytes = N_in + N_out + 4 per block; this path is VALU-issue bound, not HBM bound: see `issue`; kernel_ms_* are "
+                           "HIP events around %d separate launches AFTER the timed loop of ms_per_step (two loops: they differ by noise)"
+                           % len(r["k_ms"])}, compress_grid(B) if n > 1024 else None, r["in_bytes"])
+    rl["frac_of_device_copy"] = round(rl["achieved"] / copy_gbs, 4)
+    return rl
+
+
 def main_single(a):
     import torch
     import hdl_deflate_amd
@@ -389,25 +443,8 @@ def main_single(a):
         d_in = d_in[perm].contiguous()
         del perm
     torch.cuda.synchronize()
-    r = run_compress(torch, eng, d_in, a.cwindow, a.maxmatch, a.steps, a.warmup, a.verify)
-
-    # achievable HBM ceiling on this box: a plain device copy of the same input (read + write)
-    cp = torch.empty_like(d_in)
-    cp.copy_(d_in)
-    torch.cuda.synchronize()
-    c_ms = kernel_ms(torch, lambda: cp.copy_(d_in), 5)
-    copy_gbs = 2.0 * d_in.numel() / (sum(c_ms) / len(c_ms) * 1e-3) / 1e9
-    del cp
-
+    r = run_compress(torch, eng, d_in, a.cwindow, a.maxmatch, a.steps, a.warmup, a.verify, launches=a.full, dump=a.dump_outputs)
     value = r["in_bytes"] / (r["dt"] / a.steps) / 1e6
-    algo = r["in_bytes"] + r["out_bytes"] + 4 * B
-    kname = kname_for(a.cwindow, n)
-    rl = roofline(kname, algo, r["k_ms"], "k_compress<%d>|blocks=%d|block=%d|data=%s" % (1 if a.cwindow <= 32 else 2 if a.cwindow <= 64 else 8, B, n, a.data),
-                  {"device_copy_GBps": round(copy_gbs, 1),
-                   "note": "bytes = N_in + N_out + 4 per block; this path is VALU-issue bound, not HBM bound: see `issue`; kernel_ms_* are "
-                           "HIP events around %d separate launches AFTER the timed loop of ms_per_step (two loops: they differ by noise)"
-                           % len(r["k_ms"])}, compress_grid(B) if n > 1024 else None, r["in_bytes"])
-    rl["frac_of_device_copy"] = round(rl["achieved"] / copy_gbs, 4)
     res = {
         "metric": "compress_input_throughput (CWINDOW=%d, MATCH10=%s, static tree)" % (a.cwindow, a.maxmatch == 10),
         "value": round(value, 1), "unit": "MB/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
@@ -420,12 +457,13 @@ def main_single(a):
                    "parallelism": "single GPU; --gpus N block-shards BASELINE configs[4] (8 GiB of 64 KiB blocks) over N ranks"},
         "per_gpu_MBps": round(value, 1),
         "compression_ratio_out_over_in": round(r["out_bytes"] / r["in_bytes"], 4),
-        "roofline": rl,
     }
+    if a.full:
+        res["roofline"] = headline_roofline(torch, a, d_in, r)
     # SURVEY 8(f) rank 2 beside the pitched-row figure: the same job delivered as ONE contiguous archive + offset index
     # (exclusive scan of the lengths + hdlz_compact_batch behind the compress launch; a fused compress -> archive would save the
     # compaction's read + write of N_out, at most the compact_ms below)
-    if a.archive:
+    if a.full and a.archive:
         offs = torch.empty(B, dtype=torch.int64, device=dev)
         arch = torch.empty(r["out_bytes"], dtype=torch.uint8, device=dev)
 
@@ -466,14 +504,14 @@ def main_single(a):
                           "note": "the job as one contiguous archive + int64 offset index: compress into pitched rows, then hdlz_archive_batch "
                                   "(scan of the lengths by a decoupled look-back + the gather, one launch; HIP events around the two launches); "
                                   "two_pass: round 4's form (three scan launches + hdlz_compact_batch); both archives compared byte for byte"}
-    if a.end_to_end:
+    if a.full and a.end_to_end:
         res["end_to_end"] = end_to_end(torch, eng, d_in, r, a.cwindow, a.maxmatch)
-    if a.cpu_seconds > 0:
+    if a.full and a.cpu_seconds > 0:
         res["cpu_baseline"] = cpu_baseline(d_in, n, a)
     del r, d_in
     torch.cuda.empty_cache()
 
-    if a.secondary:
+    if a.full and a.secondary:
         sec = []
         # -- configs[4] shape, whole job on one GPU (= T(1) of the strong-scaling curve of --gpus N)
         d5 = make_blocks(a.cfg5_blocks, CFG5_BLOCK, dev, seed=0)
@@ -1016,12 +1054,18 @@ def main():
     ap.add_argument("--block-size", type=int, default=2048)
     ap.add_argument("--cwindow", type=int, default=32)
     ap.add_argument("--maxmatch", type=int, default=10)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline duration (0 = skip)")
-    ap.add_argument("--verify", type=int, default=256, help="blocks checked against zlib outside the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: besides the headline, everything else this file measures (roofline, archive, end_to_end, cpu_baseline, "
+                         "the secondary entries, the zlib spot check, the detail file); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1 headline: write what the last timed step returned to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline duration (0 = skip)")
+    ap.add_argument("--verify", type=int, default=None,
+                    help="blocks checked against zlib outside the timed region (default: 256 with --full, else none)")
     ap.add_argument("--data", default="families", choices=["families", "text"],
                     help="families = test_deflate.py families 1-4 (BASELINE configs[1]); text = Zipf pseudo-English")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="N=1: headline only (skip the configs[4]-shape / configs[2] / configs[3] entries)")
+                    help="N=1, --full: skip the configs[4]-shape / configs[2] / configs[3] entries")
     ap.add_argument("--cfg5-blocks", type=int, default=CFG5_BLOCKS, help="total 64 KiB blocks of the configs[4] job")
     ap.add_argument("--text-blocks", type=int, default=16384, help="64 KiB text blocks of the configs[2] entry (1 GiB)")
     ap.add_argument("--streams", type=int, default=1 << 20, help="inflate: zlib streams (configs[3])")
@@ -1034,15 +1078,25 @@ def main():
     ap.add_argument("--mode", default="compress", choices=["compress", "inflate", "roundtrip", "single", "few", "zlib"],
                     help="compress = BASELINE metric (default); inflate = only the configs[3] side metric (1 GPU)")
     ap.add_argument("--no-archive", dest="archive", action="store_false",
-                    help="N=1: skip the archive figure (compress + scan + hdlz_compact_batch) of the headline job")
+                    help="N=1, --full: skip the archive figure (compress + scan + hdlz_compact_batch) of the headline job")
     ap.add_argument("--no-end-to-end", dest="end_to_end", action="store_false",
-                    help="N=1: skip the PCIe-inclusive measurement of the headline job (SURVEY 8(d) Timing)")
+                    help="N=1, --full: skip the PCIe-inclusive measurement of the headline job (SURVEY 8(d) Timing)")
     ap.add_argument("--no-t1", dest="t1", action="store_false",
                     help="N>1: do not run the whole job on rank 0 first (T1_ms / speedup_vs_T1 are then absent)")
     ap.add_argument("--shuffle", type=int, default=0, help="N=1 headline: the blocks in a seeded random order (0 = the order of BASELINE configs[1])")
-    ap.add_argument("--detail", default=DETAIL_DEFAULT,
-                    help="file that receives the FULL result (notes, configs, every sub-measurement); the printed line names it ('' = none)")
+    ap.add_argument("--detail", default=None,
+                    help="file that receives the FULL result (notes, configs, every sub-measurement); the printed line names it ('' = none; "
+                         "default: %s, none in a plain N=1 run)" % DETAIL_DEFAULT)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    plain = not a.full and a.mode == "compress" and a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1
+    if a.dump_outputs and not (a.mode == "compress" and a.gpus == 1):
+        ap.error("--dump-outputs: only the N=1 headline (--mode compress, --gpus 1) writes its outputs")
+    if a.verify is None:
+        a.verify = 0 if plain else 256
+    if a.detail is None:
+        a.detail = "" if plain else DETAIL_DEFAULT
     if a.mode == "inflate":
         emit(bench_inflate(a), a)
     elif a.mode == "roundtrip":                               # only the configs[4] round-trip entry (profiling)

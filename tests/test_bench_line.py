@@ -96,3 +96,28 @@ def test_emit_writes_the_detail_file(tmp_path, capsys):
     assert len(out) == 1 and len(out[0]) < bench.LINE_MAX
     assert json.loads(out[0])["detail"] == A.detail
     assert json.load(open(A.detail)) == res                      # nothing is lost: the prose lives in the detail file
+
+
+def test_dump_outputs_stays_within_64_mb(tmp_path):
+    """--dump-outputs at the headline shape and at shapes that make it sample: at most 64 MB in float arrays, the sampled rows
+    masked past their lengths (the rows are broadcast views: the blocks are not held in memory)"""
+    import numpy as np
+    import torch
+    from hdl_deflate_amd.constants import pitch_for
+    for B, pitch in ((1 << 20, pitch_for(2048)), (16384, pitch_for(65536)), (3 << 21, 64), (5, 64)):
+        out = torch.arange(pitch, dtype=torch.int64).remainder(251).add(1).to(torch.uint8).unsqueeze(0).expand(B, pitch)
+        ol = torch.arange(B, dtype=torch.int32).remainder(pitch)
+        st = torch.zeros(B, dtype=torch.int32)
+        d = tmp_path / ("%d_%d" % (B, pitch))
+        bench.dump_outputs(torch, str(d), out, ol, st)
+        got = {f: np.load(str(d / f)) for f in ("out_len.npy", "status.npy", "out_rows_sample.npy")}
+        assert sum(os.path.getsize(str(d / f)) for f in got) < 64e6
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        rows, lens = got["out_rows_sample.npy"], got["out_len.npy"]
+        assert rows.shape[1] == pitch and 1 <= rows.shape[0] <= min(B, bench.DUMP_ROWS)
+        assert lens.shape == ((B,) if B <= (1 << 20) else (bench.DUMP_BYTES // 32,))
+        nz = (rows != 0).sum(axis=1)                              # a row keeps exactly its first out_len bytes (all non-zero here)
+        g = torch.Generator(device="cpu")
+        g.manual_seed(0)
+        idx = torch.randperm(B, generator=g)[:rows.shape[0]].sort().values
+        assert np.array_equal(nz, ol[idx].numpy())

@@ -174,7 +174,7 @@ def test_bench_single_gpu_line_is_short_and_complete(tmp_path):
     """the `--gpus 1` line (every secondary entry, reduced sizes) is ONE line below 12 KB that carries the contract's
     keys, `roofline` and `cpu_baseline`; the prose went to the detail file it names"""
     detail = str(tmp_path / "bench_detail.json")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--blocks", "65536", "--cfg5-blocks", "2048", "--text-blocks", "256",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--blocks", "65536", "--cfg5-blocks", "2048", "--text-blocks", "256",
            "--streams", "65536", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--detail", detail]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
@@ -190,3 +190,42 @@ def test_bench_single_gpu_line_is_short_and_complete(tmp_path):
     assert len(r["secondary"]) >= 9 and all(e["value"] > 0 and e["roofline"]["frac"] > 0 for e in r["secondary"])
     full = json.load(open(detail))
     assert full["value"] == r["value"] and "note" in full["roofline"] and len(full["secondary"]) == len(r["secondary"])
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain `--gpus 1` run: the headline line alone (no roofline, cpu_baseline, secondary entries or detail file), the steps asked
+    for; --dump-outputs writes what the last timed step returned -- the same arrays in two runs with the same arguments, and the
+    sampled rows are zlib streams of the benchmark's blocks"""
+    import zlib
+    import torch
+    from hdl_deflate_amd.data import make_blocks
+    B, n = 65536, 2048
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--blocks", str(B), "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["metric"] == "compress_input_throughput (CWINDOW=32, MATCH10=True, static tree)" and r["unit"] == "MB/s"
+        assert r["higher_is_better"] is True and r["dtype"] == "u8" and r["steps"] == 3 and r["warmup"] == 1
+        assert r["value"] > 0 and abs(r["value"] - B * n / (r["ms_per_step"] * 1e3)) <= 0.01 * r["value"]
+        for key in ("roofline", "cpu_baseline", "secondary", "archive", "end_to_end", "detail"):
+            assert key not in r, key
+        runs.append({f: np.load(str(d / f)) for f in ("out_len.npy", "status.npy", "out_rows_sample.npy")})
+    for f in runs[0]:
+        assert runs[0][f].dtype in (np.float32, np.float64) and np.array_equal(runs[0][f], runs[1][f]), f
+    ol, st, rows = runs[0]["out_len.npy"], runs[0]["status.npy"], runs[0]["out_rows_sample.npy"]
+    assert ol.shape == (B,) and (st == 0).all() and rows.shape[0] == 4096 and sum(a.nbytes for a in runs[0].values()) < 64e6
+    g = torch.Generator(device="cpu")
+    g.manual_seed(0)
+    idx = torch.randperm(B, generator=g)[:rows.shape[0]].sort().values
+    blocks = make_blocks(B, n, "cuda", seed=0)[idx.cuda()].cpu().numpy()
+    for k in range(0, rows.shape[0], 97):
+        L = int(ol[idx[k]])
+        assert not rows[k, L:].any()
+        assert zlib.decompress(rows[k, :L].astype(np.uint8).tobytes()) == blocks[k].tobytes(), k

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the BASELINE.json configs that fit one GPU, one JSON line each (tools, not the driver contract)
 set -u
-B="python bench.py --no-secondary --steps 5 --warmup 2"
+B="python bench.py --full --no-secondary --steps 5 --warmup 2"
 echo "## cfg[1] 2^20 x 2 KiB, CW32/M10";            $B 2>&1 | tail -1
 echo "## cfg[1] the same blocks in a shuffled order (seed 1)"; $B --cpu-seconds 0 --no-end-to-end --no-archive --shuffle 1 2>&1 | tail -1
 echo "## cfg[2] 64 KiB text, CW64/M10";             $B --cpu-seconds 0 --data text --block-size 65536 --blocks 16384 --cwindow 64 2>&1 | tail -1
