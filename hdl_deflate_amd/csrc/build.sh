@@ -9,6 +9,11 @@ if [ "${1:-}" = "forced" ]; then
   HDLZ_VARIANT=forced HDLZ_DEFS="-DHDLZ_HASH_FORCE_REORDER -DHDLZ_CHAIN_FORCE_SERIAL" \
     HDLZ_ONLY="hdlz_compress hdlz_compress_small hdlz_compress_stream hdlz_compress_chunk" exec "${BASH_SOURCE[0]}"
 fi
+# `build.sh keys` builds lib/libhdlz_keys.so: the one-tile kernel with the key-difference search instead of the bit-sliced one
+# (tests/test_gpu_search_bits.py runs its blocks through both; tools/ab.sh times them against each other)
+if [ "${1:-}" = "keys" ]; then
+  HDLZ_VARIANT=keys HDLZ_DEFS="-DHDLZ_SEARCH_KEYS" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
+fi
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"

@@ -7,11 +7,15 @@
 // walks each block in tiles of 2048 positions; lane l owns the RUN of 32 consecutive positions
 // [32l, 32l+32) of the tile.  Per tile:
 //   1. tile + 256-byte look-back halo + 16-byte look-ahead staged in LDS (coalesced 16-B loads)
-//   2. match search (R3/R4): each lane builds keys K = (3-byte-string << 8) | 4*window_index for
-//      its own 32 positions and the 32..256 positions before them, all in VGPRs.  For an own key
-//      Ko and a candidate key Kc,  Ko - Kc  equals 4*distance (<= 128) iff the three bytes are
-//      equal and is > 256 (as u32) otherwise, so the MIN over the 32 candidates IS four times the
-//      nearest matching distance: one v_sub + half a v_min3 per compare, no branches.
+//   2. match search (R3/R4).  One-tile blocks with CWINDOW <= 32 (the headline kernel): BIT-SLICED -- the lane's
+//      32 bytes as 8 bit planes, the previous lane's planes by DPP; per distance one v_alignbit per plane gives
+//      the candidate bytes of all 32 positions, v_bitop3 ORs the differences, nearest distance first
+//      (match_search_bits: ~23 instructions per distance for 32 pairs).  Every other kernel: keys
+//      K = (3-byte-string << 8) | 4*window_index for its own 32 positions and the 32..256 positions
+//      before them, all in VGPRs.  For an own key Ko and a candidate key Kc,  Ko - Kc  equals
+//      4*distance (<= 128) iff the three bytes are equal and is > 256 (as u32) otherwise, so the MIN
+//      over the 32 candidates IS four times the nearest matching distance: one v_sub + half a v_min3
+//      per compare, no branches (-DHDLZ_SEARCH_KEYS: the one-tile kernels too, for A/B).
 //   3. extension (R5): 8-byte LDS gather at p-d+3, xor with the own bytes, count-trailing-zeros.
 //   4. greedy parse ("di += m / di += 1", deflate.py:960,1008): every lane folds its run into a
 //      transfer function "entry skip (0..9) -> exit skip", 10 nibbles packed in 40 bits, by a
@@ -192,7 +196,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             if constexpr (HASH) {
                 match_search_hash<NCH>(lds.in, hl, lane, (uint32_t)a.cwindow, best);               // 2. R3/R4, wide windows
                 zero_bit_buffer(lout, lane, carry_word);                                           // (ordered before the scatter by the fences below)
-            } else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                  // 2. R3/R4 (a one-tile block: candidate keys by DPP)
+            }
+#ifndef HDLZ_SEARCH_KEYS                                                                           // (-DHDLZ_SEARCH_KEYS: the key form, for A/B)
+            else if constexpr (ONE_TILE && NCH == 1) match_search_bits(lds.in, run_dw, best);      // 2. R3/R4 (a one-tile block: bit planes, history by DPP)
+#endif
+            else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                    // 2. R3/R4 (a one-tile block: candidate keys by DPP)
             {
                 TT(2);
                 HDLZ_MARK("adler");

@@ -232,6 +232,99 @@ __device__ __forceinline__ void match_search(const uint32_t* in, uint32_t run_dw
     }
 }
 
+// ---- phase 2, BIT-SLICED (NCH == 1 with the candidates of the previous lane by DPP: the PREV_DPP case of match_search; the same best[]).
+// The key form above is built around one (position, distance) pair per lane and instruction: 1.5 instructions, ~3.96 cycles per pair.
+// Here a lane's 32 bytes are held as 8 BIT PLANES -- O_b bit i = bit b of own byte i -- and one instruction covers all 32 positions of
+// the run for one distance:
+//   C_b   = the candidate bytes at distance d: (O_b : P_b) >> (32 - d), one v_alignbit per plane (P_b = the previous lane's O_b)
+//   neq   = OR_b (O_b ^ C_b): bit i = x[p] != x[p-d]                        (one xor + seven v_bitop3)
+//   n3    = neq | neq >> 1 | neq >> 2, the bits 32, 33 from the NEXT lane's neq (one DPP move, two v_alignbit, one v_bitop3):
+//           bit i = no 3-byte match at distance d
+//   G     = positions without a match so far (distances ascend: the first one found is the nearest); D_k |= G & ~n3 for every set bit k
+//           of d (one v_bitop3 each), G &= n3
+// ~23 instructions per distance for 32 pairs.  Lane 0 takes lane 63's planes as history (the DPP is a rotate): a "match" from there lies
+// d > i = p positions back and fails make_tokens' position test, and a real one (d <= p) is always nearer -- found first (the PREV_DPP
+// argument above).  Lane 63 has no next lane (its bits 32, 33 read 0): they only feed positions 2046 and 2047, which R3 never makes eligible.
+// Planes in and out are transposes of 32 x 8 bit matrices: a 4 x 4 byte transpose (v_perm) + three exchanges of a register-index bit
+// with a bit-index bit (two shifts + two v_bitop3 per register pair).  Result byte = 4 d (found; d <= 32), 0xFF (none: above 252, and
+// above every 4 * cwindow -- make_tokens' tests reject it like the key form's raw minima >= 256).
+// v_bitop3_b32 (gfx950): any function of three words at the rate of a v_xor; its table is the function applied to 0xF0, 0xCC, 0xAA.
+constexpr uint32_t B3_SEL = 0xE4;         // c ? a : b
+constexpr uint32_t B3_OR_XOR = 0xF6;      // a | (b ^ c)
+constexpr uint32_t B3_OR3 = 0xFE;         // a | b | c
+constexpr uint32_t B3_OR_ANDN = 0xF4;     // a | (b & ~c)
+template <uint32_t F>
+__device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, F); }
+// a constant in an SGPR, set where it is used (hoisted out of the block loop, the search's masks and selectors cost the kernel SGPR spills)
+__device__ __forceinline__ uint32_t sconst(uint32_t v) { asm volatile("" : "+s"(v)); return v; }
+// w[k] bit 8 m + b <-> w[b] bit 8 m + k (b, k = 0..7, m = 0..3): exchange bit j of the register index with bit j of the bit index,
+// j = 0, 1, 2.  An involution: the same network takes bytes to planes and planes to bytes.
+__device__ __forceinline__ void exchange8(uint32_t (&w)[8]) {
+    static_for<0, 3>([&](auto J) {
+        constexpr int s = 1 << decltype(J)::value;
+        const uint32_t m0 = sconst(s == 1 ? 0x55555555u : s == 2 ? 0x33333333u : 0x0F0F0F0Fu);   // bits whose index has bit j clear
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (k & s) continue;
+            const uint32_t x = w[k], y = w[k + s];
+            w[k] = bitop3<B3_SEL>(x, y << s, m0);
+            w[k + s] = bitop3<B3_SEL>(x >> s, y, m0);
+        }
+    });
+}
+// 4 x 4 byte transpose: t[k] byte m = r[m] byte k
+__device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t& t0, uint32_t& t1,
+                                                   uint32_t& t2, uint32_t& t3) {
+    const uint32_t zip_lo = sconst(0x05010400u), zip_hi = sconst(0x07030602u), cat_lo = sconst(0x05040100u), cat_hi = sconst(0x07060302u);
+    const uint32_t a01 = __builtin_amdgcn_perm(r1, r0, zip_lo), b01 = __builtin_amdgcn_perm(r1, r0, zip_hi);     // r0.0 r1.0 r0.1 r1.1 | .2 .3
+    const uint32_t a23 = __builtin_amdgcn_perm(r3, r2, zip_lo), b23 = __builtin_amdgcn_perm(r3, r2, zip_hi);
+    t0 = __builtin_amdgcn_perm(a23, a01, cat_lo); t1 = __builtin_amdgcn_perm(a23, a01, cat_hi);
+    t2 = __builtin_amdgcn_perm(b23, b01, cat_lo); t3 = __builtin_amdgcn_perm(b23, b01, cat_hi);
+}
+__device__ __forceinline__ void match_search_bits(const uint32_t* in, uint32_t run_dw, uint32_t (&best)[RUN]) {
+    uint32_t O[8], P[8];
+    {
+        const uint4 v0 = *reinterpret_cast<const uint4*>(&in[run_dw]);
+        const uint4 v1 = *reinterpret_cast<const uint4*>(&in[run_dw + 4]);
+        // O[k] byte m = own byte k + 8 m (k = 0..7): bytes k, k + 8, k + 16, k + 24 are byte k & 3 of dwords k >> 2, +2, +4, +6
+        transpose4x4_bytes(v0.x, v0.z, v1.x, v1.z, O[0], O[1], O[2], O[3]);
+        transpose4x4_bytes(v0.y, v0.w, v1.y, v1.w, O[4], O[5], O[6], O[7]);
+    }
+    exchange8(O);                                             // O[b] bit i = bit b of own byte i
+#pragma unroll
+    for (int b = 0; b < 8; b++) P[b] = (uint32_t)__builtin_amdgcn_mov_dpp((int)O[b], 0x13C, 0xF, 0xF, false);      // wave_ror:1
+    pin(O); pin(P);
+    PHASE_FENCE();
+    uint32_t G = 0xFFFFFFFFu, D[6] = {0, 0, 0, 0, 0, 0};
+    static_for<1, RUN + 1>([&](auto Dd) {
+        constexpr int d = decltype(Dd)::value;
+        uint32_t neq = 0;
+        static_for<0, 8>([&](auto B) {
+            constexpr int b = decltype(B)::value;
+            const uint32_t c = d == 32 ? P[b] : __builtin_amdgcn_alignbit(O[b], P[b], (uint32_t)(32 - d));
+            neq = b == 0 ? O[0] ^ c : bitop3<B3_OR_XOR>(neq, O[b], c);
+        });
+        const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)neq, 0x130, 0xF, 0xF, true);                      // wave_shl:1 (lane 63: 0)
+        const uint32_t n3 = bitop3<B3_OR3>(neq, __builtin_amdgcn_alignbit(nx, neq, 1u), __builtin_amdgcn_alignbit(nx, neq, 2u));
+        static_for<0, 6>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            if constexpr ((d >> k) & 1) D[k] = bitop3<B3_OR_ANDN>(D[k], G, n3);
+        });
+        G &= n3;
+        if constexpr ((d & 3) == 0) { pin(D); asm volatile("" : "+v"(G)); PHASE_FENCE(); }     // (else hipcc hoists the alignbits of all distances)
+    });
+    // planes of the result byte: bits 0, 1 = none, bits 2..7 = d | none
+    uint32_t Q[8] = {G, G, D[0] | G, D[1] | G, D[2] | G, D[3] | G, D[4] | G, D[5] | G};
+    exchange8(Q);                                             // Q[k] byte m = result byte of own position k + 8 m
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        best[k] = Q[k] & 0xFFu;
+        best[k + 8] = __builtin_amdgcn_ubfe(Q[k], 8u, 8u);
+        best[k + 16] = __builtin_amdgcn_ubfe(Q[k], 16u, 8u);
+        best[k + 24] = Q[k] >> 24;
+    }
+}
+
 // ---- phase 2 for WIDE windows: a window-independent match finder ------------------------------------------
 // "Nearest previous occurrence of the same 3-byte string" (matcher3 x CWINDOW + first-set-bit pick, deflate.py:407-421, :966-1016)
 // is a predecessor query; its cost need not grow with the window.  match_search pays 1.5 VALU instructions per (position,
