@@ -99,7 +99,8 @@ struct NState { uint32_t q, pos, nb, req; };                          // a waiti
 constexpr uint32_t WALK_ROUNDS = 3;           // rounds of k_any_walk: up to WALK_ROUNDS - 1 false positives in a row inside one block
 constexpr uint32_t REQ_MAX = 1024;            // pieces per request (more: the rest in the next round)
 
-struct Args {
+// the kernels' arguments: the call ...
+struct Call {
     const uint8_t* z;
     uint32_t zn, flags, obsize;
     uint8_t* out;
@@ -109,10 +110,14 @@ struct Args {
     uint8_t* ws;                  // this chain's scratch of stream 0
     size_t stride;                // bytes from a stream's scratch to the next stream's
     uint32_t* srcA;               // stream 0's marker words
+};
+// ... and the scratch of one stream: the sizes of the lists and the offsets of the arrays in `ws` (lay_of, the only code that knows them)
+struct Lay {
     uint32_t nchunks, candcap, maxb, maxx, maxs, tcap, maxreq, mapcap, pb;
     size_t o_cand, o_blk, o_blen, o_shdr, o_spay, o_sidx, o_tab, o_owner, o_map, o_pent, o_prel, o_pnode, o_node, o_xitem, o_sitem,
-           o_opos, o_ntok, o_tok, o_mext, o_req, o_map2, o_nstate, o_cpos, o_cres, o_nch, o_pmap;
+           o_opos, o_ntok, o_tok, o_mext, o_req, o_map2, o_nstate, o_cpos, o_cres, o_nch, o_pmap, bytes;
 };
+struct Args : Call, Lay {};
 // one stream's view
 struct View {
     const uint8_t* z;
@@ -1174,11 +1179,6 @@ __global__ __launch_bounds__(64) void k_any_zero(Args a) {
 // must be for the chain to beat a wave per stream (profiles/r06_any_batches.txt)
 constexpr uint32_t ANY_MIN = 4096;
 __host__ inline uint32_t any_batch_max(uint32_t in_len) { return in_len >= (96u << 10) ? 1024u : in_len >= 16384u ? 512u : in_len >= 8192u ? 256u : 64u; }
-struct Lay {
-    uint32_t nchunks, candcap, maxb, maxx, maxs, tcap, maxreq, mapcap, pb;
-    size_t o_cand, o_blk, o_blen, o_shdr, o_spay, o_sidx, o_tab, o_owner, o_map, o_pent, o_prel, o_pnode, o_node, o_xitem, o_sitem,
-           o_opos, o_ntok, o_tok, o_mext, o_req, o_map2, o_nstate, o_cpos, o_cres, o_nch, o_pmap, bytes;
-};
 static Lay lay_of(uint32_t zn) {
     Lay L;
     memset(&L, 0, sizeof(L));
@@ -1199,18 +1199,18 @@ static Lay lay_of(uint32_t zn) {
     L.maxs = zn / 512u + 256u;
     static_assert((3u * 1024u / 8u) % 4u == 0u, "token lists are written 16 bytes at a time");
     L.tcap = 3u * L.pb / 8u;                                        // (hex text: 16 symbols, codes of 4 bits and a few of 5 -- a list per 4 bits overflowed in every third piece)
-    size_t off = 256;                                               // the control words in front
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255u) & ~(size_t)255u; return o; };
+    par::Carve c{0u, 0u};
+    c.take(4u * par::C_WORDS);                                      // the control words in front
     const size_t items = (size_t)L.nchunks + L.maxx;
-    L.o_cand = take(4u * (size_t)L.candcap); L.o_blk = take(sizeof(Blk) * L.maxb); L.o_blen = take(320u * (size_t)L.maxb);
-    L.o_shdr = take(4u * L.maxb); L.o_spay = take(4u * L.maxb); L.o_sidx = take(4u * L.maxb);
-    L.o_tab = take(sizeof(Tab) * ((size_t)L.maxb + 1u)); L.o_owner = take(2u * (size_t)L.nchunks); L.o_map = take(256u * (size_t)L.nchunks);
-    L.o_pent = take(L.nchunks); L.o_prel = take(4u * (size_t)L.nchunks); L.o_pnode = take(2u * (size_t)L.nchunks);
-    L.o_node = take(sizeof(Node) * ((size_t)L.maxb + 1u)); L.o_xitem = take(sizeof(XItem) * L.maxx); L.o_sitem = take(sizeof(SItem) * L.maxs);
-    L.o_opos = take(4u * items); L.o_ntok = take(4u * items); L.o_tok = take(4u * (size_t)L.tcap * items); L.o_mext = take(4u * items);
-    L.o_req = take(sizeof(Req) * L.maxreq); L.o_map2 = take(256u * (size_t)L.mapcap); L.o_nstate = take(sizeof(NState) * L.maxb);
-    L.o_cpos = take(4u * 8u * (size_t)L.nchunks); L.o_cres = take(4u * 8u * (size_t)L.nchunks); L.o_nch = take(L.nchunks); L.o_pmap = take(4u * (size_t)L.nchunks);
-    L.bytes = off;
+    L.o_cand = c.take(4u * (size_t)L.candcap); L.o_blk = c.take(sizeof(Blk) * L.maxb); L.o_blen = c.take(320u * (size_t)L.maxb);
+    L.o_shdr = c.take(4u * L.maxb); L.o_spay = c.take(4u * L.maxb); L.o_sidx = c.take(4u * L.maxb);
+    L.o_tab = c.take(sizeof(Tab) * ((size_t)L.maxb + 1u)); L.o_owner = c.take(2u * (size_t)L.nchunks); L.o_map = c.take(256u * (size_t)L.nchunks);
+    L.o_pent = c.take(L.nchunks); L.o_prel = c.take(4u * (size_t)L.nchunks); L.o_pnode = c.take(2u * (size_t)L.nchunks);
+    L.o_node = c.take(sizeof(Node) * ((size_t)L.maxb + 1u)); L.o_xitem = c.take(sizeof(XItem) * L.maxx); L.o_sitem = c.take(sizeof(SItem) * L.maxs);
+    L.o_opos = c.take(4u * items); L.o_ntok = c.take(4u * items); L.o_tok = c.take(4u * (size_t)L.tcap * items); L.o_mext = c.take(4u * items);
+    L.o_req = c.take(sizeof(Req) * L.maxreq); L.o_map2 = c.take(256u * (size_t)L.mapcap); L.o_nstate = c.take(sizeof(NState) * L.maxb);
+    L.o_cpos = c.take(4u * 8u * (size_t)L.nchunks); L.o_cres = c.take(4u * 8u * (size_t)L.nchunks); L.o_nch = c.take(L.nchunks); L.o_pmap = c.take(4u * (size_t)L.nchunks);
+    L.bytes = c.off;
     return L;
 }
 
@@ -1232,25 +1232,17 @@ size_t any_work_bytes(uint32_t in_len, uint64_t out_pitch, uint32_t flags, uint3
     return any::lay_of(in_len).bytes;
 }
 
-hipError_t launch_inflate_any(const InflateArgs& a, uint32_t nstr, uint8_t* ws, size_t ws_stride, size_t ws_off, size_t sa_off,
-                              uint32_t srcn, uint32_t cap, hipStream_t stream, uint32_t* passes_out) {
+hipError_t launch_inflate_any(const par::ParArgs& p, uint8_t* ws, uint32_t nstr, hipStream_t stream, uint32_t* passes_out) {
     using namespace any;
-    const Lay L = lay_of(a.in_len);
     Args g;
     memset(&g, 0, sizeof(g));
-    g.z = a.in; g.zn = a.in_len; g.flags = a.flags; g.obsize = a.obsize; g.out = a.out; g.cap = cap; g.srcn = srcn;
-    g.in_pitch = a.in_pitch; g.out_pitch = a.out_pitch; g.in_off = a.in_off;
-    g.ws = ws + ws_off; g.stride = ws_stride; g.srcA = reinterpret_cast<uint32_t*>(ws + sa_off);
-    g.nchunks = L.nchunks; g.candcap = L.candcap; g.maxb = L.maxb; g.maxx = L.maxx; g.maxs = L.maxs; g.tcap = L.tcap;
-    g.maxreq = L.maxreq; g.mapcap = L.mapcap; g.pb = L.pb; g.o_req = L.o_req; g.o_map2 = L.o_map2; g.o_nstate = L.o_nstate;
-    g.o_cpos = L.o_cpos; g.o_cres = L.o_cres; g.o_nch = L.o_nch; g.o_pmap = L.o_pmap;
-    g.o_cand = L.o_cand; g.o_blk = L.o_blk; g.o_blen = L.o_blen; g.o_shdr = L.o_shdr; g.o_spay = L.o_spay; g.o_sidx = L.o_sidx; g.o_tab = L.o_tab;
-    g.o_owner = L.o_owner; g.o_map = L.o_map; g.o_pent = L.o_pent; g.o_prel = L.o_prel; g.o_pnode = L.o_pnode; g.o_node = L.o_node;
-    g.o_xitem = L.o_xitem; g.o_sitem = L.o_sitem; g.o_opos = L.o_opos; g.o_ntok = L.o_ntok; g.o_tok = L.o_tok; g.o_mext = L.o_mext;
+    static_cast<Call&>(g) = Call{p.z, p.zn, p.flags, p.obsize, p.out, p.cap, p.srcn, p.in_pitch, p.out_pitch, p.in_off, ws, p.ws_stride, p.srcA};
+    static_cast<Lay&>(g) = lay_of(p.zn);
+    const Lay& L = g;
     const uint32_t nitems = L.nchunks + L.maxx;
     auto gx = [&](uint64_t work, uint32_t cap_) { const uint32_t c = par::grid_cap(work, nstr); return (unsigned)(c > cap_ ? cap_ : c); };
     hipLaunchKernelGGL(k_any_zero, dim3(1, nstr), dim3(64), 0, stream, g);
-    hipLaunchKernelGGL(k_any_find, dim3(gx((a.in_len + FIND_T - 1u) / FIND_T, 4096u), nstr), dim3(FIND_T), 0, stream, g);
+    hipLaunchKernelGGL(k_any_find, dim3(gx((g.zn + FIND_T - 1u) / FIND_T, 4096u), nstr), dim3(FIND_T), 0, stream, g);
     hipLaunchKernelGGL(k_any_headers, dim3(gx((L.candcap + 63u) / 64u, 1280u), nstr), dim3(64), 0, stream, g);
     hipLaunchKernelGGL(k_any_sort, dim3((L.maxb + SORT_T - 1u) / SORT_T, nstr), dim3(SORT_T), 4u * L.maxb, stream, g);
     hipLaunchKernelGGL(k_any_tables, dim3(gx(L.maxb + 1u, 1024u), nstr), dim3(TAB_T), 0, stream, g);
@@ -1268,19 +1260,15 @@ hipError_t launch_inflate_any(const InflateArgs& a, uint32_t nstr, uint8_t* ws, 
     hipLaunchKernelGGL(k_any_stored, dim3(gx(L.maxs, 1024u), nstr), dim3(256), 0, stream, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // the bytes: the kernels of hdlz_inflate_par.hip on this chain's items (one "piece" each, no sub-pieces)
-    par::ParArgs p;
-    memset(&p, 0, sizeof(p));
-    p.z = a.in; p.zn = a.in_len; p.flags = a.flags; p.obsize = a.obsize; p.out = a.out; p.cap = cap; p.srcn = srcn;
-    p.out_len = a.out_len; p.status = a.status; p.nchunks = nitems; p.chbits = L.pb;
-    p.ctl = reinterpret_cast<uint32_t*>(g.ws);
-    p.opos = reinterpret_cast<uint32_t*>(g.ws + L.o_opos); p.tokens = reinterpret_cast<uint32_t*>(g.ws + L.o_tok); p.tcap = L.tcap;
-    p.ntok = reinterpret_cast<uint32_t*>(g.ws + L.o_ntok); p.srcA = g.srcA; p.sub = 1u; p.cnu = par::C_NUSED;
-    p.mext = reinterpret_cast<uint32_t*>(g.ws + L.o_mext);
-    p.in_pitch = a.in_pitch; p.out_pitch = a.out_pitch; p.in_off = a.in_off; p.ws_stride = ws_stride; p.batch = nstr > 1u ? 1u : 0u;
+    // the bytes: the kernels of hdlz_inflate_par.hip on this chain's items (one "piece" each, no sub-pieces) -- the call is the other
+    // chain's, the arrays are this chain's (k_par_emit and k_par_jump read no others)
+    par::ParArgs q = p;
+    q.nchunks = nitems; q.chbits = L.pb; q.sub = 1u; q.cnu = par::C_NUSED; q.tcap = L.tcap;
+    q.ctl = reinterpret_cast<uint32_t*>(ws); q.opos = reinterpret_cast<uint32_t*>(ws + L.o_opos); q.tokens = reinterpret_cast<uint32_t*>(ws + L.o_tok);
+    q.ntok = reinterpret_cast<uint32_t*>(ws + L.o_ntok); q.mext = reinterpret_cast<uint32_t*>(ws + L.o_mext);
     const uint32_t passes = par::passes_for(nitems);
     *passes_out = passes;
-    return par::par_launch_emit_jump(p, nitems, passes, nstr, stream);
+    return par::par_launch_emit_jump(q, nitems, passes, nstr, stream);
 }
 
 }  // namespace hdlz

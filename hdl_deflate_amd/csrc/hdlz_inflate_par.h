@@ -10,12 +10,11 @@ namespace hdlz {
 namespace par {
 
 constexpr uint32_t CH_BITS_MAX = 8192;        // a piece: 1 KiB of the stream -- 512 bytes for streams below 24 MiB, 256 below 3 MiB, 128 below 1.25 MiB: a piece is ONE
-                                              // wave's (lane's) serial chain in k_par_spec and k_par_tokens, and 16 MiB in 1 KiB pieces do not fill the
+                                              // lane's serial chain in k_par_tail (a sub-piece in k_par_tokens), and 16 MiB in 1 KiB pieces do not fill the
                                               // GPU twice (16 MiB: 1.37 -> 1.24 ms, 1 MiB: 0.76 -> 0.45 ms with 512-byte pieces)
-constexpr uint32_t WIN_DW = CH_BITS_MAX / 32 + 8; // its staged window: the piece, the 31 + 64 bits a token starting at its end may read
 constexpr uint32_t FIRST_BIT = 19;            // 2 zlib header bytes, BFINAL, BTYPE
 constexpr uint32_t X_EOB = 0x40, X_BAD = 0x80;
-constexpr uint32_t SUB = 4;                   // sub-pieces per piece: the granularity of the real decode and the emit (k_par_spec)
+constexpr uint32_t SUB = 4;                   // sub-pieces per piece: the granularity of the real decode (k_par_tokens)
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 enum { C_FALLBACK = 0, C_NUSED = 1, C_TOTAL = 2, C_OK = 3, C_MARK = 4, C_FNUSED = 5, C_NCHAIN = 6, C_NCROSS = 36, C_FAILF = 37,
        C_NOTFIXED = 7,         // the stream is not ONE fixed block: the gate of the chain for any block types (hdlz_inflate_any.hip)
@@ -46,7 +45,7 @@ struct ParArgs {
     uint32_t tcap;              // words per token list
     uint32_t* ntok;             // [nchunks]
     uint32_t* srcA;             // [srcn]  marker of every output byte: the absolute position it comes from; NONE / ROOT | r: the byte is there
-    uint32_t sub;               // k_par_spec: sub-pieces per piece (SUB), whose boundaries get maps of their own
+    uint32_t sub;               // sub-pieces per piece (SUB), whose boundaries get maps of their own (k_par_tail)
     uint8_t* mexit8;            // [nchunks][SUB-1][32]  offset behind sub-boundary s for entry offset e (X_EOB: the chain ended in front of it)
     uint32_t* mnb32;            // [nchunks][SUB-1][32]  bytes of the tokens that start in front of that boundary
     uint32_t cnu;               // the control word that holds the number of pieces in use at THIS granularity (C_NUSED / C_FNUSED)
@@ -84,14 +83,24 @@ __host__ inline uint32_t passes_for(uint32_t nitems) {                 // chains
     return passes > (uint32_t)(C_ANY0 - C_PASS0) ? (uint32_t)(C_ANY0 - C_PASS0) : passes;       // (a counter per pass: control words C_PASS0 .. C_ANY0 - 1)
 }
 
+// The scratch of one stream: arrays one behind the other, each aligned to 256 bytes (so the whole is a multiple of 256, and every
+// stream's arrays are aligned like the first one's).  take(bytes) hands out the next array's offset; take(p, bytes) points p at it in
+// the scratch at `base` (0: p holds the offset -- all the size queries need).
+struct Carve {
+    uintptr_t base;
+    size_t off;                 // bytes handed out so far
+    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255u) & ~(size_t)255u; return o; }
+    template <typename T> void take(T*& p, size_t bytes) { p = reinterpret_cast<T*>(base + take(bytes)); }
+};
+
 }  // namespace par
 
 // the chain for streams of any block types (hdlz_inflate_any.hip).  Scratch of ONE stream: any_work_bytes (0: not for this shape);
 // its kernels return at once for a stream that is one fixed block (the other chain's: the same test on the stream's third byte), and
 // leave their verdict in their own control words (C_FALLBACK / C_OK / C_TOTAL / C_MARK / C_PASS0 ..)
 size_t any_work_bytes(uint32_t in_len, uint64_t out_pitch, uint32_t flags, uint32_t nstreams);
-// (ws: stream 0's scratch; ws_off / sa_off: where this chain's part and the marker words lie in it; its control words are the first
-//  par::C_WORDS words of its part -- read by k_par_finish)
-hipError_t launch_inflate_any(const InflateArgs& a, uint32_t nstr, uint8_t* ws, size_t ws_stride, size_t ws_off, size_t sa_off,
-                              uint32_t srcn, uint32_t cap, hipStream_t stream, uint32_t* passes_out);
+// (p: the other chain's arguments -- the call, the capacity, the marker words at srcA (srcn of them, shared: one of the two chains
+//  writes them), the stride between the streams' scratch; ws: this chain's part of stream 0's scratch, whose first par::C_WORDS words
+//  are its control words -- read by k_par_finish)
+hipError_t launch_inflate_any(const par::ParArgs& p, uint8_t* ws, uint32_t nstr, hipStream_t stream, uint32_t* passes_out);
 }  // namespace hdlz

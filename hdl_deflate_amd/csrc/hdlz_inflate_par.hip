@@ -9,8 +9,8 @@
 //                    boundary they share, so the lanes that stand at the same bit afterwards are ONE chain (listed once);
 //      k_par_tail    one lane per listed chain decodes the rest of its piece: where the chain leaves the piece (offset into the next one,
 //                    or EOB, or an undecodable symbol), how many bytes it produces, and the same at three sub-boundaries of the piece;
-//      k_par_resolve every (piece, offset) takes its chain's results -- a 32-entry map per piece (k_par_spec: the 32-fold decode of whole
-//                    pieces these three replace; kept for A/B with -DHDLZ_PAR_SPEC32);
+//      k_par_resolve every (piece, offset) takes its chain's results -- a 32-entry map per piece (round 2 decoded whole pieces from all
+//                    32 offsets instead: profiles/HISTORY.md);
 //   2. k_par_scan_*  the 32-entry maps are walked from the stream's first token on (per group of 64 pieces for all 32 offsets, one
 //                    wave over the groups, the pieces of every group again): the true entry offset and the output position of every
 //                    piece, the total length;
@@ -27,7 +27,8 @@
 // a fallback flag on the device and k_inflate_dyn redoes the stream from its first byte (it is launched behind the chain and
 // returns at once otherwise): status words and bytes are those of the serial decoder by construction, the parallel path
 // only ever reports HDLZ_OK.  Scratch (stream-ordered, from the library's own pool): ~1.6 KB per piece (the maps of the 32 offsets, of the sub-boundaries and of the
-// listed chains, the token lists) and 4 bytes per possible output byte (markers; 8 up to round 4: two buffers).
+// listed chains, the token lists) and 4 bytes per possible output byte (markers; 8 up to round 4: two buffers), at most BUDGET (8 GiB;
+// the caller's buffer: its size) per chain of launches -- a batch that needs more goes through in groups of streams.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -118,84 +119,15 @@ __device__ __forceinline__ uint32_t eob_mode(const ParArgs& a) {
 }
 __device__ __forceinline__ bool eob_goes_on(uint32_t mode, uint32_t hdr3) { return mode == 2u || (mode == 1u && ((hdr3 >> 1) & 3u) == 1u); }
 
-// ---- 1. speculative decode: lane (piece, offset)
-template <bool SUBMAPS>
-__global__ __launch_bounds__(64) void k_par_spec(ParArgs a_) {
-    const ParArgs a = of_stream(a_);
-    __shared__ uint32_t lit[512], dst[32], win[2][WIN_DW];
-    const uint32_t lane = threadIdx.x, half = lane >> 5, e = lane & 31u;
-    fill_tables(lit, dst, lane, 64u);
-    const uint32_t c = blockIdx.x * 2u + half;
-    const bool have = c < a.nchunks;
-    const uint32_t b_c = FIRST_BIT + c * a.chbits, end = b_c + a.chbits;
-    if (have) stage_window(win[half], a.z, a.zn, b_c, a.chbits, e, 32u);
-    __syncthreads();
-    uint32_t pos = b_c + e, nbytes = 0, exitc = 0;
-    bool run = have;
-    // one token of the chain (lengths and byte counts only), branch-free: the 32 chains of a piece stand at different kinds of tokens
-    // at any moment, so a ladder of branches runs every path anyway and pays the exec-mask bookkeeping on top (the kernel is
-    // issue-bound: 9 waves per SIMD of ~450 token steps).  A token needs at most 9 + 5 + 5 bits here: a 32-bit window (two LDS
-    // dwords, one funnel shift) instead of bits_at's 64.
-    const uint32_t bit0 = 8u * ((b_c >> 3) & ~3u);
-    const uint32_t* w_ = win[half];
-    auto token = [&]() {
-        const uint32_t rel = pos - bit0;
-        const uint32_t x = __builtin_amdgcn_alignbit(w_[(rel >> 5) + 1u], w_[rel >> 5], rel);       // (the shift is taken modulo 32)
-        const uint32_t e0 = lit[x & 511u];
-        const uint32_t nb = e0 & 15u, type = (e0 >> 13) & 3u, leb = (e0 >> 25) & 7u, lbase = (e0 >> 16) & 0x1FFu;
-        const uint32_t y = x >> nb;
-        const uint32_t tl = lbase + __builtin_amdgcn_ubfe(y, 0u, leb);
-        const uint32_t de = dst[__builtin_amdgcn_ubfe(y, leb, 5u)];
-        const bool islit = type == (uint32_t)T_LIT;
-        const bool bad = (nb == 0u) | (type == (uint32_t)T_BAD) | ((type == (uint32_t)T_LEN) & (de == 0xFFFFFFFFu));
-        const bool eob = type == (uint32_t)T_EOB;
-        const uint32_t used = islit ? nb : nb + leb + 5u + ((de >> 16) & 15u);
-        const uint32_t made = islit ? 1u : tl;
-        const bool adv = !(bad | eob);
-        exitc = bad ? X_BAD : eob ? X_EOB : exitc;
-        pos += adv ? used : 0u;
-        nbytes += adv ? made : 0u;
-        run = adv;
-    };
-    if constexpr (SUBMAPS) {
-        // The real decode (k_par_tokens) is ONE lane's serial chain per piece, ~1000 cycles per token at one wave per SIMD: for streams
-        // that do not fill the GPU it runs on pieces SUB times shorter than these -- the entry offsets and output positions at the
-        // sub-boundaries are read off here, where every chain passes them anyway (the decode work of this kernel does not depend on
-        // the piece size; its maps do not get finer).  One loop per sub-piece: the chains of the 32 offsets pass a boundary within
-        // one token of each other.  It still costs 25 % of this kernel (315 -> 393 us at 16 MiB, against -237 us in k_par_tokens);
-        // a per-token test with the stores under it cost 14 %, a shifting 64-bit bit buffer in place of bits_at 27 %.
-        const uint32_t nsub = a.sub, fb = a.chbits / nsub;
-        for (uint32_t sb = 1u; sb <= nsub; sb++) {
-            const uint32_t bound = b_c + sb * fb;            // (the last one: the end of the piece)
-            while (ballot64(run && pos < bound) != 0ull) {
-                if (run && pos < bound) token();
-            }
-            if (have && sb < nsub) {
-                const uint32_t m = (c * (nsub - 1u) + (sb - 1u)) * 32u + e;
-                a.mexit8[m] = run ? (uint8_t)(pos - bound) : (uint8_t)X_EOB;      // (X_EOB: the chain ended in front of this boundary)
-                a.mnb32[m] = nbytes;
-            }
-        }
-        if (run) exitc = pos - end;
-    } else {
-        while (ballot64(run) != 0ull) {
-            if (run) {
-                token();
-                if (run && pos >= end) { exitc = pos - end; run = false; }
-            }
-        }
-    }
-    if (have) { a.exit8[c * 32u + e] = (uint8_t)exitc; a.nb32[c * 32u + e] = nbytes; }
-}
-
-// ---- 1'. the same maps with the 32-fold work only where it is needed (round 3).  Chains that start at different offsets of a piece fall
-// into step at the first token boundary they share -- about one chance in nine per token -- and are ONE chain from there on.  So:
-//   k_par_head     all 32 offsets of a piece decode its first HEAD_BITS bits only (6 % of k_par_spec's work at 512-byte pieces); the
+// ---- 1. speculative decode: the maps of every (piece, offset) with the 32-fold work only where it is needed (round 3; round 2 decoded
+// whole pieces from all 32 offsets).  Chains that start at different offsets of a piece fall into step at the first token boundary they
+// share -- about one chance in nine per token -- and are ONE chain from there on.  So:
+//   k_par_head     all 32 offsets of a piece decode its first HEAD_BITS bits only (6 % of the 32-fold work at 512-byte pieces); the
 //                  lanes that stand at the same bit afterwards are one chain: its first lane appends it to a global chain list;
 //   k_par_tail     one LANE per listed chain decodes the rest of its piece (exit offset, byte counts, the sub-boundary maps);
 //   k_par_resolve  every (piece, offset) takes its chain's results (+ its own bytes of the head) -- the arrays k_par_scan_* read.
 // Nothing is assumed about the data: a stream whose chains never merge (a period of a few tokens) lists 32 chains per piece and costs
-// what k_par_spec cost, plus the head.  Ordinary data lists two or three.
+// the 32-fold decode, plus the head.  Ordinary data lists two or three.
 #ifndef HDLZ_HEAD_MAX
 #define HDLZ_HEAD_MAX 256
 #endif
@@ -216,7 +148,8 @@ __device__ __forceinline__ Chains of_stream(Chains ch, size_t ws_stride) {
     return ch;
 }
 
-// one token of a chain, lengths and byte counts only, branch-free (see k_par_spec); x = the next 32 stream bits
+// one token of a chain, lengths and byte counts only, branch-free: the 32 chains of a piece stand at different kinds of tokens at any
+// moment, so a ladder of branches runs every path anyway and pays the exec-mask bookkeeping on top; x = the next 32 stream bits
 __device__ __forceinline__ void spec_token(uint32_t x, const uint32_t* lit, const uint32_t* dst, uint32_t& pos, uint32_t& nbytes,
                                            uint32_t& exitc, bool& run, uint32_t& used_out, uint32_t emode) {
     const uint32_t e0 = lit[x & 511u];
@@ -512,7 +445,7 @@ __global__ __launch_bounds__(64) void k_par_scan_pieces(ParArgs a_, uint8_t* fen
     }
     __syncthreads();
     if (lane < cnt) { a.entry8[g * GROUP + lane] = ent[lane]; a.opos[g * GROUP + lane] = op[lane]; }
-    // ---- 2b. entry offsets and output positions of the SUB-pieces (what k_par_tokens works on), from the maps k_par_spec took at the
+    // ---- 2b. entry offsets and output positions of the SUB-pieces (what k_par_tokens works on), from the maps k_par_tail took at the
     // sub-boundaries and the true entry offset of the piece (one lane per piece; a launch of its own cost 9 us)
     const uint32_t c = g * GROUP + lane;
     if (lane < cnt && c < a.ctl[C_NUSED]) {
@@ -949,23 +882,26 @@ hipError_t par::par_launch_emit_jump(const ParArgs& p, uint32_t nitems, uint32_t
 // the stream --, then the serial decoder for what it gave up on: ONE stream: one wave, only if needed; several: the streams the chain
 // flagged (status HDLZ_E_DYNAMIC_UNSUPPORTED, as pass 1 of the batch kernels flags them)
 namespace par {
-// the scratch of ONE stream of the launch: every array of the chain, each aligned to 256 bytes (so `stride` is a multiple of 256 and
-// every stream's arrays are aligned like the first one's)
+// The scratch of ONE stream of the launch: every array of the chain, where layout_of puts it -- the only code that knows the arrays'
+// offsets and sizes.  The arrays are the kernels' argument fields themselves: stream 0's, in the scratch at `ws` (null: offsets only).
 struct Layout {
-    uint32_t chbits, nchunks, sub, ngroups;
-    uint64_t cap64, srcn;
-    size_t o_ctl, o_ex, o_nb, o_en, o_op, o_gx, o_gs, o_gn, o_ge, o_go, o_mx, o_mn, o_fe, o_fo, o_tk, o_nt, o_sa, o_me, o_rp, o_cp, o_cx, o_cn,
-           o_cmx, o_cmn, o_cr, o_nf, o_any, any_bytes, stride;
+    ParArgs p;                  // the pieces' arguments as far as the scratch decides them (args_of adds the call's)
+    Chains ch;                  // the listed chains (k_par_head .. k_par_resolve)
+    uint8_t* fentry8;           // [nchunks * sub]  entry offsets and output positions of the sub-pieces (k_par_scan_pieces -> k_par_tokens)
+    uint32_t* fopos;
+    uint8_t* any;               // the chain for any block types: its own arrays behind these (any_bytes; it shares the marker words)
+    uint32_t ngroups;
+    size_t any_bytes, stride;
     bool ok;
 };
-// (`batch`: the streams of the whole call when this launch is one GROUP of it -- the choice of chains is the call's, not the group's)
-static Layout layout_of(uint32_t zn, uint32_t nstr, uint64_t out_pitch, uint32_t flags, uint32_t batch = 0) {
+// (`batch`: the streams of the whole call -- when this launch is one GROUP of it, the choice of chains is still the call's)
+static Layout layout_of(uint32_t zn, uint32_t nstr, uint64_t out_pitch, uint32_t flags, uint32_t batch, uint8_t* ws = nullptr) {
     Layout L;
     memset(&L, 0, sizeof(L));
-    L.cap64 = out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00ull : out_pitch;
-    L.srcn = (uint64_t)zn * 172u + 258u;                   // a token of 13 bits makes at most 258 bytes
-    if (L.srcn > L.cap64) L.srcn = L.cap64;
-    if (L.srcn > (1ull << 30)) return L;                   // (4 GiB of scratch: leave it to the serial decoder)
+    const uint64_t cap64 = out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00ull : out_pitch;
+    uint64_t srcn = (uint64_t)zn * 172u + 258u;            // a token of 13 bits makes at most 258 bytes
+    if (srcn > cap64) srcn = cap64;
+    if (srcn > (1ull << 30)) return L;                     // (4 GiB of scratch: leave it to the serial decoder)
     // (with the de-duplicated speculation: 1024-bit pieces 1.10 ms at 16 MiB -- markers, scans --, 4096 bits with 8 sub-pieces 0.67, these 0.64)
     // measured with the final kernels, 1 / 4 / 16 MiB of output: 1024-bit pieces 0.191 / 0.328 / 1.00 ms, 2048 bits 0.241 / 0.286 / 0.65, 4096 bits 0.317 / 0.361 / 0.571
     // (the piece size follows the bytes of the whole LAUNCH: 256 streams of 1 MiB are cut like one stream of 256 MiB, not like 256 small ones)
@@ -979,37 +915,71 @@ static Layout layout_of(uint32_t zn, uint32_t nstr, uint64_t out_pitch, uint32_t
     // 19.6 -> 15.3.  (While a token was a 4-byte store the sub-boundary maps cost literal-heavy streams of 24 .. 128 MiB more than they
     // saved: 64 MiB of random bytes 1.87 -> 2.08; 4096-bit pieces instead of 8192 as well: worse throughout.)
     const uint32_t sub = SUB;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255u) & ~(size_t)255u; return o; };
     const uint32_t ngroups = (nchunks + GROUP - 1u) / GROUP;
-    L.chbits = chbits; L.nchunks = nchunks; L.sub = sub; L.ngroups = ngroups;
-    L.o_ctl = take(4u * C_WORDS); L.o_ex = take((size_t)nchunks * 32u); L.o_nb = take((size_t)nchunks * 128u);
-    L.o_en = take(nchunks); L.o_op = take((size_t)nchunks * 4u); L.o_gx = take((size_t)ngroups * 32u); L.o_gs = take((size_t)ngroups * 32u);
-    L.o_gn = take((size_t)ngroups * 128u); L.o_ge = take(ngroups); L.o_go = take((size_t)ngroups * 4u);
-    L.o_mx = take((size_t)nchunks * (sub - 1u) * 32u); L.o_mn = take((size_t)nchunks * (sub - 1u) * 128u);
-    L.o_fe = take((size_t)nchunks * sub); L.o_fo = take((size_t)nchunks * sub * 4u);
-    L.o_tk = take((size_t)nchunks * sub * tmax_of(chbits / sub) * 4u); L.o_nt = take((size_t)nchunks * sub * 4u); L.o_sa = take((size_t)L.srcn * 4u);
-    L.o_me = take((size_t)nchunks * 4u);
-    L.o_rp = take((size_t)nchunks * 128u); L.o_cp = take((size_t)nchunks * 128u); L.o_cx = take((size_t)nchunks * 32u);
-    L.o_cn = take((size_t)nchunks * 128u); L.o_cmx = take((size_t)nchunks * 32u * (sub - 1u)); L.o_cmn = take((size_t)nchunks * 128u * (sub - 1u));
-    L.o_cr = take((size_t)MAXCROSS * 16u); L.o_nf = take((size_t)nchunks * sub * 4u);
-    // the chain for any block types: its own arrays behind these (it shares the marker words: one of the two chains writes them)
-    L.any_bytes = any_work_bytes(zn, out_pitch, flags, batch ? batch : nstr);
-    L.o_any = take(L.any_bytes);
-    L.stride = off;
+    ParArgs& p = L.p;
+    p.cap = (uint32_t)cap64; p.srcn = (uint32_t)srcn; p.nchunks = nchunks; p.chbits = chbits; p.sub = sub; p.tcap = tmax_of(chbits / sub);
+    p.cnu = C_NUSED;
+    L.ngroups = ngroups;
+    Carve c{reinterpret_cast<uintptr_t>(ws), 0u};
+    c.take(p.ctl, 4u * C_WORDS); c.take(p.exit8, (size_t)nchunks * 32u); c.take(p.nb32, (size_t)nchunks * 128u);
+    c.take(p.entry8, nchunks); c.take(p.opos, (size_t)nchunks * 4u); c.take(p.gexit8, (size_t)ngroups * 32u); c.take(p.gstop8, (size_t)ngroups * 32u);
+    c.take(p.gnb32, (size_t)ngroups * 128u); c.take(p.gentry8, ngroups); c.take(p.gopos, (size_t)ngroups * 4u);
+    c.take(p.mexit8, (size_t)nchunks * (sub - 1u) * 32u); c.take(p.mnb32, (size_t)nchunks * (sub - 1u) * 128u);
+    c.take(L.fentry8, (size_t)nchunks * sub); c.take(L.fopos, (size_t)nchunks * sub * 4u);
+    c.take(p.tokens, (size_t)nchunks * sub * p.tcap * 4u); c.take(p.ntok, (size_t)nchunks * sub * 4u); c.take(p.srcA, (size_t)srcn * 4u);
+    c.take(p.mext, (size_t)nchunks * 4u);
+    c.take(L.ch.rep, (size_t)nchunks * 128u); c.take(L.ch.cpos, (size_t)nchunks * 128u); c.take(L.ch.cexit, (size_t)nchunks * 32u);
+    c.take(L.ch.cnb, (size_t)nchunks * 128u); c.take(L.ch.cmx, (size_t)nchunks * 32u * (sub - 1u)); c.take(L.ch.cmn, (size_t)nchunks * 128u * (sub - 1u));
+    c.take(p.cross, (size_t)MAXCROSS * 16u); c.take(p.nfail, (size_t)nchunks * sub * 4u);
+    L.any_bytes = any_work_bytes(zn, out_pitch, flags, batch);
+    c.take(L.any, L.any_bytes);
+    L.stride = c.off;
     L.ok = true;
     return L;
 }
+// the kernels' arguments for the streams of `a` laid out as L (in their scratch): the pieces'
+static ParArgs args_of(const Layout& L, const InflateArgs& a) {
+    ParArgs p = L.p;
+    p.z = a.in; p.zn = a.in_len; p.flags = a.flags; p.obsize = a.obsize; p.out = a.out; p.out_len = a.out_len; p.status = a.status;
+    p.in_pitch = a.in_pitch; p.out_pitch = a.out_pitch; p.in_off = a.in_off; p.ws_stride = L.stride; p.batch = a.nstreams > 1u ? 1u : 0u;
+    return p;
+}
+// ... and the same at sub-piece granularity: what the real decode works on
+static ParArgs sub_pieces(const Layout& L, ParArgs p) {
+    p.nchunks *= p.sub; p.chbits /= p.sub; p.cnu = C_FNUSED;
+    p.entry8 = L.fentry8; p.opos = L.fopos;
+    return p;
+}
+
+// Scratch per chain of launches: the caller's buffer, or at most BUDGET bytes from the library's pool.  A call whose streams need more
+// goes through in GROUPS of streams, one chain of launches each, every group on the scratch the group in front of it used (the launches
+// are stream-ordered).
+constexpr size_t BUDGET = (size_t)8 << 30;
+// how many of the nstr streams laid out as L fit in `budget` bytes: all of them, or fewer (0: not even one)
+static uint32_t fitting(const Layout& L, uint32_t nstr, size_t budget) {
+    return L.stride * nstr <= budget ? nstr : (uint32_t)(budget / L.stride);
+}
+// the streams per group: as many as fit by the whole call's layout, then fewer while the group's own layout does not fit -- the piece
+// size follows the group's bytes, and a smaller group may be cut into smaller pieces, with more lists per byte.  0: not even one stream
+static uint32_t group_size(uint32_t zn, uint32_t nstr, uint64_t out_pitch, uint32_t flags, size_t budget) {
+    const Layout L = layout_of(zn, nstr, out_pitch, flags, nstr);
+    if (!L.ok) return 0u;
+    uint32_t gs = fitting(L, nstr, budget);
+    if (gs == nstr) return gs;
+    while (gs > 1u && fitting(layout_of(zn, gs, out_pitch, flags, nstr), gs, budget) < gs) gs = gs * 3u / 4u;
+    return gs != 0u && fitting(layout_of(zn, gs, out_pitch, flags, nstr), gs, budget) == gs ? gs : 0u;
+}
 }  // namespace par
 
-// what the path asks for when all `nstreams` streams go through it at once (less: it runs them in groups, or not at all)
+// what the path asks for when all `nstreams` streams go through it at once -- beyond the budget, as many of them as fit by this layout
+// (less: it runs them in smaller groups, or not at all)
 size_t inflate_par_work_bytes(uint32_t in_len, uint64_t nstreams, uint64_t out_pitch, uint32_t flags) {
     if (nstreams == 0 || nstreams > 65535u || in_len < HDLZ_INFLATE_PAR_MIN) return 0;
-    const par::Layout L = par::layout_of(in_len, (uint32_t)nstreams, out_pitch, flags);
+    const uint32_t n = (uint32_t)nstreams;
+    const par::Layout L = par::layout_of(in_len, n, out_pitch, flags, n);
     if (!L.ok) return 0;
-    constexpr size_t BUDGET = (size_t)8 << 30;
-    const size_t all = L.stride * (size_t)nstreams;
-    return all > BUDGET && nstreams > 1 ? (BUDGET / L.stride ? (BUDGET / L.stride) * L.stride : L.stride) : all;
+    const uint32_t gs = par::fitting(L, n, par::BUDGET);
+    return (size_t)(gs ? gs : 1u) * L.stride;
 }
 
 // The two chains need nothing from each other (each looks at the stream's first block header itself), and for any given stream one of
@@ -1024,151 +994,132 @@ static hipStream_t side_stream() {
     if (!side[dev] && hipStreamCreateWithFlags(&side[dev], hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); side[dev] = nullptr; }
     return side[dev];
 }
+// The fork of one call.  From a successful fork on, the caller's stream waits for everything queued on the side stream: at join(), or
+// when the Fork goes out of scope -- on every way out, error exits included, so in front of the scratch going back.  The wait is
+// stream-ordered (an event), never a host synchronisation.  No side stream or no events: side() is the caller's stream itself.
+class Fork {
+  public:
+    Fork(hipStream_t stream, bool want) : stream_(stream), side_(stream) {
+        if (!want) return;
+        const hipStream_t s = side_stream();
+        hipEvent_t ev_fork = nullptr;
+        if (s && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming) == hipSuccess &&
+            hipEventRecord(ev_fork, stream) == hipSuccess && hipStreamWaitEvent(s, ev_fork, 0) == hipSuccess) side_ = s;
+        else (void)hipGetLastError();
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+    }
+    ~Fork() {
+        (void)join();
+        if (ev_join_) (void)hipEventDestroy(ev_join_);
+    }
+    Fork(const Fork&) = delete;
+    Fork& operator=(const Fork&) = delete;
+    hipStream_t side() const { return side_; }
+    hipError_t join() {
+        if (side_ == stream_) return hipSuccess;           // (not forked, or joined already)
+        const hipStream_t s = side_;
+        side_ = stream_;
+        const hipError_t e = hipEventRecord(ev_join_, s);
+        return e != hipSuccess ? e : hipStreamWaitEvent(stream_, ev_join_, 0);
+    }
+  private:
+    hipStream_t stream_, side_;
+    hipEvent_t ev_join_ = nullptr;
+};
 
-static hipError_t launch_inflate_par_group(const InflateArgs& a, hipStream_t stream, bool* used, const Work& w, uint32_t batch);
-hipError_t launch_inflate_par(const InflateArgs& a, hipStream_t stream, bool* used, const Work& w) {
-    return launch_inflate_par_group(a, stream, used, w, a.nstreams > 65535u ? 0u : (uint32_t)a.nstreams);
-}
-static hipError_t launch_inflate_par_group(const InflateArgs& a, hipStream_t stream, bool* used, const Work& w, uint32_t batch) {
+// both chains on the streams of `a`, laid out as L in their scratch; returns with the side stream joined
+static hipError_t launch_chains(const par::Layout& L, const InflateArgs& a, hipStream_t stream) {
     using namespace par;
-    *used = false;
-    const uint32_t zn = a.in_len;
-    const uint32_t nstr = (uint32_t)a.nstreams;
-    if (a.nstreams == 0 || a.nstreams > 65535u) return hipSuccess;
-    const Layout L = layout_of(zn, nstr, a.out_pitch, a.flags, batch);
-    if (!L.ok) return hipSuccess;
-    const uint64_t cap64 = L.cap64, srcn = L.srcn;
-    const uint32_t chbits = L.chbits, nchunks = L.nchunks, sub = L.sub, ngroups = L.ngroups;
-    const size_t o_ctl = L.o_ctl, o_ex = L.o_ex, o_nb = L.o_nb, o_en = L.o_en, o_op = L.o_op, o_gx = L.o_gx, o_gs = L.o_gs, o_gn = L.o_gn,
-                 o_ge = L.o_ge, o_go = L.o_go, o_mx = L.o_mx, o_mn = L.o_mn, o_fe = L.o_fe, o_fo = L.o_fo, o_tk = L.o_tk, o_nt = L.o_nt,
-                 o_sa = L.o_sa, o_me = L.o_me, o_rp = L.o_rp, o_cp = L.o_cp, o_cx = L.o_cx, o_cn = L.o_cn, o_cmx = L.o_cmx, o_cmn = L.o_cmn;
-    uint8_t* ws = nullptr;
-    const size_t stride = L.stride;
-    // more scratch than the budget (4 GiB from the library's pool; the caller's buffer otherwise): the batch goes through in groups of
-    // streams, one chain of launches each (its scratch is the one the group in front of it used: the launches are stream-ordered).
-    // NOTE the piece size follows the group's bytes, so a group is laid out again by the recursive call.
-    const size_t BUDGET = w.caller ? w.bytes : (size_t)8 << 30;
-    if (stride > BUDGET) return hipSuccess;                     // not even one stream: the caller's other paths
-    if (nstr > 1u && stride * (size_t)nstr > BUDGET) {
-        uint32_t gs = (uint32_t)(BUDGET / stride);
-        // (a smaller group may be cut into smaller pieces with more lists per byte: shrink until the group's own layout fits)
-        while (gs > 1u && layout_of(zn, gs, a.out_pitch, a.flags, batch).stride * (size_t)gs > BUDGET) gs = gs * 3u / 4u;
-        if (gs == 0u || layout_of(zn, gs, a.out_pitch, a.flags, batch).stride * (size_t)gs > BUDGET) return hipSuccess;
-        if (gs < nstr) {
-            for (uint32_t s0 = 0; s0 < nstr; s0 += gs) {
-                InflateArgs g = a;
-                if (a.in_off) g.in_off = a.in_off + s0;
-                else g.in = a.in + (uint64_t)s0 * a.in_pitch;
-                g.out = a.out + (uint64_t)s0 * a.out_pitch;
-                g.out_len = a.out_len + s0;
-                g.status = a.status + s0;
-                g.nstreams = nstr - s0 < gs ? nstr - s0 : gs;
-                // (the last, smaller group could be laid out with smaller pieces and need more per stream than fits)
-                if (layout_of(zn, (uint32_t)g.nstreams, a.out_pitch, a.flags, batch).stride * (size_t)g.nstreams > BUDGET) {
-                    if (s0 == 0) return hipSuccess;
-                    // hand the rest to the batch kernels: mark them as the chain's give-ups
-                    hipLaunchKernelGGL(k_par_flag_rest, dim3((unsigned)((g.nstreams + 63u) / 64u)), dim3(64), 0, stream, g.out_len, g.status, (uint32_t)g.nstreams);
-                    hipError_t er = hipGetLastError();
-                    if (er == hipSuccess) er = launch_inflate_dyn_flagged(g, stream);
-                    if (er != hipSuccess) return er;
-                    continue;
-                }
-                bool u = false;
-                const hipError_t eg = launch_inflate_par_group(g, stream, &u, w, batch);
-                if (eg != hipSuccess) return eg;
-                // (a first group without scratch: the caller's batch kernels redo the whole batch, which is harmless)
-                if (!u) {
-                    if (s0 == 0) return hipSuccess;
-                    hipLaunchKernelGGL(k_par_flag_rest, dim3((unsigned)((g.nstreams + 63u) / 64u)), dim3(64), 0, stream, g.out_len, g.status, (uint32_t)g.nstreams);
-                    hipError_t er = hipGetLastError();
-                    if (er == hipSuccess) er = launch_inflate_dyn_flagged(g, stream);
-                    if (er != hipSuccess) return er;
-                }
-            }
-            *used = true;
-            return hipSuccess;
-        }
+    const uint32_t nstr = (uint32_t)a.nstreams, nchunks = L.p.nchunks, ngroups = L.ngroups;
+    const ParArgs p = args_of(L, a), pf = sub_pieces(L, p);
+    // fork: the chain for any block types on the side stream, beside this one
+    Fork fork(stream, L.any_bytes != 0u);
+    const uint32_t* actl = nullptr;
+    uint32_t apasses = 0;
+    if (L.any_bytes != 0u) {
+        const hipError_t e = launch_inflate_any(p, L.any, nstr, fork.side(), &apasses);
+        if (e != hipSuccess) return e;
+        actl = reinterpret_cast<const uint32_t*>(L.any);
     }
-    hipError_t e = w.get(stride * nstr, stream, &ws);
-    if (e != hipSuccess) { (void)hipGetLastError(); return hipSuccess; }      // no scratch: the caller goes on with the serial decoder
-    {
-        ParArgs p{a.in, zn, a.flags, a.obsize, a.out, (uint32_t)cap64, (uint32_t)srcn, a.out_len, a.status, nchunks, chbits,
-                  reinterpret_cast<uint32_t*>(ws + o_ctl), ws + o_ex, reinterpret_cast<uint32_t*>(ws + o_nb), ws + o_en,
-                  reinterpret_cast<uint32_t*>(ws + o_op), ws + o_gx, ws + o_gs, reinterpret_cast<uint32_t*>(ws + o_gn), ws + o_ge,
-                  reinterpret_cast<uint32_t*>(ws + o_go), reinterpret_cast<uint32_t*>(ws + o_tk), tmax_of(chbits / sub),
-                  reinterpret_cast<uint32_t*>(ws + o_nt), reinterpret_cast<uint32_t*>(ws + o_sa), sub, ws + o_mx,
-                  reinterpret_cast<uint32_t*>(ws + o_mn), (uint32_t)C_NUSED, reinterpret_cast<uint32_t*>(ws + o_me),
-                  reinterpret_cast<uint32_t*>(ws + L.o_cr), reinterpret_cast<uint32_t*>(ws + L.o_nf),
-                  a.in_pitch, a.out_pitch, a.in_off, stride, nstr > 1u ? 1u : 0u};
-        // fork: the chain for any block types on the side stream, beside this one
-        const uint32_t* actl = nullptr;
-        uint32_t apasses = 0;
-        hipEvent_t ev_join = nullptr;
-        if (L.any_bytes != 0u) {
-            hipStream_t side = side_stream();
-            hipEvent_t ev_fork = nullptr;
-            bool forked = side && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess &&
-                          hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) == hipSuccess &&
-                          hipEventRecord(ev_fork, stream) == hipSuccess && hipStreamWaitEvent(side, ev_fork, 0) == hipSuccess;
-            if (!forked) { (void)hipGetLastError(); side = stream; }
-            e = launch_inflate_any(a, nstr, ws, stride, L.o_any, o_sa, (uint32_t)srcn, (uint32_t)cap64, side, &apasses);
-            actl = reinterpret_cast<const uint32_t*>(ws + L.o_any);
-            if (forked && e == hipSuccess) e = hipEventRecord(ev_join, side);
-            if (!forked && ev_join) { (void)hipEventDestroy(ev_join); ev_join = nullptr; }
-            if (ev_fork) (void)hipEventDestroy(ev_fork);
-            if (e != hipSuccess) { if (ev_join) (void)hipEventDestroy(ev_join); const hipError_t e2 = w.put(ws, stream); (void)e2; return e; }
-        }
-        hipLaunchKernelGGL(k_par_zero, dim3(1, nstr), dim3(64), 0, stream, p);
-        // the same arguments at sub-piece granularity: what the real decode and the emit work on
-        ParArgs pf = p;
-        pf.nchunks = nchunks * sub; pf.chbits = chbits / sub; pf.cnu = C_FNUSED;
-        pf.entry8 = ws + o_fe; pf.opos = reinterpret_cast<uint32_t*>(ws + o_fo);
-        const uint32_t passes = passes_for(nchunks);
-#ifdef HDLZ_PAR_SPEC32
-        if (sub > 1u) hipLaunchKernelGGL(k_par_spec<true>, dim3((nchunks + 1u) / 2u, nstr), dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(k_par_spec<false>, dim3((nchunks + 1u) / 2u, nstr), dim3(64), 0, stream, p);
-#else
-        Chains ch{reinterpret_cast<uint32_t*>(ws + o_rp), reinterpret_cast<uint32_t*>(ws + o_cp), ws + o_cx, reinterpret_cast<uint32_t*>(ws + o_cn),
-                  ws + o_cmx, reinterpret_cast<uint32_t*>(ws + o_cmn)};
-        hipLaunchKernelGGL(k_par_head, dim3((nchunks + 2u * HEAD_WAVES - 1u) / (2u * HEAD_WAVES), nstr), dim3(64 * HEAD_WAVES), 0, stream, p, ch);
-        hipLaunchKernelGGL(k_par_tail, dim3((nchunks * 32u + 63u) / 64u, nstr), dim3(64), 0, stream, p, ch);
-        hipLaunchKernelGGL(k_par_resolve, dim3((nchunks * 32u + 255u) / 256u, nstr), dim3(256), 0, stream, p, ch);
-#endif
-        hipLaunchKernelGGL(k_par_scan_groups, dim3(ngroups, nstr), dim3(64), 0, stream, p);
-        hipLaunchKernelGGL(k_par_scan_top, dim3(1, nstr), dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(k_par_scan_pieces, dim3(ngroups, nstr), dim3(64), 0, stream, p, pf.entry8, pf.opos);
-        if (pf.chbits <= CH_BITS_MAX / 2u)
-            hipLaunchKernelGGL(k_par_tokens<true>, dim3((pf.nchunks + 63u) / 64u, nstr), dim3(64), 256u * (pf.chbits / 32u + 6u), stream, pf);
-        else hipLaunchKernelGGL(k_par_tokens<false>, dim3((pf.nchunks + 63u) / 64u, nstr), dim3(64), 0, stream, pf);
-        hipLaunchKernelGGL(k_par_ends, dim3(1, nstr), dim3(256), 0, stream, p);
-        ParArgs pe = p;                                                 // the emit: pieces, reading the sub-pieces' token lists
-        pe.tokens = pf.tokens; pe.ntok = pf.ntok;
-        hipLaunchKernelGGL(k_par_emit<false>, dim3(nchunks, nstr), dim3(64), 0, stream, pe);
-        for (uint32_t j = 0; j < passes; j++) hipLaunchKernelGGL(k_par_jump, dim3(j == 0u ? nchunks : later_grid(nchunks, nstr), nstr), dim3(64), 0, stream, p, j);
+    hipLaunchKernelGGL(k_par_zero, dim3(1, nstr), dim3(64), 0, stream, p);
+    hipLaunchKernelGGL(k_par_head, dim3((nchunks + 2u * HEAD_WAVES - 1u) / (2u * HEAD_WAVES), nstr), dim3(64 * HEAD_WAVES), 0, stream, p, L.ch);
+    hipLaunchKernelGGL(k_par_tail, dim3((nchunks * 32u + 63u) / 64u, nstr), dim3(64), 0, stream, p, L.ch);
+    hipLaunchKernelGGL(k_par_resolve, dim3((nchunks * 32u + 255u) / 256u, nstr), dim3(256), 0, stream, p, L.ch);
+    hipLaunchKernelGGL(k_par_scan_groups, dim3(ngroups, nstr), dim3(64), 0, stream, p);
+    hipLaunchKernelGGL(k_par_scan_top, dim3(1, nstr), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(k_par_scan_pieces, dim3(ngroups, nstr), dim3(64), 0, stream, p, pf.entry8, pf.opos);
+    if (pf.chbits <= CH_BITS_MAX / 2u)
+        hipLaunchKernelGGL(k_par_tokens<true>, dim3((pf.nchunks + 63u) / 64u, nstr), dim3(64), 256u * (pf.chbits / 32u + 6u), stream, pf);
+    else hipLaunchKernelGGL(k_par_tokens<false>, dim3((pf.nchunks + 63u) / 64u, nstr), dim3(64), 0, stream, pf);
+    hipLaunchKernelGGL(k_par_ends, dim3(1, nstr), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(k_par_emit<false>, dim3(nchunks, nstr), dim3(64), 0, stream, p);     // (pieces, reading the sub-pieces' token lists)
+    const uint32_t passes = passes_for(nchunks);
+    for (uint32_t j = 0; j < passes; j++) hipLaunchKernelGGL(k_par_jump, dim3(j == 0u ? nchunks : later_grid(nchunks, nstr), nstr), dim3(64), 0, stream, p, j);
+    hipError_t e = hipGetLastError();
+    // join: the verdict looks at both chains' control words
+    if (e == hipSuccess) e = fork.join();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_par_finish, dim3(1, nstr), dim3(64), 0, stream, p, passes, actl, apasses);
         e = hipGetLastError();
-        // join: the verdict looks at both chains' control words
-        if (ev_join) {
-            if (e == hipSuccess) e = hipStreamWaitEvent(stream, ev_join, 0);
-            (void)hipEventDestroy(ev_join);
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_par_finish, dim3(1, nstr), dim3(64), 0, stream, p, passes, actl, apasses);
-            e = hipGetLastError();
-        }
-        // ONE stream: the serial decoder returns at once when ctl[C_OK] >= 1; several: it redoes the streams k_par_finish flagged
-        if (e == hipSuccess) e = nstr == 1u ? launch_inflate_dyn(a, stream, true, p.ctl + C_OK, 1u) : launch_inflate_dyn_flagged(a, stream);
-        *used = true;
     }
+    // ONE stream: the serial decoder returns at once when ctl[C_OK] >= 1; several: it redoes the streams k_par_finish flagged
+    if (e == hipSuccess) e = nstr == 1u ? launch_inflate_dyn(a, stream, true, p.ctl + C_OK, 1u) : launch_inflate_dyn_flagged(a, stream);
+    return e;
+}
+
+// one group: its scratch, both chains, the scratch back (*used = false: no scratch -- nothing launched)
+static hipError_t launch_group(const InflateArgs& g, uint32_t batch, size_t budget, hipStream_t stream, const Work& w, bool* used) {
+    *used = false;
+    const uint32_t n = (uint32_t)g.nstreams;
+    const size_t need = par::layout_of(g.in_len, n, g.out_pitch, g.flags, batch).stride * n;
+    if (need > budget) return hipSuccess;                      // (the last, smaller group may be cut into smaller pieces and not fit)
+    uint8_t* ws = nullptr;
+    if (w.get(need, stream, &ws) != hipSuccess) { (void)hipGetLastError(); return hipSuccess; }
+    *used = true;
+    const hipError_t e = launch_chains(par::layout_of(g.in_len, n, g.out_pitch, g.flags, batch, ws), g, stream);
     const hipError_t e2 = w.put(ws, stream);
     return e != hipSuccess ? e : e2;
+}
+
+hipError_t launch_inflate_par(const InflateArgs& a, hipStream_t stream, bool* used, const Work& w) {
+    using namespace par;
+    *used = false;
+    if (a.nstreams == 0 || a.nstreams > 65535u) return hipSuccess;
+    const uint32_t nstr = (uint32_t)a.nstreams;
+    const size_t budget = w.caller ? w.bytes : BUDGET;
+    const uint32_t gs = group_size(a.in_len, nstr, a.out_pitch, a.flags, budget);
+    if (gs == 0u) return hipSuccess;                             // not even one stream: the caller's other paths
+    for (uint32_t s0 = 0; s0 < nstr; s0 += gs) {
+        InflateArgs g = a;
+        if (a.in_off) g.in_off = a.in_off + s0;
+        else g.in = a.in + (uint64_t)s0 * a.in_pitch;
+        g.out = a.out + (uint64_t)s0 * a.out_pitch;
+        g.out_len = a.out_len + s0;
+        g.status = a.status + s0;
+        g.nstreams = nstr - s0 < gs ? nstr - s0 : gs;
+        bool u = false;
+        hipError_t e = launch_group(g, nstr, budget, stream, w, &u);
+        if (e != hipSuccess) return e;
+        if (u) continue;
+        // a group without scratch: the first one -- the caller's batch kernels take the whole batch; a later one -- hand it to the
+        // serial pass, flagged like the chain's own give-ups
+        if (s0 == 0) return hipSuccess;
+        hipLaunchKernelGGL(k_par_flag_rest, dim3((unsigned)((g.nstreams + 63u) / 64u)), dim3(64), 0, stream, g.out_len, g.status, (uint32_t)g.nstreams);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = launch_inflate_dyn_flagged(g, stream);
+        if (e != hipSuccess) return e;
+    }
+    *used = true;
+    return hipSuccess;
 }
 
 }  // namespace hdlz
 
 #ifdef HDLZ_DEBUG_EXPORTS      // (lib/libhdlz_dbg.so, tools/dev_any.py: where the control words of the two chains lie in the caller's scratch)
 extern "C" size_t hdlz_debug_par_offsets(uint32_t in_len, uint64_t nstreams, uint64_t out_pitch, uint32_t flags, size_t* o_ctl, size_t* o_any) {
-    const hdlz::par::Layout L = hdlz::par::layout_of(in_len, (uint32_t)nstreams, out_pitch, flags);
-    *o_ctl = L.o_ctl; *o_any = L.o_any;
+    const hdlz::par::Layout L = hdlz::par::layout_of(in_len, (uint32_t)nstreams, out_pitch, flags, (uint32_t)nstreams);
+    *o_ctl = reinterpret_cast<uintptr_t>(L.p.ctl); *o_any = reinterpret_cast<uintptr_t>(L.any);      // (laid out at 0: offsets)
     return L.ok ? L.stride : 0u;
 }
 #endif

@@ -1016,13 +1016,26 @@ static hipError_t bin_streams(const uint64_t* in_off, uint32_t n, uint32_t* bins
     return hipGetLastError();
 }
 
+// The lists of the lane-per-stream mapping in its scratch, in 4-byte words.  Pass 1 (ragged input of more than one wave: the lanes take
+// the streams in the order of their length class, see k_bin_*): the bins (BIN_WORDS), the ordered list behind them -- 0: no list, the
+// streams in their own order.  Pass 2 (launch_inflate_tok_dyn): its two counts, the bins of stage 1's counting sort, the collected list
+// (both stages), and -- `binned`: ragged input, not `all` -- the length-ordered list of stage 1 behind that.
+struct Lists { size_t pass1, pass2; bool binned; };
+static Lists lists_of(uint64_t nstreams, bool ragged, bool all) {
+    const bool order = ragged && nstreams > HDLZ_INFLATE_BIN_MIN && nstreams <= 0xFFFFFFFFull;        // (32-bit stream ids in the lists)
+    Lists l;
+    l.pass1 = order ? (size_t)nstreams + BIN_WORDS : 0u;
+    l.binned = order && !all;
+    l.pass2 = 2u + BIN_WORDS + (size_t)nstreams + (l.binned ? (size_t)nstreams : 0u);
+    return l;
+}
+
 }  // namespace tok
 
 size_t inflate_tok_work_bytes(uint64_t nstreams, bool ragged) {
     if (nstreams == 0 || nstreams > 0xFFFFFFFFull) return 0;
-    const size_t pass1 = ragged && nstreams > HDLZ_INFLATE_BIN_MIN ? sizeof(uint32_t) * ((size_t)nstreams + tok::BIN_WORDS) : 0u;
-    const size_t pass2 = sizeof(uint32_t) * ((size_t)2u + tok::BIN_WORDS + nstreams + (ragged && nstreams > HDLZ_INFLATE_BIN_MIN ? (size_t)nstreams : 0u));
-    return ((pass1 > pass2 ? pass1 : pass2) + 255u) & ~(size_t)255u;
+    const tok::Lists l = tok::lists_of(nstreams, ragged, false);
+    return (sizeof(uint32_t) * (l.pass1 > l.pass2 ? l.pass1 : l.pass2) + 255u) & ~(size_t)255u;
 }
 
 hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Work& w) {
@@ -1031,10 +1044,11 @@ hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Wo
     const uint64_t per_wg = 64u * L::WAVES;
     const dim3 grid((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), block(64 * L::WAVES);
     // ragged input of more than one wave: the lanes take the streams in the order of their length class (see k_bin_*)
-    if (a.in_off && a.nstreams > HDLZ_INFLATE_BIN_MIN && a.nstreams <= 0xFFFFFFFFull) {
+    const size_t nws = tok::lists_of(a.nstreams, a.in_off != nullptr, false).pass1;
+    if (nws != 0u) {
         uint32_t* ws = nullptr;                  // ws[0 .. BIN_WORDS): the bins (see tok::BIN_WORDS); the list behind them
         const uint32_t n = (uint32_t)a.nstreams;
-        hipError_t e = w.get(sizeof(uint32_t) * ((size_t)n + tok::BIN_WORDS), stream, reinterpret_cast<uint8_t**>(&ws));
+        hipError_t e = w.get(sizeof(uint32_t) * nws, stream, reinterpret_cast<uint8_t**>(&ws));
         if (e == hipSuccess) {
             e = tok::bin_streams(a.in_off, n, ws, ws + tok::BIN_WORDS, stream);
             if (e == hipSuccess) {
@@ -1063,17 +1077,16 @@ hipError_t launch_inflate_tok_dyn(const InflateArgs& a, hipStream_t stream, bool
     const dim3 grid((unsigned)((a.nstreams + 63u) / 64u)), block(64);
     const dim3 cgrid((unsigned)((a.nstreams + 255u) / 256u)), cblock(256);
     // ws[0], ws[1]: the two counts; ws[2 .. 2 + BIN_WORDS): the bins of stage 1's counting sort (zeroed with the counts in one launch);
-    // the collected list behind them (both stages: the launches are ordered; 4 bytes per stream), the length-ordered list of stage 1
-    // behind that (4 more per stream when binned)
+    // the collected list behind them, the length-ordered list of stage 1 behind that (tok::lists_of)
     uint32_t* ws = nullptr;
     // (the explicit lane hint keeps every such stream in the lane kernels)
     const uint32_t lane_min = (a.flags & HDLZ_INFLATE_LANE_PER_STREAM) ? 0u : HDLZ_INFLATE_DYN_LANE_MIN;
     // ragged input: stage 1 takes its streams in the order of their length class, like pass 1: k_collect_dyn counts the classes of the
     // streams it lists and its last block makes the first slots, so the sort adds ONE launch (the scatter)
-    const bool binned = a.in_off != nullptr && a.nstreams > HDLZ_INFLATE_BIN_MIN && a.nstreams <= 0xFFFFFFFFull && !all;   // (32-bit stream ids in the lists)
+    const tok::Lists l = tok::lists_of(a.nstreams, a.in_off != nullptr, all);
+    const bool binned = l.binned;
     const uint32_t head = 2u + tok::BIN_WORDS;
-    const size_t nws = (size_t)head + a.nstreams + (binned ? (size_t)a.nstreams : 0u);
-    hipError_t e = w.get(sizeof(uint32_t) * nws, stream, reinterpret_cast<uint8_t**>(&ws));
+    hipError_t e = w.get(sizeof(uint32_t) * l.pass2, stream, reinterpret_cast<uint8_t**>(&ws));
     if (e != hipSuccess) {                      // no scratch: the wave-per-stream pass needs none and finishes the job
         (void)hipGetLastError();
         return launch_inflate_dyn(a, stream, all);
