@@ -28,7 +28,12 @@
  *     aligned (16 recommended); d_out_len[b] receives the byte count (the reference's final
  *     o_oprogress, deflate.py:814 / :1554), d_status[b] one of HDLZ_OK / HDLZ_E_*;
  *   - the return value is HDLZ_OK or HDLZ_E_BAD_PARAM / HDLZ_E_HIP for host-side failures;
- *     per-block failures are only reported through d_status.
+ *     per-block failures are only reported through d_status;
+ *   - EXTENTS: a call writes d_out_len[0 .. nblocks), d_status[0 .. nblocks), d_work[0 .. work_bytes) and, of d_out, what its own
+ *     comment below states under "writes" -- never a byte outside row b's d_out[b*out_pitch .. (b+1)*out_pitch), and nothing else
+ *     (no input, no index, no byte in front of or behind any buffer; buffers may be sub-allocated back to back).  "reads" states how far
+ *     outside the blocks a call may LOAD: such bytes must be mapped, their values never reach a result -- nor do the initial contents of
+ *     d_out, d_out_len, d_status and d_work.  tests/test_gpu_containment.py holds every entry point to these statements.
  * There is no CPU implementation behind this ABI: without a gfx950 device every compute entry
  * point returns HDLZ_E_HIP.
  */
@@ -114,6 +119,10 @@ int hdlz_release_scratch(void);
  * otherwise, deflate.py:56-59), maxmatch 10 (MATCH10=True) or 5 (deflate.py:34-35).
  * Ragged input: a stated bound in_len <= 1024 lets the call pack several small blocks per wave; a block longer
  * than a stated bound gets HDLZ_E_BAD_PARAM in its status word.  Needs no scratch.
+ * writes: row b up to d_out_len[b] rounded up to 4 (the output goes out in 32-bit words; out_pitch % 4 == 0 keeps that inside the row);
+ *         NOTHING of the row of a block whose status is not HDLZ_OK.
+ * reads:  up to 15 bytes behind a block's last byte (16-byte loads counted from the block's first byte) and, for a block that does not
+ *         start at a multiple of 4, the up to 3 bytes in front of it down to that multiple.
  */
 int hdlz_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
                         uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
@@ -138,6 +147,12 @@ int hdlz_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t 
  * (down to d_work = NULL) the call still succeeds with the same results through mappings that need less: the whole-GPU path runs the
  * streams in groups that fit or is skipped, the lane mapping takes the streams in index order, the second pass runs a wave per stream.
  * Nothing is allocated; every launch is capturable.  hdlz_inflate_batch is the same call with scratch from the library's pool.
+ * writes: row b of a stream with status HDLZ_OK: exactly d_out_len[b] bytes.  The row of a failed stream (d_out_len[b] = 0) may hold
+ *         any part of what was decoded before the failure, anywhere in d_out[b*out_pitch .. (b+1)*out_pitch) -- with HDLZ_E_OUT_CAPACITY
+ *         up to the whole row; a stream that fails before its first output byte (too short, a bad first block header) leaves its row as
+ *         it was.  d_work: [0, work_bytes) of what was PASSED, whatever hdlz_inflate_work_bytes says.
+ * reads:  only the bytes of the streams themselves (in_off[b] .. in_off[b+1], or in_len bytes per row): every load is bounds-checked
+ *         against the stream's end, at any alignment.
  */
 size_t hdlz_inflate_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_pitch, uint32_t flags, int ragged);
 int hdlz_inflate_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
@@ -152,6 +167,7 @@ int hdlz_inflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
  * one byte per READ, deflate.py:601): copies d_len[b] bytes of row b (d_rows + b*row_pitch) to
  * d_archive + d_off[b].  d_off is the exclusive scan of the lengths, computed by the caller (across GPUs:
  * after the all-gather of the lengths).  Works for compress and inflate outputs alike; d_archive may be pinned host memory.
+ * writes: d_archive[d_off[b] .. d_off[b] + d_len[b]) for every b, nothing else.
  */
 int hdlz_compact_batch(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_off,
                        uint64_t nblocks, uint8_t* d_archive, void* stream);
@@ -162,6 +178,8 @@ int hdlz_compact_batch(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t
  * of 256 rows).  d_off is at once the ragged-input index hdlz_inflate_batch / hdlz_compress_batch take (d_in_off).  archive_cap:
  * bytes writable at d_archive; rows that would end beyond it are not copied -- compare d_off[nblocks] with archive_cap after the
  * call (sum of row bounds = always enough).  d_archive must be device memory.  nblocks < 2^31.
+ * writes: d_off[0 .. nblocks], the bytes d_archive[d_off[b] .. d_off[b+1]) of the rows that are copied (none at or behind archive_cap),
+ *         d_work[0 .. work_bytes).  reads: d_len[0 .. nblocks) and d_len[b] bytes of row b.
  * _ws: d_work of at least hdlz_archive_work_bytes(nblocks) bytes (8 per tile of 256 rows), 8-byte aligned, REQUIRED (else
  * HDLZ_E_BAD_PARAM); nothing is allocated.  hdlz_archive_batch takes the same scratch from the library's pool.
  */
@@ -179,8 +197,9 @@ int hdlz_archive_batch(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t
  * LMAX range and beyond.
  *   d_in / in_len   the stream (in_len >= 5, else *d_status = HDLZ_E_SHORT_INPUT); readable up to in_len
  *                   rounded up to 16 bytes
- *   d_out / out_cap 4-byte aligned, out_cap >= hdlz_out_bound(in_len) rounded up to 4 (else HDLZ_E_OUT_CAPACITY)
- *   d_work          device scratch of hdlz_stream_work_bytes(in_len) bytes, 8-byte aligned
+ *   d_out / out_cap 4-byte aligned, out_cap >= hdlz_out_bound(in_len) rounded up to 4 (else HDLZ_E_OUT_CAPACITY); written up to
+ *                   *d_out_len rounded up to 4, as by hdlz_compress_batch (hdlz_compress_streams: per row)
+ *   d_work          device scratch of hdlz_stream_work_bytes(in_len) bytes, 8-byte aligned; written within those bytes
  * Returns HDLZ_OK when the launches were queued; *d_out_len, *d_status as in hdlz_compress_batch. */
 size_t hdlz_stream_work_bytes(size_t in_len);
 
@@ -218,7 +237,11 @@ int hdlz_compress_stream(const uint8_t* d_in, uint32_t in_len, int cwindow, int 
  * recorded as fixtures instead.  Likewise the output memory: this engine never overwrites unread output.
  * After a call state.out_len complete output bytes are readable at d_out (the final call: the stream length, R9).
  * Violations are reported in state.status (HDLZ_E_BAD_PARAM / _OUT_CAPACITY / _SHORT_INPUT); a failed or finished session
- * ignores further calls.  One wave per call: the port adapter's path, not a throughput path. */
+ * ignores further calls.  One wave per call: the port adapter's path, not a throughput path.
+ * writes: the 64 bytes of the state and d_out below state.out_len rounded DOWN to 4, plus 4 (the word that holds the incomplete byte goes
+ *         out too); the final call ends at the stream's length rounded up to 4.  The 2400 bytes of out_cap are what a call's capacity
+ *         check asks for (a tile's worst case), not bytes it writes.  reads: as hdlz_compress_batch, counted from in_len -- the bytes
+ *         behind in_len, not yet known to the caller, do not reach the output. */
 typedef struct hdlz_cstate {
     uint32_t pos;          /* positions [0, pos) are encoded */
     uint32_t skip;         /* positions from pos on that the last match already covers (greedy-parse state) */
@@ -252,7 +275,8 @@ int hdlz_compress_chunk(const uint8_t* d_in, uint32_t in_len, uint32_t q_end, in
  *                  the bytes may not); final != 0: in_len is the stream length and the reference's end-of-input checks apply
  *   flags          HDLZ_INFLATE_ASSUME_FIXED / HDLZ_INFLATE_ONEBLOCK;  obsize as in hdlz_inflate_batch
  *   d_out/out_cap  the whole output, linear (back-references read it);  out_limit: produce at most this many bytes in total
- * Results are identical to hdlz_inflate_batch on the complete stream.  One wave per call (the port adapter's path). */
+ * Results are identical to hdlz_inflate_batch on the complete stream.  One wave per call (the port adapter's path).
+ * writes: the state (sizeof(hdlz_istate) = 384 bytes) and d_out[0 .. out_cap).  reads: d_in[0 .. in_len) only. */
 typedef struct hdlz_istate {
     uint32_t bitpos;       /* next stream bit to decode */
     uint32_t out_pos;      /* output bytes produced (final, readable) */
