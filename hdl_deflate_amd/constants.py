@@ -4,6 +4,8 @@ IDLE, WRITE, READ, STARTC, STARTD = range(5)
 (OK, E_SHORT_INPUT, E_OUT_CAPACITY, E_BAD_BTYPE, E_BAD_DISTANCE, E_NO_EOF, E_DYNAMIC_UNSUPPORTED,
  E_BAD_SYMBOL, E_BAD_PARAM, E_HIP) = range(10)
 E_BAD_TREE = 10
+E_BAD_HEADER = 11                # hdlz_inflate_checked only: CMF/FLG is not a zlib header this library reads
+E_BAD_CHECKSUM = 12              # hdlz_inflate_checked only: Adler-32 of the output != the stream's trailer
 INFLATE_ASSUME_FIXED = 1
 INFLATE_LANE_PER_STREAM = 2      # mapping hints of hdlz_inflate_batch (results are identical)
 INFLATE_WAVE_PER_STREAM = 4
@@ -13,7 +15,8 @@ INFLATE_ONEBLOCK = 8             # ONEBLOCK=True build: stop at the end of the f
 
 STATUS_NAMES = {OK: "OK", E_SHORT_INPUT: "SHORT_INPUT", E_OUT_CAPACITY: "OUT_CAPACITY", E_BAD_BTYPE: "BAD_BTYPE",
                 E_BAD_DISTANCE: "BAD_DISTANCE", E_NO_EOF: "NO_EOF", E_DYNAMIC_UNSUPPORTED: "DYNAMIC_UNSUPPORTED",
-                E_BAD_SYMBOL: "BAD_SYMBOL", E_BAD_PARAM: "BAD_PARAM", E_HIP: "HIP_ERROR", E_BAD_TREE: "BAD_TREE"}
+                E_BAD_SYMBOL: "BAD_SYMBOL", E_BAD_PARAM: "BAD_PARAM", E_HIP: "HIP_ERROR", E_BAD_TREE: "BAD_TREE",
+                E_BAD_HEADER: "BAD_HEADER", E_BAD_CHECKSUM: "BAD_CHECKSUM"}
 
 # reference defaults (deflate.py:34-76)
 CWINDOW = 32

@@ -134,6 +134,8 @@ const char* hdlz_status_string(int s) {
         case HDLZ_E_BAD_PARAM: return "BAD_PARAM";
         case HDLZ_E_HIP: return "HIP_ERROR";
         case HDLZ_E_BAD_TREE: return "BAD_TREE";
+        case HDLZ_E_BAD_HEADER: return "BAD_HEADER";
+        case HDLZ_E_BAD_CHECKSUM: return "BAD_CHECKSUM";
         default: return "?";
     }
 }
@@ -201,7 +203,7 @@ bool par_applies(uint64_t nstreams, uint32_t in_len, uint32_t flags) {
 
 int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
                        uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
-                       uint32_t* d_out_len, uint32_t* d_status, const hdlz::Work& w, void* stream) {
+                       uint32_t* d_out_len, uint32_t* d_status, const hdlz::Work& w, void* stream, uint32_t* d_in_used = nullptr) {
     if (nstreams > 0x7FFFFFFFull * 32) return fail_param("nstreams too large for one launch");
     if (nstreams && (!d_in || !d_out || !d_out_len || !d_status)) return fail_param("null device pointer");
     if (flags & ~(HDLZ_INFLATE_ASSUME_FIXED | HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_ONEBLOCK |
@@ -221,7 +223,7 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
     if (rc != HDLZ_OK) return rc;
     if (nstreams == 0) return HDLZ_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hdlz::InflateArgs a{d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status};
+    hdlz::InflateArgs a{d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, d_in_used};
     // mapping: one LANE per stream (k_inflate_tok, 64 streams in lockstep per wave) needs ~10^5 streams to fill the GPU;
     // below HDLZ_INFLATE_WAVE_THRESHOLD streams one WAVE per stream (k_inflate_dyn, window decode) is faster, for any block type;
     // in between: 16 lanes per stream (k_inflate_grp) -- from HDLZ_INFLATE_GROUP_MIN streams on it beats a wave per stream,
@@ -281,6 +283,35 @@ int hdlz_inflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
     if (nstreams) { const int rc = refuse_capture(stream, "hdlz_inflate_batch_ws"); if (rc != HDLZ_OK) return rc; }
     const hdlz::Work w{nullptr, 0u, false};                  // scratch from the library's stream-ordered pool
     return inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, w, stream);
+}
+
+size_t hdlz_inflate_checked_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_pitch, uint32_t flags, int ragged) {
+    if (nstreams == 0) return 0;
+    return hdlz::judge_work_bytes(nstreams, out_pitch) + hdlz_inflate_work_bytes(nstreams, in_len, out_pitch, flags, ragged);
+}
+
+// The decode of hdlz_inflate_batch_ws with the end positions stored in d_in_used, then the judging pass behind it on the same stream
+// (every decode path has joined its side stream when it returns).  The judging pass's share of the scratch comes off the front.
+int hdlz_inflate_checked(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
+                         uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
+                         uint32_t* d_out_len, uint32_t* d_status, uint32_t* d_in_used, uint32_t* d_adler,
+                         void* d_work, size_t work_bytes, void* stream) {
+    if (!d_in_used) return fail_param("d_in_used is required");
+    if (flags & ~(HDLZ_INFLATE_ASSUME_FIXED | HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_ONEBLOCK |
+                  HDLZ_INFLATE_GROUP_PER_STREAM | HDLZ_INFLATE_ONE_FIXED_BLOCK))
+        return fail_param("unknown flag");
+    if (flags & HDLZ_INFLATE_ONEBLOCK) return fail_param("HDLZ_INFLATE_ONEBLOCK: a stream cut at its first block has no trailer behind it");
+    const size_t share = hdlz::judge_work_bytes(nstreams, out_pitch);
+    if (share != 0u && (!d_work || work_bytes < share)) return fail_param("d_work smaller than the judging pass's share (hdlz_inflate_checked_work_bytes - hdlz_inflate_work_bytes)");
+    uint8_t* wbase = static_cast<uint8_t*>(d_work);
+    const hdlz::Work w{wbase ? wbase + share : nullptr, wbase ? work_bytes - share : 0u, true};
+    const int rc = inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, w, stream, d_in_used);
+    if (rc != HDLZ_OK || nstreams == 0) return rc;
+    const hdlz::JudgeArgs j{d_in, d_in_off, in_pitch, in_len, nstreams, d_out, out_pitch, d_out_len, d_status, d_in_used, d_adler,
+                            share ? reinterpret_cast<uint2*>(wbase) : nullptr};
+    const hipError_t e = hdlz::launch_judge(j, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch the judging pass (k_adler_*)");
+    return HDLZ_OK;
 }
 
 int hdlz_compact_batch(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_off,

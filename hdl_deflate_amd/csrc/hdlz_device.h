@@ -34,6 +34,8 @@ struct InflateArgs {
     uint64_t out_pitch;
     uint32_t* out_len;
     uint32_t* status;
+    uint32_t* in_used = nullptr;   // nullable (hdlz_inflate_checked): per stream, the index of the first byte behind the last bit of the final
+                                   // block, counted from the stream's first byte; 0 for a stream whose decode fails.  Moves with out_len / status.
 };
 
 __host__ __device__ inline uint32_t out_bound(uint32_t n) {
@@ -86,6 +88,23 @@ hipError_t launch_inflate_tok_dyn(const InflateArgs& a, hipStream_t stream, bool
 hipError_t launch_inflate_par(const InflateArgs& a, hipStream_t stream, bool* used, const Work& w);
 hipError_t launch_inflate_dyn(const InflateArgs& a, hipStream_t stream, bool all, const uint32_t* few_n = nullptr, uint32_t lane_min = 0);
 hipError_t launch_inflate_dyn_flagged(const InflateArgs& a, hipStream_t stream);
+// the judging pass of hdlz_inflate_checked (hdlz_checksum.hip): behind a decode that stored in_used, on the same stream
+struct JudgeArgs {
+    const uint8_t* in;
+    const uint64_t* in_off;     // nullable, as in InflateArgs
+    uint64_t in_pitch;
+    uint32_t in_len;
+    uint64_t nstreams;
+    const uint8_t* out;
+    uint64_t out_pitch;
+    uint32_t* out_len;          // read; set to 0 for a stream that fails the judgement
+    uint32_t* status;           // read; the verdict
+    uint32_t* in_used;          // read: the decoder's end position; written: end + 4, or 0
+    uint32_t* adler;            // nullable
+    uint2* work;                // judge_work_bytes(nstreams, out_pitch) bytes (per-tile sums; null when that is 0)
+};
+size_t judge_work_bytes(uint64_t nstreams, uint64_t out_pitch);
+hipError_t launch_judge(const JudgeArgs& a, hipStream_t stream);
 size_t stream_work_bytes(uint32_t n, uint32_t nblocks);
 hipError_t launch_compress_streams(const uint8_t* in, uint64_t in_pitch, uint32_t n, uint32_t nblocks, int cwindow, int maxmatch,
                                    uint8_t* out, uint64_t out_pitch, uint32_t* out_len, uint32_t* status, void* work,

@@ -922,7 +922,8 @@ __device__ __forceinline__ void walk_node(const Args& a, const View& v, uint32_t
         if (nb > 0xFFFFFFFFull) { ok = false; break; }
         fin = f;
     }
-    if (lane == 0u) v.node[node_id] = Node{next, (uint32_t)nb, ok ? 1u : 0u, why};        // (obase of a failed node: why its walk failed -- read by k_any_rank if it is on the chain)
+    // (obase of a failed node: why its walk failed -- read by k_any_rank if it is on the chain; of a node that ends the stream: the bit behind it)
+    if (lane == 0u) v.node[node_id] = Node{next, (uint32_t)nb, ok ? 1u : 0u, ok && next == N_END ? ebit : why};
 }
 
 // the successors from the pseudo-node on: the true chain, the output position of every block on it, the total
@@ -975,6 +976,9 @@ __global__ __launch_bounds__(RANK_T) void k_any_rank(Args a) {
             atomicOr(&v.ctl[A_WHY], nl[2u * last] == N_BAD ? ((uint32_t)W_NODE | nl[2u * last + 1u]) : (uint32_t)W_CYCLE);
         }
     }
+    // where the stream ended: the walk of the chain's last node stopped behind the final block (read before the scan below re-uses obase)
+    uint32_t endbit = 0;
+    if (good && tid == 0u) { const uint32_t last = A[Lc - 1u]; endbit = v.node[last < n ? last : a.maxb].obase; }
     unsigned long long total = 0;
     if (good) {
         // output positions: an exclusive scan of the nodes' bytes along the chain (a contiguous run of positions per thread)
@@ -1007,6 +1011,7 @@ __global__ __launch_bounds__(RANK_T) void k_any_rank(Args a) {
     if (nx_items > a.maxx || ns_items > a.maxs) { good = false; atomicOr(&v.ctl[A_WHY], (uint32_t)W_ITEMS); }
     if (!good) { give_up(v); return; }
     v.ctl[C_TOTAL] = (uint32_t)total;
+    v.ctl[par::C_END] = (endbit + 7u) >> 3;
     v.ctl[C_NUSED] = a.nchunks + nx_items;
     v.ctl[C_FNUSED] = a.nchunks + nx_items;
     v.ctl[C_OK] = 1u;

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         }
         if (zn < 5u) {                              // R0/D0: the reference never starts (only reachable when this kernel is the first pass)
             if (STREAM) { if (lane == 0) { ist->status = HDLZ_E_SHORT_INPUT; ist->out_pos = 0; } return; }
-            if (lane == 0) { a.out_len[sid] = 0; a.status[sid] = HDLZ_E_SHORT_INPUT; }
+            if (lane == 0) { a.out_len[sid] = 0; a.status[sid] = HDLZ_E_SHORT_INPUT; if (a.in_used) a.in_used[sid] = 0; }
             continue;
         }
         const uint8_t* __restrict__ z = a.in + off;
@@ -661,6 +661,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         if (lane == 0) {
             a.out_len[sid] = status == HDLZ_OK ? o : 0u;
             a.status[sid] = status;
+            // where the stream ended (hdlz_inflate_checked): the bit reader stands behind the final block's last bit
+            if (a.in_used) a.in_used[sid] = status == HDLZ_OK ? (BITPOS() + 7u) >> 3 : 0u;
         }
         __syncthreads();
 #undef REFILL

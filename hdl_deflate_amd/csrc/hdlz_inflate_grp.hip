@@ -348,6 +348,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(InflateArgs a) {
 #else
     if (exists && l == 0u) { a.out_len[sid] = out_len; a.status[sid] = status; }
 #endif
+    // where the stream ended (hdlz_inflate_checked): a stream that is done takes no more input, ipq and bc stand behind the final block's last bit
+    if (a.in_used && exists && l == 0u) a.in_used[sid] = status == HDLZ_OK ? (8u * (ipq + 2u) - bc + 7u) >> 3 : 0u;
 }
 
 }  // namespace grp

@@ -17,6 +17,7 @@ constexpr uint32_t X_EOB = 0x40, X_BAD = 0x80;
 constexpr uint32_t SUB = 4;                   // sub-pieces per piece: the granularity of the real decode (k_par_tokens)
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 enum { C_FALLBACK = 0, C_NUSED = 1, C_TOTAL = 2, C_OK = 3, C_MARK = 4, C_FNUSED = 5, C_NCHAIN = 6, C_NCROSS = 36, C_FAILF = 37,
+       C_END = 38,             // where the stream ended: the first byte behind the final block's last bit (either chain, in its own control words)
        C_NOTFIXED = 7,         // the stream is not ONE fixed block: the gate of the chain for any block types (hdlz_inflate_any.hip)
        C_PASS0 = 8, C_ANY0 = 40 /* .. 63: that chain's own counters */, C_WORDS = 64 };
 
@@ -29,6 +30,7 @@ struct ParArgs {
     uint32_t srcn;              // entries of srcA
     uint32_t* out_len;
     uint32_t* status;
+    uint32_t* in_used;          // nullable: InflateArgs::in_used (k_par_finish stores it with out_len)
     uint32_t nchunks;
     uint32_t chbits;            // bits per piece
     uint32_t* ctl;              // C_WORDS control words (zeroed)
@@ -80,7 +82,7 @@ __host__ inline uint32_t grid_cap(uint64_t work, uint32_t nstr) {
 __host__ inline uint32_t passes_for(uint32_t nitems) {                 // chains of up to `nitems` hops, HOPS-fold shorter per pass
     uint32_t passes = 1;
     for (uint64_t reach = 1; reach < (uint64_t)nitems + 1u; reach *= HOPS) passes++;
-    return passes > (uint32_t)(C_ANY0 - C_PASS0) ? (uint32_t)(C_ANY0 - C_PASS0) : passes;       // (a counter per pass: control words C_PASS0 .. C_ANY0 - 1)
+    return passes > (uint32_t)(C_NCROSS - C_PASS0) ? (uint32_t)(C_NCROSS - C_PASS0) : passes;   // (a counter per pass: control words C_PASS0 .. C_NCROSS - 1)
 }
 
 // The scratch of one stream: arrays one behind the other, each aligned to 256 bytes (so the whole is a multiple of 256, and every

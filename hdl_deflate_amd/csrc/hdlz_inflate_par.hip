@@ -72,6 +72,7 @@ __device__ __forceinline__ ParArgs of_stream(ParArgs a) {
     a.out += (uint64_t)s * a.out_pitch;
     a.out_len += s;
     a.status += s;
+    if (a.in_used) a.in_used += s;
     const size_t d = (size_t)s * a.ws_stride;
     shift_ptr(a.ctl, d); shift_ptr(a.exit8, d); shift_ptr(a.nb32, d); shift_ptr(a.entry8, d); shift_ptr(a.opos, d);
     shift_ptr(a.gexit8, d); shift_ptr(a.gstop8, d); shift_ptr(a.gnb32, d); shift_ptr(a.gentry8, d); shift_ptr(a.gopos, d);
@@ -600,6 +601,7 @@ __global__ __launch_bounds__(256) void k_par_ends(ParArgs a_) {
         const uint32_t fm = a.ctl[C_FAILF], failmin = fm ? ~fm : NONE;          // the lowest sub-piece with a failed check
         if (failmin < f_end || a.nfail[f_end] < n_end || total > a.cap || total > a.srcn) { a.ctl[C_FALLBACK] = 1u; return; }
         a.ctl[C_TOTAL] = total;
+        a.ctl[C_END] = (cr[0] + 7u + 7u) >> 3;          // (cr[0]: the first bit of the end-of-block code, 7 bits in a fixed block)
         a.ctl[C_NUSED] = f_end / a.sub + 1u;
         a.ctl[C_FNUSED] = f_end + 1u;
         a.ntok[f_end] = n_end;
@@ -842,16 +844,16 @@ __global__ __launch_bounds__(64) void k_par_finish(ParArgs a_, uint32_t passes, 
     if (threadIdx.x != 0) return;
     const uint32_t left = a.ctl[C_MARK] == 0u ? 0u : a.ctl[C_PASS0 + passes - 1u];
     bool ok = a.ctl[C_FALLBACK] == 0u && left == 0u;
-    uint32_t total = a.ctl[C_TOTAL];
+    uint32_t total = a.ctl[C_TOTAL], end = a.ctl[C_END];
     // (the other chain's result: the stream was its from the first header on, or it opened for a short fixed block in front of other types)
     if (!ok && actl) {
         actl = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(actl) + (size_t)blockIdx.y * a_.ws_stride);
         const uint32_t aleft = actl[C_MARK] == 0u ? 0u : actl[C_PASS0 + apasses - 1u];
         ok = actl[C_FALLBACK] == 0u && actl[C_OK] != 0u && aleft == 0u;
-        total = actl[C_TOTAL];
+        total = actl[C_TOTAL]; end = actl[C_END];
     }
-    if (ok) { a.out_len[0] = total; a.status[0] = HDLZ_OK; }
-    else if (a.batch) { a.out_len[0] = 0u; a.status[0] = HDLZ_E_DYNAMIC_UNSUPPORTED; }      // several streams: the serial pass redoes the flagged ones
+    if (ok) { a.out_len[0] = total; a.status[0] = HDLZ_OK; if (a.in_used) a.in_used[0] = end; }
+    else if (a.batch) { a.out_len[0] = 0u; a.status[0] = HDLZ_E_DYNAMIC_UNSUPPORTED; if (a.in_used) a.in_used[0] = 0u; }      // several streams: the serial pass redoes the flagged ones
     a.ctl[C_OK] = ok ? 1u : 0u;
 }
 
@@ -940,7 +942,7 @@ static Layout layout_of(uint32_t zn, uint32_t nstr, uint64_t out_pitch, uint32_t
 // the kernels' arguments for the streams of `a` laid out as L (in their scratch): the pieces'
 static ParArgs args_of(const Layout& L, const InflateArgs& a) {
     ParArgs p = L.p;
-    p.z = a.in; p.zn = a.in_len; p.flags = a.flags; p.obsize = a.obsize; p.out = a.out; p.out_len = a.out_len; p.status = a.status;
+    p.z = a.in; p.zn = a.in_len; p.flags = a.flags; p.obsize = a.obsize; p.out = a.out; p.out_len = a.out_len; p.status = a.status; p.in_used = a.in_used;
     p.in_pitch = a.in_pitch; p.out_pitch = a.out_pitch; p.in_off = a.in_off; p.ws_stride = L.stride; p.batch = a.nstreams > 1u ? 1u : 0u;
     return p;
 }
@@ -1097,6 +1099,7 @@ hipError_t launch_inflate_par(const InflateArgs& a, hipStream_t stream, bool* us
         g.out = a.out + (uint64_t)s0 * a.out_pitch;
         g.out_len = a.out_len + s0;
         g.status = a.status + s0;
+        if (a.in_used) g.in_used = a.in_used + s0;
         g.nstreams = nstr - s0 < gs ? nstr - s0 : gs;
         bool u = false;
         hipError_t e = launch_group(g, nstr, budget, stream, w, &u);

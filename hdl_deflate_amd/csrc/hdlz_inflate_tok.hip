@@ -68,7 +68,7 @@ constexpr uint32_t MOVES = 3;              // move iterations (up to 4 bytes per
 #define TOK_TIME(k) do { const uint64_t t_ = __builtin_readcyclecounter(); tacc[k] += t_ - tlast; tlast = t_; } while (0)
 #define TOK_TIME_ROUND() tacc[7] += 1u
 #define TOK_STORE_RESULT() do { TOK_TIME(4);       /* -DHDLZ_TOK_TIMING=1: the DYN = false kernel reports, =2: the DYN = true kernels */ \
-        if (DYN != (HDLZ_TOK_TIMING == 2)) { if (exists) { a.out_len[sid] = out_len; a.status[sid] = status; } }  \
+        if (DYN != (HDLZ_TOK_TIMING == 2)) { if (exists) { a.out_len[sid] = out_len; a.status[sid] = status; TOK_STORE_END(); } }  \
         else if (exists) { uint64_t v_ = 0;          /* by GRID lane; lanes >= 8 report 0 */                          \
         _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++) v_ = lane == (uint32_t)k_ ? tacc[k_] : v_;             \
         a.out_len[gid] = (uint32_t)v_; a.status[gid] = (uint32_t)(v_ >> 32); } } while (0)
@@ -76,8 +76,11 @@ constexpr uint32_t MOVES = 3;              // move iterations (up to 4 bytes per
 #define TOK_TIME_DECL() do {} while (0)
 #define TOK_TIME(k) do {} while (0)
 #define TOK_TIME_ROUND() do {} while (0)
-#define TOK_STORE_RESULT() do { if (exists) { a.out_len[sid] = out_len; a.status[sid] = status; } } while (0)
+#define TOK_STORE_RESULT() do { if (exists) { a.out_len[sid] = out_len; a.status[sid] = status; TOK_STORE_END(); } } while (0)
 #endif
+// where the stream ended (hdlz_inflate_checked; a.in_used is null otherwise): a lane that is done takes no more input -- every refill and
+// every decode step asks for `active` --, so ip and bc still stand where the final block's last bit left them
+#define TOK_STORE_END() do { if (a.in_used) a.in_used[sid] = status == HDLZ_OK ? (8u * ip - bc + 7u) >> 3 : 0u; } while (0)
 
 // DYN: per-lane tables in LDS, rows of 64 dwords (row j of lane l = dword j * 64 + l: every lane stays in its own bank): only the
 // literal/length symbols, sorted by (code length, value) -- CAP low bytes and CAP ninth bits.  Everything else a lane needs of its

@@ -143,6 +143,33 @@ class Engine(object):
         self._check(rc, "hdlz_inflate_batch_ws")
         return out, out_len, status
 
+    # -- STARTD for a batch, verified: zlib header, Adler-32 trailer, bytes consumed
+    @_on_device
+    def inflate_checked(self, d_in, in_off=None, in_len=None, nblocks=None, out_pitch=None, flags=0, obsize=0,
+                        out=None, work=None):
+        """inflate_batch through hdlz_inflate_checked: the same decode, then every stream is judged -- E_BAD_HEADER, E_BAD_CHECKSUM, or
+        E_NO_EOF for a cut trailer, with out_len 0 -- and reports the bytes it consumed (zlib's len - len(unused_data)) and the Adler-32
+        of its output.  `work`: as inflate_batch, sized by hdlz_inflate_checked_work_bytes (the judging pass takes its share off the front).
+        -> (out uint8[B, out_pitch], out_len int32[B], status int32[B], in_used int32[B], adler int32[B]: the 32 bits of the checksum)."""
+        off_ptr, pitch, ilen, nb = self._prep(d_in, in_off, in_len, nblocks)
+        assert out_pitch is not None and out_pitch % 4 == 0
+        if out is None:
+            out = torch.empty((nb, out_pitch), dtype=torch.uint8, device=d_in.device)
+        out_len = torch.empty(nb, dtype=torch.int32, device=d_in.device)
+        status = torch.empty(nb, dtype=torch.int32, device=d_in.device)
+        in_used = torch.empty(nb, dtype=torch.int32, device=d_in.device)
+        adler = torch.empty(nb, dtype=torch.int32, device=d_in.device)
+        if work is None:
+            work = torch.empty(self.lib.hdlz_inflate_checked_work_bytes(nb, ilen, out_pitch, flags, 0 if in_off is None else 1),
+                               dtype=torch.uint8, device=d_in.device)
+        assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
+        rc = self.lib.hdlz_inflate_checked(d_in.data_ptr(), off_ptr, pitch, ilen, nb, flags, obsize,
+                                           out.data_ptr(), out_pitch, out_len.data_ptr(), status.data_ptr(),
+                                           in_used.data_ptr(), adler.data_ptr(),
+                                           work.data_ptr() if work.numel() else None, work.numel(), self._stream())
+        self._check(rc, "hdlz_inflate_checked")
+        return out, out_len, status, in_used, adler
+
     # -- archive compaction (SURVEY 8(f) rank 2)
     @_on_device
     def compact(self, rows, lens, offsets=None, archive=None):
@@ -429,8 +456,8 @@ class Engine(object):
         return st, bytes(out[0, :int(ol.item())].cpu().numpy().tobytes())
 
     @_on_device
-    def inflate_bytes(self, z, out_cap=None, flags=0, obsize=0):
-        """-> (status, bytes).  Default capacity: deflate expands at most 1032:1 (a 258-byte match costs 2 bits), so
+    def inflate_bytes(self, z, out_cap=None, flags=0, obsize=0, verify=False):
+        """-> (status, bytes); verify=True: through the checked call (header, Adler-32, trailer present).  Default capacity: deflate expands at most 1032:1 (a 258-byte match costs 2 bits), so
         1032 n + 258 bytes hold any stream, capped at the reference's 2^LMAX counter range (deflate.py:73-76)."""
         n = len(z)
         pad = (n + 15) // 16 * 16 + 16
@@ -442,7 +469,10 @@ class Engine(object):
         cap = (cap + 15) // 16 * 16
         if n >= 5 and (z[2] & 7) == 3:           # the bytes are here: BFINAL = 1, BTYPE = 01 -- a single fixed block takes that chain only
             flags |= INFLATE_ONE_FIXED_BLOCK
-        out, ol, st = self.inflate_batch(d, in_len=n, out_pitch=cap, flags=flags, obsize=obsize)
+        if verify:
+            out, ol, st = self.inflate_checked(d, in_len=n, out_pitch=cap, flags=flags, obsize=obsize)[:3]
+        else:
+            out, ol, st = self.inflate_batch(d, in_len=n, out_pitch=cap, flags=flags, obsize=obsize)
         st = int(st.item())
         return st, bytes(out[0, :int(ol.item())].cpu().numpy().tobytes())
 

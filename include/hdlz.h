@@ -67,6 +67,9 @@ enum {
     HDLZ_E_BAD_TREE = 10            /* dynamic block header does not describe a valid prefix code (the reference
                                        builds garbage tables there, deflate.py:1204-1400; zlib's rules are used) */
 };
+/* ... and the two verdicts only hdlz_inflate_checked gives (the reference verifies neither, so no other call returns them) */
+#define HDLZ_E_BAD_HEADER   11   /* checked call: CMF/FLG is not a zlib header this library reads */
+#define HDLZ_E_BAD_CHECKSUM 12   /* checked call: Adler-32 of the output != the stream's trailer   */
 
 /* ---- inflate flags (semantics) */
 #define HDLZ_INFLATE_ASSUME_FIXED 1u     /* DYNAMIC=False build: every block is decoded as BTYPE=1 (deflate.py:724-732) */
@@ -161,6 +164,45 @@ int hdlz_inflate_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_
 int hdlz_inflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
                        uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
                        uint32_t* d_out_len, uint32_t* d_status, void* stream);
+
+/*
+ * STARTD with the checks the reference leaves out: hdlz_inflate_checked decodes exactly as hdlz_inflate_batch_ws does with the same
+ * arguments (same mapping choice, same hints, same obsize / HDLZ_INFLATE_ASSUME_FIXED semantics) and then JUDGES every stream whose decode
+ * succeeded, in a pass of its own behind the decode (it reads every output byte once more).  With end = the index of the first byte behind
+ * the last bit of the final block (rounded up to a byte), counted from the stream's first byte, and len = the stream's length
+ * (in_off[b+1] - in_off[b], or in_len), in this order of precedence:
+ *   the decode fails                                  d_status[b] = the decoder's status, as in hdlz_inflate_batch_ws;
+ *                                                     d_out_len[b] = d_in_used[b] = d_adler[b] = 0
+ *   end + 4 > len (the trailer is cut)                HDLZ_E_NO_EOF; d_out_len[b] = d_in_used[b] = d_adler[b] = 0
+ *                                                     (the reference's own "4 trailer bytes" test lets a stream that lost its last byte pass)
+ *   CMF & 15 != 8, CMF >> 4 > 7, (CMF * 256 + FLG) % 31 != 0 or FDICT (FLG & 0x20) set
+ *                                                     HDLZ_E_BAD_HEADER; d_out_len[b] = 0, d_in_used[b] = end + 4, d_adler[b] = computed
+ *   the big-endian word at [end, end + 4) != Adler-32 of the d_out_len[b] decoded bytes
+ *                                                     HDLZ_E_BAD_CHECKSUM; d_out_len[b] = 0, d_in_used[b] = end + 4, d_adler[b] = computed
+ *   otherwise                                         HDLZ_OK; d_out_len[b] = n, d_in_used[b] = end + 4, d_adler[b] = computed (= the trailer)
+ * d_in_used of an OK stream is what zlib reports as consumed (len - len(unused_data)): bytes behind it are no error -- slack of a pitched
+ * row, the next member, other data.  NLEN of a stored block is NOT compared with LEN (the reference does not, D2): a damaged LEN changes
+ * the output and is caught by the checksum, a damaged NLEN changes nothing.
+ * d_in_used is REQUIRED, d_adler may be NULL.  Parameter errors beyond those of hdlz_inflate_batch_ws (HDLZ_E_BAD_PARAM before the device is
+ * looked at): d_in_used == NULL; HDLZ_INFLATE_ONEBLOCK (a stream cut at its first block has no trailer behind it); work_bytes below the
+ * judging pass's own share of the scratch.  That share is hdlz_inflate_checked_work_bytes(..) - hdlz_inflate_work_bytes(..) for the same
+ * arguments -- 0 for rows below 64 KiB, else 8 bytes per 32 KiB of row capacity (per-tile partial sums), rounded up to 256 -- and is taken
+ * from the FRONT of d_work; what is left goes to the decode, with hdlz_inflate_batch_ws's rule that less scratch means a mapping that
+ * needs less and the same results.  Nothing is allocated; every launch is capturable; only this form exists (no pool-scratch sibling).
+ * writes: as hdlz_inflate_batch_ws, plus d_in_used[0 .. nstreams) and, when given, d_adler[0 .. nstreams).  The row of a stream that fails
+ *         the judgement keeps its decoded bytes (a failed row may hold anything inside the row).
+ * reads:  the bytes of the streams themselves, as hdlz_inflate_batch_ws; the judging pass LOADS row b up to d_out_len[b] rounded up to 4
+ *         (whole 16-byte loads below d_out_len[b] when d_out and out_pitch are multiples of 16, dwords otherwise and for the last partial
+ *         16 bytes; a caller may assume no more than "rounded up to 16, never beyond the row"); bytes at or behind d_out_len[b] never
+ *         reach a result -- nor do the initial contents of d_in_used and d_adler.
+ */
+size_t hdlz_inflate_checked_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_pitch, uint32_t flags, int ragged);
+int hdlz_inflate_checked(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
+                         uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
+                         uint32_t* d_out_len, uint32_t* d_status,
+                         uint32_t* d_in_used,   /* required */
+                         uint32_t* d_adler,     /* nullable */
+                         void* d_work, size_t work_bytes, void* stream);
 
 /*
  * Archive compaction (no reference counterpart -- the reference drains its output
