@@ -2,16 +2,51 @@
 Python or CPU implementation to fall back to."""
 import ctypes
 import os
+from ctypes import c_char_p as cs, c_int as ci, c_size_t as sz, c_uint32 as u32, c_uint64 as u64, c_void_p as vp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HDLZ_LIB") or os.path.join(_HERE, "lib", "libhdlz.so")   # HDLZ_LIB: A/B builds
-EXPORTS = ("hdlz_version", "hdlz_status_string", "hdlz_last_error", "hdlz_device_count", "hdlz_out_bound",
-           "hdlz_compress_batch", "hdlz_inflate_batch", "hdlz_compact_batch", "hdlz_archive_batch",
-           "hdlz_stream_work_bytes", "hdlz_compress_stream", "hdlz_streams_work_bytes", "hdlz_compress_streams",
-           "hdlz_compress_chunk", "hdlz_inflate_chunk", "hdlz_release_scratch",
-           "hdlz_inflate_work_bytes", "hdlz_inflate_batch_ws", "hdlz_archive_work_bytes", "hdlz_archive_batch_ws",
-           "hdlz_inflate_checked_work_bytes", "hdlz_inflate_checked")
+_BATCH_IN = [vp, vp, u64, u32, u64]                   # d_in, d_in_off, in_pitch, in_len, nblocks
+_INFLATE = _BATCH_IN + [u32, u32, vp, u64, vp, vp]    # ... flags, obsize, d_out, out_pitch, d_out_len, d_status
+# name -> (restype, argtypes): every entry point of include/hdlz.h (tests/test_cabi_load.py holds the counts to the header)
+SIGNATURES = {
+    "hdlz_version": (ci, []),
+    "hdlz_status_string": (cs, [ci]),
+    "hdlz_last_error": (cs, []),
+    "hdlz_device_count": (ci, []),
+    "hdlz_out_bound": (sz, [sz]),
+    "hdlz_release_scratch": (ci, []),
+    "hdlz_compress_batch": (ci, _BATCH_IN + [ci, ci, vp, u64, vp, vp, vp]),
+    "hdlz_inflate_work_bytes": (sz, [u64, u32, u64, u32, ci]),
+    "hdlz_inflate_batch_ws": (ci, _INFLATE + [vp, sz, vp]),
+    "hdlz_inflate_batch": (ci, _INFLATE + [vp]),
+    "hdlz_inflate_checked_work_bytes": (sz, [u64, u32, u64, u32, ci]),
+    "hdlz_inflate_checked": (ci, _INFLATE + [vp, vp, vp, sz, vp]),
+    "hdlz_compact_batch": (ci, [vp, u64, vp, vp, u64, vp, vp]),
+    "hdlz_archive_work_bytes": (sz, [u64]),
+    "hdlz_archive_batch_ws": (ci, [vp, u64, vp, u64, vp, u64, vp, vp, sz, vp]),
+    "hdlz_archive_batch": (ci, [vp, u64, vp, u64, vp, u64, vp, vp]),
+    "hdlz_stream_work_bytes": (sz, [sz]),
+    "hdlz_streams_work_bytes": (sz, [sz, u64]),
+    "hdlz_compress_streams": (ci, [vp, u64, u32, u64, ci, ci, vp, u64, vp, vp, vp, sz, vp]),
+    "hdlz_compress_stream": (ci, [vp, u32, ci, ci, vp, u64, vp, vp, vp, sz, vp]),
+    "hdlz_compress_chunk": (ci, [vp, u32, u32, ci, ci, ci, vp, u64, vp, vp]),
+    "hdlz_inflate_chunk": (ci, [vp, u32, ci, u32, u32, vp, u64, u32, vp, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 _lib = None
+
+
+class CState(ctypes.Structure):
+    """hdlz_cstate: the session of hdlz_compress_chunk (64 bytes)"""
+    _fields_ = [(f, u32) for f in ("pos", "skip", "out_words", "base_bits", "carry_word", "adler_a", "adler_c", "started",
+                                   "done", "out_len", "status")] + [("reserved", u32 * 5)]
+
+
+class IState(ctypes.Structure):
+    """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
+    _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
+                                   "done", "status", "need")] + [("reserved", u32 * 4), ("lengths", ctypes.c_uint8 * 320)]
 
 
 def load():
@@ -26,46 +61,8 @@ def load():
     # two HIP runtimes in one process and torch's streams/pointers would be foreign to ours.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    vp, u64, u32, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-    L.hdlz_version.restype = ci
-    L.hdlz_status_string.restype = ctypes.c_char_p
-    L.hdlz_status_string.argtypes = [ci]
-    L.hdlz_last_error.restype = ctypes.c_char_p
-    L.hdlz_device_count.restype = ci
-    L.hdlz_out_bound.restype = ctypes.c_size_t
-    L.hdlz_out_bound.argtypes = [ctypes.c_size_t]
-    L.hdlz_compress_batch.restype = ci
-    L.hdlz_compress_batch.argtypes = [vp, vp, u64, u32, u64, ci, ci, vp, u64, vp, vp, vp]
-    L.hdlz_inflate_batch.restype = ci
-    L.hdlz_inflate_batch.argtypes = [vp, vp, u64, u32, u64, u32, u32, vp, u64, vp, vp, vp]
-    L.hdlz_compact_batch.restype = ci
-    L.hdlz_compact_batch.argtypes = [vp, u64, vp, vp, u64, vp, vp]
-    L.hdlz_archive_batch.restype = ci
-    L.hdlz_archive_batch.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp]
-    L.hdlz_stream_work_bytes.restype = ctypes.c_size_t
-    L.hdlz_stream_work_bytes.argtypes = [ctypes.c_size_t]
-    L.hdlz_compress_stream.restype = ci
-    L.hdlz_compress_stream.argtypes = [vp, u32, ci, ci, vp, u64, vp, vp, vp, ctypes.c_size_t, vp]
-    L.hdlz_streams_work_bytes.restype = ctypes.c_size_t
-    L.hdlz_streams_work_bytes.argtypes = [ctypes.c_size_t, u64]
-    L.hdlz_compress_streams.restype = ci
-    L.hdlz_compress_streams.argtypes = [vp, u64, u32, u64, ci, ci, vp, u64, vp, vp, vp, ctypes.c_size_t, vp]
-    L.hdlz_compress_chunk.restype = ci
-    L.hdlz_compress_chunk.argtypes = [vp, u32, u32, ci, ci, ci, vp, u64, vp, vp]
-    L.hdlz_inflate_chunk.restype = ci
-    L.hdlz_inflate_chunk.argtypes = [vp, u32, ci, u32, u32, vp, u64, u32, vp, vp]
-    L.hdlz_release_scratch.restype = ci
-    L.hdlz_inflate_work_bytes.restype = ctypes.c_size_t
-    L.hdlz_inflate_work_bytes.argtypes = [u64, u32, u64, u32, ci]
-    L.hdlz_inflate_batch_ws.restype = ci
-    L.hdlz_inflate_batch_ws.argtypes = [vp, vp, u64, u32, u64, u32, u32, vp, u64, vp, vp, vp, ctypes.c_size_t, vp]
-    L.hdlz_inflate_checked_work_bytes.restype = ctypes.c_size_t
-    L.hdlz_inflate_checked_work_bytes.argtypes = [u64, u32, u64, u32, ci]
-    L.hdlz_inflate_checked.restype = ci
-    L.hdlz_inflate_checked.argtypes = [vp, vp, u64, u32, u64, u32, u32, vp, u64, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.hdlz_archive_work_bytes.restype = ctypes.c_size_t
-    L.hdlz_archive_work_bytes.argtypes = [u64]
-    L.hdlz_archive_batch_ws.restype = ci
-    L.hdlz_archive_batch_ws.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp, ctypes.c_size_t, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L

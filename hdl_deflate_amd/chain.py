@@ -46,13 +46,7 @@ def compress_chained(engine, d_in, block=8 << 20, cwindow=32, maxmatch=10):
         lens.append(ol)
     pitch = pitch_for(block)
     for off, ln in plan[nfull:]:                            # at most two shorter blocks at the end
-        piece = torch.zeros((ln + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
-        piece[:ln] = d_in[off:off + ln]
-        if ln >= engine.STREAM_MIN:
-            o, ol, st = engine.compress_stream(piece, ln, cwindow=cwindow, maxmatch=maxmatch)
-        else:
-            o, ol, st = engine.compress_batch(piece.view(1, -1), in_len=ln, cwindow=cwindow, maxmatch=maxmatch)
-            o = o[0]
+        o, ol, st = engine._compress_one(engine._stage(d_in[off:off + ln]), ln, cwindow, maxmatch)
         if int(st.item()) != OK:
             raise Error("compress_chained: the tail block failed")
         row = torch.zeros((1, pitch), dtype=torch.uint8, device=dev)

@@ -29,6 +29,12 @@ def out_bound(n):
     return 6 + (9 * n + 10 + 7) // 8
 
 
+def inflate_cap(n, lmax=LMAX):
+    """default output capacity for a stream of n bytes: deflate expands at most 1032:1 (a 258-byte match costs 2 bits), capped at
+    the reference's 2^LMAX counter range (deflate.py:73-76)"""
+    return min(1 << lmax, max(1 << 16, 1032 * n + 258))
+
+
 def pitch_for(n, align=16):
     """an out_pitch >= out_bound(n) rounded up to `align` bytes"""
     b = out_bound(n)

@@ -39,7 +39,7 @@ Protocol facts honoured in both modes:
   * o_done rises only when all output is readable; final o_oprogress = output length (deflate.py:814);
   * where the reference raises myhdl.Error (or hangs: N < 5), cycle() raises hdl_deflate_amd.Error.
 """
-from .constants import IDLE, WRITE, STARTC, STARTD, OK, CWINDOW, MAXMATCH, LMAX
+from .constants import IDLE, WRITE, STARTC, STARTD, OK, E_SHORT_INPUT, E_OUT_CAPACITY, CWINDOW, MAXMATCH, LMAX, inflate_cap
 from .errors import HdlzStatusError, HdlzRangeError
 
 
@@ -202,17 +202,14 @@ class DeflatePort(object):
             what = "STARTC"
         else:
             # a stream may expand 1032:1; the counters are LMAX bits wide (deflate.py:73-76)
-            st, res = self.engine.inflate_bytes(data, flags=self.inflate_flags, obsize=self.obsize,
-                                                out_cap=min(1 << self.lmax, max(1 << 16, 1032 * n + 258)))
+            st, res = self.engine.inflate_bytes(data, flags=self.inflate_flags, obsize=self.obsize, out_cap=inflate_cap(n, self.lmax))
             what = "STARTD"
-            if st == 2 and 1032 * n + 258 > (1 << self.lmax):      # E_OUT_CAPACITY at the counter range
+            if st == E_OUT_CAPACITY and 1032 * n + 258 > (1 << self.lmax):      # ... at the counter range
                 self.state = self.ST_IDLE
                 raise HdlzRangeError("STARTD: output does not fit the %d-bit progress counters (deflate.py:73-76)" % self.lmax)
         self.state = self.ST_IDLE
         if st != OK:
-            # the reference raises myhdl.Error from inside Simulation.run (or never finishes)
-            self._set(self.o_done, True)
-            raise HdlzStatusError(st, what)
+            self._fail(st, what)
         if len(res) > self.mask:
             raise HdlzRangeError("%s: %d output bytes do not fit the %d-bit progress counters (deflate.py:73-76)"
                                  % (what, len(res), self.lmax))
@@ -276,6 +273,12 @@ class DeflatePort(object):
         else:
             self._step_inflate(s, ra, room)
 
+    def _fail(self, st, what):
+        """the reference raises myhdl.Error from inside Simulation.run (or never finishes)"""
+        self.state = self.ST_IDLE
+        self._set(self.o_done, True)
+        raise HdlzStatusError(st, what)
+
     def _publish(self, produced, done, what):
         """new output bytes [len(oram), produced) become readable"""
         if produced > self.mask:
@@ -295,9 +298,7 @@ class DeflatePort(object):
         pending = s.n - s.pos
         if self.ended:
             if s.n < 5:                                  # R0: the reference never starts (deflate.py:429-431) -- it hangs; we say so
-                self.state = self.ST_IDLE
-                self._set(self.o_done, True)
-                raise HdlzStatusError(1, "STARTC")
+                self._fail(E_SHORT_INPUT, "STARTC")
             if pending <= bound:
                 st = s.step(final=True)                  # everything that is left, EOB and the trailer fit
             elif fit >= 32 and s.encodable() >= 32:
@@ -310,9 +311,7 @@ class DeflatePort(object):
             st = s.step(max_positions=min(fit, self.window))
         self.launches += 1
         if st != OK:
-            self.state = self.ST_IDLE
-            self._set(self.o_done, True)
-            raise HdlzStatusError(st, "STARTC")
+            self._fail(st, "STARTC")
         self._publish(s.out_len, s.done, "STARTC")
 
     def _step_inflate(self, s, ra, room):
@@ -328,9 +327,7 @@ class DeflatePort(object):
         st = s.step(final=self.ended, out_limit=ra + self.stream_obsize)
         self.launches += 1
         if st != OK:
-            self.state = self.ST_IDLE
-            self._set(self.o_done, True)
-            raise HdlzStatusError(st, "STARTD")
+            self._fail(st, "STARTD")
         self._publish(s.out_pos, s.done, "STARTD")
 
     @staticmethod

@@ -7,10 +7,13 @@ import re
 from conftest import REPO
 
 
-def _declared():
+def _header():
     src = open(os.path.join(REPO, "include", "hdlz.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _declared():
+    return sorted(set(re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(", _header())))
 
 
 def test_library_exports_every_declared_symbol():
@@ -20,6 +23,51 @@ def test_library_exports_every_declared_symbol():
     L = ctypes.CDLL(_lib.LIB_PATH)
     for n in names:
         assert hasattr(L, n), n
+
+
+def test_signature_table_matches_the_header():
+    """every entry point has a restype and an argtypes list as long as its declaration's parameter list ((void) = 0), and load()
+    puts exactly those on the library's functions"""
+    from hdl_deflate_amd import _lib
+    params = {name: 0 if args.strip() == "void" else args.count(",") + 1
+              for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", _header())}
+    assert len(params) == 22 and sorted(params) == sorted(_lib.EXPORTS) == sorted(_lib.SIGNATURES)
+    assert sorted(set(params.values())) == [0, 1, 2, 5, 7, 8, 10, 11, 12, 13, 14, 16]
+    L = _lib.load()
+    for name in _lib.EXPORTS:
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is not None and isinstance(argtypes, list) and len(argtypes) == params[name], name
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    for name in ("hdlz_version", "hdlz_last_error", "hdlz_device_count", "hdlz_release_scratch"):
+        assert params[name] == 0 and _lib.SIGNATURES[name][1] == []
+
+
+def _struct_members(name):
+    """[(member, array length or None)] and the byte size of `typedef struct <name> { ... }` (uint32_t / uint8_t members; one line
+    may declare several: `uint32_t nlen, ndist;`)"""
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), _header(), flags=re.S).group(1)
+    members, size = [], 0
+    for ctype, decls in re.findall(r"\b(uint32_t|uint8_t)\s+([^;]+);", body):
+        for d in decls.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", d)
+            members.append((m.group(1), int(m.group(2)) if m.group(2) else None))
+            size += (4 if ctype == "uint32_t" else 1) * int(m.group(2) or 1)
+    return members, size
+
+
+def test_state_structs_mirror_the_header():
+    """CState / IState: the header's member names in the header's order, arrays of the header's lengths, 64 and 384 bytes (the sizes
+    the header's comments state) -- the sessions read the state by these names"""
+    from hdl_deflate_amd import _lib
+    for cls, name, size in ((_lib.CState, "hdlz_cstate", 64), (_lib.IState, "hdlz_istate", 384)):
+        members, hsize = _struct_members(name)
+        assert [f[0] for f in cls._fields_] == [m[0] for m in members], name
+        assert [getattr(f[1], "_length_", None) for f in cls._fields_] == [m[1] for m in members], name
+        assert ctypes.sizeof(cls) == hsize == size, name
+    assert [m for m in _struct_members("hdlz_cstate")[0] if m[1]] == [("reserved", 5)]
+    assert [m for m in _struct_members("hdlz_istate")[0] if m[1]] == [("reserved", 4), ("lengths", 320)]
+    assert _lib.IState.status.offset == 40 and _lib.CState.status.offset == 40 and _lib.IState.lengths.offset == 64
 
 
 def test_version_bound_and_strings():

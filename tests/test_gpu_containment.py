@@ -28,6 +28,7 @@ import pytest
 import torch
 
 import guards
+from hdl_deflate_amd._lib import CState, IState
 
 pytestmark = pytest.mark.gpu
 
@@ -367,8 +368,8 @@ def test_compress_chunk_state_and_output_slack(engine, oracle):
 
             a, clean, runs = two_runs(specs, setup, call, ("out", "state"))
             for r in runs:
-                st = r["state"].view(np.uint32)
-                assert (st[0], st[8], st[9], st[10]) == (n, 1, len(ref), 0), (n, step, st[:11])
+                st = CState.from_buffer_copy(r["state"])
+                assert (st.pos, st.done, st.out_len, st.status) == (n, 1, len(ref), 0), (n, step, r["state"].view(np.uint32)[:11])
                 assert r["out"][:len(ref)].tobytes() == ref, (n, step)
             assert np.array_equal(runs[0]["state"], runs[1]["state"]), (n, step)
             assert guards.violations(a, clean, {"out": EXTENT_WORD(len(ref)), "state": True}) == [], (n, step)
@@ -649,21 +650,21 @@ def test_inflate_chunk_exact_capacity_and_state(engine, oracle):
                     limit = min(cap, limit + step)
                     assert L.hdlz_inflate_chunk(a.ptr("in"), len(zz), 1, 0, 0, a.ptr("out"), cap, limit, a.ptr("state"), stream_ptr()) == 0
                     if step > 1 or limit == cap:
-                        st = a.view("state")[:48].cpu().numpy().view(np.uint32)
-                        assert st[1] <= limit
-                        if st[9] or st[10]:
+                        st = IState.from_buffer_copy(a.view("state").cpu().numpy())
+                        assert st.out_pos <= limit
+                        if st.done or st.status:
                             break
                 seen.append(limit)
 
             a, clean, runs = two_runs(specs, setup, call, ("out", "state"))
             for k in runs:
-                st = k["state"].view(np.uint32)
+                st, words = IState.from_buffer_copy(k["state"]), k["state"].view(np.uint32)[:12]
                 if rc == 0:
-                    assert (st[1], st[9], st[10]) == (len(data), 1, 0), (name, step, st[:12])
+                    assert (st.out_pos, st.done, st.status) == (len(data), 1, 0), (name, step, words)
                     assert k["out"].tobytes() == data
                 else:
-                    assert st[10] == rc and st[9] == 0, (name, step, st[:12])
-                    assert k["out"][:st[1]].tobytes() == data[:st[1]]
+                    assert st.status == rc and st.done == 0, (name, step, words)
+                    assert k["out"][:st.out_pos].tobytes() == data[:st.out_pos]
             assert np.array_equal(runs[0]["state"][:48], runs[1]["state"][:48]) and seen[0] == seen[1], (name, step)
             assert guards.violations(a, clean, {"out": True, "state": True}) == [], (name, step)
 
