@@ -16,7 +16,12 @@
 //      4*distance (<= 128) iff the three bytes are equal and is > 256 (as u32) otherwise, so the MIN
 //      over the 32 candidates IS four times the nearest matching distance: one v_sub + half a v_min3
 //      per compare, no branches (-DHDLZ_SEARCH_KEYS: the one-tile kernels too, for A/B).
-//   3. extension (R5): 8-byte LDS gather at p-d+3, xor with the own bytes, count-trailing-zeros.
+//   3. extension (R5): 8-byte LDS gather at p-d+3, xor with the own bytes, count-trailing-zeros.  The one-tile kernels with the bit
+//      search gather from LANE-PRIVATE WINDOWS: behind the stage every lane copies the 19 dwords [32l - 32, 32l + 44) of the tile -- all
+//      it can gather -- to W[l] at an odd dword stride (copy_windows, WaveLdsWin), so lanes at the same relative offset sit in 64
+//      different banks instead of 8 (the shared layout: 32 bytes per lane); W overlays the tile and the bit buffer (zeroed behind the
+//      extension), and the own bytes of the search, the Adler sums and the extension stay in the copy's registers.
+//      (-DHDLZ_EXT_SHARED: the shared layout, for A/B.)
 //   4. greedy parse ("di += m / di += 1", deflate.py:960,1008): every lane folds its run into a
 //      transfer function "entry skip (0..9) -> exit skip", 10 nibbles packed in 40 bits, by a
 //      backward pass; a 64-step scalar readlane chain composes them across the wave.
@@ -81,7 +86,8 @@ __device__ __forceinline__ void store_words(uint32_t* __restrict__ dst, const ui
 template <int NCH, bool FULLWIN, bool ONE_TILE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH>(), waves_eu<NCH>()))) void k_compress(CompressArgs a) {
     constexpr bool HASH = wide_hash<NCH>();         // windows > 32: the window-independent finder
-    __shared__ typename std::conditional<HASH, WaveLdsNoOut, WaveLds>::type lds;
+    constexpr bool WIN = ONE_TILE && NCH == 1 && ext_windows();      // lane-private candidate windows for the extension (WaveLdsWin)
+    __shared__ typename std::conditional<HASH, WaveLdsNoOut, typename std::conditional<WIN, WaveLdsWin, WaveLds>::type>::type lds;
     __shared__ typename std::conditional<HASH, HashLds<NCH>, uint32_t>::type hl;
     // the bit buffer of a tile: HASH kernels keep it in the finder's transposition buffer, which is dead once best[] is in registers
     // (28 KB of LDS per wave left ONE wave per SIMD: VALU 31 %, LDS 39 % busy -- this kernel lives on overlapping the two)
@@ -174,8 +180,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                     if (lane == 0u) *reinterpret_cast<uint4*>(lin8 + HALO + nfull * 16u) = load_chunk16(src, t0 + nfull * 16u, n, aligned16, mis);
                 }
             }
-            // zero the bit buffer, seed the carry
-            if constexpr (!HASH) zero_bit_buffer(lout, lane, carry_word);
+            // zero the bit buffer, seed the carry (WIN: it overlays the tile -- behind the extension, like the hash kernels)
+            if constexpr (!HASH && !WIN) zero_bit_buffer(lout, lane, carry_word);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the tile has landed (and the last tile's output stores have left)
             wave_lds_order();
 
@@ -184,6 +190,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             const uint32_t p_run = t0 + lane * RUN;                   // first position of this run
             const uint32_t nrem = n - min(p_run, n);                  // positions of the block from p_run on
             uint32_t best[RUN], tok[RUN], code[RUN];
+            [[maybe_unused]] uint32_t oww[12];                    // WIN: the own bytes, in registers from here to the extension
+            if constexpr (WIN) {
+                copy_windows(lds.in, lds.win, lane, oww);         // the tile -> one 19-dword window per lane; `in` is dead from here on
+                wave_lds_order();
+            }
             TT(1);                                                // stage (HBM latency, LDS writes, bit buffer zeroing)
             // Wave priorities (round 5): the search is the one phase that is pure VALU work; every other phase is a chain of LDS round
             // trips, scalar work or memory waits with little to issue.  With the search at the LOWEST priority a wave in any other phase
@@ -198,6 +209,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 zero_bit_buffer(lout, lane, carry_word);                                           // (ordered before the scatter by the fences below)
             }
 #ifndef HDLZ_SEARCH_KEYS                                                                           // (-DHDLZ_SEARCH_KEYS: the key form, for A/B)
+            else if constexpr (WIN) match_search_bits(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], best);
             else if constexpr (ONE_TILE && NCH == 1) match_search_bits(lds.in, run_dw, best);      // 2. R3/R4 (a one-tile block: bit planes, history by DPP)
 #endif
             else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                    // 2. R3/R4 (a one-tile block: candidate keys by DPP)
@@ -205,7 +217,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 TT(2);
                 HDLZ_MARK("adler");
                 uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (reloaded: see match_search)
-                load_own(lds.in, run_dw, ow);
+                if constexpr (WIN) {
+#pragma unroll
+                    for (int k = 0; k < 12; k++) ow[k] = oww[k];
+                } else load_own(lds.in, run_dw, ow);
                 {                                                                                  // 6. Adler partials
                     uint32_t sa, sc;
                     adler_run(ow, sa, sc);
@@ -221,11 +236,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 if constexpr (!HASH) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(HDLZ_HP_EXTEND);
                 HDLZ_MARK("extend");
+                if constexpr (WIN) {
+                    make_tokens<NCH, FULLWIN, true, GATHER_NOMASK>(lds.win, (uint32_t)(WIN_PAD + WIN_OWN) + 4u * WIN_DW * lane, ow, best, cw4, kmax,
+                                                                   4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));      // 3. R5, from W[lane]
+                } else
                 make_tokens<NCH, FULLWIN, true>(lds.in, HALO + lane * RUN, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5
             }
             pin(tok);
             PHASE_FENCE();
             TT(4);
+            if constexpr (WIN) {                                  // W is dead (every gather has returned: tok is pinned): the bit buffer takes its place,
+                HDLZ_MARK("zero");                                // ordered before the scatter by the fences below
+                wave_lds_order();
+                zero_bit_buffer(lout, lane, carry_word);
+            }
             if constexpr (HASH) __builtin_amdgcn_s_setprio(HDLZ_HP_REST);
             HDLZ_MARK("parse");
             const uint64_t P = run_transfer(tok);                                                  // 4. greedy parse

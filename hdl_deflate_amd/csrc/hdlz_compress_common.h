@@ -40,8 +40,43 @@ struct __attribute__((aligned(16))) WaveLds {
     uint32_t lut[LUT_LIT + LUT_MATCH + LUT_LEN];
 };
 
+constexpr uint32_t GATHER_NOMASK = 0x3FFFFFFFu;           // make_tokens' GMASK of a layout whose gathers need none
 constexpr uint32_t GATHER_SPAN = 4u * (0x3FFu + 3u);      // bytes behind `in` that make_tokens' masked gather may touch (GMASK = 0x3FF)
 static_assert(sizeof(WaveLds) >= GATHER_SPAN, "make_tokens: masked gather inside the LDS block");
+
+// ---- the one-tile kernels with the bit-sliced search (k_compress<1, ., true>): LANE-PRIVATE CANDIDATE WINDOWS for the extension.
+// In `in` lane l owns the 32 bytes at HALO + 32 l, so 64 lanes that gather at the same relative offset hit 8 of the 64 banks: every
+// gather of make_tokens is 8-way conflicted by construction.  All a lane gathers there (positions 32 l + i, d <= 32, bytes p - d + 3 ..
+// p - d + 14) lies in the 76 bytes [32 l - 32, 32 l + 44) = 19 dwords: copy_windows gives every lane its own copy W[l] at a stride of 19
+// dwords -- odd, so lanes at the same offset sit in 64 different banks.  W overlays `in` (the bytes go through registers) and the bit
+// buffer (zeroed behind the extension); WIN_PAD bytes in front keep the gather of a position without a candidate (result 0xFF: distance
+// 63) inside the block without a mask.  -DHDLZ_EXT_SHARED (and the key search, whose raw minima need the mask): the shared layout, for A/B.
+constexpr int WIN_DW = 19;                                // dwords of a lane's window: 32 bytes of history, 32 own, 12 look-ahead
+constexpr int WIN_PAD = 32;                               // bytes in front of W[0]
+constexpr int WIN_OWN = 32;                               // byte offset of the lane's own run inside its window
+constexpr int WIN_BYTES = WIN_PAD + 64 * 4 * WIN_DW;      // 4896
+constexpr bool ext_windows() {
+#if defined(HDLZ_EXT_SHARED) || defined(HDLZ_SEARCH_KEYS)
+    return false;
+#else
+    return true;
+#endif
+}
+struct __attribute__((aligned(16))) WaveLdsWin {
+    union {
+        uint32_t in[IN_BYTES / 4];      // the staged tile, until copy_windows has read it
+        uint32_t win[WIN_BYTES / 4];    // pad + W[0 .. 64): what make_tokens gathers from
+        uint32_t out[OUT_WORDS];        // bit buffer of the tile, zeroed once the extension is through
+    };
+    uint32_t lut[LUT_LIT + LUT_MATCH + LUT_LEN];
+};
+// the gather of position i of lane l at distance d (1 .. 32 found, 63 = none) reads the three dwords from byte
+// (WIN_PAD + 76 l + WIN_OWN + i + 3 - d) & ~3 on: inside [0, WIN_BYTES) for every lane, position and distance -- no mask
+static_assert(WIN_PAD + WIN_OWN + 3 - 63 >= 0, "make_tokens: the gather of a position without a candidate starts inside the LDS block");
+static_assert(((WIN_PAD + 4 * WIN_DW * 63 + WIN_OWN + 31 + 3 - 1) & ~3) + 12 <= WIN_BYTES, "make_tokens: the farthest gather ends inside W");
+static_assert(WIN_OWN + 3 - 32 >= 0 && ((WIN_OWN + 31 + 3 - 1) & ~3) + 12 <= 4 * WIN_DW, "a real candidate's gather stays inside the lane's window");
+static_assert(WIN_BYTES % 16 == 0 && WIN_BYTES >= IN_BYTES && WIN_BYTES >= 4 * OUT_WORDS && sizeof(WaveLdsWin) <= 8192 - 16, "20 waves per CU");
+static_assert(HALO >= 32 && LOOKAHEAD >= 16, "copy_windows: lane 0 reads 32 bytes of halo, lane 63 sixteen behind the tile");
 
 struct __attribute__((aligned(16))) WaveLdsNoOut {       // kernels with the hash finder: the bit buffer lives in HashLds::D's memory
     uint32_t in[IN_BYTES / 4];
@@ -128,6 +163,30 @@ __device__ __forceinline__ void load_own(const uint32_t* in, uint32_t run_dw, ui
     ow[0] = v0.x; ow[1] = v0.y; ow[2] = v0.z; ow[3] = v0.w;
     ow[4] = v1.x; ow[5] = v1.y; ow[6] = v1.z; ow[7] = v1.w;
     ow[8] = v2.x; ow[9] = v2.y; ow[10] = v2.z; ow[11] = v2.w;
+}
+
+// ---- the lane's candidate window (WaveLdsWin): the 19 dwords at HALO + 32 l - 32 of the staged tile (16-byte aligned: five
+// ds_read_b128; lane 0 gets the zero halo, lane 63 the zero look-ahead) -> W[l], 19 dwords at a 19-dword stride (4-byte aligned:
+// ds_write2_b32, bank 19 l + k: conflict-free).  `win` overlays `in`: every lane's reads have returned (lgkmcnt(0)) before any lane
+// writes.  The own 32 bytes + 12 of look-ahead stay in registers (ow[11], the 20th dword read, is not part of the window: make_tokens indexes ow[10] at most),
+// so neither the search nor the later phases read them back.
+__device__ __forceinline__ void copy_windows(const uint32_t* in, uint32_t* win, uint32_t lane, uint32_t (&ow)[12]) {
+    const uint32_t src_dw = (HALO / 4) + lane * (RUN / 4) - 8u;
+    const uint4 v0 = *reinterpret_cast<const uint4*>(&in[src_dw]);
+    const uint4 v1 = *reinterpret_cast<const uint4*>(&in[src_dw + 4]);
+    const uint4 v2 = *reinterpret_cast<const uint4*>(&in[src_dw + 8]);
+    const uint4 v3 = *reinterpret_cast<const uint4*>(&in[src_dw + 12]);
+    const uint4 v4 = *reinterpret_cast<const uint4*>(&in[src_dw + 16]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    uint32_t* w = win + (WIN_PAD / 4) + (uint32_t)WIN_DW * lane;
+    w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w;
+    w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
+    w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
+    w[12] = v3.x; w[13] = v3.y; w[14] = v3.z; w[15] = v3.w;
+    w[16] = v4.x; w[17] = v4.y; w[18] = v4.z;
+    ow[0] = v2.x; ow[1] = v2.y; ow[2] = v2.z; ow[3] = v2.w;
+    ow[4] = v3.x; ow[5] = v3.y; ow[6] = v3.z; ow[7] = v3.w;
+    ow[8] = v4.x; ow[9] = v4.y; ow[10] = v4.z; ow[11] = v4.w;
 }
 
 // ---- phase 2, match search (R3/R4; the reference's matcher3 x CWINDOW + first-set-bit pick, deflate.py:407-421, :975-994):
@@ -281,15 +340,13 @@ __device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uin
     t0 = __builtin_amdgcn_perm(a23, a01, cat_lo); t1 = __builtin_amdgcn_perm(a23, a01, cat_hi);
     t2 = __builtin_amdgcn_perm(b23, b01, cat_lo); t3 = __builtin_amdgcn_perm(b23, b01, cat_hi);
 }
-__device__ __forceinline__ void match_search_bits(const uint32_t* in, uint32_t run_dw, uint32_t (&best)[RUN]) {
+// (x0 .. x7: the lane's own 32 bytes as dwords, from LDS or -- copy_windows -- already in registers)
+__device__ __forceinline__ void match_search_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t x5, uint32_t x6,
+                                                  uint32_t x7, uint32_t (&best)[RUN]) {
     uint32_t O[8], P[8];
-    {
-        const uint4 v0 = *reinterpret_cast<const uint4*>(&in[run_dw]);
-        const uint4 v1 = *reinterpret_cast<const uint4*>(&in[run_dw + 4]);
-        // O[k] byte m = own byte k + 8 m (k = 0..7): bytes k, k + 8, k + 16, k + 24 are byte k & 3 of dwords k >> 2, +2, +4, +6
-        transpose4x4_bytes(v0.x, v0.z, v1.x, v1.z, O[0], O[1], O[2], O[3]);
-        transpose4x4_bytes(v0.y, v0.w, v1.y, v1.w, O[4], O[5], O[6], O[7]);
-    }
+    // O[k] byte m = own byte k + 8 m (k = 0..7): bytes k, k + 8, k + 16, k + 24 are byte k & 3 of dwords k >> 2, +2, +4, +6
+    transpose4x4_bytes(x0, x2, x4, x6, O[0], O[1], O[2], O[3]);
+    transpose4x4_bytes(x1, x3, x5, x7, O[4], O[5], O[6], O[7]);
     exchange8(O);                                             // O[b] bit i = bit b of own byte i
 #pragma unroll
     for (int b = 0; b < 8; b++) P[b] = (uint32_t)__builtin_amdgcn_mov_dpp((int)O[b], 0x13C, 0xF, 0xF, false);      // wave_ror:1
@@ -323,6 +380,11 @@ __device__ __forceinline__ void match_search_bits(const uint32_t* in, uint32_t r
         best[k + 16] = __builtin_amdgcn_ubfe(Q[k], 16u, 8u);
         best[k + 24] = Q[k] >> 24;
     }
+}
+__device__ __forceinline__ void match_search_bits(const uint32_t* in, uint32_t run_dw, uint32_t (&best)[RUN]) {
+    const uint4 v0 = *reinterpret_cast<const uint4*>(&in[run_dw]);
+    const uint4 v1 = *reinterpret_cast<const uint4*>(&in[run_dw + 4]);
+    match_search_bits(v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, best);
 }
 
 // ---- phase 2 for WIDE windows: a window-independent match finder ------------------------------------------
@@ -370,6 +432,7 @@ template <int NCH> struct __attribute__((aligned(16))) HashLds {
 };
 
 __device__ __forceinline__ uint32_t* lds_out(WaveLds& l, uint32_t&) { return l.out; }
+__device__ __forceinline__ uint32_t* lds_out(WaveLdsWin& l, uint32_t&) { return l.out; }
 template <int NCH> __device__ __forceinline__ uint32_t* lds_out(WaveLdsNoOut&, HashLds<NCH>& h) {
     static_assert(sizeof(h.T) >= sizeof(uint32_t) * OUT_WORDS, "the bit buffer overlays T / D");
     return h.T;
@@ -594,6 +657,8 @@ template <int NCH> constexpr int waves_eu() { return NCH == 1 ? HDLZ_W1 : HDLZ_W
 //            2^32 - 1 stands for "none") would address LDS far outside `in`; masked, it stays inside the first 4 (GMASK + 3) bytes behind
 //            `in` -- which every caller's LDS block covers (static_assert there) -- and its result is discarded as before.  The mask
 //            replaces the ~3 of the dword address: no instruction more.  (an out-of-allocation LDS read.)
+//            GATHER_NOMASK (the lane-private windows of WaveLdsWin, whose search returns 4 d <= 128 or 0xFF): no address leaves the block
+//            (static_asserts there); what remains is the ~3 itself.
 template <int NCH, bool FULLWIN, bool SCALAR_TAIL = false, uint32_t GMASK = 0x3FFu>
 __device__ __forceinline__ void make_tokens(const uint32_t* in, uint32_t lds_run, uint32_t (&ow)[12], uint32_t (&best)[RUN],
                                             uint32_t cw4, uint32_t kmax, uint32_t p4_run, uint32_t nrem, uint32_t (&tok)[RUN],
