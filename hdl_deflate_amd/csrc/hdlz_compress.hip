@@ -152,8 +152,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
         const bool aligned16 = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
 
         uint32_t gw = 0;            // output words already flushed to HBM
-        uint32_t base_bits = 19;    // R1: 78 9C + bits 1,1,0
-        uint32_t carry_word = 0x78u | (0x9Cu << 8) | (0x3u << 16);
+        uint32_t base_bits = HEADER_BITS;    // R1
+        uint32_t carry_word = HEADER_WORD;
         uint32_t skip_in = 0;       // positions at the tile start covered by the previous tile's last match
         // per-lane Adler partials: ad_a = sum x (plain: reduced once per GiB and at the end), ad_w = sum (N-p) x mod 65521 with
         // ONE modulo per tile -- the weight N - p_run is carried mod 65521 from tile to tile instead of being reduced every time
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             {
                 TT(2);
                 HDLZ_MARK("adler");
-                uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (reloaded: see match_search)
+                uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (WIN: still in registers; else reloaded: see match_search)
                 if constexpr (WIN) {
 #pragma unroll
                     for (int k = 0; k < 12; k++) ow[k] = oww[k];
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             PHASE_FENCE();
             TT(7);
             HDLZ_MARK("scan");
-            uint32_t incl = wave_scan_incl(lane_bits, lane);
+            uint32_t incl = wave_scan_incl(lane_bits);
             const uint32_t tile_bits_all = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             pin(code); asm volatile("" : "+v"(incl), "+v"(lane_bits));
             PHASE_FENCE();
@@ -290,26 +290,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 // every position >= N of this tile was emitted as one 8-bit literal (zero byte, never a match,
                 // and the last two real bytes are always literals so the parse lands exactly on N)
                 const uint32_t ninv = t0 + TILE - n;
-                const uint32_t end_bits = base_bits + tile_bits_all - 8u * ninv;
-                // wipe everything behind the real end: partial word masked, later words zeroed
-                // (only the words that go out: the partial word, the EOB / pad bits and the trailer end within four words of `ew`, and
-                //  ew + 3 <= (19 + 9 * 2048) / 32 + 3 < OUT_WORDS; the rest of the buffer is zeroed when the next tile is staged)
-                {
-                    const uint32_t ew = end_bits >> 5, rb = end_bits & 31u;
-                    if (lane < 4u) lout[ew + lane] = (lane == 0u) ? (lout[ew] & ((1u << rb) - 1u)) : 0u;
-                }
-                // R8: EOB = 7 zero bits, zero pad to a byte, Adler-32 big-endian (s2 then s1)
-                uint32_t s1 = wave_sum(ad_a % ADLER_MOD), s2 = wave_sum(ad_w);
-                s1 = (s1 + 1u) % ADLER_MOD;
-                s2 = (s2 + n % ADLER_MOD) % ADLER_MOD;
-                const uint32_t nbytes = (end_bits + 7u + 7u) >> 3;
+                const uint32_t end_bits = base_bits + tile_bits_all - PAD_BITS * ninv;
+                // (only the words that go out: the partial word, the EOB / pad bits and the trailer end within four words of the end's, and
+                //  that word + 3 <= (19 + 9 * 2048) / 32 + 3 < OUT_WORDS; the rest of the buffer is zeroed when the next tile is staged)
+                if (lane < 4u) wipe_behind(lout, end_bits, lane);
+                // R8: EOB, zero pad to a byte, Adler-32
+                uint32_t s1, s2;
+                adler_finish(wave_sum(ad_a % ADLER_MOD), wave_sum(ad_w), n, s1, s2);
+                const uint32_t nbytes = block_nbytes(end_bits);
                 wave_lds_order();
-                if (lane == 0) {
-                    out8[nbytes] = (uint8_t)(s2 >> 8);
-                    out8[nbytes + 1] = (uint8_t)s2;
-                    out8[nbytes + 2] = (uint8_t)(s1 >> 8);
-                    out8[nbytes + 3] = (uint8_t)s1;
-                }
+                if (lane == 0) put_adler(out8, nbytes, s1, s2);
                 wave_lds_order();
                 const uint32_t total = nbytes + 4u;
                 const uint32_t words = (total + 3u) >> 2;
@@ -363,7 +353,7 @@ hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
     }
     // small blocks (the reference's own input scale): several blocks per wave-tile -- uniform 16-byte aligned batches,
     // or ragged ones whose caller states an upper bound on the block lengths in in_len
-    if (a.cwindow <= 256 && a.in_len >= 5u && a.in_len <= 1024u && a.out_pitch >= (uint64_t)out_bound(a.in_len) &&
+    if (a.in_len >= 5u && a.in_len <= 1024u && a.out_pitch >= (uint64_t)out_bound(a.in_len) &&
         (a.in_off || ((a.in_pitch & 15u) == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0)))
         return launch_compress_small(a, stream, ncu);
     // (round 5: 256 waves queued per CU instead of 64 -- a wave's blocks all belong to one family when the families alternate with a
@@ -374,14 +364,12 @@ hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
     const dim3 grid((unsigned)g), block(64);
     // every block within one wave-tile (fixed size, or a ragged batch whose caller states such a bound in in_len)
     const bool one_tile = a.in_len >= 5u && a.in_len <= (uint32_t)TILE;
-    if (a.cwindow == 32 && one_tile) hipLaunchKernelGGL((k_compress<1, true, true>), grid, block, 0, stream, a);
-    else if (a.cwindow < 32 && one_tile) hipLaunchKernelGGL((k_compress<1, false, true>), grid, block, 0, stream, a);
-    else if (a.cwindow == 32) hipLaunchKernelGGL((k_compress<1, true, false>), grid, block, 0, stream, a);
-    else if (a.cwindow < 32) hipLaunchKernelGGL((k_compress<1, false, false>), grid, block, 0, stream, a);
-    else if (a.cwindow == 64) hipLaunchKernelGGL((k_compress<2, true, false>), grid, block, 0, stream, a);
-    else if (a.cwindow < 64) hipLaunchKernelGGL((k_compress<2, false, false>), grid, block, 0, stream, a);
-    else if (a.cwindow == 256) hipLaunchKernelGGL((k_compress<8, true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((k_compress<8, false, false>), grid, block, 0, stream, a);
+    with_window(a.cwindow, [&](auto N, auto FW) {
+        constexpr int NCH = decltype(N)::value;
+        constexpr bool FULLWIN = decltype(FW)::value;
+        if (NCH == 1 && one_tile) hipLaunchKernelGGL((k_compress<1, FULLWIN, true>), grid, block, 0, stream, a);      // (32-wide windows only)
+        else hipLaunchKernelGGL((k_compress<NCH, FULLWIN, false>), grid, block, 0, stream, a);
+    });
     return hipGetLastError();
 }
 

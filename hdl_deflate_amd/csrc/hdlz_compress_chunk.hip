@@ -45,9 +45,7 @@ __global__ __launch_bounds__(64) void k_compress_chunk(ChunkArgs a) {
     const uint32_t n = a.n;
     ChunkState st = *a.st;                                   // (uniform load)
     if (st.done || st.status != HDLZ_OK) return;             // a finished or failed session stays as it is
-    if (!st.started) {                                       // R1: 78 9C + bits 1,1,0
-        st.started = 1; st.base_bits = 19; st.carry_word = 0x78u | (0x9Cu << 8) | (0x3u << 16);
-    }
+    if (!st.started) { st.started = 1; st.base_bits = HEADER_BITS; st.carry_word = HEADER_WORD; }      // R1
     const bool final_ = a.final_ != 0;
     uint32_t fail = HDLZ_OK;
     if (final_ && n < 5u) fail = HDLZ_E_SHORT_INPUT;         // R0: the reference never starts
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(64) void k_compress_chunk(ChunkArgs a) {
         uint32_t lane_bits = token_codes<NCH, false>(lut8, tok, c0, 0u, code);
         pin(code);
         PHASE_FENCE();
-        uint32_t incl = wave_scan_incl(lane_bits, lane);
+        uint32_t incl = wave_scan_incl(lane_bits);
         const uint32_t tile_bits_all = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         pin(code); asm volatile("" : "+v"(incl), "+v"(lane_bits));
         PHASE_FENCE();
@@ -115,15 +113,10 @@ __global__ __launch_bounds__(64) void k_compress_chunk(ChunkArgs a) {
             gw += full;
             base_bits = end_bits & 31u;
         } else {
-            // positions >= N of this tile were emitted as one 8-bit literal each (see hdlz_compress.hip): wipe them
-            const uint32_t ninv = t0 + TILE - n;
-            const uint32_t end_bits = base_bits + tile_bits_all - 8u * ninv;
-            {
-                const uint32_t ew = end_bits >> 5, rb = end_bits & 31u;
-                for (uint32_t w = ew + lane; w < OUT_WORDS; w += 64)
-                    lds.out[w] = (w == ew) ? (lds.out[w] & ((1u << rb) - 1u)) : 0u;
-            }
-            // R8: EOB = 7 zero bits, zero pad to a byte, Adler-32 big-endian (s2 then s1)
+            const uint32_t ninv = t0 + TILE - n;                  // positions >= N of this tile: one 8-bit literal each
+            const uint32_t end_bits = base_bits + tile_bits_all - PAD_BITS * ninv;
+            for (uint32_t k = lane; k < (uint32_t)OUT_WORDS - (end_bits >> 5); k += 64) wipe_behind(lds.out, end_bits, k);      // (to the end of the buffer)
+            // R8: EOB, zero pad to a byte, Adler-32
             uint32_t sA = ad_a, sC = ad_c;
 #pragma unroll
             for (int ofs = 32; ofs > 0; ofs >>= 1) { sA += __shfl_xor(sA, ofs, 64); sC += __shfl_xor(sC, ofs, 64); }
@@ -131,14 +124,9 @@ __global__ __launch_bounds__(64) void k_compress_chunk(ChunkArgs a) {
             const uint64_t nm = n % ADLER_MOD;
             const uint32_t s1 = (uint32_t)((A + 1u) % ADLER_MOD);
             const uint32_t s2 = (uint32_t)((nm + nm * A + ADLER_MOD - C) % ADLER_MOD);   // N + sum (N - p) x_p
-            const uint32_t nbytes = (end_bits + 7u + 7u) >> 3;
+            const uint32_t nbytes = block_nbytes(end_bits);
             __syncthreads();
-            if (lane == 0) {
-                out8[nbytes] = (uint8_t)(s2 >> 8);
-                out8[nbytes + 1] = (uint8_t)s2;
-                out8[nbytes + 2] = (uint8_t)(s1 >> 8);
-                out8[nbytes + 3] = (uint8_t)s1;
-            }
+            if (lane == 0) put_adler(out8, nbytes, s1, s2);
             __syncthreads();
             const uint32_t total = nbytes + 4u;
             const uint32_t words = (total + 3u) >> 2;
@@ -181,9 +169,7 @@ template __global__ void k_compress_chunk<8>(ChunkArgs);
 hipError_t launch_compress_chunk(const uint8_t* in, uint32_t n, uint32_t q_end, int final_, int cwindow, int maxmatch, uint8_t* out,
                                  uint64_t out_cap, void* state, hipStream_t stream) {
     ChunkArgs a{in, n, q_end, (uint32_t)(final_ != 0), cwindow, maxmatch, out, out_cap, static_cast<ChunkState*>(state)};
-    if (cwindow <= 32) hipLaunchKernelGGL(k_compress_chunk<1>, dim3(1), dim3(64), 0, stream, a);
-    else if (cwindow <= 64) hipLaunchKernelGGL(k_compress_chunk<2>, dim3(1), dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL(k_compress_chunk<8>, dim3(1), dim3(64), 0, stream, a);
+    with_window(cwindow, [&](auto N, auto) { hipLaunchKernelGGL(k_compress_chunk<decltype(N)::value>, dim3(1), dim3(64), 0, stream, a); });
     return hipGetLastError();
 }
 

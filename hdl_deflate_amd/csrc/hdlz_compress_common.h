@@ -507,7 +507,7 @@ __device__ __forceinline__ void match_search_hash(const uint32_t* in, HashLds<NC
             constexpr int j = decltype(J)::value;
             inv |= (base + 64u * (uint32_t)(g0 + j) + lane) - q.c0[j];
         });
-#ifdef HDLZ_HASH_FORCE_REORDER                     // test build (tools/r4_exp13.sh): every group takes the path the hardware never asks for
+#ifdef HDLZ_HASH_FORCE_REORDER                     // test build (build.sh forced, tests/test_gpu_forced_paths.py): every group takes the path the hardware never asks for
         inv = 0x80000000u;
 #endif
         if (ballot64((int32_t)inv < 0) != 0ull) {
@@ -640,6 +640,20 @@ __device__ __forceinline__ void match_search_hash(const uint32_t* in, HashLds<NC
 template <int NCH> constexpr bool wide_hash() { return NCH > 1; }      // every window > 32 (round 4: CWINDOW = 64 too, 279 against 246 GB/s for the one-pass brute force, which is gone)
 template <int NCH> constexpr int waves_eu() { return NCH == 1 ? HDLZ_W1 : HDLZ_WH; }
 
+// ---- THE window rule of every compress launcher (host): cwindow (1 .. 256) -> NCH = 1, 2 or 8 chunks of 32 candidate distances and
+// FULLWIN = "cwindow == 32 * NCH" (the reference's own windows 32 and 256, and 64), handed to f as types: f(std::integral_constant<int,
+// NCH>{}, std::bool_constant<FULLWIN>{}).  Two things rest on it: cwindow <= 32 * NCH <= HashCfg<NCH>::PRE (the hash finder's chain walks
+// stay inside the entries a tile wrote), and FULLWIN only where make_tokens may drop its window compare (kernels built without it ignore it).
+template <int NCH, class F> inline void window_case(int cwindow, F& f) {
+    static_assert(32 * NCH <= HashCfg<NCH>::PRE && 32 * NCH <= HALO, "the window of this NCH inside what a tile stages and inserts");
+    if (cwindow == 32 * NCH) f(std::integral_constant<int, NCH>{}, std::true_type{});
+    else f(std::integral_constant<int, NCH>{}, std::false_type{});
+}
+template <class F> inline void with_window(int cwindow, F&& f) {
+    if (cwindow <= 32) window_case<1>(cwindow, f);
+    else if (cwindow <= 64) window_case<2>(cwindow, f);
+    else window_case<8>(cwindow, f);
+}
 
 // ---- phase 3, eligibility + extension (R3/R5; SEARCHF / SEARCH10, deflate.py:899-964, :1018-1062):
 // tok[i] = 4 * (len-1) << 16 | LUT byte offset of the token  (len-1 = 0 for a literal).
@@ -836,7 +850,7 @@ __device__ __forceinline__ uint32_t token_codes(const uint8_t* lut8, uint32_t (&
 // inclusive wave scan (all 64 lanes must call it): Hillis-Steele inside the rows of 16 (row_shr 1, 2, 4, 8; a lane without a source adds 0),
 // then the row totals across (row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3) -- six DPP adds; the shuffle form
 // (__shfl_up = ds_bpermute + compare + select per step) was 38 VALU + 6 LDS instructions
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t) {
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);      // row_shr:1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);      // row_shr:2
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);      // row_shr:4
@@ -888,6 +902,36 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
            (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
 
+// ---- the framing of a zlib block (R1, R8, R9): ONE source for the four drivers (k_compress, k_compress_small, k_compress_chunk and
+// k_stream_place with the scans that feed it)
+constexpr uint32_t HEADER_WORD = 0x78u | (0x9Cu << 8) | (0x3u << 16);      // R1: 78 9C + bits 1,1,0 (BFINAL, BTYPE = 01) ...
+constexpr uint32_t HEADER_BITS = 19;                                         // ... the first token starts at this bit
+// Positions >= N of a block's last tile are zero bytes: they never match (R3), each is parsed as one 8-bit literal, and the bits of
+// all of them sit behind the real end of the block -- which is therefore PAD_BITS * (t0 + TILE - n) bits in front of the tile's last bit
+constexpr uint32_t PAD_BITS = 8;
+// wipe what was written behind the real end (bit end_bits), word k counted from the one the end lies in: that word masked, the ones
+// behind it zeroed.  (How far: the driver's extent -- k_compress the four words that can still go out, k_compress_chunk its whole buffer.)
+__device__ __forceinline__ void wipe_behind(uint32_t* lout, uint32_t end_bits, uint32_t k) {
+    const uint32_t ew = end_bits >> 5, rb = end_bits & 31u;
+    lout[ew + k] = (k == 0u) ? (lout[ew] & ((1u << rb) - 1u)) : 0u;
+}
+// R8: bytes of the block up to the trailer = the tokens, EOB (7 zero bits), zero padding to a byte (32- and 64-bit bit counts)
+template <class U> __device__ __forceinline__ U block_nbytes(U end_bits) { return (end_bits + 7u + 7u) >> 3; }
+// R8: Adler-32 of the block from A = sum x_p and W = sum (N - p) x_p (any residues mod 65521, 32 or 64 bits wide)
+template <class U> __device__ __forceinline__ void adler_finish(U A, U W, uint32_t n, uint32_t& s1, uint32_t& s2) {
+    s1 = (uint32_t)((A + 1u) % ADLER_MOD);
+    s2 = (uint32_t)((W + n % ADLER_MOD) % ADLER_MOD);
+}
+// R8: byte k (0 .. 3) of the trailer -- big-endian, s2 then s1 -- and the four of them behind the block's nbytes bytes
+__device__ __forceinline__ uint32_t adler_byte(uint32_t k, uint32_t s1, uint32_t s2) {
+    const uint32_t s = k < 2u ? s2 : s1;
+    return (k & 1u) ? (s & 255u) : (s >> 8);
+}
+__device__ __forceinline__ void put_adler(uint8_t* out8, uint32_t nbytes, uint32_t s1, uint32_t s2) {
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) out8[nbytes + k] = (uint8_t)adler_byte(k, s1, s2);
+}
+
 // zero the bit buffer of a tile and seed its first word (16-byte stores: 3 LDS instructions per lane instead of 10)
 __device__ __forceinline__ void zero_bit_buffer(uint32_t* lout, uint32_t lane, uint32_t carry_word) {
     static_assert(OUT_WORDS % 4 == 0, "16-byte stores");
@@ -904,6 +948,17 @@ __device__ __forceinline__ void fill_luts(uint32_t* lut, uint32_t lane) {
         else lut[LUT_LIT + e] = dist_entry(e + 1u);
     }
     if (lane < (uint32_t)LUT_LEN) lut[LUT_LIT + LUT_MATCH + lane] = lane ? length_code(lane + 1u) : 0u;      // index len-1; 0: a literal
+}
+
+// bytes at or beyond `valid` of a 16-byte chunk in registers read as zero (valid >= 16: the chunk as it is)
+__device__ __forceinline__ void zero_tail16(uint4& v, uint32_t valid) {
+    uint32_t* vv = reinterpret_cast<uint32_t*>(&v);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t lo = 4u * k;
+        const uint32_t m = valid <= lo ? 0u : (valid >= lo + 4u ? 0xFFFFFFFFu : ((1u << (8u * (valid - lo))) - 1u));
+        vv[k] &= m;
+    }
 }
 
 // one 16-byte chunk of a block at position p (p < n), from a source of any alignment; bytes at or beyond n read as zero
@@ -923,18 +978,9 @@ __device__ __forceinline__ uint4 load_chunk16(const uint8_t* __restrict__ src, u
         v.w = alignbyte(d4, d3, mis);
     }
     const uint32_t valid = n - p;                // bytes of this chunk inside the block
-    if (valid < 16u) {                           // positions >= N must read as zero bytes
-        uint32_t* vv = reinterpret_cast<uint32_t*>(&v);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t lo = 4u * k;
-            const uint32_t m = valid <= lo ? 0u : (valid >= lo + 4u ? 0xFFFFFFFFu : ((1u << (8u * (valid - lo))) - 1u));
-            vv[k] &= m;
-        }
-    }
+    if (valid < 16u) zero_tail16(v, valid);      // positions >= N must read as zero bytes
     return v;
 }
-
 
 // ---- stage the tile that starts at position t0: [t0 - 256, t0 + 2048 + 16) straight from HBM (no carried halo: tiles are independent)
 __device__ __forceinline__ void stage_tile(uint8_t* lin8, const uint8_t* __restrict__ src, uint32_t t0, uint32_t n, bool aligned16,
@@ -948,6 +994,5 @@ __device__ __forceinline__ void stage_tile(uint8_t* lin8, const uint8_t* __restr
         *reinterpret_cast<uint4*>(lin8 + c * 16u) = v;
     }
 }
-
 
 }  // namespace hdlz

@@ -119,16 +119,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(small_waves<
                     v1.x = alignbyte(dwd[5], dwd[4], mis); v1.y = alignbyte(dwd[6], dwd[5], mis);
                     v1.z = alignbyte(dwd[7], dwd[6], mis); v1.w = alignbyte(dwd[8], dwd[7], mis);
                 }
-                // bytes at or beyond N must read as zero
-                uint32_t* vv = reinterpret_cast<uint32_t*>(&v0);
-                uint32_t* ww = reinterpret_cast<uint32_t*>(&v1);
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t lo = 4u * k;
-                    vv[k] &= nrem <= lo ? 0u : (nrem >= lo + 4u ? 0xFFFFFFFFu : ((1u << (8u * (nrem - lo))) - 1u));
-                    const uint32_t hi = 16u + lo;
-                    ww[k] &= nrem <= hi ? 0u : (nrem >= hi + 4u ? 0xFFFFFFFFu : ((1u << (8u * (nrem - hi))) - 1u));
-                }
+                zero_tail16(v0, nrem);                                        // bytes at or beyond N must read as zero
+                zero_tail16(v1, nrem - min(nrem, 16u));
             }
             *reinterpret_cast<uint4*>(lin8 + HALO + lane * RUN) = v0;
             *reinterpret_cast<uint4*>(lin8 + HALO + lane * RUN + 16) = v1;
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(small_waves<
         auto clear_out = [&]() {
             for (uint32_t q = lane; q < (uint32_t)SMALL_OUT_WORDS / 4u; q += 64) *reinterpret_cast<uint4*>(&lout[4u * q]) = make_uint4(0, 0, 0, 0);
             wave_lds_order();
-            if (lane_ok && r == 0u) lout[g * Wb] = 0x78u | (0x9Cu << 8) | (0x3u << 16);   // R1 per block
+            if (lane_ok && r == 0u) lout[g * Wb] = HEADER_WORD;                   // R1 per block
             wave_lds_order();
         };
         if constexpr (NCH == 1) clear_out();
@@ -182,7 +174,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(small_waves<
         pin(code);
         PHASE_FENCE();
         // wave scan of lane_bits; bit offsets are per block (segmented by the block's first lane)
-        uint32_t incl = wave_scan_incl(lane_bits, lane);
+        uint32_t incl = wave_scan_incl(lane_bits);
         const uint32_t first_lane = g * Rb;
         // (shuffles must be executed by ALL lanes: a source lane that skipped it reads as garbage)
         const uint32_t prev_incl = (uint32_t)__shfl((int)incl, (int)((first_lane - 1u) & 63u), 64);
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(small_waves<
         pin(code); asm volatile("" : "+v"(incl), "+v"(lane_bits));
         PHASE_FENCE();
         // OR every token into the block's region of the LDS bit buffer (a lane without a block emits nothing: all codes are zero)
-        scatter_codes(out8, code, lane_ok ? 32u * g * Wb + 19u + (incl - lane_bits - before_blk) : 0u);
+        scatter_codes(out8, code, lane_ok ? 32u * g * Wb + HEADER_BITS + (incl - lane_bits - before_blk) : 0u);
         wave_lds_order();
         // -------------------------------------------------------------- 7. per block: trailer, length, flush
         // the block's first lane finishes its block (R8/R9)
@@ -201,13 +193,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(small_waves<
             uint32_t s1 = 1u, s2 = nb;
             for (uint32_t k = 0; k < Rb; k++) { s1 += lds.ad[0][first_lane + k]; s2 += lds.ad[1][first_lane + k]; }
             s1 %= ADLER_MOD; s2 %= ADLER_MOD;
-            const uint32_t end_bits = 19u + blk_bits;
-            const uint32_t nbytes = (end_bits + 7u + 7u) >> 3;     // EOB = 7 zero bits, then zero padding
-            uint8_t* ob = out8 + 4u * g * Wb;
-            ob[nbytes] = (uint8_t)(s2 >> 8);
-            ob[nbytes + 1] = (uint8_t)s2;
-            ob[nbytes + 2] = (uint8_t)(s1 >> 8);
-            ob[nbytes + 3] = (uint8_t)s1;
+            const uint32_t nbytes = block_nbytes(HEADER_BITS + blk_bits);
+            put_adler(out8 + 4u * g * Wb, nbytes, s1, s2);
             total = nbytes + 4u;
             a.out_len[blk] = total;
             a.status[blk] = HDLZ_OK;
@@ -234,14 +221,12 @@ hipError_t launch_compress_small(const CompressArgs& a, hipStream_t stream, int 
     if (grid > groups) grid = groups;
     const dim3 g((unsigned)grid), b(64);
     const bool rag = a.in_off != nullptr;
-#define SMALL_LAUNCH(R, F, N) hipLaunchKernelGGL((k_compress_small<R, F, N>), g, b, 0, stream, a)
-#define SMALL_BY_NCH(N, full) do { if (rag) { if (full) SMALL_LAUNCH(true, true, N); else SMALL_LAUNCH(true, false, N); } \
-                                   else { if (full) SMALL_LAUNCH(false, true, N); else SMALL_LAUNCH(false, false, N); } } while (0)
-    if (a.cwindow <= 32) SMALL_BY_NCH(1, a.cwindow == 32);
-    else if (a.cwindow <= 64) SMALL_BY_NCH(2, a.cwindow == 64);
-    else SMALL_BY_NCH(8, a.cwindow == 256);
-#undef SMALL_BY_NCH
-#undef SMALL_LAUNCH
+    with_window(a.cwindow, [&](auto N, auto FW) {
+        constexpr int NCH = decltype(N)::value;
+        constexpr bool FULLWIN = decltype(FW)::value;
+        if (rag) hipLaunchKernelGGL((k_compress_small<true, FULLWIN, NCH>), g, b, 0, stream, a);
+        else hipLaunchKernelGGL((k_compress_small<false, FULLWIN, NCH>), g, b, 0, stream, a);
+    });
     return hipGetLastError();
 }
 

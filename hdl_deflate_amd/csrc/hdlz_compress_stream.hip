@@ -41,7 +41,7 @@ struct StreamArgs {
     uint32_t* skip;      // [ntiles] entry skip of tile t
     uint32_t* bits;      // [ntiles] token bits of tile t
     uint64_t* bitoff;    // [ntiles] bit offset of tile t in the output stream
-    uint32_t* totals;    // [2 * nblocks] s1, s2 of every block
+    uint32_t* totals;    // [16 + 2 * nblocks] s1, s2 of every block (the 16 words behind them: unused, kept for the offsets)
     uint32_t nchunks;    // chunks of 256 tiles
     uint64_t* cxfer;     // [nchunks] composed transfer function of the chunk
     uint32_t* centry;    // [nchunks] entry skip of the chunk
@@ -54,38 +54,38 @@ constexpr bool FULLWIN = false;      // the stream passes keep the per-position 
 constexpr uint64_t XF_IDENT = 0x9876543210ull;                     // transfer function: identity
 constexpr uint64_t XF_MARK = 0xFFFFFFFFFFFFFFFFull;                  // "not known yet: needs the full pass"
 
-#define HDLZ_STREAM_PROLOGUE()                                                                         \
-    constexpr bool HASH = wide_hash<NCH>();           /* wide windows: the window-independent finder */ \
-    __shared__ typename std::conditional<HASH, WaveLdsNoOut, WaveLds>::type lds;                       \
-    __shared__ typename std::conditional<HASH, HashLds<NCH>, uint32_t>::type hl;                       \
-    uint32_t* const lout = lds_out(lds, hl);          /* HASH: the bit buffer overlays the dead tables */ \
-    const uint32_t lane = threadIdx.x;                                                                 \
-    fill_luts<NCH>(lds.lut, lane);                                                                     \
-    __syncthreads();                                                                                   \
-    const uint32_t cw4 = 4u * (uint32_t)a.cwindow;                                                     \
-    const uint32_t kmax = (uint32_t)a.maxmatch;                                                        \
-    const uint32_t n = a.n;                                                                            \
-    uint8_t* lin8 = reinterpret_cast<uint8_t*>(lds.in);                                                \
-    const uint8_t* lut8 = reinterpret_cast<const uint8_t*>(lds.lut);                                   \
-    uint8_t* out8 = reinterpret_cast<uint8_t*>(lout);                                                  \
-    (void)lut8; (void)out8; (void)kmax; (void)cw4;
-// tile t -> its block, its first position inside the block, the block's bytes
-#define HDLZ_TILE_COORDS(t)                                                                            \
-    const uint32_t blk = (t) / a.tpb;                                                                  \
-    const uint32_t t0 = ((t) - blk * a.tpb) * (uint32_t)TILE;                                          \
-    const uint8_t* __restrict__ src = a.in + (size_t)blk * a.in_pitch;                                 \
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u);                            \
-    const bool aligned16 = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+// ---- what the two passes that run whole tiles (k_stream_xfer, k_stream_tile) share.  The LDS of their wave: wide windows (the
+// window-independent finder) keep the bit buffer in the finder's dead tables
+template <int NCH> using StreamLds = typename std::conditional<wide_hash<NCH>(), WaveLdsNoOut, WaveLds>::type;
+template <int NCH> using StreamHashLds = typename std::conditional<wide_hash<NCH>(), HashLds<NCH>, uint32_t>::type;
+// the constants of a kernel; fills the wave's LUTs on the way (once per wave lifetime)
+struct StreamConsts { uint32_t lane, cw4, kmax, n; };
+template <int NCH> __device__ __forceinline__ StreamConsts stream_consts(const StreamArgs& a, uint32_t* lut) {
+    const uint32_t lane = threadIdx.x;
+    fill_luts<NCH>(lut, lane);
+    __syncthreads();
+    return {lane, 4u * (uint32_t)a.cwindow, (uint32_t)a.maxmatch, a.n};
+}
+// tile t -> its first position inside its block, the block's bytes and their alignment
+struct TileCoords { uint32_t t0; const uint8_t* src; uint32_t mis; bool aligned16; };
+__device__ __forceinline__ TileCoords tile_coords(const StreamArgs& a, uint32_t t) {
+    const uint32_t blk = t / a.tpb;
+    const uint8_t* src = a.in + (size_t)blk * a.in_pitch;
+    return {(t - blk * a.tpb) * (uint32_t)TILE, src, (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u), (reinterpret_cast<uintptr_t>(src) & 15u) == 0};
+}
 
 // ------------------------------------------------------------------------------------------------ pass A
 template <int NCH>
 __global__ __launch_bounds__(64) void k_stream_xfer(StreamArgs a) {
-    HDLZ_STREAM_PROLOGUE()
+    constexpr bool HASH = wide_hash<NCH>();
+    __shared__ StreamLds<NCH> lds;
+    __shared__ StreamHashLds<NCH> hl;
+    const auto [lane, cw4, kmax, n] = stream_consts<NCH>(a, lds.lut);
     for (uint32_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
         if (a.xfer[t] != XF_MARK) continue;                          // k_stream_tails already has this tile's function
-        HDLZ_TILE_COORDS(t)
+        const auto [t0, src, mis, aligned16] = tile_coords(a, t);
 
-        stage_tile(lin8, src, t0, n, aligned16, mis, lane);
+        stage_tile(reinterpret_cast<uint8_t*>(lds.in), src, t0, n, aligned16, mis, lane);
         __syncthreads();
         const uint32_t p_run = t0 + lane * RUN;
         const uint32_t nrem = n - min(p_run, n);
@@ -200,14 +200,11 @@ __global__ __launch_bounds__(64) void k_stream_offsets_top(StreamArgs a) {
         const uint64_t o = shfl_up64(incl, ofs);
         if (lane >= (uint32_t)ofs) incl += o;
     }
-    uint64_t off = 19u + incl - sb;                                 // R1: 78 9C + bits 1,1,0
+    uint64_t off = HEADER_BITS + incl - sb;                         // R1
     for (uint32_t c = b; c < e; c++) { const uint64_t v = a.csum[3 * c]; a.csum[3 * c] = off; off += v; }
 #pragma unroll
     for (int ofs = 32; ofs > 0; ofs >>= 1) { sa += shfl_xor64(sa, ofs); sw += shfl_xor64(sw, ofs); }
-    if (lane == 0) {
-        a.totals[0] = (uint32_t)((sa + 1u) % ADLER_MOD);
-        a.totals[1] = (uint32_t)((sw + a.n % ADLER_MOD) % ADLER_MOD);
-    }
+    if (lane == 0) adler_finish(sa, sw, a.n, a.totals[0], a.totals[1]);
 }
 
 // APPLY = 0: chunk c -> its sums (bits, Adler partials) in csum[c];  APPLY = 1: bit offset of each of its tiles
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(64) void k_stream_offsets_one(StreamArgs a) {
         const uint32_t o = __shfl_up(incl, ofs, 64);
         if (lane >= (uint32_t)ofs) incl += o;
     }
-    uint64_t off = 19u + (incl - own);                               // R1: 78 9C + bits 1,1,0
+    uint64_t off = HEADER_BITS + (incl - own);                       // R1
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (b + k < a.ntiles) a.bitoff[b + k] = off;
@@ -292,16 +289,13 @@ __global__ __launch_bounds__(64) void k_stream_offsets_one(StreamArgs a) {
     }
 #pragma unroll
     for (int ofs = 32; ofs > 0; ofs >>= 1) { sa += shfl_xor64(sa, ofs); sw += shfl_xor64(sw, ofs); }
-    if (lane == 0) {
-        a.totals[0] = (uint32_t)((sa + 1u) % ADLER_MOD);
-        a.totals[1] = (uint32_t)((sw + a.n % ADLER_MOD) % ADLER_MOD);
-    }
+    if (lane == 0) adler_finish(sa, sw, a.n, a.totals[0], a.totals[1]);
 }
 
-// several blocks: one wave per block walks its tiles 64 at a time (bit offsets restart at 19 in every block)
+// several blocks: one wave per block walks its tiles 64 at a time (bit offsets restart behind the header in every block)
 __global__ __launch_bounds__(64) void k_stream_offsets_blocks(StreamArgs a) {
     const uint32_t lane = threadIdx.x, b = blockIdx.x;
-    uint64_t off = 19u, sa = 0, sw = 0;                              // R1: 78 9C + bits 1,1,0
+    uint64_t off = HEADER_BITS, sa = 0, sw = 0;                      // R1
     for (uint32_t base = 0; base < a.tpb; base += 64u) {
         const uint32_t lt = base + lane, t = b * a.tpb + lt;
         uint32_t v = 0;
@@ -317,22 +311,25 @@ __global__ __launch_bounds__(64) void k_stream_offsets_blocks(StreamArgs a) {
     }
 #pragma unroll
     for (int ofs = 32; ofs > 0; ofs >>= 1) { sa += shfl_xor64(sa, ofs); sw += shfl_xor64(sw, ofs); }
-    if (lane == 0) {
-        a.totals[2 * b] = (uint32_t)((sa + 1u) % ADLER_MOD);
-        a.totals[2 * b + 1] = (uint32_t)((sw + a.n % ADLER_MOD) % ADLER_MOD);
-    }
+    if (lane == 0) adler_finish(sa, sw, a.n, a.totals[2 * b], a.totals[2 * b + 1]);
 }
 
 // ------------------------------------------------------------------------------------------------ pass C
 template <int NCH>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NCH == 1 ? HDLZ_W1 : wide_hash<NCH>() ? HDLZ_WH : 4, NCH == 1 ? HDLZ_W1 : wide_hash<NCH>() ? HDLZ_WH : 4))) void k_stream_tile(StreamArgs a) {
-    HDLZ_STREAM_PROLOGUE()
+    constexpr bool HASH = wide_hash<NCH>();
+    __shared__ StreamLds<NCH> lds;
+    __shared__ StreamHashLds<NCH> hl;
+    uint32_t* const lout = lds_out(lds, hl);                         // HASH: the bit buffer overlays the dead tables
+    const auto [lane, cw4, kmax, n] = stream_consts<NCH>(a, lds.lut);
+    const uint8_t* lut8 = reinterpret_cast<const uint8_t*>(lds.lut);
+    uint8_t* out8 = reinterpret_cast<uint8_t*>(lout);
     for (uint32_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-        HDLZ_TILE_COORDS(t)
+        const auto [t0, src, mis, aligned16] = tile_coords(a, t);
         uint32_t skip_in = a.skip[t];
         const uint32_t base_bits = 0;                                // the tile's bits are built from local bit 0
 
-        stage_tile(lin8, src, t0, n, aligned16, mis, lane);
+        stage_tile(reinterpret_cast<uint8_t*>(lds.in), src, t0, n, aligned16, mis, lane);
         if constexpr (!HASH) for (uint32_t w = lane; w < OUT_WORDS; w += 64) lout[w] = 0u;
         __syncthreads();
         const uint32_t p_run = t0 + lane * RUN;
@@ -363,13 +360,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NCH == 1 ? H
         uint32_t lane_bits = token_codes<NCH, false>(lut8, tok, myskip, 0u, code);                 // 5. R6/R7
         pin(code);
         PHASE_FENCE();
-        uint32_t incl = wave_scan_incl(lane_bits, lane);
+        uint32_t incl = wave_scan_incl(lane_bits);
         const uint32_t tile_bits_all = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         // positions >= N of the last tile were parsed as one 8-bit literal each (see hdlz_compress.hip); their
         // bits sit behind the real end and are cut off by k_stream_place, which only takes bits[t] bits
         const bool last = (t0 + (uint32_t)TILE >= n);
         const uint32_t ninv = last ? t0 + (uint32_t)TILE - n : 0u;
-        const uint32_t tile_bits = tile_bits_all - 8u * ninv;
+        const uint32_t tile_bits = tile_bits_all - PAD_BITS * ninv;
         {
             // bits and Adler partials of the tile
             uint32_t wsum = ((nrem % ADLER_MOD) * sa) % ADLER_MOD + ADLER_MOD * 8u - (sc % ADLER_MOD);   // < 10 * 65521
@@ -429,7 +426,7 @@ __global__ __launch_bounds__(256) void k_stream_place(StreamArgs a) {
         // the bits below this tile in its first word: header (tile 0) or the tail of the previous tile
         uint32_t below = 0;
         if (s != 0u) {
-            if (lt == 0u) below = 0x78u | (0x9Cu << 8) | (0x3u << 16);          // s == 19
+            if (lt == 0u) below = HEADER_WORD;                                   // s == HEADER_BITS
             else below = slot_bits(slot - OUT_WORDS, a.bits[t - 1u] - s, s);
         }
         // all loads first (the kernel is a copy: what counts is bytes in flight), local words cut to the tile's nb bits
@@ -456,17 +453,16 @@ __global__ __launch_bounds__(256) void k_stream_place(StreamArgs a) {
         }
         if (lastt && lane == 0u) {
             const uint64_t E = B + nb;                               // first bit behind the last token
-            const uint64_t nbytes = (E + 7u + 7u) >> 3;              // EOB = 7 zero bits, then pad to a byte
+            const uint64_t nbytes = block_nbytes(E);
             const uint64_t total = nbytes + 4u;
             const uint32_t s1 = a.totals[2u * blk], s2 = a.totals[2u * blk + 1u];
-            const uint32_t tr[4] = {s2 >> 8, s2 & 255u, s1 >> 8, s1 & 255u};
             // words from the one holding bit E-1 (already stored above, but without the trailer) to the last one
             const uint64_t wa = (E - 1u) >> 5, wb = (total - 1u) >> 2;
             for (uint64_t w = wa; w <= wb; w++) {
                 uint32_t v = (w == wa) ? tailword : 0u;
                 for (uint32_t k = 0; k < 4u; k++) {
                     const uint64_t bpos = nbytes + k;
-                    if ((bpos >> 2) == w) v |= tr[k] << (8u * (uint32_t)(bpos & 3u));
+                    if ((bpos >> 2) == w) v |= adler_byte(k, s1, s2) << (8u * (uint32_t)(bpos & 3u));
                 }
                 outw[w] = v;
             }
@@ -550,12 +546,25 @@ template __global__ void k_stream_tile<1>(StreamArgs);
 template __global__ void k_stream_tile<2>(StreamArgs);
 template __global__ void k_stream_tile<8>(StreamArgs);
 
-size_t stream_work_bytes(uint32_t n, uint32_t nblocks) {
-    const size_t tpb = ((size_t)n + TILE - 1) / TILE;
-    const size_t nt = tpb * nblocks;
-    const size_t nc = (nt + CHUNK_TILES - 1) / CHUNK_TILES;
-    return nt * 32 + nc * 40 + 64 + (size_t)nblocks * 8 + nt * (size_t)OUT_WORDS * 4;
+// THE scratch layout of a call: nblocks blocks of n bytes -> the tile counts of `a` and its ten arrays, one behind the other from `base`
+// on (null: only the size is wanted), 8-byte elements first so that each is aligned like its elements; returns the bytes to ask for.
+// Per tile 32 bytes + the 2368-byte slot, per chunk 36 bytes, 64 + 8 bytes per block of totals -- and a tail of 4 bytes per chunk
+// that no array uses: hdlz_streams_work_bytes has always asked for it, callers size buffers by that value, so it stays.
+static size_t stream_layout(uint32_t n, uint32_t nblocks, void* base, StreamArgs& a) {
+    const size_t tpb = ((size_t)n + TILE - 1) / TILE, nt = tpb * nblocks, nc = (nt + CHUNK_TILES - 1) / CHUNK_TILES;
+    a.tpb = (uint32_t)tpb; a.ntiles = (uint32_t)nt; a.nchunks = (uint32_t)nc;
+    size_t off = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + off);
+        off += count * sizeof(*p);
+    };
+    take(a.xfer, nt); take(a.bitoff, nt); take(a.ad, nt); take(a.cxfer, nc); take(a.csum, 3 * nc);
+    take(a.skip, nt); take(a.bits, nt); take(a.centry, nc); take(a.totals, 16 + 2 * (size_t)nblocks);
+    take(a.tmp, nt * (size_t)OUT_WORDS);
+    return off + 4 * nc;                                      // (the unused tail)
 }
+
+size_t stream_work_bytes(uint32_t n, uint32_t nblocks) { StreamArgs a; return stream_layout(n, nblocks, nullptr, a); }
 
 template <int NCH>
 static void launch_passes(const StreamArgs& a, hipStream_t stream) {
@@ -589,24 +598,8 @@ hipError_t launch_compress_streams(const uint8_t* in, uint64_t in_pitch, uint32_
     StreamArgs a;
     a.in = in; a.n = n; a.cwindow = cwindow; a.maxmatch = maxmatch; a.out = out; a.out_len = out_len; a.status = status;
     a.nblocks = nblocks; a.in_pitch = in_pitch; a.out_pitch = out_pitch;
-    a.tpb = (uint32_t)(((uint64_t)n + TILE - 1) / TILE);
-    a.ntiles = a.tpb * nblocks;
-    a.nchunks = (a.ntiles + CHUNK_TILES - 1) / CHUNK_TILES;
-    uint8_t* w = static_cast<uint8_t*>(work);
-    const size_t nt = a.ntiles, nc = a.nchunks;
-    a.xfer = reinterpret_cast<uint64_t*>(w);                 w += nt * 8;     // 8-byte arrays first
-    a.bitoff = reinterpret_cast<uint64_t*>(w);               w += nt * 8;
-    a.ad = reinterpret_cast<uint2*>(w);                      w += nt * 8;
-    a.cxfer = reinterpret_cast<uint64_t*>(w);                w += nc * 8;
-    a.csum = reinterpret_cast<uint64_t*>(w);                 w += nc * 24;
-    a.skip = reinterpret_cast<uint32_t*>(w);                 w += nt * 4;
-    a.bits = reinterpret_cast<uint32_t*>(w);                 w += nt * 4;
-    a.centry = reinterpret_cast<uint32_t*>(w);               w += nc * 4;
-    a.totals = reinterpret_cast<uint32_t*>(w);               w += 64 + (size_t)nblocks * 8;
-    a.tmp = reinterpret_cast<uint32_t*>(w);
-    if (cwindow <= 32) launch_passes<1>(a, stream);
-    else if (cwindow <= 64) launch_passes<2>(a, stream);
-    else launch_passes<8>(a, stream);
+    stream_layout(n, nblocks, work, a);
+    with_window(cwindow, [&](auto N, auto) { launch_passes<decltype(N)::value>(a, stream); });
     return hipGetLastError();
 }
 

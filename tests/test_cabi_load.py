@@ -139,6 +139,50 @@ def test_tile_phases_have_one_source():
         assert "match_search<" in txt and "make_tokens<" in txt and "run_transfer(" in txt, f
         assert "umin3(m[i]" not in txt and "v_lshl_add_u32" not in txt, f      # no pasted phase bodies
     assert not os.path.exists(os.path.join(REPO, "tools", "gen_stream_kernel.py"))
+    # what stands around the phases has one source as well: the R1 header, the scratch layout of the stream passes, the window rule
+    five = {f: open(os.path.join(csrc, f)).read() for f in ("hdlz_compress.hip", "hdlz_compress_small.hip", "hdlz_compress_stream.hip",
+                                                            "hdlz_compress_chunk.hip", "hdlz_compress_common.h")}
+    assert sum(t.count("0x9Cu") for t in five.values()) == 1 and common.count("HEADER_WORD = 0x78u | (0x9Cu << 8)") == 1
+    body = re.search(r"size_t stream_work_bytes\([^)]*\)\s*\{(.*?)\n?\}", five["hdlz_compress_stream.hip"], flags=re.S).group(1)
+    assert "stream_layout(" in body and not re.search(r"[*+]|\d\d", body), body       # no per-array arithmetic of its own
+    assert five["hdlz_compress_stream.hip"].count("stream_layout(") == 3              # the definition, the size query, the launcher
+    compares = r"cwindow\s*(?:<=|>=|==|!=|<|>)\s*(?:32|64|256)\b"
+    helper = re.search(r"inline void window_case\(.*?inline void with_window\(.*?\n\}\n", common, flags=re.S).group(0)
+    assert len(re.findall(compares, helper)) == 3                                      # <= 32, <= 64, == 32 * NCH
+    for f, t in five.items():
+        code = re.sub(r"//[^\n]*", "", t.replace(helper, ""))
+        assert not re.search(compares, code), (f, re.search(compares, code).group(0))
+        assert f == "hdlz_compress_common.h" or "with_window(" in code, f
+    assert "SMALL_LAUNCH" not in five["hdlz_compress_small.hip"] and "SMALL_BY_NCH" not in five["hdlz_compress_small.hip"]
+
+
+def test_stream_scratch_size_is_the_closed_form():
+    """hdlz_streams_work_bytes is host arithmetic (no device needed) and callers size buffers by it: for nt = ceil(n / 2048) * nblocks
+    tiles and nc = ceil(nt / 256) chunks it stays nt * 32 + nc * 40 + 64 + nblocks * 8 + nt * 2368 -- the value it had when the formula
+    and the carve were two texts -- at the tile counts around a chunk (255, 256, 257), at one tile and at 4097; and it refuses
+    (returns 0) no blocks, a block of 2^31 bytes and 2^31 tiles"""
+    from hdl_deflate_amd import _lib
+    L = _lib.load()
+
+    def closed(n, nblocks):
+        nt = (n + 2047) // 2048 * nblocks
+        nc = (nt + 255) // 256
+        return nt * 32 + nc * 40 + 64 + nblocks * 8 + nt * 2368
+
+    seen = set()
+    for tiles in (1, 255, 256, 257, 4097):
+        for n in ((tiles - 1) * 2048 + 1, tiles * 2048 - 1, tiles * 2048):
+            for nblocks in (1, 3, 37):
+                assert L.hdlz_streams_work_bytes(n, nblocks) == closed(n, nblocks), (n, nblocks)
+                seen.add((n + 2047) // 2048 * nblocks)
+            assert L.hdlz_stream_work_bytes(n) == L.hdlz_streams_work_bytes(n, 1) == closed(n, 1), n
+    assert {1, 255, 256, 257, 4097} <= seen
+    assert L.hdlz_streams_work_bytes(0, 5) == closed(0, 5) == 64 + 40                # (no tiles: the totals alone)
+    assert L.hdlz_streams_work_bytes(2048, 0) == 0 and L.hdlz_streams_work_bytes(2048, 1 << 32) == 0
+    assert L.hdlz_streams_work_bytes(1 << 31, 1) == 0 and L.hdlz_stream_work_bytes(1 << 31) == 0
+    assert L.hdlz_streams_work_bytes((1 << 31) - 1, 1) == closed((1 << 31) - 1, 1)
+    assert L.hdlz_streams_work_bytes((1 << 31) - 1, 2047) == closed((1 << 31) - 1, 2047)      # 2^31 - 2^20 tiles
+    assert L.hdlz_streams_work_bytes((1 << 31) - 1, 2048) == 0 and L.hdlz_streams_work_bytes(2048, 1 << 31) == 0      # 2^31 tiles
 
 
 def test_inflate_group_decode_has_one_source():
