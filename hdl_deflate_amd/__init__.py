@@ -13,6 +13,11 @@ from .constants import (IDLE, WRITE, READ, STARTC, STARTD, OK, E_SHORT_INPUT, E_
 from .port import Sig, DeflatePort, deflate                         # noqa: F401
 
 
+def join_bound(nblocks, in_len):
+    """bytes that hold the joined stream of nblocks blocks of at most in_len bytes (same as hdlz_join_bound)"""
+    return 8 + nblocks * (out_bound(in_len) - 1)
+
+
 def Engine(*a, **kw):
     """The HIP batch engine (imports torch lazily)."""
     from .engine import Engine as _E

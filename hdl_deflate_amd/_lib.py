@@ -34,6 +34,15 @@ SIGNATURES = {
     "hdlz_inflate_chunk": (ci, [vp, u32, ci, u32, u32, vp, u64, u32, vp, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
+# ... and every entry point of include/hdlz_join.h, the additive extension header (tests/test_joined_cabi.py holds these to that header)
+JOIN_SIGNATURES = {
+    "hdlz_join_bound": (sz, [u64, u32]),
+    "hdlz_join_work_bytes": (sz, [u64]),
+    "hdlz_compress_batch_bits": (ci, _BATCH_IN + [ci, ci, vp, u64, vp, vp, vp, vp]),
+    # d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off, d_result, d_work, work_bytes, stream
+    "hdlz_join_batch_ws": (ci, [vp, u64, vp, vp, vp, vp, u32, u64, vp, u64, vp, vp, vp, sz, vp]),
+}
+JOIN_EXPORTS = tuple(JOIN_SIGNATURES)
 _lib = None
 
 
@@ -41,6 +50,11 @@ class CState(ctypes.Structure):
     """hdlz_cstate: the session of hdlz_compress_chunk (64 bytes)"""
     _fields_ = [(f, u32) for f in ("pos", "skip", "out_words", "base_bits", "carry_word", "adler_a", "adler_c", "started",
                                    "done", "out_len", "status")] + [("reserved", u32 * 5)]
+
+
+class JoinResult(ctypes.Structure):
+    """hdlz_join_result: the result record of hdlz_join_batch_ws (16 bytes)"""
+    _fields_ = [("stream_len", u64), ("status", u32), ("adler", u32)]
 
 
 class IState(ctypes.Structure):
@@ -61,7 +75,7 @@ def load():
     # two HIP runtimes in one process and torch's streams/pointers would be foreign to ours.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -161,9 +161,9 @@ int hdlz_release_scratch(void) {
     return HDLZ_OK;
 }
 
-int hdlz_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
-                        uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
-                        uint32_t* d_out_len, uint32_t* d_status, void* stream) {
+static int compress_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
+                               uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
+                               uint32_t* d_out_len, uint32_t* d_status, uint64_t* d_end_bits, void* stream) {
     if (cwindow < 1 || cwindow > 256) return fail_param("cwindow must be in [1,256]");
     if (maxmatch != 5 && maxmatch != 10) return fail_param("maxmatch must be 5 (MATCH10=False) or 10 (MATCH10=True)");
     if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch");
@@ -172,9 +172,47 @@ int hdlz_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t 
     if (!d_in_off && in_len >= 0x80000000u) return fail_param("in_len too large");
     int rc = check_device();
     if (rc != HDLZ_OK) return rc;
-    hdlz::CompressArgs a{d_in, d_in_off, in_pitch, in_len, nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status};
+    hdlz::CompressArgs a{d_in, d_in_off, in_pitch, in_len, nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status, d_end_bits};
     hipError_t e = hdlz::launch_compress(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(e, "launch k_compress");
+    return HDLZ_OK;
+}
+
+int hdlz_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
+                        uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
+                        uint32_t* d_out_len, uint32_t* d_status, void* stream) {
+    return compress_batch_impl(d_in, d_in_off, in_pitch, in_len, nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status,
+                               nullptr, stream);
+}
+
+// ---- include/hdlz_join.h: the batch call that also reports where every block ended, and the join of its rows into one zlib stream
+int hdlz_compress_batch_bits(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
+                             uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
+                             uint32_t* d_out_len, uint32_t* d_status, uint64_t* d_end_bits, void* stream) {
+    if (!d_end_bits) return fail_param("d_end_bits is required");
+    if (reinterpret_cast<uintptr_t>(d_end_bits) & 7u) return fail_param("d_end_bits must be 8-byte aligned");
+    return compress_batch_impl(d_in, d_in_off, in_pitch, in_len, nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status,
+                               d_end_bits, stream);
+}
+
+size_t hdlz_join_bound(uint64_t nblocks, uint32_t in_len) { return 8u + (size_t)nblocks * (hdlz_out_bound(in_len) - 1u); }
+
+size_t hdlz_join_work_bytes(uint64_t nblocks) { return nblocks > 0x7FFFFFFFull ? 0u : hdlz::join_work_bytes(nblocks); }
+
+int hdlz_join_batch_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                       const uint32_t* d_status, const uint64_t* d_in_off, uint32_t in_len, uint64_t nblocks,
+                       uint8_t* d_stream, uint64_t stream_cap, uint64_t* d_off, hdlz_join_result* d_result, void* d_work,
+                       size_t work_bytes, void* stream) {
+    if (!d_stream || !d_off || !d_result || (nblocks && (!d_rows || !d_len || !d_end_bits || !d_status))) return fail_param("null device pointer");
+    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");   // (32-bit tile and word counts)
+    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_join_work_bytes(nblocks)");
+    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u)) return fail_param("d_off / d_result must be 8-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    hipError_t e = hdlz::launch_join(d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off,
+                                     d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_join");
     return HDLZ_OK;
 }
 

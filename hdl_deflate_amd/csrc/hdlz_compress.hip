@@ -82,8 +82,10 @@ __device__ __forceinline__ void store_words(uint32_t* __restrict__ dst, const ui
 // NCH = ceil(cwindow / 32): 1, 2 or 8 chunks of 32 candidate distances; FULLWIN: cwindow == 32 * NCH (the reference's
 // own windows 32 and 256, and 64), which spares the per-position window compare; ONE_TILE: every block of the batch fits one
 // wave-tile (N <= 2048: BASELINE configs[1]'s block size and the reference's own IBSIZE scale) -- no tile loop, no halo
-// carried from a previous tile, no carried bit / Adler state
-template <int NCH, bool FULLWIN, bool ONE_TILE>
+// carried from a previous tile, no carried bit / Adler state; ENDBITS: the block's end bit goes to a.end_bits beside out_len / status
+// (hdlz_compress_batch_bits).  A template flag, not a test of the pointer: as a runtime field it cost k_compress<1, true, true> five
+// spilled SGPRs and three VGPRs (90 -> 93) -- with the flag the kernels of the calls that do not ask keep their registers as they were.
+template <int NCH, bool FULLWIN, bool ONE_TILE, bool ENDBITS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH>(), waves_eu<NCH>()))) void k_compress(CompressArgs a) {
     constexpr bool HASH = wide_hash<NCH>();         // windows > 32: the window-independent finder
     constexpr bool WIN = ONE_TILE && NCH == 1 && ext_windows();      // lane-private candidate windows for the extension (WaveLdsWin)
@@ -144,7 +146,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
         uint32_t n;
         const uint32_t bst = block_params(blk, src, n);
         if (bst != HDLZ_OK) {
-            if (lane == 0) { a.out_len[blk] = 0; a.status[blk] = bst; }
+            if (lane == 0) {
+                a.out_len[blk] = 0; a.status[blk] = bst;
+                if constexpr (ENDBITS) a.end_bits[blk] = 0;
+            }
             continue;
         }
         uint32_t* __restrict__ outw = reinterpret_cast<uint32_t*>(a.out + blk * a.out_pitch);
@@ -307,6 +312,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 if (lane == 0) {
                     a.out_len[blk] = gw * 4u + total;     // R9
                     a.status[blk] = HDLZ_OK;
+                    if constexpr (ENDBITS) a.end_bits[blk] = 32ull * gw + end_bits;      // where the end-of-block code starts, from the row's first bit
                 }
             }
             TT(11);                                               // flush
@@ -336,6 +342,14 @@ template __global__ void k_compress<2, true, false>(CompressArgs);
 template __global__ void k_compress<2, false, false>(CompressArgs);
 template __global__ void k_compress<8, true, false>(CompressArgs);
 template __global__ void k_compress<8, false, false>(CompressArgs);
+template __global__ void k_compress<1, true, true, true>(CompressArgs);
+template __global__ void k_compress<1, false, true, true>(CompressArgs);
+template __global__ void k_compress<1, true, false, true>(CompressArgs);
+template __global__ void k_compress<1, false, false, true>(CompressArgs);
+template __global__ void k_compress<2, true, false, true>(CompressArgs);
+template __global__ void k_compress<2, false, false, true>(CompressArgs);
+template __global__ void k_compress<8, true, false, true>(CompressArgs);
+template __global__ void k_compress<8, false, false, true>(CompressArgs);
 
 hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
     if (a.nblocks == 0) return hipSuccess;
@@ -353,7 +367,8 @@ hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
     }
     // small blocks (the reference's own input scale): several blocks per wave-tile -- uniform 16-byte aligned batches,
     // or ragged ones whose caller states an upper bound on the block lengths in in_len
-    if (a.in_len >= 5u && a.in_len <= 1024u && a.out_pitch >= (uint64_t)out_bound(a.in_len) &&
+    // (a call that asks for the end bits stays with k_compress, which reports them: the bytes are the same either way)
+    if (!a.end_bits && a.in_len >= 5u && a.in_len <= 1024u && a.out_pitch >= (uint64_t)out_bound(a.in_len) &&
         (a.in_off || ((a.in_pitch & 15u) == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0)))
         return launch_compress_small(a, stream, ncu);
     // (round 5: 256 waves queued per CU instead of 64 -- a wave's blocks all belong to one family when the families alternate with a
@@ -367,7 +382,10 @@ hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
     with_window(a.cwindow, [&](auto N, auto FW) {
         constexpr int NCH = decltype(N)::value;
         constexpr bool FULLWIN = decltype(FW)::value;
-        if (NCH == 1 && one_tile) hipLaunchKernelGGL((k_compress<1, FULLWIN, true>), grid, block, 0, stream, a);      // (32-wide windows only)
+        if (a.end_bits) {
+            if (NCH == 1 && one_tile) hipLaunchKernelGGL((k_compress<1, FULLWIN, true, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_compress<NCH, FULLWIN, false, true>), grid, block, 0, stream, a);
+        } else if (NCH == 1 && one_tile) hipLaunchKernelGGL((k_compress<1, FULLWIN, true>), grid, block, 0, stream, a);      // (32-wide windows only)
         else hipLaunchKernelGGL((k_compress<NCH, FULLWIN, false>), grid, block, 0, stream, a);
     });
     return hipGetLastError();

@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
-#include "../../include/hdlz.h"
+#include "../../include/hdlz_join.h"      // (includes hdlz.h)
 
 namespace hdlz {
 
@@ -20,6 +20,9 @@ struct CompressArgs {
     uint64_t out_pitch;
     uint32_t* out_len;
     uint32_t* status;
+    uint64_t* end_bits = nullptr;  // nullable (hdlz_compress_batch_bits): per block, the bit index -- from the row's first bit -- of the first bit of the
+                                   // end-of-block code; 0 for a block that fails.  Moves with out_len / status.  k_compress only: a call that asks
+                                   // for it never takes k_compress_small.
 };
 
 struct InflateArgs {
@@ -128,5 +131,11 @@ hipError_t launch_compact(const uint8_t* rows, uint64_t pitch, const uint32_t* l
 
 hipError_t launch_archive(const uint8_t* rows, uint64_t pitch, const uint32_t* len, uint64_t nblocks, uint8_t* archive, uint64_t cap,
                           uint64_t* off, hipStream_t stream, const Work& w);
+
+// hdlz_join.hip: the rows of hdlz_compress_batch_bits -> one zlib stream.  `work`: join_work_bytes(nblocks) bytes (null when that is 0).
+size_t join_work_bytes(uint64_t nblocks);
+hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
+                       const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, uint8_t* stream_out, uint64_t cap, uint64_t* off,
+                       hdlz_join_result* result, void* work, hipStream_t stream);
 
 }  // namespace hdlz

@@ -5,9 +5,9 @@ import functools
 import torch
 
 from . import _lib, host
-from .constants import OK, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
+from .constants import OK, E_SHORT_INPUT, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
 from .session import CompressSession, InflateSession
-from .errors import Error
+from .errors import Error, HdlzStatusError
 
 
 def _on_device(fn):
@@ -115,6 +115,49 @@ class Engine(object):
                                           self._stream())
         self._check(rc, "hdlz_compress_batch")
         return out, out_len, status
+
+    # -- STARTC for a flat buffer, block by block, as ONE standard zlib stream (include/hdlz_join.h)
+    @_on_device
+    def compress_joined(self, d_in, block=1 << 16, cwindow=32, maxmatch=10, out=None):
+        """d_in: flat uint8 device tensor of at least 5 bytes.  It is cut into blocks of `block` bytes (chain.plan_blocks: a tail under
+        5 bytes shortens the block before it), the blocks are compressed independently (hdlz_compress_batch_bits, a ragged batch with
+        the bound `block`) and joined into one stream that any inflater reads back as d_in (hdlz_join_batch_ws).
+        -> (stream uint8[stream_len], member_offsets int64[B + 1]): member b starts at member_offsets[b], the final empty block at
+        member_offsets[B].  `out`: the stream's buffer (default: hdlz_join_bound(B, block) bytes).  One host sync (the result record);
+        raises HdlzStatusError on a status that is not OK.  An input that does not start at a multiple of 16 or has fewer than 16
+        bytes of its storage behind it (the compress kernels load whole 16-byte pieces) is copied to a padded buffer first."""
+        from .chain import plan_blocks
+        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.dim() == 1 and d_in.is_contiguous() and d_in.device == self.device
+        if not 32 <= block < (1 << 31):
+            raise ValueError("block must be in [32, 2^31)")           # (plan_blocks may shorten a block by 16 bytes; a block is below 2 GiB)
+        n = d_in.numel()
+        plan = plan_blocks(n, block)
+        B, dev = len(plan), d_in.device
+        slack = d_in.untyped_storage().nbytes() - d_in.storage_offset() - n
+        if d_in.data_ptr() % 16 or slack < 16:
+            d_in = self._stage(d_in)
+        in_off = torch.tensor([o for o, _ in plan] + [n], dtype=torch.int64).to(dev)
+        pitch = pitch_for(block)
+        rows, out_len, status = self._results(None, (B, pitch), B, dev)
+        end_bits = torch.empty(B, dtype=torch.int64, device=dev)
+        cap = self.lib.hdlz_join_bound(B, block)
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+        offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        result = torch.empty(2, dtype=torch.int64, device=dev)                     # hdlz_join_result: 16 bytes
+        work = torch.empty(max(8, self.lib.hdlz_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)
+        rc = self.lib.hdlz_compress_batch_bits(d_in.data_ptr(), in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
+                                               out_len.data_ptr(), status.data_ptr(), end_bits.data_ptr(), self._stream())
+        self._check(rc, "hdlz_compress_batch_bits")
+        rc = self.lib.hdlz_join_batch_ws(rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(),
+                                         in_off.data_ptr(), block, B, out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
+                                         work.data_ptr(), work.numel() * 8, self._stream())
+        self._check(rc, "hdlz_join_batch_ws")
+        rec = _lib.JoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+        if rec.status != OK:
+            raise HdlzStatusError(rec.status, "compress_joined")
+        return out[:rec.stream_len], offsets
 
     # -- STARTC for ONE large stream, spread over the whole GPU (same bytes as compress_batch with one block)
     STREAM_MIN = 1 << 14          # measured crossover with the single-wave batch path: ~8 KiB
@@ -265,8 +308,17 @@ class Engine(object):
 
     # -- single-stream conveniences used by the port adapter (one START = one block)
     @_on_device
-    def compress_bytes(self, data, cwindow=32, maxmatch=10):
-        """-> (status, bytes)"""
+    def compress_bytes(self, data, cwindow=32, maxmatch=10, block=None):
+        """-> (status, bytes).  block=None: ONE block, what STARTC writes; a number: the input in blocks of that many bytes, joined into
+        one standard zlib stream (compress_joined)"""
+        if block is not None:
+            if len(data) < 5:
+                return E_SHORT_INPUT, b""
+            try:
+                z, _ = self.compress_joined(self._stage(data)[:len(data)], block=block, cwindow=cwindow, maxmatch=maxmatch)
+            except HdlzStatusError as e:
+                return e.status, b""
+            return OK, bytes(z.cpu().numpy().tobytes())
         out, ol, st = self._compress_one(self._stage(data), len(data), cwindow, maxmatch)
         return int(st.item()), bytes(out[:int(ol.item())].cpu().numpy().tobytes())
 
