@@ -14,11 +14,6 @@ fi
 if [ "${1:-}" = "keys" ]; then
   HDLZ_VARIANT=keys HDLZ_DEFS="-DHDLZ_SEARCH_KEYS" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
 fi
-# `build.sh shared` builds lib/libhdlz_shared.so: the one-tile kernel with the extension's gathers from the shared tile layout instead of
-# the lane-private candidate windows (tools/ab.sh times the two against each other)
-if [ "${1:-}" = "shared" ]; then
-  HDLZ_VARIANT=shared HDLZ_DEFS="-DHDLZ_EXT_SHARED" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
-fi
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"

@@ -17,11 +17,11 @@
 //      over the 32 candidates IS four times the nearest matching distance: one v_sub + half a v_min3
 //      per compare, no branches (-DHDLZ_SEARCH_KEYS: the one-tile kernels too, for A/B).
 //   3. extension (R5): 8-byte LDS gather at p-d+3, xor with the own bytes, count-trailing-zeros.  The one-tile kernels with the bit
-//      search gather from LANE-PRIVATE WINDOWS: behind the stage every lane copies the 19 dwords [32l - 32, 32l + 44) of the tile -- all
-//      it can gather -- to W[l] at an odd dword stride (copy_windows, WaveLdsWin), so lanes at the same relative offset sit in 64
-//      different banks instead of 8 (the shared layout: 32 bytes per lane); W overlays the tile and the bit buffer (zeroed behind the
-//      extension), and the own bytes of the search, the Adler sums and the extension stay in the copy's registers.
-//      (-DHDLZ_EXT_SHARED: the shared layout, for A/B.)
+//      search compare nothing again: the search keeps its mismatch word of every distance in LDS (NEQ[d & 31][lane], WaveLdsBits), and
+//      the length is the run of zero bits from bit i + 3 of the chosen distance's word (make_tokens_bits: one or two conflict-free
+//      ds_read_b32 and 12 VALU instructions per position).  NEQ is the wave's whole LDS: it overlays the staged tile (the own bytes of
+//      the search, the Adler sums and the literals stay in registers), and behind the extension the bit buffer and the LUT -- a constant
+//      table, fetched per tile by LDS-DMA under the parse -- take its place.
 //   4. greedy parse ("di += m / di += 1", deflate.py:960,1008): every lane folds its run into a
 //      transfer function "entry skip (0..9) -> exit skip", 10 nibbles packed in 40 bits, by a
 //      backward pass; a 64-step scalar readlane chain composes them across the wave.
@@ -88,16 +88,18 @@ __device__ __forceinline__ void store_words(uint32_t* __restrict__ dst, const ui
 template <int NCH, bool FULLWIN, bool ONE_TILE, bool ENDBITS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH>(), waves_eu<NCH>()))) void k_compress(CompressArgs a) {
     constexpr bool HASH = wide_hash<NCH>();         // windows > 32: the window-independent finder
-    constexpr bool WIN = ONE_TILE && NCH == 1 && ext_windows();      // lane-private candidate windows for the extension (WaveLdsWin)
-    __shared__ typename std::conditional<HASH, WaveLdsNoOut, typename std::conditional<WIN, WaveLdsWin, WaveLds>::type>::type lds;
+    constexpr bool BITS = ONE_TILE && NCH == 1 && search_bits();     // bit-sliced search whose mismatch words are the extension (WaveLdsBits)
+    __shared__ typename std::conditional<HASH, WaveLdsNoOut, typename std::conditional<BITS, WaveLdsBits, WaveLds>::type>::type lds;
     __shared__ typename std::conditional<HASH, HashLds<NCH>, uint32_t>::type hl;
     // the bit buffer of a tile: HASH kernels keep it in the finder's transposition buffer, which is dead once best[] is in registers
     // (28 KB of LDS per wave left ONE wave per SIMD: VALU 31 %, LDS 39 % busy -- this kernel lives on overlapping the two)
     uint32_t* const lout = lds_out(lds, hl);
     const uint32_t lane = threadIdx.x;
 
-    fill_luts<NCH>(lds.lut, lane);                  // per-wave look-up tables (once per wave lifetime)
-    __syncthreads();
+    if constexpr (!BITS) {                          // (BITS: the LUT's memory is NEQ's until the extension is through -- fetched per tile)
+        fill_luts<NCH>(lds.lut, lane);              // per-wave look-up tables (once per wave lifetime)
+        __syncthreads();
+    }
 
     const uint32_t cw4 = 4u * (uint32_t)a.cwindow;
     const uint32_t kmax = (uint32_t)a.maxmatch;
@@ -138,6 +140,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
         if (lane < nfull) lds_dma16(tsrc + 16u * lane, in_base);
         if (lane + 64u < nfull) lds_dma16(tsrc + 16u * (lane + 64u), in_base + 1024u);
         if (nfull > 128u) { if (lane == 0u) lds_dma16(tsrc + 2048u, in_base + 2048u); }
+    };
+    // BITS: the constant LUT (2 KB, L2-resident) -> lds.lut, two requests per lane; covered by the vmcnt wait in front of `codes`
+    [[maybe_unused]] const uint32_t lut_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)reinterpret_cast<uintptr_t>(lds.lut));
+    auto request_lut = [&]() {
+        const uint8_t* t = reinterpret_cast<const uint8_t*>(FIXED_LUT.e) + 16u * lane;
+        lds_dma16(t, lut_base);
+        lds_dma16(t + 1024u, lut_base + 1024u);
     };
 
     TT_DECL();
@@ -185,8 +194,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                     if (lane == 0u) *reinterpret_cast<uint4*>(lin8 + HALO + nfull * 16u) = load_chunk16(src, t0 + nfull * 16u, n, aligned16, mis);
                 }
             }
-            // zero the bit buffer, seed the carry (WIN: it overlays the tile -- behind the extension, like the hash kernels)
-            if constexpr (!HASH && !WIN) zero_bit_buffer(lout, lane, carry_word);
+            // zero the bit buffer, seed the carry (BITS: it overlays the tile and NEQ -- behind the extension, like the hash kernels)
+            if constexpr (!HASH && !BITS) zero_bit_buffer(lout, lane, carry_word);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the tile has landed (and the last tile's output stores have left)
             wave_lds_order();
 
@@ -195,9 +204,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             const uint32_t p_run = t0 + lane * RUN;                   // first position of this run
             const uint32_t nrem = n - min(p_run, n);                  // positions of the block from p_run on
             uint32_t best[RUN], tok[RUN], code[RUN];
-            [[maybe_unused]] uint32_t oww[12];                    // WIN: the own bytes, in registers from here to the extension
-            if constexpr (WIN) {
-                copy_windows(lds.in, lds.win, lane, oww);         // the tile -> one 19-dword window per lane; `in` is dead from here on
+            [[maybe_unused]] uint32_t oww[12];                    // BITS: the own bytes, in registers from here to the extension
+            if constexpr (BITS) {
+                load_own(lds.in, run_dw, oww);                    // `in` is dead from here on: every lane's reads have returned before
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the search writes the first row of NEQ over it
                 wave_lds_order();
             }
             TT(1);                                                // stage (HBM latency, LDS writes, bit buffer zeroing)
@@ -214,15 +224,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 zero_bit_buffer(lout, lane, carry_word);                                           // (ordered before the scatter by the fences below)
             }
 #ifndef HDLZ_SEARCH_KEYS                                                                           // (-DHDLZ_SEARCH_KEYS: the key form, for A/B)
-            else if constexpr (WIN) match_search_bits(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], best);
-            else if constexpr (ONE_TILE && NCH == 1) match_search_bits(lds.in, run_dw, best);      // 2. R3/R4 (a one-tile block: bit planes, history by DPP)
+            else if constexpr (BITS)                                                               // 2. R3/R4 (a one-tile block: bit planes, history by DPP)
+                match_search_bits<true>(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], best, lds.neq + lane);
 #endif
             else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                    // 2. R3/R4 (a one-tile block: candidate keys by DPP)
             {
                 TT(2);
                 HDLZ_MARK("adler");
-                uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (WIN: still in registers; else reloaded: see match_search)
-                if constexpr (WIN) {
+                uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (BITS: still in registers; else reloaded: see match_search)
+                if constexpr (BITS) {
 #pragma unroll
                     for (int k = 0; k < 12; k++) ow[k] = oww[k];
                 } else load_own(lds.in, run_dw, ow);
@@ -241,18 +251,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 if constexpr (!HASH) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(HDLZ_HP_EXTEND);
                 HDLZ_MARK("extend");
-                if constexpr (WIN) {
-                    make_tokens<NCH, FULLWIN, true, GATHER_NOMASK>(lds.win, (uint32_t)(WIN_PAD + WIN_OWN) + 4u * WIN_DW * lane, ow, best, cw4, kmax,
-                                                                   4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));      // 3. R5, from W[lane]
+                if constexpr (BITS) {
+                    wave_lds_order();                             // (every lane's rows are written)
+                    make_tokens_bits<FULLWIN>(lds.neq, lane, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5, from NEQ
                 } else
                 make_tokens<NCH, FULLWIN, true>(lds.in, HALO + lane * RUN, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5
             }
             pin(tok);
             PHASE_FENCE();
             TT(4);
-            if constexpr (WIN) {                                  // W is dead (every gather has returned: tok is pinned): the bit buffer takes its place,
-                HDLZ_MARK("zero");                                // ordered before the scatter by the fences below
+            if constexpr (BITS) {                                 // NEQ is dead (every read has returned: tok is pinned): the LUT and the bit buffer
+                HDLZ_MARK("zero");                                // take its place, ordered before codes / the scatter by the wait and the fences below
                 wave_lds_order();
+                request_lut();
                 zero_bit_buffer(lout, lane, carry_word);
             }
             if constexpr (HASH) __builtin_amdgcn_s_setprio(HDLZ_HP_REST);
@@ -265,6 +276,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             PHASE_FENCE();
             TT(6);
             HDLZ_MARK("codes");
+            if constexpr (BITS) {                                 // the LUT has landed (its latency ran under zero, parse and chain)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                wave_lds_order();
+            }
             uint32_t lane_bits = token_codes<NCH, false>(lut8, tok, myskip, 0u, code);             // 5. R6/R7
             pin(code);
             PHASE_FENCE();

@@ -3,6 +3,7 @@
 //  hdlz_compress_stream.hip: one large stream / a few large blocks spread over the whole GPU)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "hdlz_device.h"
 
@@ -40,43 +41,45 @@ struct __attribute__((aligned(16))) WaveLds {
     uint32_t lut[LUT_LIT + LUT_MATCH + LUT_LEN];
 };
 
-constexpr uint32_t GATHER_NOMASK = 0x3FFFFFFFu;           // make_tokens' GMASK of a layout whose gathers need none
 constexpr uint32_t GATHER_SPAN = 4u * (0x3FFu + 3u);      // bytes behind `in` that make_tokens' masked gather may touch (GMASK = 0x3FF)
 static_assert(sizeof(WaveLds) >= GATHER_SPAN, "make_tokens: masked gather inside the LDS block");
 
-// ---- the one-tile kernels with the bit-sliced search (k_compress<1, ., true>): LANE-PRIVATE CANDIDATE WINDOWS for the extension.
-// In `in` lane l owns the 32 bytes at HALO + 32 l, so 64 lanes that gather at the same relative offset hit 8 of the 64 banks: every
-// gather of make_tokens is 8-way conflicted by construction.  All a lane gathers there (positions 32 l + i, d <= 32, bytes p - d + 3 ..
-// p - d + 14) lies in the 76 bytes [32 l - 32, 32 l + 44) = 19 dwords: copy_windows gives every lane its own copy W[l] at a stride of 19
-// dwords -- odd, so lanes at the same offset sit in 64 different banks.  W overlays `in` (the bytes go through registers) and the bit
-// buffer (zeroed behind the extension); WIN_PAD bytes in front keep the gather of a position without a candidate (result 0xFF: distance
-// 63) inside the block without a mask.  -DHDLZ_EXT_SHARED (and the key search, whose raw minima need the mask): the shared layout, for A/B.
-constexpr int WIN_DW = 19;                                // dwords of a lane's window: 32 bytes of history, 32 own, 12 look-ahead
-constexpr int WIN_PAD = 32;                               // bytes in front of W[0]
-constexpr int WIN_OWN = 32;                               // byte offset of the lane's own run inside its window
-constexpr int WIN_BYTES = WIN_PAD + 64 * 4 * WIN_DW;      // 4896
-constexpr bool ext_windows() {
-#if defined(HDLZ_EXT_SHARED) || defined(HDLZ_SEARCH_KEYS)
+// ---- the one-tile kernels with the bit-sliced search (k_compress<1, ., true>): THE SEARCH'S MISMATCH WORDS are the extension.
+// For every distance d match_search_bits computes neq_d -- bit j = byte j of the lane's run differs from the byte d positions earlier --
+// and the match length at position i is the run of zero bits of (neq_d of the next lane : neq_d) from bit i + 3 on.  The search keeps the
+// words: NEQ[(d & 31) * 64 + lane], one ds_write_b32 per distance at a fixed address register + immediate offset; make_tokens_bits reads
+// the word of the position's distance back (column = lane: bank = lane, conflict-free whatever the rows) instead of gathering and
+// comparing bytes.  d = 32 aliases row 0 (no distance 0 exists); "none" (result byte 0xFF) reads row 31, inside the array, and is discarded.
+// The LDS timeline of a tile:   stage: in | own bytes -> registers | search: NEQ | extend: NEQ | fixed LUT -> lut (LDS-DMA), zero: out |
+// parse, chain | codes: lut | scatter, flush: out.   NEQ is the whole LDS budget of a wave (8192 bytes: 20 waves per CU), so the staged
+// tile in front of the search and the bit buffer + the LUT behind the extension share its memory.
+constexpr int NEQ_ROWS = 32;                              // row = d & 31
+constexpr int NEQ_WORDS = NEQ_ROWS * 64;                  // [row][lane]
+constexpr int FIXED_LUT_WORDS = LUT_LIT + LUT_MATCH;      // the 512 entries these kernels use (LUT_LEN belongs to the wide windows)
+constexpr bool search_bits() {                            // -DHDLZ_SEARCH_KEYS: the key search + WaveLds + the byte-gather make_tokens, for A/B
+#ifdef HDLZ_SEARCH_KEYS
     return false;
 #else
     return true;
 #endif
 }
-struct __attribute__((aligned(16))) WaveLdsWin {
+struct __attribute__((aligned(16))) WaveLdsBits {
     union {
-        uint32_t in[IN_BYTES / 4];      // the staged tile, until copy_windows has read it
-        uint32_t win[WIN_BYTES / 4];    // pad + W[0 .. 64): what make_tokens gathers from
-        uint32_t out[OUT_WORDS];        // bit buffer of the tile, zeroed once the extension is through
+        uint32_t in[IN_BYTES / 4];      // the staged tile, until load_own has read the runs
+        uint32_t neq[NEQ_WORDS];        // the mismatch words, from the search to the end of the extension
+        struct {
+            uint32_t out[OUT_WORDS];    // bit buffer of the tile, zeroed once the extension is through
+            uint32_t gap[NEQ_WORDS - OUT_WORDS - FIXED_LUT_WORDS];
+            uint32_t lut[FIXED_LUT_WORDS];      // FIXED_LUT, fetched once the extension is through
+        };
     };
-    uint32_t lut[LUT_LIT + LUT_MATCH + LUT_LEN];
 };
-// the gather of position i of lane l at distance d (1 .. 32 found, 63 = none) reads the three dwords from byte
-// (WIN_PAD + 76 l + WIN_OWN + i + 3 - d) & ~3 on: inside [0, WIN_BYTES) for every lane, position and distance -- no mask
-static_assert(WIN_PAD + WIN_OWN + 3 - 63 >= 0, "make_tokens: the gather of a position without a candidate starts inside the LDS block");
-static_assert(((WIN_PAD + 4 * WIN_DW * 63 + WIN_OWN + 31 + 3 - 1) & ~3) + 12 <= WIN_BYTES, "make_tokens: the farthest gather ends inside W");
-static_assert(WIN_OWN + 3 - 32 >= 0 && ((WIN_OWN + 31 + 3 - 1) & ~3) + 12 <= 4 * WIN_DW, "a real candidate's gather stays inside the lane's window");
-static_assert(WIN_BYTES % 16 == 0 && WIN_BYTES >= IN_BYTES && WIN_BYTES >= 4 * OUT_WORDS && sizeof(WaveLdsWin) <= 8192 - 16, "20 waves per CU");
-static_assert(HALO >= 32 && LOOKAHEAD >= 16, "copy_windows: lane 0 reads 32 bytes of halo, lane 63 sixteen behind the tile");
+// make_tokens_bits reads byte (d4 & 0x7C) * 64 + 4 * column, d4 = 4 d (d = 1 .. 32) or 0xFF, column = lane or min(lane + 1, 63)
+static_assert((0x7C << 6) + 4 * 63 + 4 <= 4 * NEQ_WORDS && ((0xFF & 0x7C) << 6) == 4 * 64 * 31, "every read of the extension inside NEQ; none -> row 31");
+static_assert(((4 * 32) & 0x7C) == 0 && (31 * 64 + 63) < NEQ_WORDS, "d = 32 aliases row 0; the search's last row ends inside NEQ");
+static_assert(sizeof(WaveLdsBits) == 8192 && 4 * NEQ_WORDS >= IN_BYTES, "20 waves per CU; the staged tile inside the block");
+static_assert(offsetof(WaveLdsBits, lut) >= 4 * OUT_WORDS && offsetof(WaveLdsBits, lut) % 16 == 0 && 4 * FIXED_LUT_WORDS == 2 * 64 * 16,
+              "zero_bit_buffer leaves the LUT alone; the LUT is two 16-byte LDS-DMA requests per lane");
 
 struct __attribute__((aligned(16))) WaveLdsNoOut {       // kernels with the hash finder: the bit buffer lives in HashLds::D's memory
     uint32_t in[IN_BYTES / 4];
@@ -121,7 +124,7 @@ __device__ __forceinline__ uint32_t key3(const uint32_t* d, uint32_t tag) {
 // ---- fixed Huffman token bits (used to fill the LUTs) ---------------------------------------
 // literal (R7, deflate.py:1005-1016 + out_codes :112-149): sym<144 -> 8 bits rev8(0x30+sym),
 // else 9 bits rev9(0x100+sym)
-__device__ __forceinline__ uint32_t literal_entry(uint32_t b) {
+__host__ __device__ constexpr uint32_t literal_entry(uint32_t b) {
     const bool big = b >= 144u;
     const uint32_t v = big ? (0x100u + b) : (0x30u + b);
     const uint32_t nb = big ? 9u : 8u;
@@ -129,12 +132,10 @@ __device__ __forceinline__ uint32_t literal_entry(uint32_t b) {
 }
 // distance part of a match token (R6, deflate.py:836-882): rev5(dist code) | extra<<5 in 5+eb bits,
 // placed behind the 7-bit length code; nbits = 12 + eb
-__device__ __forceinline__ uint32_t dist_entry(uint32_t d) {
+__host__ __device__ constexpr uint32_t dist_entry(uint32_t d) {
     const uint32_t dd = d - 1u;
-    uint32_t c, eb, extra;
-    if (dd < 4u) {
-        c = dd; eb = 0; extra = 0;
-    } else {
+    uint32_t c = dd, eb = 0, extra = 0;
+    if (dd >= 4u) {
         const uint32_t hb = 31u - (uint32_t)__builtin_clz(dd);
         eb = hb - 1u;
         c = 2u * hb + ((dd >> eb) & 1u);
@@ -144,7 +145,30 @@ __device__ __forceinline__ uint32_t dist_entry(uint32_t d) {
     return ((dcode | (extra << 5)) << 7) | ((12u + eb) << NB_SHIFT);
 }
 // 7-bit code of length symbol 254+m (no extra bits for m <= 10)
-__device__ __forceinline__ uint32_t length_code(uint32_t m) { return __builtin_bitreverse32(m - 2u) >> 25; }
+__host__ __device__ constexpr uint32_t length_code(uint32_t m) { return __builtin_bitreverse32(m - 2u) >> 25; }
+// pinned against RFC 1951 3.2.5 / 3.2.6 (codes go out LSB first, so a Huffman code is stored bit-reversed; extra bits are not):
+static_assert(literal_entry(0) == (0x0Cu | 8u << NB_SHIFT), "literal 0: 8 bits, 00110000 reversed");
+static_assert(literal_entry(143) == (0xFDu | 8u << NB_SHIFT), "literal 143: 8 bits, 10111111 reversed");
+static_assert(literal_entry(144) == (0x13u | 9u << NB_SHIFT), "literal 144: 9 bits, 110010000 reversed");
+static_assert(literal_entry(255) == (0x1FFu | 9u << NB_SHIFT), "literal 255: 9 bits, all ones");
+static_assert(length_code(3) == 0x40u && length_code(10) == 0x08u, "lengths 3 / 10: symbols 257 / 264 = 7-bit codes 0000001 / 0001000 reversed");
+static_assert(dist_entry(1) == (12u << NB_SHIFT), "distance 1: code 0, no extra bits: 7 + 5 bits");
+static_assert(dist_entry(5) == ((0x04u << 7) | 13u << NB_SHIFT), "distance 5: code 4 (00100), one extra bit 0");
+static_assert(dist_entry(32) == (((0x12u | 7u << 5) << 7) | 15u << NB_SHIFT), "distance 32: code 9 (01001 reversed), three extra bits 111");
+
+// the LUT of the CWINDOW <= 32 kernels -- literal [byte] at word 0, match [len-3][dist-1] at word 256 -- depends on nothing: ONE constant
+// table.  The one-tile kernels with the bit search fetch it into LDS per tile (their LDS is the mismatch words until the extension is
+// through: WaveLdsBits); fill_luts computes the same entries per wave for the kernels that keep a resident LUT.
+__host__ __device__ constexpr uint32_t match_entry32(uint32_t e) { return dist_entry((e & 31u) + 1u) | length_code((e >> 5) + 3u); }
+struct __attribute__((aligned(16))) FixedLut { uint32_t e[LUT_LIT + LUT_MATCH]; };
+constexpr FixedLut make_fixed_lut() {
+    FixedLut t{};
+    for (uint32_t k = 0; k < (uint32_t)LUT_LIT; k++) t.e[k] = literal_entry(k);
+    for (uint32_t k = 0; k < (uint32_t)LUT_MATCH; k++) t.e[LUT_LIT + k] = match_entry32(k);
+    return t;
+}
+static __device__ const FixedLut FIXED_LUT = make_fixed_lut();
+static_assert(make_fixed_lut().e[LUT_LIT + 32 * 7 + 31] == (dist_entry(32) | length_code(10)), "match [len - 3][dist - 1]");
 
 // =====================================================================================================================
 // The tile phases.  ONE source for all compress kernels: k_compress (one block per wave, hdlz_compress.hip),
@@ -163,30 +187,6 @@ __device__ __forceinline__ void load_own(const uint32_t* in, uint32_t run_dw, ui
     ow[0] = v0.x; ow[1] = v0.y; ow[2] = v0.z; ow[3] = v0.w;
     ow[4] = v1.x; ow[5] = v1.y; ow[6] = v1.z; ow[7] = v1.w;
     ow[8] = v2.x; ow[9] = v2.y; ow[10] = v2.z; ow[11] = v2.w;
-}
-
-// ---- the lane's candidate window (WaveLdsWin): the 19 dwords at HALO + 32 l - 32 of the staged tile (16-byte aligned: five
-// ds_read_b128; lane 0 gets the zero halo, lane 63 the zero look-ahead) -> W[l], 19 dwords at a 19-dword stride (4-byte aligned:
-// ds_write2_b32, bank 19 l + k: conflict-free).  `win` overlays `in`: every lane's reads have returned (lgkmcnt(0)) before any lane
-// writes.  The own 32 bytes + 12 of look-ahead stay in registers (ow[11], the 20th dword read, is not part of the window: make_tokens indexes ow[10] at most),
-// so neither the search nor the later phases read them back.
-__device__ __forceinline__ void copy_windows(const uint32_t* in, uint32_t* win, uint32_t lane, uint32_t (&ow)[12]) {
-    const uint32_t src_dw = (HALO / 4) + lane * (RUN / 4) - 8u;
-    const uint4 v0 = *reinterpret_cast<const uint4*>(&in[src_dw]);
-    const uint4 v1 = *reinterpret_cast<const uint4*>(&in[src_dw + 4]);
-    const uint4 v2 = *reinterpret_cast<const uint4*>(&in[src_dw + 8]);
-    const uint4 v3 = *reinterpret_cast<const uint4*>(&in[src_dw + 12]);
-    const uint4 v4 = *reinterpret_cast<const uint4*>(&in[src_dw + 16]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    uint32_t* w = win + (WIN_PAD / 4) + (uint32_t)WIN_DW * lane;
-    w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w;
-    w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
-    w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
-    w[12] = v3.x; w[13] = v3.y; w[14] = v3.z; w[15] = v3.w;
-    w[16] = v4.x; w[17] = v4.y; w[18] = v4.z;
-    ow[0] = v2.x; ow[1] = v2.y; ow[2] = v2.z; ow[3] = v2.w;
-    ow[4] = v3.x; ow[5] = v3.y; ow[6] = v3.z; ow[7] = v3.w;
-    ow[8] = v4.x; ow[9] = v4.y; ow[10] = v4.z; ow[11] = v4.w;
 }
 
 // ---- phase 2, match search (R3/R4; the reference's matcher3 x CWINDOW + first-set-bit pick, deflate.py:407-421, :975-994):
@@ -340,9 +340,12 @@ __device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uin
     t0 = __builtin_amdgcn_perm(a23, a01, cat_lo); t1 = __builtin_amdgcn_perm(a23, a01, cat_hi);
     t2 = __builtin_amdgcn_perm(b23, b01, cat_lo); t3 = __builtin_amdgcn_perm(b23, b01, cat_hi);
 }
-// (x0 .. x7: the lane's own 32 bytes as dwords, from LDS or -- copy_windows -- already in registers)
+// (x0 .. x7: the lane's own 32 bytes as dwords, in registers)
+// KEEP: neq_d of every distance goes to neq_col[(d & 31) * 64] (neq_col = NEQ + lane: one ds_write_b32 at a fixed address register +
+// immediate offset, where neq is complete and before the DPP for nx) -- what make_tokens_bits reads instead of comparing bytes again
+template <bool KEEP>
 __device__ __forceinline__ void match_search_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t x5, uint32_t x6,
-                                                  uint32_t x7, uint32_t (&best)[RUN]) {
+                                                  uint32_t x7, uint32_t (&best)[RUN], [[maybe_unused]] uint32_t* neq_col = nullptr) {
     uint32_t O[8], P[8];
     // O[k] byte m = own byte k + 8 m (k = 0..7): bytes k, k + 8, k + 16, k + 24 are byte k & 3 of dwords k >> 2, +2, +4, +6
     transpose4x4_bytes(x0, x2, x4, x6, O[0], O[1], O[2], O[3]);
@@ -361,6 +364,7 @@ __device__ __forceinline__ void match_search_bits(uint32_t x0, uint32_t x1, uint
             const uint32_t c = d == 32 ? P[b] : __builtin_amdgcn_alignbit(O[b], P[b], (uint32_t)(32 - d));
             neq = b == 0 ? O[0] ^ c : bitop3<B3_OR_XOR>(neq, O[b], c);
         });
+        if constexpr (KEEP) neq_col[(d & (NEQ_ROWS - 1)) * 64] = neq;
         const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)neq, 0x130, 0xF, 0xF, true);                      // wave_shl:1 (lane 63: 0)
         const uint32_t n3 = bitop3<B3_OR3>(neq, __builtin_amdgcn_alignbit(nx, neq, 1u), __builtin_amdgcn_alignbit(nx, neq, 2u));
         static_for<0, 6>([&](auto K) {
@@ -381,12 +385,6 @@ __device__ __forceinline__ void match_search_bits(uint32_t x0, uint32_t x1, uint
         best[k + 24] = Q[k] >> 24;
     }
 }
-__device__ __forceinline__ void match_search_bits(const uint32_t* in, uint32_t run_dw, uint32_t (&best)[RUN]) {
-    const uint4 v0 = *reinterpret_cast<const uint4*>(&in[run_dw]);
-    const uint4 v1 = *reinterpret_cast<const uint4*>(&in[run_dw + 4]);
-    match_search_bits(v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, best);
-}
-
 // ---- phase 2 for WIDE windows: a window-independent match finder ------------------------------------------
 // "Nearest previous occurrence of the same 3-byte string" (matcher3 x CWINDOW + first-set-bit pick, deflate.py:407-421, :966-1016)
 // is a predecessor query; its cost need not grow with the window.  match_search pays 1.5 VALU instructions per (position,
@@ -432,7 +430,7 @@ template <int NCH> struct __attribute__((aligned(16))) HashLds {
 };
 
 __device__ __forceinline__ uint32_t* lds_out(WaveLds& l, uint32_t&) { return l.out; }
-__device__ __forceinline__ uint32_t* lds_out(WaveLdsWin& l, uint32_t&) { return l.out; }
+__device__ __forceinline__ uint32_t* lds_out(WaveLdsBits& l, uint32_t&) { return l.out; }
 template <int NCH> __device__ __forceinline__ uint32_t* lds_out(WaveLdsNoOut&, HashLds<NCH>& h) {
     static_assert(sizeof(h.T) >= sizeof(uint32_t) * OUT_WORDS, "the bit buffer overlays T / D");
     return h.T;
@@ -671,8 +669,6 @@ template <class F> inline void with_window(int cwindow, F&& f) {
 //            2^32 - 1 stands for "none") would address LDS far outside `in`; masked, it stays inside the first 4 (GMASK + 3) bytes behind
 //            `in` -- which every caller's LDS block covers (static_assert there) -- and its result is discarded as before.  The mask
 //            replaces the ~3 of the dword address: no instruction more.  (an out-of-allocation LDS read.)
-//            GATHER_NOMASK (the lane-private windows of WaveLdsWin, whose search returns 4 d <= 128 or 0xFF): no address leaves the block
-//            (static_asserts there); what remains is the ~3 itself.
 template <int NCH, bool FULLWIN, bool SCALAR_TAIL = false, uint32_t GMASK = 0x3FFu>
 __device__ __forceinline__ void make_tokens(const uint32_t* in, uint32_t lds_run, uint32_t (&ow)[12], uint32_t (&best)[RUN],
                                             uint32_t cw4, uint32_t kmax, uint32_t p4_run, uint32_t nrem, uint32_t (&tok)[RUN],
@@ -731,6 +727,60 @@ __device__ __forceinline__ void make_tokens(const uint32_t* in, uint32_t lds_run
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(mt) : "v"(l3), "s"(tok_mul), "v"(d4 + tok_k));
         asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(tok[i]) : "v"(lit), "v"(mt), "s"(okm));      // tok = ok ? mt : lit
         // (positions per scheduling group: the gathers of a group are in flight together; profiles/r05_tile_timing.txt)
+        constexpr int EG = HDLZ_EXT_GROUP;
+        if constexpr ((i & (EG - 1)) == EG - 1) { pin_range<(i & ~(EG - 1)), (i & ~(EG - 1)) + EG>(tok); PHASE_FENCE(); }
+    });
+}
+
+// ---- phase 3 of the one-tile kernels with the bit search: the same tok[] and the same eligibility test, the LENGTH from the mismatch
+// words the search kept (WaveLdsBits::neq) instead of a byte compare.  For position i of the lane and its distance d, bit j of neq_d says
+// x[32 l + j] != x[32 l + j - d], so len - 3 = the zero bits of (neq_d of lane l + 1 : neq_d) from bit i + 3 on, capped like the byte form:
+//   word   NEQ[(d & 31) * 64 + l]: byte offset (d4 & 0x7C) << 6 + 4 l.  d = 32 reads row 0, "none" (0xFF) row 31 (discarded)
+//   i <= 22: bits i + 3 .. i + 9 lie in the lane's own word -- a plain shift (at most Kmax - 3 <= 7 bits count);  i = 23 .. 28: the
+//          next lane's word of the same row too, one v_alignbit;  i >= 29: bit i + 3 is bit i - 29 of the next lane's word -- that word
+//          alone, a plain shift.  Lane 63 has no next lane: it reads its own word in that place (col_hi = 4 * min(l + 1, 63)), and
+//          N - 5 - p <= 27 - i caps what those bits could add (i + 3 + 27 - i <= 31: inside the own word; i >= 28 is not eligible there)
+//   l3     min3(ffbl(x), Kmax - 3, N - 5 - p): v_ffbl_b32(0) = 0xFFFFFFFF needs no sentinel under the cap
+// Lane 0's bits j < d compare against lane 63's bytes (the search's rotate): a position i of lane 0 is eligible only for d <= i, and its
+// bits j >= i + 3 > d look at the block's own bytes.  12 VALU instructions per position (13 for i >= 23) against 22, one or two
+// conflict-free ds_read_b32 (bank = column, whatever the row) against three gathered dwords.
+template <bool FULLWIN>
+__device__ __forceinline__ void make_tokens_bits(const uint32_t* neq, uint32_t lane, uint32_t (&ow)[12], uint32_t (&best)[RUN], uint32_t cw4,
+                                                 uint32_t kmax, uint32_t p4_run, uint32_t nrem, uint32_t (&tok)[RUN], int32_t tile_rem) {
+    pin(best); pin_range<0, 8>(ow);
+    PHASE_FENCE();
+    const uint32_t nrem_m5 = nrem - 5u;                       // (wraps when nrem < 5: then nothing is eligible)
+    const uint32_t kmax_m3 = min(kmax - 3u, 7u);              // (MAXMATCH is 5 or 10: the clamp keeps the single-word shift exact whatever comes in)
+    const int32_t rem5 = tile_rem - 5;                        // R3's "p <= N - 5" as lane masks: see make_tokens (SCALAR_TAIL)
+    const uint32_t thr = rem5 >= 0 ? ((uint32_t)rem5 & 31u) : 0u;
+    const int32_t cnt_hi = rem5 >= 0 ? (rem5 >> 5) + 1 : 0, cnt_lo = rem5 >= 0 ? (rem5 >> 5) : 0;
+    const uint64_t m_hi = cnt_hi >= 64 ? ~0ull : ((1ull << cnt_hi) - 1ull), m_lo = cnt_lo >= 64 ? ~0ull : ((1ull << cnt_lo) - 1ull);
+    const uint32_t tok_k = (2u << 18) + LUT_MATCH_BYTE - 4u;  // token word of a match: l3 * tok_mul + 4 d + tok_k (make_tokens)
+    const uint32_t tok_mul = 4u * 65536u + 128u;
+    const uint8_t* neq8 = reinterpret_cast<const uint8_t*>(neq);
+    const uint32_t col_lo = 4u * lane, dcol = 4u * min(lane + 1u, 63u) - col_lo;      // col_hi = col_lo + dcol
+    static_for<0, RUN>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        const uint32_t d4 = best[i];
+        uint64_t okm = __builtin_amdgcn_ballot_w64(d4 <= p4_run + (uint32_t)(4 * i));
+        if constexpr (!FULLWIN) okm &= __builtin_amdgcn_ballot_w64(d4 <= cw4);
+        okm &= ((uint32_t)i <= thr ? m_hi : m_lo);
+        uint32_t a0;     // ((d4 & 0x7C) << 6) + col_lo  (hipcc shifts first, masks and adds: three instructions)
+        asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(a0) : "v"(d4 & 0x7Cu), "v"(col_lo));
+        uint32_t x;      // (next lane's word : own word) >> (i + 3)
+        if constexpr (i + 3 + 7 <= 32) x = *reinterpret_cast<const uint32_t*>(neq8 + a0) >> (i + 3);
+        else if constexpr (i + 3 >= 32) x = *reinterpret_cast<const uint32_t*>(neq8 + (a0 + dcol)) >> (i + 3 - 32);      // (v_alignbit shifts by 0 .. 31)
+        else x = __builtin_amdgcn_alignbit(*reinterpret_cast<const uint32_t*>(neq8 + (a0 + dcol)), *reinterpret_cast<const uint32_t*>(neq8 + a0), (uint32_t)(i + 3));
+        uint32_t z;                                              // v_ffbl_b32(0) = 0xFFFFFFFF: "no difference in sight"
+        asm("v_ffbl_b32 %0, %1" : "=v"(z) : "v"(x));             // (asm: hipcc turns ffs()-1 + min into a compare and a select)
+        const uint32_t l3 = umin3(z, kmax_m3, nrem_m5 - (uint32_t)i);
+        constexpr int bsh = 8 * (i & 3);                         // literal byte -> LUT offset 4*byte
+        uint32_t lit;
+        if constexpr (bsh == 0) lit = (ow[i >> 2] << 2) & 0x3FCu;
+        else lit = (ow[i >> 2] >> (bsh - 2)) & 0x3FCu;
+        uint32_t mt;     // l3 * tok_mul + d4 + tok_k  (hipcc folds the C form into a quarter-rate v_mul_lo_u32)
+        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(mt) : "v"(l3), "s"(tok_mul), "v"(d4 + tok_k));
+        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(tok[i]) : "v"(lit), "v"(mt), "s"(okm));      // tok = ok ? mt : lit
         constexpr int EG = HDLZ_EXT_GROUP;
         if constexpr ((i & (EG - 1)) == EG - 1) { pin_range<(i & ~(EG - 1)), (i & ~(EG - 1)) + EG>(tok); PHASE_FENCE(); }
     });
@@ -944,7 +994,7 @@ template <int NCH>
 __device__ __forceinline__ void fill_luts(uint32_t* lut, uint32_t lane) {
     for (uint32_t e = lane; e < (uint32_t)LUT_LIT; e += 64) lut[e] = literal_entry(e);
     for (uint32_t e = lane; e < (uint32_t)LUT_MATCH; e += 64) {
-        if (NCH == 1) lut[LUT_LIT + e] = dist_entry((e & 31u) + 1u) | length_code((e >> 5) + 3u);
+        if (NCH == 1) lut[LUT_LIT + e] = match_entry32(e);
         else lut[LUT_LIT + e] = dist_entry(e + 1u);
     }
     if (lane < (uint32_t)LUT_LEN) lut[LUT_LIT + LUT_MATCH + lane] = lane ? length_code(lane + 1u) : 0u;      // index len-1; 0: a literal
