@@ -18,6 +18,12 @@ def join_bound(nblocks, in_len):
     return 8 + nblocks * (out_bound(in_len) - 1)
 
 
+def unjoin_work_bytes(nmembers, total_out, flags=0):
+    """the scratch hdlz_unjoin_ws asks for (hdlz_unjoin_work_bytes: host arithmetic of the library)"""
+    from . import _lib
+    return _lib.load().hdlz_unjoin_work_bytes(nmembers, total_out, flags)
+
+
 def Engine(*a, **kw):
     """The HIP batch engine (imports torch lazily)."""
     from .engine import Engine as _E

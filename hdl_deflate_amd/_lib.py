@@ -43,6 +43,13 @@ JOIN_SIGNATURES = {
     "hdlz_join_batch_ws": (ci, [vp, u64, vp, vp, vp, vp, u32, u64, vp, u64, vp, vp, vp, sz, vp]),
 }
 JOIN_EXPORTS = tuple(JOIN_SIGNATURES)
+# ... and of include/hdlz_unjoin.h, the extension of that one (tests/test_unjoin_cabi.py)
+UNJOIN_SIGNATURES = {
+    "hdlz_unjoin_work_bytes": (sz, [u64, u64, u32]),
+    # d_stream, stream_len, d_off, d_out_off, out_len, nmembers, flags, d_out, out_cap, d_member_status, d_result, d_work, work_bytes, stream
+    "hdlz_unjoin_ws": (ci, [vp, u64, vp, vp, u32, u64, u32, vp, u64, vp, vp, vp, sz, vp]),
+}
+UNJOIN_EXPORTS = tuple(UNJOIN_SIGNATURES)
 _lib = None
 
 
@@ -55,6 +62,11 @@ class CState(ctypes.Structure):
 class JoinResult(ctypes.Structure):
     """hdlz_join_result: the result record of hdlz_join_batch_ws (16 bytes)"""
     _fields_ = [("stream_len", u64), ("status", u32), ("adler", u32)]
+
+
+class UnjoinResult(ctypes.Structure):
+    """hdlz_unjoin_result: the result record of hdlz_unjoin_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("adler", u32)]
 
 
 class IState(ctypes.Structure):
@@ -75,7 +87,7 @@ def load():
     # two HIP runtimes in one process and torch's streams/pointers would be foreign to ours.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

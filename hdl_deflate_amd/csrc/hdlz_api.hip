@@ -467,4 +467,58 @@ int hdlz_inflate_chunk(const uint8_t* d_in, uint32_t in_len, int final, uint32_t
     return HDLZ_OK;
 }
 
+// ---- include/hdlz_unjoin.h: a joined stream read back member by member (the member view of the batch decoders; hdlz_unjoin.hip)
+static size_t r256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+size_t hdlz_unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) {
+    if (nmembers > 0x7FFFFFFFull) return 0;
+    return r256(12u * (size_t)nmembers) + r256(sizeof(uint2) * hdlz::unjoin_tiles(total_out)) +
+           r256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1));
+}
+
+int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
+                   uint64_t nmembers, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status,
+                   hdlz_unjoin_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_stream || !d_off || !d_result || (out_cap && !d_out)) return fail_param("null device pointer");
+    if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
+    const uint32_t hints = HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_GROUP_PER_STREAM;
+    if (flags & ~hints) return fail_param("unknown flag (hdlz_unjoin_ws takes the three mapping hints only)");
+    if (flags & (flags - 1u)) return fail_param("contradictory mapping flags");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail_param("d_out must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return fail_param("d_off / d_out_off / d_result must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
+    const size_t need = hdlz_unjoin_work_bytes(nmembers, out_cap, flags);
+    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_unjoin_work_bytes(nmembers, out_cap, flags)");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t* wb = static_cast<uint8_t*>(d_work);
+    uint32_t* words = reinterpret_cast<uint32_t*>(wb);
+    const size_t per = r256(12u * (size_t)nmembers), tiles = r256(sizeof(uint2) * hdlz::unjoin_tiles(out_cap));
+    const hdlz::UnjoinArgs u{d_stream, stream_len, d_off, d_out_off, out_len, nmembers, d_out, out_cap, d_member_status, d_result,
+                             words, words + nmembers, words + 2u * nmembers, reinterpret_cast<uint2*>(wb + per)};
+    hipError_t e = hdlz::launch_unjoin_index(u, st);
+    if (e != hipSuccess) return fail_hip(e, "launch k_unjoin_index");
+    if (nmembers) {
+        hdlz::MemberArgs a;
+        a.in = d_stream; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = nmembers;
+        a.flags = HDLZ_INFLATE_ONEBLOCK;                       // BFINAL is not read: a member is one block
+        a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.len; a.status = u.status; a.in_used = u.end_bit;
+        a.m_off = d_off; a.m_out_off = d_out_off; a.m_out_len = out_len; a.m_out_cap = out_cap;
+        // the mapping: the thresholds of hdlz_inflate_batch_ws, or the hint; never the whole-GPU chains
+        const bool group = (flags & HDLZ_INFLATE_GROUP_PER_STREAM) ||
+                           (flags == 0u && nmembers >= HDLZ_INFLATE_GROUP_MIN && nmembers <= HDLZ_INFLATE_GROUP_MAX);
+        const bool wave_all = !group && ((flags & HDLZ_INFLATE_WAVE_PER_STREAM) ||
+                                         (!(flags & HDLZ_INFLATE_LANE_PER_STREAM) && nmembers <= HDLZ_INFLATE_WAVE_THRESHOLD));
+        const hdlz::Work w{wb + per + tiles, work_bytes - per - tiles, true};
+        e = wave_all ? hdlz::launch_inflate_dyn_members(a, st) : group ? hdlz::launch_inflate_grp_members(a, st)
+                                                                       : hdlz::launch_inflate_tok_members(a, st, w);
+        if (e != hipSuccess) return fail_hip(e, "launch the member decode");
+    }
+    e = hdlz::launch_unjoin_judge(u, st);
+    if (e != hipSuccess) return fail_hip(e, "launch k_unjoin_judge");
+    return HDLZ_OK;
+}
+
 }  // extern "C"

@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
-#include "../../include/hdlz_join.h"      // (includes hdlz.h)
+#include "../../include/hdlz_unjoin.h"    // (includes hdlz_join.h and hdlz.h)
 
 namespace hdlz {
 
@@ -40,6 +40,31 @@ struct InflateArgs {
     uint32_t* in_used = nullptr;   // nullable (hdlz_inflate_checked): per stream, the index of the first byte behind the last bit of the final
                                    // block, counted from the stream's first byte; 0 for a stream whose decode fails.  Moves with out_len / status.
 };
+
+// The MEMBER VIEW of the batch decoders (hdlz_unjoin_ws): stream b is member b of a joined stream, its output slot a
+// piece of one flat buffer.  The <..., MEMBERS = true> twins of k_inflate_tok, k_inflate_grp and k_inflate_dyn take this record in place
+// of InflateArgs; of the base they use in, out, nstreams, flags (HDLZ_INFLATE_ONEBLOCK: BFINAL is not read), obsize and the three
+// result arrays -- status[b] is READ first: a member the index checks refused (status != HDLZ_OK) is not touched --, and in_used[b]
+// receives the END BIT, the bit behind the end-of-block code counted from byte m_off[b] - 2, instead of a rounded byte.
+struct MemberArgs : InflateArgs {
+    const uint64_t* m_off;       // nmembers + 1 words: member b is in[m_off[b] .. m_off[b + 1])
+    const uint64_t* m_out_off;   // nullable: then member b decodes to out + b * m_out_len, m_out_len bytes
+    uint32_t m_out_len;
+    uint64_t m_out_cap;          // no store at or behind out + m_out_cap
+};
+// the stream a decoder sees is in[m_off[b] - 2 .. m_off[b + 1]): it skips two bytes unvalidated (never loaded: the FF FF of the marker in
+// front, or 78 9C), and the member's own marker supplies the bytes the end-of-input rules want behind the end-of-block code
+__device__ __forceinline__ void member_view(const MemberArgs& a, uint64_t b, uint64_t& off, uint32_t& zn, uint64_t& o, uint32_t& cap) {
+    const uint64_t lo = a.m_off[b];
+    off = lo - 2u;
+    zn = (uint32_t)(a.m_off[b + 1] - lo) + 2u;
+    uint64_t n;
+    if (a.m_out_off) { o = a.m_out_off[b]; n = a.m_out_off[b + 1] - o; }
+    else { o = b * (uint64_t)a.m_out_len; n = a.m_out_len; }
+    const uint64_t room = a.m_out_cap - o;                    // (the index checks: o + n <= m_out_cap)
+    n = n < room ? n : room;
+    cap = n > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)n;     // o + 258 never wraps
+}
 
 __host__ __device__ inline uint32_t out_bound(uint32_t n) {
     return 6u + (uint32_t)((9ull * n + 10ull + 7ull) >> 3);
@@ -106,6 +131,30 @@ struct JudgeArgs {
     uint32_t* adler;            // nullable
     uint2* work;                // judge_work_bytes(nstreams, out_pitch) bytes (per-tile sums; null when that is 0)
 };
+// hdlz_unjoin_ws: the member twins of the three batch mappings (a.in_off is not used: the lane mapping orders its lists by a.m_off)
+hipError_t launch_inflate_tok_members(const MemberArgs& a, hipStream_t stream, const Work& w);
+hipError_t launch_inflate_grp_members(const MemberArgs& a, hipStream_t stream);
+hipError_t launch_inflate_dyn_members(const MemberArgs& a, hipStream_t stream);
+// hdlz_unjoin.hip: the index checks in front of the decode, the checksum tiles, the judgement and the record behind it
+struct UnjoinArgs {
+    const uint8_t* in;
+    uint64_t in_len;
+    const uint64_t* off;
+    const uint64_t* out_off;     // nullable
+    uint32_t out_len;
+    uint64_t nmembers;
+    uint8_t* out;
+    uint64_t out_cap;
+    uint32_t* member_status;     // nullable
+    hdlz_unjoin_result* result;
+    uint32_t* len;               // scratch, per member: the decoded length; behind the judgement word 256 g holds workgroup g's lowest failed member
+    uint32_t* status;            // ... the status: written by the index checks, then by the decode, then by the judgement
+    uint32_t* end_bit;           // ... the end bit
+    uint2* tiles;                // scratch: (A, C) per 32 KiB tile of out[0 .. out_cap)
+};
+hipError_t launch_unjoin_index(const UnjoinArgs& a, hipStream_t stream);
+hipError_t launch_unjoin_judge(const UnjoinArgs& a, hipStream_t stream);
+size_t unjoin_tiles(uint64_t total_out);
 size_t judge_work_bytes(uint64_t nstreams, uint64_t out_pitch);
 hipError_t launch_judge(const JudgeArgs& a, hipStream_t stream);
 size_t stream_work_bytes(uint32_t n, uint32_t nblocks);

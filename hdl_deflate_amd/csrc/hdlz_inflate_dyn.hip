@@ -161,8 +161,9 @@ __device__ __forceinline__ void xwalk(const XCode& X, uint32_t bits15, uint32_t&
 // state lives in a device-resident hdlz_istate between the calls; a call decodes until the stream ends, the input known so
 // far runs out (the reference's `di >= isize - 4 and not i_mode == IDLE` stall, deflate.py:1529-1530) or the output limit
 // is reached (its `do >= i_raddr + OBSIZE` hold, deflate.py:1531-1534, :1597-1599), always stopping BETWEEN two tokens.
-template <bool STREAM>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_inflate_dyn(InflateArgs a, hdlz_istate* ist, uint32_t out_limit, const uint32_t* few_n, uint32_t lane_min) {
+// MEMBERS = true (with STREAM = false): the member view (hdlz_device.h: MemberArgs), as in k_inflate_tok.
+template <bool STREAM, bool MEMBERS = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_inflate_dyn(std::conditional_t<MEMBERS, MemberArgs, InflateArgs> a, hdlz_istate* ist, uint32_t out_limit, const uint32_t* few_n, uint32_t lane_min) {
     __shared__ DynLds L;
     const uint32_t lane = threadIdx.x;
     // second pass of the lane mapping: this kernel takes the flagged streams only when they are few (*few_n of them, counted by
@@ -174,7 +175,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         if (!STREAM && !(a.flags & DYN_ALL) && a.status[sid] != HDLZ_E_DYNAMIC_UNSUPPORTED) continue;   // pass 1 finished this stream
         uint64_t off;
         uint32_t zn;
-        if (a.in_off) {
+        [[maybe_unused]] uint64_t m_o = 0;
+        [[maybe_unused]] uint32_t m_cap = 0;
+        if constexpr (MEMBERS) {
+            if (a.status[sid] != HDLZ_OK) continue;                     // refused by the index checks: left alone
+            member_view(a, sid, off, zn, m_o, m_cap);
+        } else if (a.in_off) {
             off = a.in_off[sid];
             zn = (uint32_t)(a.in_off[sid + 1] - off);
         } else {
@@ -196,8 +202,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             continue;
         }
         const uint8_t* __restrict__ z = a.in + off;
-        uint8_t* __restrict__ out = a.out + sid * a.out_pitch;
-        const uint32_t cap0 = a.out_pitch > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)a.out_pitch;
+        uint8_t* __restrict__ out = a.out + (MEMBERS ? m_o : sid * a.out_pitch);
+        const uint32_t cap0 = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)a.out_pitch;
         const uint32_t cap = STREAM ? (out_limit < cap0 ? out_limit : cap0) : cap0;      // STREAM: reaching it is a stop, not an error
         const uint32_t inbits = 8u * zn;                                                 // (zn < 2^28)
         const uint32_t obsize = a.obsize ? a.obsize : 32768u;
@@ -662,7 +668,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             a.out_len[sid] = status == HDLZ_OK ? o : 0u;
             a.status[sid] = status;
             // where the stream ended (hdlz_inflate_checked): the bit reader stands behind the final block's last bit
-            if (a.in_used) a.in_used[sid] = status == HDLZ_OK ? (BITPOS() + 7u) >> 3 : 0u;
+            // (MEMBERS: the end bit itself)
+            if (a.in_used) a.in_used[sid] = status != HDLZ_OK ? 0u : MEMBERS ? BITPOS() : (BITPOS() + 7u) >> 3;
         }
         __syncthreads();
 #undef REFILL
@@ -690,6 +697,16 @@ hipError_t launch_inflate_dyn(const InflateArgs& a0, hipStream_t stream, bool al
     uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
     if (few_n && lane_min != 0u && g > lane_min) g = lane_min;       // (list mode runs for fewer than lane_min streams: no more blocks than that)
     hipLaunchKernelGGL(k_inflate_dyn<false>, dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, few_n, lane_min);
+    return hipGetLastError();
+}
+
+// the member twin (hdlz_unjoin_ws): every member the index checks passed, one wave each
+hipError_t launch_inflate_dyn_members(const MemberArgs& a0, hipStream_t stream) {
+    if (a0.nstreams == 0) return hipSuccess;
+    MemberArgs a = a0;
+    a.flags |= DYN_ALL;
+    const uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
+    hipLaunchKernelGGL((k_inflate_dyn<false, true>), dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, (const uint32_t*)nullptr, 0u);
     return hipGetLastError();
 }
 

@@ -55,7 +55,9 @@ __device__ __forceinline__ uint64_t load8(const uint8_t* __restrict__ z, uint32_
     return v;
 }
 
-__global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(InflateArgs a) {
+// MEMBERS = true: the member view (hdlz_device.h: MemberArgs), as in k_inflate_tok
+template <bool MEMBERS>
+__global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(std::conditional_t<MEMBERS, MemberArgs, InflateArgs> a) {
     __shared__ Lds lds;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t l = lane & (G - 1u), g = lane / G;
@@ -63,20 +65,25 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(InflateArgs a) {
     __syncthreads();                 // the only workgroup barrier: the waves are independent from here on
 
     const uint64_t sid = ((uint64_t)blockIdx.x * WAVES + wave) * NS + g;
-    const bool exists = sid < a.nstreams;
+    // (MEMBERS: a member the index checks refused is left alone)
+    const bool exists = sid < a.nstreams && (!MEMBERS || a.status[sid] == HDLZ_OK);
     uint64_t off = 0;
     uint32_t zn = 0;
-    if (exists) {
+    [[maybe_unused]] uint64_t m_o = 0;
+    [[maybe_unused]] uint32_t m_cap = 0;
+    if constexpr (MEMBERS) {
+        if (exists) member_view(a, sid, off, zn, m_o, m_cap);
+    } else if (exists) {
         if (a.in_off) { off = a.in_off[sid]; zn = (uint32_t)(a.in_off[sid + 1] - off); }
         else { off = sid * a.in_pitch; zn = a.in_len; }
     }
     // D0: the two zlib header bytes are skipped unvalidated -- the FIFO is filled from byte 2 on, which keeps the reader's dwords aligned
     const uint8_t* __restrict__ z2 = a.in + off + 2u;
     const uint32_t zn2 = zn >= 2u ? zn - 2u : 0u;
-    uint8_t* out = a.out + (exists ? sid : 0ull) * a.out_pitch;
+    uint8_t* out = a.out + (MEMBERS ? m_o : (exists ? sid : 0ull) * a.out_pitch);
     uint8_t* ring = lds.ring[wave][g];
     uint32_t* fifo = lds.fifo[wave][g];
-    const uint32_t cap = a.out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)a.out_pitch;   // o + 258 never wraps
+    const uint32_t cap = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)a.out_pitch;   // o + 258 never wraps
     const uint32_t obsize = a.obsize ? a.obsize : 32768u;
     const uint32_t len_mask = a.obsize ? ((1u << (31u - (uint32_t)__builtin_clz(a.obsize))) - 1u) : 0xFFFFu;   // deflate.py:329,:714
     const bool assume_fixed = (a.flags & HDLZ_INFLATE_ASSUME_FIXED) != 0;
@@ -349,7 +356,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(InflateArgs a) {
     if (exists && l == 0u) { a.out_len[sid] = out_len; a.status[sid] = status; }
 #endif
     // where the stream ended (hdlz_inflate_checked): a stream that is done takes no more input, ipq and bc stand behind the final block's last bit
-    if (a.in_used && exists && l == 0u) a.in_used[sid] = status == HDLZ_OK ? (8u * (ipq + 2u) - bc + 7u) >> 3 : 0u;
+    // (MEMBERS: the end bit itself)
+    if (a.in_used && exists && l == 0u) a.in_used[sid] = status != HDLZ_OK ? 0u : MEMBERS ? 8u * (ipq + 2u) - bc : (8u * (ipq + 2u) - bc + 7u) >> 3;
 }
 
 }  // namespace grp
@@ -357,7 +365,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(InflateArgs a) {
 hipError_t launch_inflate_grp(const InflateArgs& a, hipStream_t stream) {
     if (a.nstreams == 0) return hipSuccess;
     const uint64_t per_wg = (uint64_t)grp::NS * grp::WAVES;
-    hipLaunchKernelGGL(grp::k_inflate_grp, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);
+    hipLaunchKernelGGL(grp::k_inflate_grp<false>, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_inflate_grp_members(const MemberArgs& a, hipStream_t stream) {
+    if (a.nstreams == 0) return hipSuccess;
+    const uint64_t per_wg = (uint64_t)grp::NS * grp::WAVES;
+    hipLaunchKernelGGL(grp::k_inflate_grp<true>, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -80,7 +80,8 @@ constexpr uint32_t MOVES = 3;              // move iterations (up to 4 bytes per
 #endif
 // where the stream ended (hdlz_inflate_checked; a.in_used is null otherwise): a lane that is done takes no more input -- every refill and
 // every decode step asks for `active` --, so ip and bc still stand where the final block's last bit left them
-#define TOK_STORE_END() do { if (a.in_used) a.in_used[sid] = status == HDLZ_OK ? (8u * ip - bc + 7u) >> 3 : 0u; } while (0)
+// MEMBERS (hdlz_unjoin_ws): the END BIT itself, the first bit behind the end-of-block code -- the judge finds the member's marker from it
+#define TOK_STORE_END() do { if (a.in_used) a.in_used[sid] = status != HDLZ_OK ? 0u : MEMBERS ? 8u * ip - bc : (8u * ip - bc + 7u) >> 3; } while (0)
 
 // DYN: per-lane tables in LDS, rows of 64 dwords (row j of lane l = dword j * 64 + l: every lane stays in its own bank): only the
 // literal/length symbols, sorted by (code length, value) -- CAP low bytes and CAP ninth bits.  Everything else a lane needs of its
@@ -187,8 +188,11 @@ __device__ __forceinline__ void x_decode(const uint32_t (&X)[NL], uint32_t bits,
 }
 
 constexpr uint32_t ORDER_BAD = 0xFFFFFFFFu;      // list length word of a counting sort whose counts did not add up (see bin_flush_and_finish)
-template <bool DYN, uint32_t CAP>
-__global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(InflateArgs a, const uint32_t* __restrict__ list,
+// MEMBERS = true is the member view (hdlz_device.h: MemberArgs), the twin hdlz_unjoin_ws launches: a template flag like
+// k_compress's ENDBITS -- what differs is the prologue (where the stream and its output slot are, and which streams are left alone) and
+// the word stored in in_used; the <.., false> instantiations are the kernels they were.
+template <bool DYN, uint32_t CAP, bool MEMBERS = false>
+__global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional_t<MEMBERS, MemberArgs, InflateArgs> a, const uint32_t* __restrict__ list,
                                                                 const uint32_t* __restrict__ list_n, uint32_t lane_min,
                                                                 const uint32_t* __restrict__ order_word = nullptr,
                                                                 const uint32_t* __restrict__ list_alt = nullptr
@@ -217,7 +221,12 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(InflateArgs a, c
     }
     uint64_t off = 0;
     uint32_t zn = 0;
-    if (exists) {
+    [[maybe_unused]] uint64_t m_o = 0;          // MEMBERS: where the member's output slot starts, and its capacity
+    [[maybe_unused]] uint32_t m_cap = 0;
+    if constexpr (MEMBERS) {
+        if (exists && a.status[sid] != HDLZ_OK) exists = false;      // refused by the index checks: its index words may be garbage
+        if (exists) member_view(a, sid, off, zn, m_o, m_cap);
+    } else if (exists) {
         if (a.in_off) {
             off = a.in_off[sid];
             zn = (uint32_t)(a.in_off[sid + 1] - off);
@@ -227,10 +236,10 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(InflateArgs a, c
         }
     }
     const uint8_t* __restrict__ z = a.in + off;
-    uint8_t* out = a.out + sid * a.out_pitch;
+    uint8_t* out = a.out + (MEMBERS ? m_o : sid * a.out_pitch);
     uint8_t* ring8 = reinterpret_cast<uint8_t*>(lds.ring[wave]);
     const uint32_t lane4 = lane << 2;
-    const uint32_t cap = a.out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)a.out_pitch;   // o + 258 never wraps
+    const uint32_t cap = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)a.out_pitch;   // o + 258 never wraps
     const uint32_t obsize = a.obsize ? a.obsize : 32768u;
     const uint32_t len_mask = a.obsize ? ((1u << (31u - (uint32_t)__builtin_clz(a.obsize))) - 1u) : 0xFFFFu;   // deflate.py:329,:714
     const bool assume_fixed = (a.flags & HDLZ_INFLATE_ASSUME_FIXED) != 0;
@@ -1066,6 +1075,34 @@ hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Wo
         (void)hipGetLastError();                 // no scratch: stream order
     }
     hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL>), grid, block, 0, stream, a, (const uint32_t*)nullptr,
+                       (const uint32_t*)nullptr, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+    return hipGetLastError();
+}
+
+// the member twin (hdlz_unjoin_ws): launch_inflate_tok with the lists ordered by the MEMBER lengths (a.m_off as in_off); no second pass
+hipError_t launch_inflate_tok_members(const MemberArgs& a, hipStream_t stream, const Work& w) {
+    if (a.nstreams == 0) return hipSuccess;
+    typedef tok::Lds<false, tok::CAP_FULL> L;
+    const uint64_t per_wg = 64u * L::WAVES;
+    const dim3 grid((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), block(64 * L::WAVES);
+    const size_t nws = tok::lists_of(a.nstreams, true, false).pass1;
+    if (nws != 0u) {
+        uint32_t* ws = nullptr;
+        hipError_t e = w.get(sizeof(uint32_t) * nws, stream, reinterpret_cast<uint8_t**>(&ws));
+        if (e == hipSuccess) {
+            e = tok::bin_streams(a.m_off, (uint32_t)a.nstreams, ws, ws + tok::BIN_WORDS, stream);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL, true>), grid, block, 0, stream, a,
+                                   (const uint32_t*)(ws + tok::BIN_WORDS), (const uint32_t*)(ws + tok::NBIN), 0u,
+                                   (const uint32_t*)(ws + tok::NBIN), (const uint32_t*)nullptr);
+                e = hipGetLastError();
+            }
+            const hipError_t e2 = w.put(reinterpret_cast<uint8_t*>(ws), stream);
+            return e != hipSuccess ? e : e2;
+        }
+        (void)hipGetLastError();                 // no scratch: stream order
+    }
+    hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL, true>), grid, block, 0, stream, a, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
     return hipGetLastError();
 }

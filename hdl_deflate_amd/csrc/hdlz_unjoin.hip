@@ -1,0 +1,247 @@
+// hdlz_unjoin.hip -- what hdlz_unjoin_ws (include/hdlz_unjoin.h) runs around the member decode: the index checks in front
+// of it, the Adler-32 of the flat output and the judgement of every member and of the stream's frame behind it.
+//
+// The decode itself is the member view of the three batch decoders (hdlz_device.h: MemberArgs).  A decoder trusts its index words,
+// so k_unjoin_index looks at them first: a member whose words are unusable, or whose first block is not a fixed one, gets its status
+// here and the decoders leave it alone.  Behind the decode k_unjoin_tiles sums the CONTIGUOUS output in 32 KiB tiles over the whole GPU
+// (the arithmetic of k_adler_tiles, hdlz_checksum.hip: restated here, not shared -- its kernels stay the code objects they were),
+// k_unjoin_judge compares every member's decoded length with its slot and looks for the sync marker behind the END BIT the decoder
+// left (the first bit behind the end-of-block code, counted from two bytes in front of the member), and k_unjoin_finish, one
+// workgroup, reduces the tiles and the verdicts, reads the final empty block and the trailer and writes the record.
+//
+// Adler-32 of the output X (N bytes) from the tiles: with A_t = the byte sum of tile t and C_t = sum q x_q over its bytes (q relative to
+// the tile), A = sum A_t and C = sum (32768 t A_t + C_t), s1 = 1 + A, s2 = N + N A - C (mod 65521).  Bounds: inside a tile as in
+// k_adler_tiles (a lane adds 8 terms below 1.34e8); k_unjoin_finish folds (32768 t mod 65521) A_t + C_t < 2^32 per tile into 64 bits --
+// exact for up to 2^31 tiles, an output of 2^46 bytes.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "hdlz_device.h"
+
+namespace hdlz {
+namespace unj {
+
+constexpr uint32_t MOD = 65521u;
+constexpr uint32_t TILE = 32768u;             // bytes per workgroup step of k_unjoin_tiles: 4 waves x 8 steps x 64 lanes x 16 bytes
+constexpr uint32_t TILE_WAVES = 4u, TILE_STEPS = 8u;
+static_assert(TILE == TILE_WAVES * TILE_STEPS * 1024u, "a tile is what its workgroup's waves cover");
+constexpr uint32_t JT = 256u;                 // members per workgroup of the index checks and of the judge
+constexpr uint32_t NONE = 0xFFFFFFFFu;        // a workgroup without a failed member
+constexpr uint64_t MEMBER_MAX = 1ull << 28;   // bit positions are 32-bit in the decoders
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// Sx and W of one chunk (hdlz_checksum.hip)
+__device__ __forceinline__ void sums16(const u32x4 v, uint32_t& sx, uint32_t& w) {
+    sx = __builtin_amdgcn_sad_u8(v.x, 0u, 0u);
+    sx = __builtin_amdgcn_sad_u8(v.y, 0u, sx);
+    sx = __builtin_amdgcn_sad_u8(v.z, 0u, sx);
+    sx = __builtin_amdgcn_sad_u8(v.w, 0u, sx);
+    w = __builtin_amdgcn_udot4(v.x, 0x03020100u, 0u, false);
+    w = __builtin_amdgcn_udot4(v.y, 0x07060504u, w, false);
+    w = __builtin_amdgcn_udot4(v.z, 0x0B0A0908u, w, false);
+    w = __builtin_amdgcn_udot4(v.w, 0x0F0E0D0Cu, w, false);
+}
+// the dword at p of which only `cnt` bytes (1 .. 3) may be loaded: the output's capacity need not be a multiple of 4
+__device__ __forceinline__ uint32_t load_tail(const uint8_t* __restrict__ p, int32_t cnt) {
+    uint32_t d = p[0];
+    if (cnt > 1) d |= (uint32_t)p[1] << 8;
+    if (cnt > 2) d |= (uint32_t)p[2] << 16;
+    return d;
+}
+// the chunk at byte q of `p` (q a multiple of 16, below n; p 4-byte aligned): bytes at or behind n read as zero and are not loaded
+template <bool A16>
+__device__ __forceinline__ u32x4 load_chunk(const uint8_t* __restrict__ p, uint32_t q, uint32_t n) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(p + q);
+    if (q + 16u <= n) {
+        if constexpr (A16) v = *reinterpret_cast<const u32x4*>(d);
+        else { v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3]; }
+    } else {
+        const int32_t cnt = (int32_t)(n - q);                 // 1 .. 15
+        auto part = [&](int32_t k) -> uint32_t {
+            const int32_t c = cnt - 4 * k;
+            return c >= 4 ? d[k] : c > 0 ? load_tail(p + q + 4 * k, c) : 0u;
+        };
+        v.x = part(0); v.y = part(1); v.z = part(2); v.w = part(3);
+    }
+    return v;
+}
+
+// member b's slot of the output: [o, e) -- the caller checks what it relies on
+__device__ __forceinline__ void slot_of(const UnjoinArgs& a, uint64_t b, uint64_t& o, uint64_t& e) {
+    if (a.out_off) { o = a.out_off[b]; e = a.out_off[b + 1]; }
+    else { o = b * (uint64_t)a.out_len; e = o + a.out_len; }
+}
+// the length of the output as the index states it, never beyond the capacity (a member the index checks refused may say anything)
+__device__ __forceinline__ uint64_t total_of(const UnjoinArgs& a) {
+    const uint64_t t = a.nmembers == 0 ? 0ull : a.out_off ? a.out_off[a.nmembers] : a.nmembers * (uint64_t)a.out_len;
+    return t < a.out_cap ? t : a.out_cap;
+}
+
+// ---- in front of the decode: one thread per member, check 1 of the header and the first block's type
+__global__ __launch_bounds__(JT) void k_unjoin_index(UnjoinArgs a) {
+    const uint64_t b = (uint64_t)blockIdx.x * JT + threadIdx.x;
+    if (b >= a.nmembers) return;
+    const uint64_t lo = a.off[b], hi = a.off[b + 1];
+    // (a member that ends inside the stream can be read; whether the frame's last six bytes are there is the stream's own check)
+    bool bad = hi < lo || hi - lo < 5u || hi - lo >= MEMBER_MAX || hi > a.in_len;
+    uint64_t o, e;
+    slot_of(a, b, o, e);
+    bad = bad || e < o || (o & 3u) != 0u || e > a.out_cap || (b == 0u && o != 0u);
+    uint32_t st = bad ? (uint32_t)HDLZ_E_BAD_PARAM : (uint32_t)HDLZ_OK;
+    if (!bad && ((a.in[lo] >> 1) & 3u) != 1u) st = HDLZ_E_BAD_BTYPE;       // (lo < hi <= in_len)
+    a.status[b] = st;
+    a.len[b] = 0u;
+    a.end_bit[b] = 0u;
+}
+
+// ---- behind the decode: (A, C) of every 32 KiB tile of out[0 .. total), positions relative to the tile; (0, 0) for the tiles behind it
+template <bool A16>
+__global__ __launch_bounds__(64 * TILE_WAVES) void k_unjoin_tiles(UnjoinArgs a, uint32_t ntiles) {
+    __shared__ uint32_t sa[TILE_WAVES], sc[TILE_WAVES];
+    const uint64_t total = total_of(a);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t base = (uint64_t)t * TILE;
+        uint32_t a32 = 0, c32 = 0;
+        if (base < total) {
+            const uint32_t tn = total - base < TILE ? (uint32_t)(total - base) : TILE;
+            const uint8_t* __restrict__ p = a.out + base;
+#pragma unroll
+            for (uint32_t k = 0; k < TILE_STEPS; k++) {
+                const uint32_t q = (wave * TILE_STEPS + k) * 1024u + 16u * lane;
+                if (q < tn) {
+                    uint32_t sx, w;
+                    sums16(load_chunk<A16>(p, q, tn), sx, w);
+                    a32 += sx;
+                    c32 += __umul24(q, sx) + w;
+                }
+            }
+            c32 %= MOD;
+#pragma unroll
+            for (int ofs = 32; ofs > 0; ofs >>= 1) { a32 += (uint32_t)__shfl_xor((int)a32, ofs, 64); c32 += (uint32_t)__shfl_xor((int)c32, ofs, 64); }
+        }
+        if (lane == 0u) { sa[wave] = a32; sc[wave] = c32; }
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            uint32_t A = 0, C = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < TILE_WAVES; k++) { A += sa[k]; C += sc[k]; }
+            a.tiles[t] = make_uint2(A % MOD, C % MOD);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- one thread per member: checks 3 and 4 of the header behind the decoder's status; the member's status, and per workgroup the
+// lowest member that failed -- in the length word of the workgroup's first member, which every thread has read by then
+__global__ __launch_bounds__(JT) void k_unjoin_judge(UnjoinArgs a) {
+    __shared__ uint32_t s_first[JT / 64u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t b = (uint64_t)blockIdx.x * JT + tid;
+    uint32_t st = HDLZ_OK;
+    if (b < a.nmembers) {
+        st = a.status[b];
+        if (st == HDLZ_OK) {
+            const uint64_t lo = a.off[b], zn = a.off[b + 1] - lo + 2u;        // (the index checks passed: these words are sound)
+            uint64_t o, e;
+            slot_of(a, b, o, e);
+            const uint32_t eb = a.end_bit[b];
+            const uint8_t* __restrict__ z = a.in + lo - 2u;                   // bit positions count from here; bytes 0 and 1 are not read
+            const uint64_t q = ((uint64_t)eb + 3u + 7u) >> 3;                 // the first byte behind the stored block's header bits
+            if ((uint64_t)a.len[b] < e - o) st = HDLZ_E_BAD_PARAM;            // the index contradicts the stream
+            else if (eb < 16u || q + 4u != zn) st = HDLZ_E_NO_EOF;
+            else {
+                uint32_t hdr = 0;
+                for (uint32_t k = 0; k < 3u; k++) hdr |= ((uint32_t)z[(eb + k) >> 3] >> ((eb + k) & 7u)) & 1u;
+                if (hdr != 0u || z[q] != 0u || z[q + 1u] != 0u || z[q + 2u] != 0xFFu || z[q + 3u] != 0xFFu) st = HDLZ_E_NO_EOF;
+            }
+            if (st != HDLZ_OK) a.status[b] = st;
+        }
+        if (a.member_status) a.member_status[b] = st;
+    }
+    const uint64_t m = ballot64(st != HDLZ_OK);
+    if (lane == 0u) s_first[wave] = m ? wave * 64u + (uint32_t)__builtin_ctzll(m) : NONE;
+    __syncthreads();
+    if (tid == 0u) {
+        uint32_t f = NONE;
+#pragma unroll
+        for (uint32_t k = 0; k < JT / 64u; k++) f = min(f, s_first[k]);
+        a.len[b] = f == NONE ? NONE : (uint32_t)b + f;                        // (b: the workgroup's first member; nmembers < 2^31)
+    }
+}
+
+// ---- one workgroup: the tiles -> the checksum, the verdicts -> the first failure; the stream's own frame; the record
+__global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t ntiles, uint32_t ngroups) {
+    __shared__ uint64_t s_a[256], s_c[256];
+    __shared__ uint32_t s_f[256];
+    const uint32_t tid = threadIdx.x;
+    uint64_t A64 = 0, C64 = 0;
+    for (uint32_t t = tid; t < ntiles; t += 256u) {
+        const uint2 s = a.tiles[t];
+        const uint32_t base = ((t % MOD) * (TILE % MOD)) % MOD;           // 32768 t mod 65521 (the product stays below 2^32)
+        A64 += s.x;
+        C64 += (uint64_t)base * s.x + s.y;
+    }
+    uint32_t f = NONE;
+    for (uint32_t g = tid; g < ngroups; g += 256u) f = min(f, a.len[(size_t)g * JT]);
+    s_a[tid] = A64 % MOD; s_c[tid] = C64 % MOD; s_f[tid] = f;
+    __syncthreads();
+    for (uint32_t o = 128u; o > 0u; o >>= 1) {
+        if (tid < o) { s_a[tid] += s_a[tid + o]; s_c[tid] += s_c[tid + o]; s_f[tid] = min(s_f[tid], s_f[tid + o]); }
+        __syncthreads();
+    }
+    if (tid != 0u) return;
+    const uint64_t total = total_of(a);
+    const uint32_t A = (uint32_t)(s_a[0] % MOD), C = (uint32_t)(s_c[0] % MOD), nm = (uint32_t)(total % MOD);
+    const uint32_t s1 = (1u + A) % MOD, s2 = (uint32_t)(((uint64_t)nm + (uint64_t)nm * A + MOD - C) % MOD);
+    hdlz_unjoin_result res;
+    res.out_len = total; res.first_bad = ~0ull; res.status = HDLZ_OK; res.adler = (s2 << 16) | s1;
+    if (s_f[0] != NONE) {
+        res.status = a.status[s_f[0]]; res.first_bad = s_f[0]; res.adler = 0u;
+    } else {
+        const uint64_t end = a.off[a.nmembers];
+        bool head = a.off[0] == 2u && a.in_len >= 2u;
+        if (head) {
+            const uint32_t cmf = a.in[0], flg = a.in[1];
+            head = (cmf & 15u) == 8u && (cmf >> 4) <= 7u && (cmf * 256u + flg) % 31u == 0u && (flg & 0x20u) == 0u;
+        }
+        if (!head) res.status = HDLZ_E_BAD_HEADER;
+        else if (a.in_len < 6u || end > a.in_len - 6u || a.in[end] != 3u || a.in[end + 1u] != 0u) res.status = HDLZ_E_NO_EOF;
+        else {
+            const uint8_t* t = a.in + end + 2u;
+            const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | (uint32_t)t[3];
+            if (want != res.adler) res.status = HDLZ_E_BAD_CHECKSUM;
+        }
+        if (res.status != HDLZ_OK) res.first_bad = a.nmembers;
+    }
+    if (res.status != HDLZ_OK) res.out_len = 0u;
+    *a.result = res;
+}
+
+}  // namespace unj
+
+size_t unjoin_tiles(uint64_t total_out) { return (size_t)((total_out + unj::TILE - 1u) / unj::TILE); }
+
+hipError_t launch_unjoin_index(const UnjoinArgs& a, hipStream_t stream) {
+    if (a.nmembers == 0) return hipSuccess;
+    hipLaunchKernelGGL(unj::k_unjoin_index, dim3((unsigned)((a.nmembers + unj::JT - 1u) / unj::JT)), dim3(unj::JT), 0, stream, a);
+    return hipGetLastError();
+}
+
+// the tiles, the judge and the finishing workgroup, behind the decode on the same stream
+hipError_t launch_unjoin_judge(const UnjoinArgs& a, hipStream_t stream) {
+    using namespace unj;
+    const uint64_t nt64 = a.nmembers ? unjoin_tiles(a.out_cap) : 0u;
+    const uint32_t ntiles = (uint32_t)(nt64 < 0x80000000ull ? nt64 : 0x80000000ull);      // (2^46 bytes: the ABI's bound)
+    const uint32_t ngroups = (uint32_t)((a.nmembers + JT - 1u) / JT);
+    if (ntiles) {
+        const dim3 grid(ntiles < (1u << 22) ? ntiles : (1u << 22)), block(64 * TILE_WAVES);
+        if ((reinterpret_cast<uintptr_t>(a.out) & 15u) == 0u) hipLaunchKernelGGL(k_unjoin_tiles<true>, grid, block, 0, stream, a, ntiles);
+        else hipLaunchKernelGGL(k_unjoin_tiles<false>, grid, block, 0, stream, a, ntiles);
+    }
+    if (ngroups) hipLaunchKernelGGL(k_unjoin_judge, dim3(ngroups), dim3(JT), 0, stream, a);
+    hipLaunchKernelGGL(k_unjoin_finish, dim3(1), dim3(256), 0, stream, a, ntiles, ngroups);
+    return hipGetLastError();
+}
+
+}  // namespace hdlz

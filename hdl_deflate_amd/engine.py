@@ -159,6 +159,61 @@ class Engine(object):
             raise HdlzStatusError(rec.status, "compress_joined")
         return out[:rec.stream_len], offsets
 
+    # -- STARTD for a joined stream, member by member in parallel (include/hdlz_unjoin.h)
+    @_on_device
+    def inflate_joined(self, d_stream, member_offsets, block=None, out_offsets=None, total=None, out=None, work=None, flags=0):
+        """d_stream: flat uint8 device tensor, the stream compress_joined returned; member_offsets: its int64[B + 1] index.  Where the
+        members go is stated like the compress call's input: `block` (with `total`, the length of the data: the output offsets are
+        rebuilt from chain.plan_blocks, the plan compress_joined used) or `out_offsets` int64[B + 1] on the device (`total` defaults
+        to out.numel(), else to out_offsets[B], which costs a second host sync).  Every member is decoded by the batch kernels straight
+        into the flat output and the stream is verified (markers, final block, Adler-32): hdlz_unjoin_ws.
+        -> out uint8[total].  One host sync (the result record); raises HdlzStatusError -- with .first_bad, the record's word -- on a
+        status that is not OK.  flags: one of the three INFLATE_*_PER_STREAM mapping hints, or 0.  `work`: the call's scratch, a uint8
+        device tensor of at least unjoin_work_bytes(B, total, flags) bytes (default: allocated here)."""
+        from .chain import plan_blocks
+        assert d_stream.is_cuda and d_stream.dtype == torch.uint8 and d_stream.dim() == 1 and d_stream.is_contiguous() and d_stream.device == self.device
+        assert member_offsets.is_cuda and member_offsets.dtype == torch.int64 and member_offsets.is_contiguous()
+        B, dev = member_offsets.numel() - 1, d_stream.device
+        out_len = 0
+        if block is not None:
+            if block % 4:
+                raise ValueError("block = %d is not a multiple of 4: the members' output slots would not start at dword boundaries; "
+                                 "read such a stream with inflate_bytes(z, verify=True)" % block)
+            if total is None:
+                raise ValueError("block= needs total=, the length of the data")
+            plan = plan_blocks(total, block) if B else []
+            if len(plan) != B:
+                raise ValueError("%d bytes in blocks of %d are %d members, the index has %d" % (total, block, len(plan), B))
+            if B and all(ln == block for _, ln in plan):
+                out_len = block                                      # uniform: no offset array at all
+            else:
+                out_offsets = torch.tensor([o for o, _ in plan] + [total], dtype=torch.int64).to(dev)
+        elif out_offsets is None:
+            raise ValueError("one of block= and out_offsets= says where the members go")
+        if out_offsets is not None:
+            assert out_offsets.is_cuda and out_offsets.dtype == torch.int64 and out_offsets.numel() == B + 1 and out_offsets.is_contiguous()
+        if total is None:
+            total = out.numel() if out is not None else int(out_offsets[B].item())
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.numel() >= total
+        need = self.lib.hdlz_unjoin_work_bytes(B, total, flags)
+        if work is None:
+            work = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
+        result = torch.empty(3, dtype=torch.int64, device=dev)                     # hdlz_unjoin_result: 24 bytes
+        rc = self.lib.hdlz_unjoin_ws(d_stream.data_ptr(), d_stream.numel(), member_offsets.data_ptr(),
+                                     out_offsets.data_ptr() if out_offsets is not None else None, out_len, B, flags,
+                                     out.data_ptr() if total else None, total, None, result.data_ptr(),
+                                     work.data_ptr() if work.numel() else None, work.numel(), self._stream())
+        self._check(rc, "hdlz_unjoin_ws")
+        rec = _lib.UnjoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+        if rec.status != OK:
+            err = HdlzStatusError(rec.status, "inflate_joined")
+            err.first_bad = rec.first_bad
+            raise err
+        return out[:rec.out_len]
+
     # -- STARTC for ONE large stream, spread over the whole GPU (same bytes as compress_batch with one block)
     STREAM_MIN = 1 << 14          # measured crossover with the single-wave batch path: ~8 KiB
     LARGE_BLOCK, MANY_WAVES = 1 << 16, 1200   # compress_batch: up to this many blocks of at least this size -> stream passes
@@ -323,9 +378,30 @@ class Engine(object):
         return int(st.item()), bytes(out[:int(ol.item())].cpu().numpy().tobytes())
 
     @_on_device
-    def inflate_bytes(self, z, out_cap=None, flags=0, obsize=0, verify=False):
+    def inflate_bytes(self, z, out_cap=None, flags=0, obsize=0, verify=False, members=None):
         """-> (status, bytes); verify=True: through the checked call (header, Adler-32, trailer present).  Default capacity: deflate expands at most 1032:1 (a 258-byte match costs 2 bits), so
-        1032 n + 258 bytes hold any stream, capped at the reference's 2^LMAX counter range (deflate.py:73-76)."""
+        1032 n + 258 bytes hold any stream, capped at the reference's 2^LMAX counter range (deflate.py:73-76).
+        members=(offsets, block): z is a joined stream (compress_joined / compress_bytes(block=...)) with its member index -- a
+        sequence or tensor of B + 1 offsets -- and the block size it was cut with: every member is decoded in parallel and the stream
+        verified (inflate_joined).  The length of the data is not part of a stream: it is taken from out_cap when given, else the last
+        two members are decoded once more as one short stream to measure them."""
+        if members is not None:
+            offsets, block = members
+            offs = [int(o) for o in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]
+            B = len(offs) - 1
+            total = out_cap
+            if total is None and B:
+                k = max(B - 2, 0)                                # members 0 .. k - 1 hold `block` bytes each (chain.plan_blocks)
+                st, tail = self.inflate_bytes(z[offs[k] - 2:], out_cap=2 * block + 16)
+                if st != OK:
+                    return st, b""
+                total = k * block + len(tail)
+            try:
+                out = self.inflate_joined(self._stage(z)[:len(z)], torch.tensor(offs, dtype=torch.int64).to(self.device), block=block,
+                                          total=total or 0, flags=flags)
+            except HdlzStatusError as e:
+                return e.status, b""
+            return OK, bytes(out.cpu().numpy().tobytes())
         n = len(z)
         d = self._stage(z).view(1, -1)
         cap = out_cap if out_cap is not None else inflate_cap(n)
