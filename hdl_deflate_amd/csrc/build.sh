@@ -28,7 +28,8 @@ only="${HDLZ_ONLY:-$srcs}"
 pids=()
 for f in $only; do
   src="$here/$f.hip"; obj="$objdir/$f.o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$here/hdlz_device.h" -nt "$obj" ] || [ "$here/hdlz_compress_common.h" -nt "$obj" ] || [ "$here/hdlz_inflate_tables.h" -nt "$obj" ] || [ "$here/hdlz_inflate_par.h" -nt "$obj" ] || [ "$here/../../include/hdlz.h" -nt "$obj" ] || [ "$here/../../include/hdlz_join.h" -nt "$obj" ] || [ "$here/../../include/hdlz_unjoin.h" -nt "$obj" ] || [ "${BASH_SOURCE[0]}" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "${BASH_SOURCE[0]}" -nt "$obj" ] ||
+     [ -n "$(find "$here" "$here/../../include" -maxdepth 1 -name '*.h' -newer "$obj" -print -quit)" ]; then
     ( "$HIPCC" $FLAGS -c "$src" -o "$obj" ) &
     pids+=($!)
   fi

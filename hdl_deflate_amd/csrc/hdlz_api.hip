@@ -225,6 +225,21 @@ int hdlz_join_batch_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t
 }  // extern "C"
 
 namespace {
+constexpr uint32_t MAPPING_HINTS = HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_GROUP_PER_STREAM;
+constexpr uint32_t INFLATE_FLAGS = MAPPING_HINTS | HDLZ_INFLATE_ASSUME_FIXED | HDLZ_INFLATE_ONEBLOCK | HDLZ_INFLATE_ONE_FIXED_BLOCK;
+
+// the batch mapping of n streams (hdlz_inflate_batch_ws) or members (hdlz_unjoin_ws).  One LANE per stream (k_inflate_tok, 64 streams
+// in lockstep per wave) needs ~10^5 streams to fill the GPU; up to HDLZ_INFLATE_WAVE_THRESHOLD streams one WAVE per stream
+// (k_inflate_dyn, window decode) is faster, for any block type; in between, from HDLZ_INFLATE_GROUP_MIN to HDLZ_INFLATE_GROUP_MAX
+// streams, 16 lanes per stream (k_inflate_grp) beat both.  A hint (at most one: the callers check) decides alone.
+enum class Mapping { lane, group, wave };
+Mapping mapping_of(uint64_t n, uint32_t flags) {
+    const bool group = (flags & HDLZ_INFLATE_GROUP_PER_STREAM) ||
+                       ((flags & MAPPING_HINTS) == 0u && n >= HDLZ_INFLATE_GROUP_MIN && n <= HDLZ_INFLATE_GROUP_MAX);
+    const bool wave = (flags & HDLZ_INFLATE_WAVE_PER_STREAM) || (!(flags & HDLZ_INFLATE_LANE_PER_STREAM) && n <= HDLZ_INFLATE_WAVE_THRESHOLD);
+    return group ? Mapping::group : wave ? Mapping::wave : Mapping::lane;
+}
+
 // does a batch of this shape take the whole-GPU path (hdlz_inflate_par.hip)?  ONE large stream: cut into pieces and decoded by the whole
 // GPU.  A FEW large streams: the same chain with every kernel launched once for all of them (blockIdx.y = the stream): the batch kernels
 // decode a stream as ONE serial chain (64 KiB: 5.9 ms, 1 MiB: 94 ms, however few there are); this path costs the launch chain once plus
@@ -244,15 +259,13 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
                        uint32_t* d_out_len, uint32_t* d_status, const hdlz::Work& w, void* stream, uint32_t* d_in_used = nullptr) {
     if (nstreams > 0x7FFFFFFFull * 32) return fail_param("nstreams too large for one launch");
     if (nstreams && (!d_in || !d_out || !d_out_len || !d_status)) return fail_param("null device pointer");
-    if (flags & ~(HDLZ_INFLATE_ASSUME_FIXED | HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_ONEBLOCK |
-                  HDLZ_INFLATE_GROUP_PER_STREAM | HDLZ_INFLATE_ONE_FIXED_BLOCK))
-        return fail_param("unknown flag");
+    if (flags & ~INFLATE_FLAGS) return fail_param("unknown flag");
     // the kernels keep stream lengths and bit positions in 32 bits (8 * length must not wrap)
     if (!d_in_off && in_len >= 0x10000000u) return fail_param("in_len too large (streams are limited to 256 MiB - 1)");
     if (d_in_off && in_len >= 0x10000000u) in_len = 0;      // ragged: a bound nobody can use is no bound
     if (!d_in_off && nstreams > 1 && in_pitch < in_len) return fail_param("in_pitch < in_len");
     {
-        const uint32_t mf = flags & (HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_GROUP_PER_STREAM);
+        const uint32_t mf = flags & MAPPING_HINTS;
         if (mf & (mf - 1u)) return fail_param("contradictory mapping flags");
     }
     if ((out_pitch & 3u) || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return fail_param("d_out / out_pitch must be 4-byte aligned");
@@ -262,16 +275,8 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
     if (nstreams == 0) return HDLZ_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hdlz::InflateArgs a{d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, d_in_used};
-    // mapping: one LANE per stream (k_inflate_tok, 64 streams in lockstep per wave) needs ~10^5 streams to fill the GPU;
-    // below HDLZ_INFLATE_WAVE_THRESHOLD streams one WAVE per stream (k_inflate_dyn, window decode) is faster, for any block type;
-    // in between: 16 lanes per stream (k_inflate_grp) -- from HDLZ_INFLATE_GROUP_MIN streams on it beats a wave per stream,
-    // up to HDLZ_INFLATE_GROUP_MAX a lane per stream; the streams it flags (dynamic-tree blocks) take the second pass below
-    const uint32_t hint = flags & (HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_GROUP_PER_STREAM);
     if ((flags & HDLZ_INFLATE_GROUP_PER_STREAM) && nstreams > 0x7FFFFFFFull * 16) return fail_param("nstreams too large for the 16-lanes-per-stream mapping");
-    const bool group = (flags & HDLZ_INFLATE_GROUP_PER_STREAM) ||
-                       (hint == 0u && nstreams >= HDLZ_INFLATE_GROUP_MIN && nstreams <= HDLZ_INFLATE_GROUP_MAX);
-    const bool wave_all = !group && ((flags & HDLZ_INFLATE_WAVE_PER_STREAM) ||
-                                     (!(flags & HDLZ_INFLATE_LANE_PER_STREAM) && nstreams <= HDLZ_INFLATE_WAVE_THRESHOLD));
+    const Mapping map = mapping_of(nstreams, flags);
     if (par_applies(nstreams, in_len, flags)) {
         bool used = false;
         hipError_t e = hdlz::launch_inflate_par(a, st, &used, w);
@@ -279,13 +284,13 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
         if (used) return HDLZ_OK;
         // (no scratch, or a shape the path leaves alone: the batch kernels below)
     }
-    if (wave_all) {
+    if (map == Mapping::wave) {
         hipError_t e = hdlz::launch_inflate_dyn(a, st, true);
         if (e != hipSuccess) return fail_hip(e, "launch k_inflate_dyn");
         return HDLZ_OK;
     }
     // lane per stream, one TOKEN group per round (k_inflate_tok), or 16 lanes per stream
-    hipError_t e = group ? hdlz::launch_inflate_grp(a, st) : hdlz::launch_inflate_tok(a, st, w);
+    hipError_t e = map == Mapping::group ? hdlz::launch_inflate_grp(a, st) : hdlz::launch_inflate_tok(a, st, w);
     if (e != hipSuccess) return fail_hip(e, "launch k_inflate");
     // second pass, same stream: streams in which pass 1 met a dynamic-tree block (status 6) are redone, again one lane each
     // (k_inflate_tok<true>); everything else is left untouched
@@ -335,9 +340,7 @@ int hdlz_inflate_checked(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t
                          uint32_t* d_out_len, uint32_t* d_status, uint32_t* d_in_used, uint32_t* d_adler,
                          void* d_work, size_t work_bytes, void* stream) {
     if (!d_in_used) return fail_param("d_in_used is required");
-    if (flags & ~(HDLZ_INFLATE_ASSUME_FIXED | HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_ONEBLOCK |
-                  HDLZ_INFLATE_GROUP_PER_STREAM | HDLZ_INFLATE_ONE_FIXED_BLOCK))
-        return fail_param("unknown flag");
+    if (flags & ~INFLATE_FLAGS) return fail_param("unknown flag");
     if (flags & HDLZ_INFLATE_ONEBLOCK) return fail_param("HDLZ_INFLATE_ONEBLOCK: a stream cut at its first block has no trailer behind it");
     const size_t share = hdlz::judge_work_bytes(nstreams, out_pitch);
     if (share != 0u && (!d_work || work_bytes < share)) return fail_param("d_work smaller than the judging pass's share (hdlz_inflate_checked_work_bytes - hdlz_inflate_work_bytes)");
@@ -468,12 +471,10 @@ int hdlz_inflate_chunk(const uint8_t* d_in, uint32_t in_len, int final, uint32_t
 }
 
 // ---- include/hdlz_unjoin.h: a joined stream read back member by member (the member view of the batch decoders; hdlz_unjoin.hip)
-static size_t r256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
 size_t hdlz_unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) {
     if (nmembers > 0x7FFFFFFFull) return 0;
-    return r256(12u * (size_t)nmembers) + r256(sizeof(uint2) * hdlz::unjoin_tiles(total_out)) +
-           r256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1));
+    return hdlz::round256(12u * (size_t)nmembers) + hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(total_out)) +
+           hdlz::round256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1));
 }
 
 int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
@@ -481,8 +482,7 @@ int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t*
                    hdlz_unjoin_result* d_result, void* d_work, size_t work_bytes, void* stream) {
     if (!d_stream || !d_off || !d_result || (out_cap && !d_out)) return fail_param("null device pointer");
     if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
-    const uint32_t hints = HDLZ_INFLATE_LANE_PER_STREAM | HDLZ_INFLATE_WAVE_PER_STREAM | HDLZ_INFLATE_GROUP_PER_STREAM;
-    if (flags & ~hints) return fail_param("unknown flag (hdlz_unjoin_ws takes the three mapping hints only)");
+    if (flags & ~MAPPING_HINTS) return fail_param("unknown flag (hdlz_unjoin_ws takes the three mapping hints only)");
     if (flags & (flags - 1u)) return fail_param("contradictory mapping flags");
     if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail_param("d_out must be 4-byte aligned");
     if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
@@ -495,7 +495,7 @@ int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t*
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint8_t* wb = static_cast<uint8_t*>(d_work);
     uint32_t* words = reinterpret_cast<uint32_t*>(wb);
-    const size_t per = r256(12u * (size_t)nmembers), tiles = r256(sizeof(uint2) * hdlz::unjoin_tiles(out_cap));
+    const size_t per = hdlz::round256(12u * (size_t)nmembers), tiles = hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(out_cap));
     const hdlz::UnjoinArgs u{d_stream, stream_len, d_off, d_out_off, out_len, nmembers, d_out, out_cap, d_member_status, d_result,
                              words, words + nmembers, words + 2u * nmembers, reinterpret_cast<uint2*>(wb + per)};
     hipError_t e = hdlz::launch_unjoin_index(u, st);
@@ -507,13 +507,10 @@ int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t*
         a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.len; a.status = u.status; a.in_used = u.end_bit;
         a.m_off = d_off; a.m_out_off = d_out_off; a.m_out_len = out_len; a.m_out_cap = out_cap;
         // the mapping: the thresholds of hdlz_inflate_batch_ws, or the hint; never the whole-GPU chains
-        const bool group = (flags & HDLZ_INFLATE_GROUP_PER_STREAM) ||
-                           (flags == 0u && nmembers >= HDLZ_INFLATE_GROUP_MIN && nmembers <= HDLZ_INFLATE_GROUP_MAX);
-        const bool wave_all = !group && ((flags & HDLZ_INFLATE_WAVE_PER_STREAM) ||
-                                         (!(flags & HDLZ_INFLATE_LANE_PER_STREAM) && nmembers <= HDLZ_INFLATE_WAVE_THRESHOLD));
+        const Mapping map = mapping_of(nmembers, flags);
         const hdlz::Work w{wb + per + tiles, work_bytes - per - tiles, true};
-        e = wave_all ? hdlz::launch_inflate_dyn_members(a, st) : group ? hdlz::launch_inflate_grp_members(a, st)
-                                                                       : hdlz::launch_inflate_tok_members(a, st, w);
+        e = map == Mapping::wave ? hdlz::launch_inflate_dyn_members(a, st) : map == Mapping::group ? hdlz::launch_inflate_grp_members(a, st)
+                                                                                                 : hdlz::launch_inflate_tok_members(a, st, w);
         if (e != hipSuccess) return fail_hip(e, "launch the member decode");
     }
     e = hdlz::launch_unjoin_judge(u, st);

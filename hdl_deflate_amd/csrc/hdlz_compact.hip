@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void k_archive(const uint8_t* __restrict__ row
 
 size_t archive_work_bytes(uint64_t nblocks) {                  // ticket (+ pad), then one 64-bit descriptor per tile
     const uint64_t ntiles = (nblocks + AT - 1u) / AT;
-    return ntiles ? (sizeof(uint32_t) * (2u + 2u * (size_t)ntiles) + 255u) & ~(size_t)255u : 0u;
+    return ntiles ? round256(sizeof(uint32_t) * (2u + 2u * (size_t)ntiles)) : 0u;
 }
 
 hipError_t launch_archive(const uint8_t* rows, uint64_t pitch, const uint32_t* len, uint64_t nblocks, uint8_t* archive, uint64_t cap,

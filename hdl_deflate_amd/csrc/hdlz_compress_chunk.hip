@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64) void k_compress_chunk(ChunkArgs a) {
             const uint64_t A = ((uint64_t)st.adler_a + sA) % ADLER_MOD, C = ((uint64_t)st.adler_c + sC) % ADLER_MOD;
             const uint64_t nm = n % ADLER_MOD;
             const uint32_t s1 = (uint32_t)((A + 1u) % ADLER_MOD);
-            const uint32_t s2 = (uint32_t)((nm + nm * A + ADLER_MOD - C) % ADLER_MOD);   // N + sum (N - p) x_p
+            const uint32_t s2 = (uint32_t)((nm + nm * A + ADLER_MOD - C) % ADLER_MOD);   // N + sum (N - p) x_p: adler32_from (hdlz_adler.h) in this kernel's 64-bit form
             const uint32_t nbytes = block_nbytes(end_bits);
             __syncthreads();
             if (lane == 0) put_adler(out8, nbytes, s1, s2);

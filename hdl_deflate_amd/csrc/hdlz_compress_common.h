@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "hdlz_device.h"
+#include "hdlz_adler.h"                  // ADLER_MOD
 
 namespace hdlz {
 
@@ -31,7 +32,6 @@ constexpr int LUT_MATCH = 256;      // [len-3][dist-1] (CWINDOW <= 32) or [dist-
 constexpr uint32_t LUT_MATCH_BYTE = 4u * LUT_LIT;
 constexpr int LUT_LEN = 16;         // [len-1] -> the length code (wide windows: the match LUT is [dist-1] only)   at LUT word 512
 constexpr uint32_t LUT_LEN_BYTE = 4u * (LUT_LIT + LUT_MATCH);
-constexpr uint32_t ADLER_MOD = 65521u;
 constexpr uint32_t NB_SHIFT = 27;   // LUT entry = code (27 bits) | nbits << 27
 constexpr uint32_t CODE_MASK = (1u << NB_SHIFT) - 1u;
 

@@ -69,6 +69,8 @@ __device__ __forceinline__ void member_view(const MemberArgs& a, uint64_t b, uin
 __host__ __device__ inline uint32_t out_bound(uint32_t n) {
     return 6u + (uint32_t)((9ull * n + 10ull + 7ull) >> 3);
 }
+// scratch is handed out in pieces of 256 bytes
+constexpr size_t round256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
 // wave64 ballot straight from the compare.  (HIP's __ballot(int) takes the predicate through a 0/1 VGPR: v_cndmask + v_cmp_ne per
 // call -- 19 such pairs in a round of k_inflate_tok.)

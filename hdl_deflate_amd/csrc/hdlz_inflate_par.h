@@ -91,7 +91,7 @@ __host__ inline uint32_t passes_for(uint32_t nitems) {                 // chains
 struct Carve {
     uintptr_t base;
     size_t off;                 // bytes handed out so far
-    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255u) & ~(size_t)255u; return o; }
+    size_t take(size_t bytes) { const size_t o = off; off = round256(off + bytes); return o; }
     template <typename T> void take(T*& p, size_t bytes) { p = reinterpret_cast<T*>(base + take(bytes)); }
 };
 

@@ -1047,7 +1047,7 @@ static Lists lists_of(uint64_t nstreams, bool ragged, bool all) {
 size_t inflate_tok_work_bytes(uint64_t nstreams, bool ragged) {
     if (nstreams == 0 || nstreams > 0xFFFFFFFFull) return 0;
     const tok::Lists l = tok::lists_of(nstreams, ragged, false);
-    return (sizeof(uint32_t) * (l.pass1 > l.pass2 ? l.pass1 : l.pass2) + 255u) & ~(size_t)255u;
+    return round256(sizeof(uint32_t) * (l.pass1 > l.pass2 ? l.pass1 : l.pass2));
 }
 
 hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Work& w) {

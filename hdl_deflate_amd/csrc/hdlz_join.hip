@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
-#include "hdlz_compress_common.h"                        // the framing constants: HEADER_WORD, HEADER_BITS, block_nbytes, ADLER_MOD
+#include "hdlz_compress_common.h"                        // the framing constants: HEADER_WORD, HEADER_BITS, block_nbytes; hdlz_adler.h: ADLER_MOD
 
 namespace hdlz {
 
@@ -232,7 +232,7 @@ static inline uint64_t join_tiles(uint64_t nblocks) { return (nblocks + JT - 1u)
 
 size_t join_work_bytes(uint64_t nblocks) {                     // ticket (+ pad), one 64-bit look-back word and PARTS words per tile
     const uint64_t ntiles = join_tiles(nblocks);
-    return ntiles ? (sizeof(uint32_t) * (2u + (2u + PARTS) * (size_t)ntiles) + 255u) & ~(size_t)255u : 0u;
+    return ntiles ? round256(sizeof(uint32_t) * (2u + (2u + PARTS) * (size_t)ntiles)) : 0u;
 }
 
 hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,

@@ -4,67 +4,22 @@
 // The decode itself is the member view of the three batch decoders (hdlz_device.h: MemberArgs).  A decoder trusts its index words,
 // so k_unjoin_index looks at them first: a member whose words are unusable, or whose first block is not a fixed one, gets its status
 // here and the decoders leave it alone.  Behind the decode k_unjoin_tiles sums the CONTIGUOUS output in 32 KiB tiles over the whole GPU
-// (the arithmetic of k_adler_tiles, hdlz_checksum.hip: restated here, not shared -- its kernels stay the code objects they were),
+// (the tile loop of k_adler_tiles, unrotated; chunk sums, tail rule and bounds: hdlz_adler.h -- out_cap may be any number, so nothing
+// at or behind the total is loaded),
 // k_unjoin_judge compares every member's decoded length with its slot and looks for the sync marker behind the END BIT the decoder
 // left (the first bit behind the end-of-block code, counted from two bytes in front of the member), and k_unjoin_finish, one
 // workgroup, reduces the tiles and the verdicts, reads the final empty block and the trailer and writes the record.
-//
-// Adler-32 of the output X (N bytes) from the tiles: with A_t = the byte sum of tile t and C_t = sum q x_q over its bytes (q relative to
-// the tile), A = sum A_t and C = sum (32768 t A_t + C_t), s1 = 1 + A, s2 = N + N A - C (mod 65521).  Bounds: inside a tile as in
-// k_adler_tiles (a lane adds 8 terms below 1.34e8); k_unjoin_finish folds (32768 t mod 65521) A_t + C_t < 2^32 per tile into 64 bits --
-// exact for up to 2^31 tiles, an output of 2^46 bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
+#include "hdlz_adler.h"
 
 namespace hdlz {
 namespace unj {
 
-constexpr uint32_t MOD = 65521u;
-constexpr uint32_t TILE = 32768u;             // bytes per workgroup step of k_unjoin_tiles: 4 waves x 8 steps x 64 lanes x 16 bytes
-constexpr uint32_t TILE_WAVES = 4u, TILE_STEPS = 8u;
-static_assert(TILE == TILE_WAVES * TILE_STEPS * 1024u, "a tile is what its workgroup's waves cover");
 constexpr uint32_t JT = 256u;                 // members per workgroup of the index checks and of the judge
 constexpr uint32_t NONE = 0xFFFFFFFFu;        // a workgroup without a failed member
 constexpr uint64_t MEMBER_MAX = 1ull << 28;   // bit positions are 32-bit in the decoders
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// Sx and W of one chunk (hdlz_checksum.hip)
-__device__ __forceinline__ void sums16(const u32x4 v, uint32_t& sx, uint32_t& w) {
-    sx = __builtin_amdgcn_sad_u8(v.x, 0u, 0u);
-    sx = __builtin_amdgcn_sad_u8(v.y, 0u, sx);
-    sx = __builtin_amdgcn_sad_u8(v.z, 0u, sx);
-    sx = __builtin_amdgcn_sad_u8(v.w, 0u, sx);
-    w = __builtin_amdgcn_udot4(v.x, 0x03020100u, 0u, false);
-    w = __builtin_amdgcn_udot4(v.y, 0x07060504u, w, false);
-    w = __builtin_amdgcn_udot4(v.z, 0x0B0A0908u, w, false);
-    w = __builtin_amdgcn_udot4(v.w, 0x0F0E0D0Cu, w, false);
-}
-// the dword at p of which only `cnt` bytes (1 .. 3) may be loaded: the output's capacity need not be a multiple of 4
-__device__ __forceinline__ uint32_t load_tail(const uint8_t* __restrict__ p, int32_t cnt) {
-    uint32_t d = p[0];
-    if (cnt > 1) d |= (uint32_t)p[1] << 8;
-    if (cnt > 2) d |= (uint32_t)p[2] << 16;
-    return d;
-}
-// the chunk at byte q of `p` (q a multiple of 16, below n; p 4-byte aligned): bytes at or behind n read as zero and are not loaded
-template <bool A16>
-__device__ __forceinline__ u32x4 load_chunk(const uint8_t* __restrict__ p, uint32_t q, uint32_t n) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    const uint32_t* d = reinterpret_cast<const uint32_t*>(p + q);
-    if (q + 16u <= n) {
-        if constexpr (A16) v = *reinterpret_cast<const u32x4*>(d);
-        else { v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3]; }
-    } else {
-        const int32_t cnt = (int32_t)(n - q);                 // 1 .. 15
-        auto part = [&](int32_t k) -> uint32_t {
-            const int32_t c = cnt - 4 * k;
-            return c >= 4 ? d[k] : c > 0 ? load_tail(p + q + 4 * k, c) : 0u;
-        };
-        v.x = part(0); v.y = part(1); v.z = part(2); v.w = part(3);
-    }
-    return v;
-}
 
 // member b's slot of the output: [o, e) -- the caller checks what it relies on
 __device__ __forceinline__ void slot_of(const UnjoinArgs& a, uint64_t b, uint64_t& o, uint64_t& e) {
@@ -96,27 +51,27 @@ __global__ __launch_bounds__(JT) void k_unjoin_index(UnjoinArgs a) {
 
 // ---- behind the decode: (A, C) of every 32 KiB tile of out[0 .. total), positions relative to the tile; (0, 0) for the tiles behind it
 template <bool A16>
-__global__ __launch_bounds__(64 * TILE_WAVES) void k_unjoin_tiles(UnjoinArgs a, uint32_t ntiles) {
-    __shared__ uint32_t sa[TILE_WAVES], sc[TILE_WAVES];
+__global__ __launch_bounds__(64 * ADLER_TILE_WAVES) void k_unjoin_tiles(UnjoinArgs a, uint32_t ntiles) {
+    __shared__ uint32_t sa[ADLER_TILE_WAVES], sc[ADLER_TILE_WAVES];
     const uint64_t total = total_of(a);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t base = (uint64_t)t * TILE;
+        const uint64_t base = (uint64_t)t * ADLER_TILE;
         uint32_t a32 = 0, c32 = 0;
         if (base < total) {
-            const uint32_t tn = total - base < TILE ? (uint32_t)(total - base) : TILE;
+            const uint32_t tn = total - base < ADLER_TILE ? (uint32_t)(total - base) : ADLER_TILE;
             const uint8_t* __restrict__ p = a.out + base;
 #pragma unroll
-            for (uint32_t k = 0; k < TILE_STEPS; k++) {
-                const uint32_t q = (wave * TILE_STEPS + k) * 1024u + 16u * lane;
+            for (uint32_t k = 0; k < ADLER_TILE_STEPS; k++) {
+                const uint32_t q = (wave * ADLER_TILE_STEPS + k) * 1024u + 16u * lane;
                 if (q < tn) {
                     uint32_t sx, w;
-                    sums16(load_chunk<A16>(p, q, tn), sx, w);
+                    sums16(load_chunk<A16, false>(p, q, tn), sx, w);
                     a32 += sx;
                     c32 += __umul24(q, sx) + w;
                 }
             }
-            c32 %= MOD;
+            c32 %= ADLER_MOD;
 #pragma unroll
             for (int ofs = 32; ofs > 0; ofs >>= 1) { a32 += (uint32_t)__shfl_xor((int)a32, ofs, 64); c32 += (uint32_t)__shfl_xor((int)c32, ofs, 64); }
         }
@@ -125,8 +80,8 @@ __global__ __launch_bounds__(64 * TILE_WAVES) void k_unjoin_tiles(UnjoinArgs a, 
         if (threadIdx.x == 0u) {
             uint32_t A = 0, C = 0;
 #pragma unroll
-            for (uint32_t k = 0; k < TILE_WAVES; k++) { A += sa[k]; C += sc[k]; }
-            a.tiles[t] = make_uint2(A % MOD, C % MOD);
+            for (uint32_t k = 0; k < ADLER_TILE_WAVES; k++) { A += sa[k]; C += sc[k]; }
+            a.tiles[t] = make_uint2(A % ADLER_MOD, C % ADLER_MOD);
         }
         __syncthreads();
     }
@@ -178,13 +133,11 @@ __global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t nt
     uint64_t A64 = 0, C64 = 0;
     for (uint32_t t = tid; t < ntiles; t += 256u) {
         const uint2 s = a.tiles[t];
-        const uint32_t base = ((t % MOD) * (TILE % MOD)) % MOD;           // 32768 t mod 65521 (the product stays below 2^32)
-        A64 += s.x;
-        C64 += (uint64_t)base * s.x + s.y;
+        fold_tile(A64, C64, t, s.x, s.y);
     }
     uint32_t f = NONE;
     for (uint32_t g = tid; g < ngroups; g += 256u) f = min(f, a.len[(size_t)g * JT]);
-    s_a[tid] = A64 % MOD; s_c[tid] = C64 % MOD; s_f[tid] = f;
+    s_a[tid] = A64 % ADLER_MOD; s_c[tid] = C64 % ADLER_MOD; s_f[tid] = f;
     __syncthreads();
     for (uint32_t o = 128u; o > 0u; o >>= 1) {
         if (tid < o) { s_a[tid] += s_a[tid + o]; s_c[tid] += s_c[tid + o]; s_f[tid] = min(s_f[tid], s_f[tid + o]); }
@@ -192,8 +145,9 @@ __global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t nt
     }
     if (tid != 0u) return;
     const uint64_t total = total_of(a);
-    const uint32_t A = (uint32_t)(s_a[0] % MOD), C = (uint32_t)(s_c[0] % MOD), nm = (uint32_t)(total % MOD);
-    const uint32_t s1 = (1u + A) % MOD, s2 = (uint32_t)(((uint64_t)nm + (uint64_t)nm * A + MOD - C) % MOD);
+    // (adler32_from, restated: called here, the kernel comes out 11 instructions shorter -- another code object, profiles/adler_shared.txt)
+    const uint32_t A = (uint32_t)(s_a[0] % ADLER_MOD), C = (uint32_t)(s_c[0] % ADLER_MOD), nm = (uint32_t)(total % ADLER_MOD);
+    const uint32_t s1 = (1u + A) % ADLER_MOD, s2 = (uint32_t)(((uint64_t)nm + (uint64_t)nm * A + ADLER_MOD - C) % ADLER_MOD);
     hdlz_unjoin_result res;
     res.out_len = total; res.first_bad = ~0ull; res.status = HDLZ_OK; res.adler = (s2 << 16) | s1;
     if (s_f[0] != NONE) {
@@ -203,13 +157,12 @@ __global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t nt
         bool head = a.off[0] == 2u && a.in_len >= 2u;
         if (head) {
             const uint32_t cmf = a.in[0], flg = a.in[1];
-            head = (cmf & 15u) == 8u && (cmf >> 4) <= 7u && (cmf * 256u + flg) % 31u == 0u && (flg & 0x20u) == 0u;
+            head = !HDLZ_ZLIB_HEADER_BAD(cmf, flg);
         }
         if (!head) res.status = HDLZ_E_BAD_HEADER;
         else if (a.in_len < 6u || end > a.in_len - 6u || a.in[end] != 3u || a.in[end + 1u] != 0u) res.status = HDLZ_E_NO_EOF;
         else {
-            const uint8_t* t = a.in + end + 2u;
-            const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | (uint32_t)t[3];
+            const uint32_t want = load_be32(a.in + end + 2u);
             if (want != res.adler) res.status = HDLZ_E_BAD_CHECKSUM;
         }
         if (res.status != HDLZ_OK) res.first_bad = a.nmembers;
@@ -220,7 +173,7 @@ __global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t nt
 
 }  // namespace unj
 
-size_t unjoin_tiles(uint64_t total_out) { return (size_t)((total_out + unj::TILE - 1u) / unj::TILE); }
+size_t unjoin_tiles(uint64_t total_out) { return (size_t)((total_out + ADLER_TILE - 1u) / ADLER_TILE); }
 
 hipError_t launch_unjoin_index(const UnjoinArgs& a, hipStream_t stream) {
     if (a.nmembers == 0) return hipSuccess;
@@ -235,7 +188,7 @@ hipError_t launch_unjoin_judge(const UnjoinArgs& a, hipStream_t stream) {
     const uint32_t ntiles = (uint32_t)(nt64 < 0x80000000ull ? nt64 : 0x80000000ull);      // (2^46 bytes: the ABI's bound)
     const uint32_t ngroups = (uint32_t)((a.nmembers + JT - 1u) / JT);
     if (ntiles) {
-        const dim3 grid(ntiles < (1u << 22) ? ntiles : (1u << 22)), block(64 * TILE_WAVES);
+        const dim3 grid(ntiles < (1u << 22) ? ntiles : (1u << 22)), block(64 * ADLER_TILE_WAVES);
         if ((reinterpret_cast<uintptr_t>(a.out) & 15u) == 0u) hipLaunchKernelGGL(k_unjoin_tiles<true>, grid, block, 0, stream, a, ntiles);
         else hipLaunchKernelGGL(k_unjoin_tiles<false>, grid, block, 0, stream, a, ntiles);
     }

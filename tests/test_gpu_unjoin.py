@@ -140,6 +140,14 @@ def test_three_large_members(engine):
     roundtrip(engine, "large", blocks, cw=256)
 
 
+def test_all_ff_across_tile_edges(engine):
+    """the worst case of the checksum's bounds (hdlz_adler.h) through the flat finish: every byte FF, two and three full 32 KiB tiles
+    and an odd tail of 3 and 5 bytes, the capacity the total itself"""
+    for lengths, total in (([32768, 32764, 7], 65539), ([32768, 32768, 32768, 5], 98309)):
+        assert sum(lengths) == total
+        roundtrip(engine, ("ff", total), [b"\xff" * n for n in lengths])
+
+
 def test_no_members(engine):
     for flags in HINTS:
         r = Run(engine.lib, b"\x78\x9c\x03\x00\x00\x00\x00\x01", [2], out_cap=0, flags=flags)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Evidence for hdlz_unjoin_ws (include/hdlz_unjoin.h), three sections of profiles/unjoin.txt, one sub-command each:
 
-  codeobj --parent OBJDIR   (no GPU) the code-object metadata of every kernel in hdlz_inflate_tok / _grp / _dyn / hdlz_checksum of a
-                            build of the parent commit (its csrc/_obj) beside this build's: the existing instantiations must be the
-                            same, the member twins are listed next to them.
+  codeobj --parent OBJDIR   (no GPU) the code-object metadata of every kernel in hdlz_inflate_tok / _grp / _dyn / hdlz_checksum (or of
+                            --sources A,B,...) of a build of the parent commit (its csrc/_obj) beside this build's: the existing
+                            instantiations must be the same, the member twins are listed next to them.  Each kernel's instructions
+                            (llvm-objdump -d) are compared too: identical / same opcodes, registers renamed / differs.
   time                      (a) hdlz_inflate_checked of the per-block rows as a ragged archive, forced to the mapping (b) chooses,
                             (b) hdlz_unjoin_ws of the joined stream; 2 GiB of the four bench families as 2 KiB and as 64 KiB blocks,
                             HIP events, calls alternated in one process.  Yardstick: (b) <= 1.15 x (a).
@@ -45,23 +46,39 @@ def put_section(path, title, lines):
 
 
 def kernels_of(obj):
-    """{demangled kernel name: {field: value}} of the gfx950 code object inside a hipcc object file"""
+    """{demangled kernel name: {field: value, "code": [instruction text]}} of the gfx950 code object inside a hipcc object file"""
     with tempfile.TemporaryDirectory() as d:
         fat, co = os.path.join(d, "fat"), os.path.join(d, "co")
         subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj])
         subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat, "--output=" + co,
                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"])
         notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co]).decode()
+        asm = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", co]).decode()
+    code = {}                                                  # symbol -> its instructions without address and encoding
+    for part in re.split(r"(?m)^[0-9a-f]+ <", asm)[1:]:
+        code[part[:part.index(">")]] = [l.split("//")[0].strip() for l in part.splitlines()[1:] if l.strip()]
     out = {}
     for blk in re.split(r"(?m)^\s*- \.agpr_count", notes)[1:]:
-        name = re.search(r"(?m)^\s*\.name:\s*(\S+)", blk).group(1)
-        name = subprocess.check_output(["c++filt", name]).decode().strip()
-        out[re.sub(r"\(.*", "", name).replace("void ", "")] = {f: int(re.search(r"(?m)^\s*%s:\s*(\d+)" % re.escape(f), blk).group(1)) for f in FIELDS}
+        sym = re.search(r"(?m)^\s*\.name:\s*(\S+)", blk).group(1)
+        name = subprocess.check_output(["c++filt", sym]).decode().strip()
+        k = out[re.sub(r"\(.*", "", name).replace("void ", "")] = {f: int(re.search(r"(?m)^\s*%s:\s*(\d+)" % re.escape(f), blk).group(1)) for f in FIELDS}
+        k["code"] = code[sym]
     return out
 
 
+def code_tag(old, new):
+    """how two instruction sequences compare; register numbers (v12, s[4:5], a3) are what "renamed" forgives"""
+    if old == new:
+        return "identical (%d instructions)" % len(new)
+    blank = lambda seq: [re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", i) for i in seq]
+    if blank(old) == blank(new):
+        return "same opcodes, registers renamed (%d instructions)" % len(new)
+    return "differs (%d -> %d instructions)" % (len(old), len(new))
+
+
 def canon(name):
-    """an existing instantiation under the name it had before the MEMBERS flag: the default (false) flag dropped"""
+    """an existing instantiation under the name it had before the MEMBERS flag: the default (false) flag dropped (on both sides: a
+    parent that has the flag already compares like with like)"""
     name = re.sub(r"(k_inflate_tok<[^,]+, \d+u), false>", r"\1>", name)
     name = re.sub(r"(k_inflate_dyn<(?:true|false)), false>", r"\1>", name)
     return name.replace("k_inflate_grp<false>", "k_inflate_grp")
@@ -70,19 +87,21 @@ def canon(name):
 def cmd_codeobj(args):
     new_dir = os.path.join(ROOT, "hdl_deflate_amd", "csrc", "_obj")
     lines = ["code-object metadata, parent build | this build (%s)" % ", ".join(f[1:] for f in FIELDS),
-             "command: python tools/probe_unjoin.py codeobj --parent <csrc/_obj of a build of the parent commit>", ""]
+             "command: python tools/probe_unjoin.py codeobj --parent <csrc/_obj of a build of the parent commit>" +
+             (" --sources " + args.sources if args.sources else ""), ""]
     differ, notes = 0, []
-    for src in SOURCES:
-        old = kernels_of(os.path.join(args.parent, src + ".o"))
+    for src in (args.sources.split(",") if args.sources else SOURCES):
+        old = {canon(k): v for k, v in kernels_of(os.path.join(args.parent, src + ".o")).items()}
         new = {canon(k): (k, v) for k, v in kernels_of(os.path.join(new_dir, src + ".o")).items()}
         lines.append(src + ":")
         for name in sorted(set(old) | set(new)):
             o = old.get(name)
             full, n = new.get(name, (name, None))
             fmt = lambda v: "-" if v is None else " ".join("%d" % v[f] for f in FIELDS)
-            tag = "twin (new)" if o is None else "MISSING" if n is None else "same" if o == n else "DIFFERS"
-            differ += tag in ("MISSING", "DIFFERS")
-            lines.append("  %-60s %-24s | %-24s %s" % (full, fmt(o), fmt(n), tag))
+            tag = "twin (new)" if o is None else "MISSING" if n is None else "same" if fmt(o) == fmt(n) else "DIFFERS"
+            code = code_tag(o["code"], n["code"]) if o and n else ""
+            differ += tag in ("MISSING", "DIFFERS") or code.startswith("differs")
+            lines.append("  %-60s %-24s | %-24s %s%s" % (full, fmt(o), fmt(n), tag, code and "; " + code))
             if o is None and (n[".private_segment_fixed_size"] or n[".vgpr_spill_count"] or n[".sgpr_spill_count"]):
                 notes.append("  finding: %s -- scratch %d bytes, %d VGPRs and %d SGPRs spilled" %
                              (full, n[".private_segment_fixed_size"], n[".vgpr_spill_count"], n[".sgpr_spill_count"]))
@@ -237,6 +256,7 @@ def main():
     ap.add_argument("cmd", choices=("codeobj", "time", "ab", "ab-child"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unjoin.txt"))
     ap.add_argument("--parent")
+    ap.add_argument("--sources", help="codeobj: comma-separated source names in place of the default four")
     ap.add_argument("--log2-bytes", type=int, default=31)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
