@@ -50,6 +50,18 @@ UNJOIN_SIGNATURES = {
     "hdlz_unjoin_ws": (ci, [vp, u64, vp, vp, u32, u64, u32, vp, u64, vp, vp, vp, sz, vp]),
 }
 UNJOIN_EXPORTS = tuple(UNJOIN_SIGNATURES)
+# ... and of include/hdlz_gzip.h: CRC-32 on the device, the joined stream as one gzip member (tests/test_gzip_cabi.py)
+GZIP_SIGNATURES = {
+    "hdlz_crc32_work_bytes": (sz, [u64]),
+    "hdlz_crc32_ws": (ci, [vp, u64, vp, vp, sz, vp]),    # d_data, n, d_crc, d_work, work_bytes, stream
+    "hdlz_join_gzip_bound": (sz, [u64, u32]),
+    "hdlz_join_gzip_work_bytes": (sz, [u64]),
+    # the first eight parameters of hdlz_join_batch_ws, d_crc, d_stream, stream_cap, d_off, d_result, d_work, work_bytes, stream
+    "hdlz_join_gzip_ws": (ci, [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp, sz, vp]),
+    "hdlz_unjoin_gzip_work_bytes": (sz, [u64, u64, u32]),
+    "hdlz_unjoin_gzip_ws": (ci, [vp, u64, vp, vp, u32, u64, u32, vp, u64, vp, vp, vp, sz, vp]),      # as hdlz_unjoin_ws
+}
+GZIP_EXPORTS = tuple(GZIP_SIGNATURES)
 _lib = None
 
 
@@ -67,6 +79,16 @@ class JoinResult(ctypes.Structure):
 class UnjoinResult(ctypes.Structure):
     """hdlz_unjoin_result: the result record of hdlz_unjoin_ws (24 bytes)"""
     _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("adler", u32)]
+
+
+class JoinGzipResult(ctypes.Structure):
+    """hdlz_join_gzip_result: the result record of hdlz_join_gzip_ws (16 bytes)"""
+    _fields_ = [("stream_len", u64), ("status", u32), ("crc", u32)]
+
+
+class UnjoinGzipResult(ctypes.Structure):
+    """hdlz_unjoin_gzip_result: the result record of hdlz_unjoin_gzip_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("crc", u32)]
 
 
 class IState(ctypes.Structure):
@@ -87,7 +109,8 @@ def load():
     # two HIP runtimes in one process and torch's streams/pointers would be foreign to ours.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
+            list(GZIP_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -14,6 +14,11 @@ fi
 if [ "${1:-}" = "keys" ]; then
   HDLZ_VARIANT=keys HDLZ_DEFS="-DHDLZ_SEARCH_KEYS" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
 fi
+# `build.sh crcbank` builds lib/libhdlz_crcbank.so: the CRC-32 tile kernels with the bank-private table layout (hdlz_crc32.h;
+# tools/probe_gzip.py times and counts it against the sliced tables)
+if [ "${1:-}" = "crcbank" ]; then
+  HDLZ_VARIANT=crcbank HDLZ_DEFS="-DHDLZ_CRC_BANK_PRIVATE" HDLZ_ONLY="hdlz_crc32 hdlz_unjoin" exec "${BASH_SOURCE[0]}"
+fi
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
@@ -23,7 +28,7 @@ lib="$out/libhdlz${var:+_$var}.so"
 mkdir -p "$out" "$objdir"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function ${HDLZ_DEFS:-}"
-srcs="hdlz_compress hdlz_compress_small hdlz_compress_stream hdlz_compress_chunk hdlz_inflate_tok hdlz_inflate_grp hdlz_inflate_par hdlz_inflate_any hdlz_inflate_dyn hdlz_checksum hdlz_compact hdlz_join hdlz_unjoin hdlz_api"
+srcs="hdlz_compress hdlz_compress_small hdlz_compress_stream hdlz_compress_chunk hdlz_inflate_tok hdlz_inflate_grp hdlz_inflate_par hdlz_inflate_any hdlz_inflate_dyn hdlz_checksum hdlz_compact hdlz_join hdlz_unjoin hdlz_crc32 hdlz_api"
 only="${HDLZ_ONLY:-$srcs}"
 pids=()
 for f in $only; do

@@ -471,31 +471,37 @@ int hdlz_inflate_chunk(const uint8_t* d_in, uint32_t in_len, int final, uint32_t
 }
 
 // ---- include/hdlz_unjoin.h: a joined stream read back member by member (the member view of the batch decoders; hdlz_unjoin.hip)
-size_t hdlz_unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) {
-    if (nmembers > 0x7FFFFFFFull) return 0;
-    return hdlz::round256(12u * (size_t)nmembers) + hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(total_out)) +
-           hdlz::round256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1));
+// (and include/hdlz_gzip.h: the gzip form differs in the checksum's share of the scratch and in what runs behind the decode)
+static size_t unjoin_tile_bytes(uint64_t total_out, bool gzip) {
+    return gzip ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(total_out)) : hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(total_out));
 }
+static size_t unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags, bool gzip) {
+    if (nmembers > 0x7FFFFFFFull) return 0;
+    return hdlz::round256(12u * (size_t)nmembers) + unjoin_tile_bytes(total_out, gzip) + hdlz::round256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1));
+}
+size_t hdlz_unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) { return unjoin_work_bytes(nmembers, total_out, flags, false); }
+size_t hdlz_unjoin_gzip_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) { return unjoin_work_bytes(nmembers, total_out, flags, true); }
 
-int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
-                   uint64_t nmembers, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status,
-                   hdlz_unjoin_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+static int unjoin_impl(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
+                       uint64_t nmembers, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status,
+                       hdlz_unjoin_result* d_result, void* d_work, size_t work_bytes, void* stream, bool gzip) {
     if (!d_stream || !d_off || !d_result || (out_cap && !d_out)) return fail_param("null device pointer");
     if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
-    if (flags & ~MAPPING_HINTS) return fail_param("unknown flag (hdlz_unjoin_ws takes the three mapping hints only)");
+    if (flags & ~MAPPING_HINTS) return fail_param("unknown flag (hdlz_unjoin_ws and hdlz_unjoin_gzip_ws take the three mapping hints only)");
     if (flags & (flags - 1u)) return fail_param("contradictory mapping flags");
     if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail_param("d_out must be 4-byte aligned");
     if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
         return fail_param("d_off / d_out_off / d_result must be 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
-    const size_t need = hdlz_unjoin_work_bytes(nmembers, out_cap, flags);
-    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_unjoin_work_bytes(nmembers, out_cap, flags)");
+    const size_t need = unjoin_work_bytes(nmembers, out_cap, flags, gzip);
+    if (need != 0u && (!d_work || work_bytes < need))
+        return fail_param(gzip ? "d_work smaller than hdlz_unjoin_gzip_work_bytes(nmembers, out_cap, flags)" : "d_work smaller than hdlz_unjoin_work_bytes(nmembers, out_cap, flags)");
     int rc = check_device();
     if (rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint8_t* wb = static_cast<uint8_t*>(d_work);
     uint32_t* words = reinterpret_cast<uint32_t*>(wb);
-    const size_t per = hdlz::round256(12u * (size_t)nmembers), tiles = hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(out_cap));
+    const size_t per = hdlz::round256(12u * (size_t)nmembers), tiles = unjoin_tile_bytes(out_cap, gzip);
     const hdlz::UnjoinArgs u{d_stream, stream_len, d_off, d_out_off, out_len, nmembers, d_out, out_cap, d_member_status, d_result,
                              words, words + nmembers, words + 2u * nmembers, reinterpret_cast<uint2*>(wb + per)};
     hipError_t e = hdlz::launch_unjoin_index(u, st);
@@ -513,8 +519,60 @@ int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t*
                                                                                                  : hdlz::launch_inflate_tok_members(a, st, w);
         if (e != hipSuccess) return fail_hip(e, "launch the member decode");
     }
-    e = hdlz::launch_unjoin_judge(u, st);
+    e = gzip ? hdlz::launch_unjoin_gzip_judge(u, st) : hdlz::launch_unjoin_judge(u, st);
     if (e != hipSuccess) return fail_hip(e, "launch k_unjoin_judge");
+    return HDLZ_OK;
+}
+
+int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
+                   uint64_t nmembers, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status,
+                   hdlz_unjoin_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    return unjoin_impl(d_stream, stream_len, d_off, d_out_off, out_len, nmembers, flags, d_out, out_cap, d_member_status, d_result, d_work,
+                       work_bytes, stream, false);
+}
+
+// ---- include/hdlz_gzip.h: CRC-32 on the device, the joined stream as one gzip member, and that member read back
+int hdlz_unjoin_gzip_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
+                        uint64_t nmembers, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status,
+                        hdlz_unjoin_gzip_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    return unjoin_impl(d_stream, stream_len, d_off, d_out_off, out_len, nmembers, flags, d_out, out_cap, d_member_status,
+                       reinterpret_cast<hdlz_unjoin_result*>(d_result), d_work, work_bytes, stream, true);      // (one record layout: hdlz_unjoin.hip)
+}
+
+size_t hdlz_crc32_work_bytes(uint64_t n) { return hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(n)); }
+
+int hdlz_crc32_ws(const uint8_t* d_data, uint64_t n, uint32_t* d_crc, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_crc || (n && !d_data)) return fail_param("null device pointer");
+    const size_t need = hdlz_crc32_work_bytes(n);
+    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_crc32_work_bytes(n)");
+    if ((reinterpret_cast<uintptr_t>(d_crc) & 3u) || (reinterpret_cast<uintptr_t>(d_work) & 3u)) return fail_param("d_crc / d_work must be 4-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    const hipError_t e = hdlz::launch_crc32(d_data, n, d_crc, static_cast<uint32_t*>(d_work), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_crc32_tiles");
+    return HDLZ_OK;
+}
+
+size_t hdlz_join_gzip_bound(uint64_t nblocks, uint32_t in_len) { return hdlz_join_bound(nblocks, in_len) + 12u; }
+
+size_t hdlz_join_gzip_work_bytes(uint64_t nblocks) { return hdlz_join_work_bytes(nblocks); }
+
+int hdlz_join_gzip_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                      const uint32_t* d_status, const uint64_t* d_in_off, uint32_t in_len, uint64_t nblocks, const uint32_t* d_crc,
+                      uint8_t* d_stream, uint64_t stream_cap, uint64_t* d_off, hdlz_join_gzip_result* d_result, void* d_work,
+                      size_t work_bytes, void* stream) {
+    if (!d_crc) return fail_param("d_crc is required");
+    if (!d_stream || !d_off || !d_result || (nblocks && (!d_rows || !d_len || !d_end_bits || !d_status))) return fail_param("null device pointer");
+    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");
+    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_join_gzip_work_bytes(nblocks)");
+    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u)) return fail_param("d_off / d_result must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    hipError_t e = hdlz::launch_join_gzip(d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_crc, d_stream, stream_cap,
+                                          d_off, d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_join");
     return HDLZ_OK;
 }
 

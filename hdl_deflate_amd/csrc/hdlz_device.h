@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
-#include "../../include/hdlz_unjoin.h"    // (includes hdlz_join.h and hdlz.h)
+#include "../../include/hdlz_gzip.h"      // (includes hdlz_unjoin.h, hdlz_join.h and hdlz.h)
 
 namespace hdlz {
 
@@ -157,6 +157,9 @@ struct UnjoinArgs {
 hipError_t launch_unjoin_index(const UnjoinArgs& a, hipStream_t stream);
 hipError_t launch_unjoin_judge(const UnjoinArgs& a, hipStream_t stream);
 size_t unjoin_tiles(uint64_t total_out);
+// ... and the gzip form's twin of launch_unjoin_judge (hdlz_unjoin_gzip_ws): a.tiles holds ONE word per 32 KiB tile, a.result is a
+// hdlz_unjoin_gzip_result (the same layout)
+hipError_t launch_unjoin_gzip_judge(const UnjoinArgs& a, hipStream_t stream);
 size_t judge_work_bytes(uint64_t nstreams, uint64_t out_pitch);
 hipError_t launch_judge(const JudgeArgs& a, hipStream_t stream);
 size_t stream_work_bytes(uint32_t n, uint32_t nblocks);
@@ -188,5 +191,13 @@ size_t join_work_bytes(uint64_t nblocks);
 hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
                        const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, uint8_t* stream_out, uint64_t cap, uint64_t* off,
                        hdlz_join_result* result, void* work, hipStream_t stream);
+// ... -> one gzip member (hdlz_join_gzip_ws): the same scratch; `crc`: the device word that holds CRC-32 of the input
+hipError_t launch_join_gzip(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
+                            const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* stream_out,
+                            uint64_t cap, uint64_t* off, hdlz_join_gzip_result* result, void* work, hipStream_t stream);
+
+// hdlz_crc32.hip: CRC-32 of data[0 .. n) -> crc[0].  `words`: one word per 32 KiB tile (crc32_tiles(n) of them; null when n is 0).
+size_t crc32_tiles(uint64_t n);
+hipError_t launch_crc32(const uint8_t* data, uint64_t n, uint32_t* crc, uint32_t* words, hipStream_t stream);
 
 }  // namespace hdlz

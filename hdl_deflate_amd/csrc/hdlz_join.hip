@@ -228,6 +228,51 @@ __global__ __launch_bounds__(256) void k_join_finish(JoinArgs a, uint32_t ntiles
     }
 }
 
+// ---- the gzip form (include/hdlz_gzip.h).  Its header is 10 = 8 + 2 bytes: k_join, pointed at stream + 8 with a capacity
+// 8 smaller, puts every member where the gzip stream wants it and leaves the zlib form's index.  This kernel, in place of
+// k_join_finish, lifts the index by 8 (every workgroup its share of d_off[0 .. nblocks); the word d_off[nblocks] is workgroup 0's:
+// it reads the end from it) and, in workgroup 0, reduces the tiles' worst status and writes the header, the final block, the trailer
+// -- the caller's CRC-32 word and N mod 2^32, little-endian -- and the result record.  a.stream / a.cap are k_join's view.
+constexpr uint64_t GZ_HEAD = 10, GZ_LIFT = GZ_HEAD - STREAM_HEAD;
+constexpr uint32_t GZ_TAIL = 10;                         // 03 00 + CRC-32 + ISIZE
+__constant__ const uint8_t GZ_HEADER[GZ_HEAD] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF};      // CM 8, FLG 0, MTIME 0, XFL 0, OS 255
+
+__global__ __launch_bounds__(256) void k_join_gzip_finish(JoinArgs a, uint32_t ntiles, const uint32_t* __restrict__ crc, uint8_t* gz,
+                                                          uint64_t gz_cap, hdlz_join_gzip_result* result) {
+    __shared__ uint32_t s_st[256];
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t b = (uint64_t)blockIdx.x * 256u + tid; b < a.nblocks; b += (uint64_t)gridDim.x * 256u) a.off[b] += GZ_LIFT;
+    if (blockIdx.x != 0u) return;
+    uint32_t st = HDLZ_OK;
+    for (uint32_t t = tid; t < ntiles; t += 256u) st = max(st, a.part[(size_t)PARTS * t + 3u]);
+    s_st[tid] = st;
+    __syncthreads();
+    for (uint32_t o = 128u; o > 0u; o >>= 1) {
+        if (tid < o) s_st[tid] = max(s_st[tid], s_st[tid + o]);
+        __syncthreads();
+    }
+    if (tid != 0u) return;
+    st = s_st[0];
+    uint64_t N = 0;
+    if (a.nblocks) N = a.in_off ? a.in_off[a.nblocks] - a.in_off[0] : a.nblocks * (uint64_t)a.in_len;
+    const uint64_t end = (a.nblocks ? a.off[a.nblocks] : STREAM_HEAD) + GZ_LIFT;      // (k_join's last tile wrote it, in front of this launch)
+    a.off[a.nblocks] = end;
+    const uint64_t total = end + GZ_TAIL;
+    const uint32_t c = crc[0], isize = (uint32_t)N;
+    hdlz_join_gzip_result res;
+    res.stream_len = st != HDLZ_OK ? 0u : total;
+    res.status = st != HDLZ_OK ? st : total > gz_cap ? (uint32_t)HDLZ_E_OUT_CAPACITY : (uint32_t)HDLZ_OK;
+    res.crc = st != HDLZ_OK ? 0u : c;
+    *result = res;
+    if (gz_cap >= GZ_HEAD)
+        for (uint32_t k = 0; k < GZ_HEAD; k++) gz[k] = GZ_HEADER[k];
+    if (st == HDLZ_OK && total <= gz_cap) {
+        uint8_t* t = gz + end;
+        t[0] = (uint8_t)FINAL_EMPTY; t[1] = 0;
+        for (uint32_t k = 0; k < 4u; k++) { t[2u + k] = (uint8_t)(c >> (8u * k)); t[6u + k] = (uint8_t)(isize >> (8u * k)); }
+    }
+}
+
 static inline uint64_t join_tiles(uint64_t nblocks) { return (nblocks + JT - 1u) / JT; }
 
 size_t join_work_bytes(uint64_t nblocks) {                     // ticket (+ pad), one 64-bit look-back word and PARTS words per tile
@@ -250,6 +295,26 @@ hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len,
         if (e2 != hipSuccess) return e2;
     }
     hipLaunchKernelGGL(k_join_finish, dim3(1), dim3(256), 0, stream, a, (uint32_t)ntiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_gzip(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
+                            const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* stream_out,
+                            uint64_t cap, uint64_t* off, hdlz_join_gzip_result* result, void* work, hipStream_t stream) {
+    const uint64_t ntiles = join_tiles(nblocks);
+    uint32_t* ws = static_cast<uint32_t*>(work);
+    // k_join's view: the stream from byte 8 on (a capacity below 8 leaves it no room at all: it then writes no byte)
+    JoinArgs a{rows, pitch, len, end_bits, status, in_off, in_len, nblocks, stream_out + GZ_LIFT, cap > GZ_LIFT ? cap - GZ_LIFT : 0u, off,
+               nullptr, ws, reinterpret_cast<unsigned long long*>(ws + 2), ws + 2u + 2u * (size_t)ntiles};
+    if (ntiles) {
+        const hipError_t e = zero_words(ws, (uint32_t)(2u + 2u * ntiles), stream);      // the ticket and the look-back words
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_join, dim3((unsigned)ntiles), dim3(256), 0, stream, a);
+        const hipError_t e2 = hipGetLastError();
+        if (e2 != hipSuccess) return e2;
+    }
+    const unsigned grid = (unsigned)(ntiles < 1024u ? (ntiles ? ntiles : 1u) : 1024u);
+    hipLaunchKernelGGL(k_join_gzip_finish, dim3(grid), dim3(256), 0, stream, a, (uint32_t)ntiles, crc, stream_out, cap, result);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "hdlz_device.h"
 #include "hdlz_adler.h"
+#include "hdlz_crc32.h"
 
 namespace hdlz {
 namespace unj {
@@ -171,6 +172,50 @@ __global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t nt
     *a.result = res;
 }
 
+// ---- the gzip form (include/hdlz_gzip.h): the index checks, the decode and k_unjoin_judge are the zlib form's; the
+// checksum tiles and the finishing workgroup are these two.  a.tiles holds ONE raw CRC word per 32 KiB tile of out[0 .. total) (tile
+// loop, tree and bounds: hdlz_crc32.h -- nothing at or behind the total is loaded), a.result is a hdlz_unjoin_gzip_result.
+static_assert(sizeof(hdlz_unjoin_gzip_result) == sizeof(hdlz_unjoin_result) && sizeof(hdlz_unjoin_gzip_result) == 24u, "one record layout");
+
+__global__ __launch_bounds__(CRC_THREADS) void k_unjoin_gzip_tiles(UnjoinArgs a) {
+    __shared__ CrcTileLds s;
+    crc_tiles(a.out, total_of(a), reinterpret_cast<uint32_t*>(a.tiles), s);
+}
+
+__device__ __forceinline__ uint32_t load_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// one workgroup of CRC_FIN_THREADS: the tile words -> the CRC-32, the verdicts -> the first failure; the gzip frame; the record
+__global__ __launch_bounds__(CRC_FIN_THREADS) void k_unjoin_gzip_finish(UnjoinArgs a, uint32_t ngroups) {
+    __shared__ uint32_t s_fin[CRC_FIN_THREADS], s_f[CRC_FIN_THREADS];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t total = total_of(a);
+    uint32_t f = NONE;
+    for (uint32_t g = tid; g < ngroups; g += CRC_FIN_THREADS) f = min(f, a.len[(size_t)g * JT]);
+    s_f[tid] = f;
+    const uint32_t crc = crc_finish(reinterpret_cast<const uint32_t*>(a.tiles), total, s_fin);      // (synchronises: s_f is written)
+    for (uint32_t o = CRC_FIN_THREADS / 2u; o > 0u; o >>= 1) {
+        if (tid < o) s_f[tid] = min(s_f[tid], s_f[tid + o]);
+        __syncthreads();
+    }
+    if (tid != 0u) return;
+    hdlz_unjoin_gzip_result res;
+    res.out_len = total; res.first_bad = ~0ull; res.status = HDLZ_OK; res.crc = crc;
+    if (s_f[0] != NONE) {
+        res.status = a.status[s_f[0]]; res.first_bad = s_f[0]; res.crc = 0u;
+    } else {
+        const uint64_t end = a.off[a.nmembers];
+        const bool head = a.off[0] == 10u && a.in_len >= 10u && a.in[0] == 0x1Fu && a.in[1] == 0x8Bu && a.in[2] == 8u && a.in[3] == 0u;
+        if (!head) res.status = HDLZ_E_BAD_HEADER;
+        else if (end > a.in_len - 10u || a.in[end] != 3u || a.in[end + 1u] != 0u) res.status = HDLZ_E_NO_EOF;
+        else if (load_le32(a.in + end + 2u) != crc || load_le32(a.in + end + 6u) != (uint32_t)total) res.status = HDLZ_E_BAD_CHECKSUM;
+        if (res.status != HDLZ_OK) res.first_bad = a.nmembers;
+    }
+    if (res.status != HDLZ_OK) res.out_len = 0u;
+    *reinterpret_cast<hdlz_unjoin_gzip_result*>(a.result) = res;
+}
+
 }  // namespace unj
 
 size_t unjoin_tiles(uint64_t total_out) { return (size_t)((total_out + ADLER_TILE - 1u) / ADLER_TILE); }
@@ -194,6 +239,17 @@ hipError_t launch_unjoin_judge(const UnjoinArgs& a, hipStream_t stream) {
     }
     if (ngroups) hipLaunchKernelGGL(k_unjoin_judge, dim3(ngroups), dim3(JT), 0, stream, a);
     hipLaunchKernelGGL(k_unjoin_finish, dim3(1), dim3(256), 0, stream, a, ntiles, ngroups);
+    return hipGetLastError();
+}
+
+// the gzip form's tiles, the judge (the zlib form's kernel) and the finishing workgroup
+hipError_t launch_unjoin_gzip_judge(const UnjoinArgs& a, hipStream_t stream) {
+    using namespace unj;
+    const size_t ntiles = a.nmembers ? crc32_tiles(a.out_cap) : 0u;
+    const uint32_t ngroups = (uint32_t)((a.nmembers + JT - 1u) / JT);
+    if (ntiles) hipLaunchKernelGGL(k_unjoin_gzip_tiles, dim3((unsigned)(ntiles < CRC_GRID_MAX ? ntiles : CRC_GRID_MAX)), dim3(CRC_THREADS), 0, stream, a);
+    if (ngroups) hipLaunchKernelGGL(k_unjoin_judge, dim3(ngroups), dim3(JT), 0, stream, a);
+    hipLaunchKernelGGL(k_unjoin_gzip_finish, dim3(1), dim3(CRC_FIN_THREADS), 0, stream, a, ngroups);
     return hipGetLastError();
 }
 

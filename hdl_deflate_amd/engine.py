@@ -5,9 +5,16 @@ import functools
 import torch
 
 from . import _lib, host
-from .constants import OK, E_SHORT_INPUT, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
+from .constants import OK, E_SHORT_INPUT, E_NO_EOF, E_BAD_CHECKSUM, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
 from .session import CompressSession, InflateSession
 from .errors import Error, HdlzStatusError
+
+
+def _container_is_gzip(container):
+    """the joined stream's two frames: "zlib" (include/hdlz_join.h) and "gzip" (include/hdlz_gzip.h)"""
+    if container not in ("zlib", "gzip"):
+        raise ValueError("container must be \"zlib\" or \"gzip\", not %r" % (container,))
+    return container == "gzip"
 
 
 def _on_device(fn):
@@ -116,17 +123,40 @@ class Engine(object):
         self._check(rc, "hdlz_compress_batch")
         return out, out_len, status
 
-    # -- STARTC for a flat buffer, block by block, as ONE standard zlib stream (include/hdlz_join.h)
+    # -- CRC-32 of a flat device buffer (include/hdlz_gzip.h)
     @_on_device
-    def compress_joined(self, d_in, block=1 << 16, cwindow=32, maxmatch=10, out=None):
+    def crc32(self, d_buf, out=None, work=None):
+        """d_buf: flat uint8 device tensor, any alignment -> uint32 device tensor[1] holding zlib.crc32 of its bytes (hdlz_crc32_ws).
+        No host sync: the word is ready in stream order.  `out`: the tensor to write (default: allocated here); `work`: the call's
+        scratch, a device tensor of at least hdlz_crc32_work_bytes(n) bytes (default: allocated here)."""
+        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.dim() == 1 and d_buf.is_contiguous() and d_buf.device == self.device
+        n, dev = d_buf.numel(), d_buf.device
+        if out is None:
+            out = torch.empty(1, dtype=torch.uint32, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint32 and out.numel() >= 1 and out.device == self.device
+        need = self.lib.hdlz_crc32_work_bytes(n)
+        if work is None:
+            work = torch.empty((need + 3) // 4, dtype=torch.int32, device=dev)
+        assert work.is_cuda and work.is_contiguous() and work.device == self.device and work.numel() * work.element_size() >= need
+        rc = self.lib.hdlz_crc32_ws(d_buf.data_ptr() if n else None, n, out.data_ptr(), work.data_ptr() if need else None,
+                                    work.numel() * work.element_size(), self._stream())
+        self._check(rc, "hdlz_crc32_ws")
+        return out
+
+    # -- STARTC for a flat buffer, block by block, as ONE standard zlib stream (include/hdlz_join.h) or gzip member (include/hdlz_gzip.h)
+    @_on_device
+    def compress_joined(self, d_in, block=1 << 16, cwindow=32, maxmatch=10, out=None, container="zlib"):
         """d_in: flat uint8 device tensor of at least 5 bytes.  It is cut into blocks of `block` bytes (chain.plan_blocks: a tail under
         5 bytes shortens the block before it), the blocks are compressed independently (hdlz_compress_batch_bits, a ragged batch with
         the bound `block`) and joined into one stream that any inflater reads back as d_in (hdlz_join_batch_ws).
         -> (stream uint8[stream_len], member_offsets int64[B + 1]): member b starts at member_offsets[b], the final empty block at
         member_offsets[B].  `out`: the stream's buffer (default: hdlz_join_bound(B, block) bytes).  One host sync (the result record);
         raises HdlzStatusError on a status that is not OK.  An input that does not start at a multiple of 16 or has fewer than 16
-        bytes of its storage behind it (the compress kernels load whole 16-byte pieces) is copied to a padded buffer first."""
+        bytes of its storage behind it (the compress kernels load whole 16-byte pieces) is copied to a padded buffer first.
+        container="gzip": the same members in the gzip frame (hdlz_join_gzip_ws; member_offsets[0] = 10): the CRC-32 of d_in is computed
+        on the same stream in front of the compression (hdlz_crc32_ws), `out` defaults to hdlz_join_gzip_bound(B, block) bytes."""
         from .chain import plan_blocks
+        gz = _container_is_gzip(container)
         assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.dim() == 1 and d_in.is_contiguous() and d_in.device == self.device
         if not 32 <= block < (1 << 31):
             raise ValueError("block must be in [32, 2^31)")           # (plan_blocks may shorten a block by 16 bytes; a block is below 2 GiB)
@@ -140,20 +170,27 @@ class Engine(object):
         pitch = pitch_for(block)
         rows, out_len, status = self._results(None, (B, pitch), B, dev)
         end_bits = torch.empty(B, dtype=torch.int64, device=dev)
-        cap = self.lib.hdlz_join_bound(B, block)
+        cap = self.lib.hdlz_join_gzip_bound(B, block) if gz else self.lib.hdlz_join_bound(B, block)
         if out is None:
             out = torch.empty(cap, dtype=torch.uint8, device=dev)
         assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
         offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
         result = torch.empty(2, dtype=torch.int64, device=dev)                     # hdlz_join_result: 16 bytes
-        work = torch.empty(max(8, self.lib.hdlz_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)
+        work = torch.empty(max(8, self.lib.hdlz_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)      # (the gzip join asks for the same)
+        crc = self.crc32(d_in[:n]) if gz else None
         rc = self.lib.hdlz_compress_batch_bits(d_in.data_ptr(), in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
                                                out_len.data_ptr(), status.data_ptr(), end_bits.data_ptr(), self._stream())
         self._check(rc, "hdlz_compress_batch_bits")
-        rc = self.lib.hdlz_join_batch_ws(rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(),
-                                         in_off.data_ptr(), block, B, out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
-                                         work.data_ptr(), work.numel() * 8, self._stream())
-        self._check(rc, "hdlz_join_batch_ws")
+        if gz:
+            rc = self.lib.hdlz_join_gzip_ws(rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(),
+                                            in_off.data_ptr(), block, B, crc.data_ptr(), out.data_ptr(), out.numel(), offsets.data_ptr(),
+                                            result.data_ptr(), work.data_ptr(), work.numel() * 8, self._stream())
+            self._check(rc, "hdlz_join_gzip_ws")
+        else:
+            rc = self.lib.hdlz_join_batch_ws(rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(),
+                                             in_off.data_ptr(), block, B, out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
+                                             work.data_ptr(), work.numel() * 8, self._stream())
+            self._check(rc, "hdlz_join_batch_ws")
         rec = _lib.JoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
         if rec.status != OK:
             raise HdlzStatusError(rec.status, "compress_joined")
@@ -161,7 +198,8 @@ class Engine(object):
 
     # -- STARTD for a joined stream, member by member in parallel (include/hdlz_unjoin.h)
     @_on_device
-    def inflate_joined(self, d_stream, member_offsets, block=None, out_offsets=None, total=None, out=None, work=None, flags=0):
+    def inflate_joined(self, d_stream, member_offsets, block=None, out_offsets=None, total=None, out=None, work=None, flags=0,
+                       container="zlib"):
         """d_stream: flat uint8 device tensor, the stream compress_joined returned; member_offsets: its int64[B + 1] index.  Where the
         members go is stated like the compress call's input: `block` (with `total`, the length of the data: the output offsets are
         rebuilt from chain.plan_blocks, the plan compress_joined used) or `out_offsets` int64[B + 1] on the device (`total` defaults
@@ -169,8 +207,13 @@ class Engine(object):
         into the flat output and the stream is verified (markers, final block, Adler-32): hdlz_unjoin_ws.
         -> out uint8[total].  One host sync (the result record); raises HdlzStatusError -- with .first_bad, the record's word -- on a
         status that is not OK.  flags: one of the three INFLATE_*_PER_STREAM mapping hints, or 0.  `work`: the call's scratch, a uint8
-        device tensor of at least unjoin_work_bytes(B, total, flags) bytes (default: allocated here)."""
+        device tensor of at least unjoin_work_bytes(B, total, flags) bytes (default: allocated here).
+        container="gzip": the stream of compress_joined(container="gzip"), verified as gzip (header, final block, CRC-32, ISIZE):
+        hdlz_unjoin_gzip_ws; its scratch is hdlz_unjoin_gzip_work_bytes(B, total, flags) bytes."""
         from .chain import plan_blocks
+        gz = _container_is_gzip(container)
+        work_bytes, unjoin = (self.lib.hdlz_unjoin_gzip_work_bytes, self.lib.hdlz_unjoin_gzip_ws) if gz else \
+            (self.lib.hdlz_unjoin_work_bytes, self.lib.hdlz_unjoin_ws)
         assert d_stream.is_cuda and d_stream.dtype == torch.uint8 and d_stream.dim() == 1 and d_stream.is_contiguous() and d_stream.device == self.device
         assert member_offsets.is_cuda and member_offsets.dtype == torch.int64 and member_offsets.is_contiguous()
         B, dev = member_offsets.numel() - 1, d_stream.device
@@ -197,16 +240,16 @@ class Engine(object):
         if out is None:
             out = torch.empty(total, dtype=torch.uint8, device=dev)
         assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.numel() >= total
-        need = self.lib.hdlz_unjoin_work_bytes(B, total, flags)
+        need = work_bytes(B, total, flags)
         if work is None:
             work = torch.empty(need, dtype=torch.uint8, device=dev)
         assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
-        result = torch.empty(3, dtype=torch.int64, device=dev)                     # hdlz_unjoin_result: 24 bytes
-        rc = self.lib.hdlz_unjoin_ws(d_stream.data_ptr(), d_stream.numel(), member_offsets.data_ptr(),
-                                     out_offsets.data_ptr() if out_offsets is not None else None, out_len, B, flags,
-                                     out.data_ptr() if total else None, total, None, result.data_ptr(),
-                                     work.data_ptr() if work.numel() else None, work.numel(), self._stream())
-        self._check(rc, "hdlz_unjoin_ws")
+        result = torch.empty(3, dtype=torch.int64, device=dev)                     # hdlz_unjoin_result / hdlz_unjoin_gzip_result: 24 bytes
+        rc = unjoin(d_stream.data_ptr(), d_stream.numel(), member_offsets.data_ptr(),
+                    out_offsets.data_ptr() if out_offsets is not None else None, out_len, B, flags,
+                    out.data_ptr() if total else None, total, None, result.data_ptr(),
+                    work.data_ptr() if work.numel() else None, work.numel(), self._stream())
+        self._check(rc, "hdlz_unjoin_gzip_ws" if gz else "hdlz_unjoin_ws")
         rec = _lib.UnjoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
         if rec.status != OK:
             err = HdlzStatusError(rec.status, "inflate_joined")
@@ -363,14 +406,16 @@ class Engine(object):
 
     # -- single-stream conveniences used by the port adapter (one START = one block)
     @_on_device
-    def compress_bytes(self, data, cwindow=32, maxmatch=10, block=None):
+    def compress_bytes(self, data, cwindow=32, maxmatch=10, block=None, container="zlib"):
         """-> (status, bytes).  block=None: ONE block, what STARTC writes; a number: the input in blocks of that many bytes, joined into
-        one standard zlib stream (compress_joined)"""
+        one standard zlib stream (compress_joined) or, with container="gzip", into one gzip member"""
+        if _container_is_gzip(container) and block is None:
+            raise ValueError("container=\"gzip\" is the joined stream's: give block=")
         if block is not None:
             if len(data) < 5:
                 return E_SHORT_INPUT, b""
             try:
-                z, _ = self.compress_joined(self._stage(data)[:len(data)], block=block, cwindow=cwindow, maxmatch=maxmatch)
+                z, _ = self.compress_joined(self._stage(data)[:len(data)], block=block, cwindow=cwindow, maxmatch=maxmatch, container=container)
             except HdlzStatusError as e:
                 return e.status, b""
             return OK, bytes(z.cpu().numpy().tobytes())
@@ -378,28 +423,56 @@ class Engine(object):
         return int(st.item()), bytes(out[:int(ol.item())].cpu().numpy().tobytes())
 
     @_on_device
-    def inflate_bytes(self, z, out_cap=None, flags=0, obsize=0, verify=False, members=None):
+    def inflate_bytes(self, z, out_cap=None, flags=0, obsize=0, verify=False, members=None, container="zlib"):
         """-> (status, bytes); verify=True: through the checked call (header, Adler-32, trailer present).  Default capacity: deflate expands at most 1032:1 (a 258-byte match costs 2 bits), so
         1032 n + 258 bytes hold any stream, capped at the reference's 2^LMAX counter range (deflate.py:73-76).
         members=(offsets, block): z is a joined stream (compress_joined / compress_bytes(block=...)) with its member index -- a
         sequence or tensor of B + 1 offsets -- and the block size it was cut with: every member is decoded in parallel and the stream
         verified (inflate_joined).  The length of the data is not part of a stream: it is taken from out_cap when given, else the last
-        two members are decoded once more as one short stream to measure them."""
+        two members are decoded once more as one short stream to measure them.  container="gzip" (with members=): z is the gzip form;
+        without out_cap the length is the trailer's ISIZE, the length mod 2^32 -- exact for data below 4 GiB.  The word is read before
+        the stream is verified: an ISIZE that the index cannot belong to, or that makes the decode fail where the measured length
+        would not, answers E_BAD_CHECKSUM."""
+        from .chain import plan_blocks
+        gz = _container_is_gzip(container)
+        if gz and members is None:
+            raise ValueError("container=\"gzip\" is the joined stream's: give members=")
         if members is not None:
             offsets, block = members
             offs = [int(o) for o in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]
             B = len(offs) - 1
             total = out_cap
-            if total is None and B:
+
+            def measured():
+                """-> (status, length of the data): the last two members decoded once more as one short stream"""
                 k = max(B - 2, 0)                                # members 0 .. k - 1 hold `block` bytes each (chain.plan_blocks)
                 st, tail = self.inflate_bytes(z[offs[k] - 2:], out_cap=2 * block + 16)
+                return st, k * block + len(tail)
+            from_isize = total is None and gz
+            if from_isize:
+                end = offs[B]
+                if len(z) < end + 10:
+                    return E_NO_EOF, b""
+                # ISIZE is read before anything is verified: a length the index cannot belong to is a damaged trailer
+                total = int.from_bytes(bytes(z[end + 6:end + 10]), "little")
+                try:
+                    fits = len(plan_blocks(total, block)) == B if B else total == 0
+                except Error:
+                    fits = False
+                if not fits:
+                    return E_BAD_CHECKSUM, b""
+            elif total is None and B:
+                st, total = measured()
                 if st != OK:
                     return st, b""
-                total = k * block + len(tail)
             try:
                 out = self.inflate_joined(self._stage(z)[:len(z)], torch.tensor(offs, dtype=torch.int64).to(self.device), block=block,
-                                          total=total or 0, flags=flags)
+                                          total=total or 0, flags=flags, container=container)
             except HdlzStatusError as e:
+                if from_isize and B:                             # the members' slots came from ISIZE: was it the word that was wrong?
+                    st, true_total = measured()
+                    if st == OK and true_total != total:
+                        return E_BAD_CHECKSUM, b""
                 return e.status, b""
             return OK, bytes(out.cpu().numpy().tobytes())
         n = len(z)
