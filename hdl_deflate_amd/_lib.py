@@ -62,6 +62,21 @@ GZIP_SIGNATURES = {
     "hdlz_unjoin_gzip_ws": (ci, [vp, u64, vp, vp, u32, u64, u32, vp, u64, vp, vp, vp, sz, vp]),      # as hdlz_unjoin_ws
 }
 GZIP_EXPORTS = tuple(GZIP_SIGNATURES)
+# ... and of include/hdlz_bgzf.h: BGZF, the self-indexing blocked gzip, written and read on the device (tests/test_bgzf_cabi.py)
+BGZF_SIGNATURES = {
+    "hdlz_crc32_batch_ws": (ci, [vp, vp, u64, u32, u64, vp, vp]),      # d_data, d_off, pitch, len, nblocks, d_crc, stream
+    "hdlz_bgzf_bound": (sz, [u64, u32]),
+    "hdlz_bgzf_join_work_bytes": (sz, [u64]),
+    # d_rows, row_pitch, d_len, d_status, d_in_off, in_len, nblocks, d_crc, d_file, file_cap, d_off, d_result, d_work, work_bytes, stream
+    "hdlz_bgzf_join_ws": (ci, [vp, u64, vp, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp, sz, vp]),
+    "hdlz_bgzf_index_work_bytes": (sz, [u64]),
+    # d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, work_bytes, stream
+    "hdlz_bgzf_index_ws": (ci, [vp, u64, u64, vp, vp, vp, vp, sz, vp]),
+    "hdlz_bgzf_inflate_work_bytes": (sz, [u64, u32]),
+    # d_file, file_len, d_off, d_out_off, nmembers, flags, d_out, out_cap, d_member_status, d_result, d_work, work_bytes, stream
+    "hdlz_bgzf_inflate_ws": (ci, [vp, u64, vp, vp, u64, u32, vp, u64, vp, vp, vp, sz, vp]),
+}
+BGZF_EXPORTS = tuple(BGZF_SIGNATURES)
 _lib = None
 
 
@@ -91,6 +106,21 @@ class UnjoinGzipResult(ctypes.Structure):
     _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("crc", u32)]
 
 
+class BgzfJoinResult(ctypes.Structure):
+    """hdlz_bgzf_join_result: the result record of hdlz_bgzf_join_ws (16 bytes)"""
+    _fields_ = [("file_len", u64), ("status", u32), ("first_bad", u32)]
+
+
+class BgzfIndexResult(ctypes.Structure):
+    """hdlz_bgzf_index_result: the result record of hdlz_bgzf_index_ws (32 bytes)"""
+    _fields_ = [("nmembers", u64), ("total_out", u64), ("file_used", u64), ("status", u32), ("eof_marker", u32)]
+
+
+class BgzfInflateResult(ctypes.Structure):
+    """hdlz_bgzf_inflate_result: the result record of hdlz_bgzf_inflate_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -110,7 +140,7 @@ def load():
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
-            list(GZIP_SIGNATURES.items()):
+            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -576,4 +576,101 @@ int hdlz_join_gzip_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t*
     return HDLZ_OK;
 }
 
+// ---- include/hdlz_bgzf.h: the CRC-32 of every block of a batch, the BGZF writer, the member index and the reader
+int hdlz_crc32_batch_ws(const uint8_t* d_data, const uint64_t* d_off, uint64_t pitch, uint32_t len, uint64_t nblocks, uint32_t* d_crc,
+                        void* stream) {
+    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one call (2^31 - 1 blocks)");
+    if (nblocks && (!d_crc || (!d_data && (d_off || len)))) return fail_param("null device pointer");
+    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_off) & 7u) return fail_param("d_off must be 8-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    const hipError_t e = hdlz::launch_crc32_batch(d_data, d_off, pitch, len, nblocks, d_crc, nullptr, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_crc32_batch");
+    return HDLZ_OK;
+}
+
+size_t hdlz_bgzf_bound(uint64_t nblocks, uint32_t in_len) { return 28u + (size_t)nblocks * (hdlz_out_bound(in_len) + 20u); }
+
+size_t hdlz_bgzf_join_work_bytes(uint64_t nblocks) { return hdlz_join_work_bytes(nblocks); }
+
+int hdlz_bgzf_join_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint32_t* d_status, const uint64_t* d_in_off,
+                      uint32_t in_len, uint64_t nblocks, const uint32_t* d_crc, uint8_t* d_file, uint64_t file_cap, uint64_t* d_off,
+                      hdlz_bgzf_join_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_file || !d_off || !d_result || (nblocks && (!d_rows || !d_len || !d_status || !d_crc))) return fail_param("null device pointer");
+    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");
+    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_bgzf_join_work_bytes(nblocks)");
+    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_in_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return fail_param("d_off / d_in_off / d_result must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    const hipError_t e = hdlz::launch_bgzf_join(d_rows, row_pitch, d_len, d_status, d_in_off, in_len, nblocks, d_crc, d_file, file_cap, d_off,
+                                                d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_join<bgzf>");
+    return HDLZ_OK;
+}
+
+size_t hdlz_bgzf_index_work_bytes(uint64_t file_len) { return hdlz::bgzf_index_work_bytes(file_len); }
+
+int hdlz_bgzf_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off,
+                       hdlz_bgzf_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_off || !d_out_off || !d_result || (file_len && !d_file)) return fail_param("null device pointer");
+    if (member_cap >= (1ull << 40)) return fail_param("member_cap too large (below 2^40)");
+    const size_t need = hdlz::bgzf_index_work_bytes(file_len);
+    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_bgzf_index_work_bytes(file_len)");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_work) & 7u))
+        return fail_param("d_off / d_out_off / d_result / d_work must be 8-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    const hipError_t e = hdlz::launch_bgzf_index(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_scan");
+    return HDLZ_OK;
+}
+
+size_t hdlz_bgzf_inflate_work_bytes(uint64_t nmembers, uint32_t flags) {
+    if (nmembers == 0 || nmembers > 0x7FFFFFFFull || flags != 0u) return 0;
+    return hdlz::round256(12u * (size_t)nmembers) + hdlz::round256(16u * ((size_t)nmembers + 1u)) + hdlz::round256(4u * (size_t)nmembers);
+}
+
+int hdlz_bgzf_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_off, const uint64_t* d_out_off, uint64_t nmembers,
+                         uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status, hdlz_bgzf_inflate_result* d_result,
+                         void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || (nmembers && (!d_file || !d_off || !d_out_off)) || (out_cap && !d_out)) return fail_param("null device pointer");
+    if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
+    if (flags != 0u) return fail_param("flags must be 0 (hdlz_bgzf_inflate_ws decodes a wave per member: the mapping hints do not apply)");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return fail_param("d_off / d_out_off / d_result must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
+    const size_t need = hdlz_bgzf_inflate_work_bytes(nmembers, flags);
+    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_bgzf_inflate_work_bytes(nmembers, flags)");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t* wb = static_cast<uint8_t*>(d_work);
+    uint32_t* words = reinterpret_cast<uint32_t*>(wb);
+    const size_t per = hdlz::round256(12u * (size_t)nmembers), idx = hdlz::round256(16u * ((size_t)nmembers + 1u));
+    uint64_t* moff = reinterpret_cast<uint64_t*>(wb + per);
+    const hdlz::BgzfArgs u{d_file, file_len, d_off, d_out_off, nmembers, d_out, out_cap, d_member_status, d_result, words, words + nmembers,
+                           words + 2u * nmembers, moff, moff + nmembers + 1u, reinterpret_cast<uint32_t*>(wb + per + idx)};
+    hipError_t e = hdlz::launch_bgzf_check(u, st);
+    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_check");
+    if (nmembers) {
+        hdlz::MemberArgs a;
+        a.in = d_file; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = nmembers;
+        a.flags = 0;                                           // BFINAL is honoured: a member may hold any number of blocks of any type
+        a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.len; a.status = u.status; a.in_used = u.end_bit;
+        a.m_off = u.m_off; a.m_out_off = u.m_out_off; a.m_out_len = 0; a.m_out_cap = out_cap; a.m_gap = 18u;
+        e = hdlz::launch_inflate_dyn_members(a, st);
+        if (e != hipSuccess) return fail_hip(e, "launch the member decode");
+        e = hdlz::launch_crc32_batch(d_out, u.m_out_off, 0, 0, nmembers, u.crc, u.status, st);
+        if (e != hipSuccess) return fail_hip(e, "launch k_crc32_batch");
+    }
+    e = hdlz::launch_bgzf_judge(u, st);
+    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_judge");
+    return HDLZ_OK;
+}
+
 }  // extern "C"

@@ -1,5 +1,6 @@
 // hdlz_crc32.h -- CRC-32 (the one of zlib, gzip and PNG) without a carry-less multiply: the one copy of the arithmetic, the tile loop
-// and the tree that hdlz_crc32_ws (hdlz_crc32.hip) and the gzip judgement of hdlz_unjoin_gzip_ws (hdlz_unjoin.hip) share.
+// and the tree that hdlz_crc32_ws (hdlz_crc32.hip), the gzip judgement of hdlz_unjoin_gzip_ws (hdlz_unjoin.hip) and the per-block
+// checksums of hdlz_crc32_batch_ws (hdlz_bgzf.hip: crc_block, a workgroup per block) share.
 //
 // Arithmetic.  Bytes are polynomials over GF(2), lowest bit first; a 32-bit word w stands for w(x) with bit 31 = x^0 .. bit 0 = x^31
 // (zlib's "reflected" register), P = x^32 + 0xEDB88320(x), `*` is the product mod P (crc_mul: 32 shift-and-xor steps; with one
@@ -167,10 +168,43 @@ __device__ __forceinline__ uint32_t crc_piece_at(uint32_t k) {      // coalesced
     return ((threadIdx.x >> 6) * CRC_STEPS + k) * 1024u + 16u * (threadIdx.x & 63u);
 }
 
+// the staged pieces of a tile -> its strips in LDS (piece k of this thread is the one crc_piece_at(k) names)
+__device__ __forceinline__ void crc_stage(CrcTileLds& s, const crc_u32x4 (&piece)[CRC_STEPS]) {
+#pragma unroll
+    for (uint32_t k = 0; k < CRC_STEPS; k++) {
+        const uint32_t q = crc_piece_at(k);
+        uint32_t* d = &s.strip[(q >> 7) * CRC_STRIP_PITCH + ((q & 127u) >> 2)];
+        d[0] = piece[k].x; d[1] = piece[k].y; d[2] = piece[k].z; d[3] = piece[k].w;
+    }
+}
+// raw() of the staged tile -> the return value of thread 0 (other threads: 0).  The strips in front of `first_strip` are taken as
+// zeros without being read (a register of 0 stays 0 over zero bytes).  The caller synchronises between the staging and this call;
+// the synchronisation in here is behind the last read of a strip: the next tile may be staged as soon as the call returns.
+__device__ __forceinline__ uint32_t crc_tile_word(CrcTileLds& s, uint32_t first_strip) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t c = 0;
+    if (tid >= first_strip) {
+        const uint32_t* mine = &s.strip[tid * CRC_STRIP_PITCH];
+#pragma unroll 8
+        for (uint32_t w = 0; w < CRC_STRIP_WORDS; w++) c = crc_step(s, c, mine[w]);
+    }
+    // the wave's 64 strips: lane l keeps strips l .. l + 2^(k+1) - 1 after level k
+#pragma unroll
+    for (uint32_t k = 0; k < 6u; k++) c = crc_mul(c, XP2.v[10u + k]) ^ (uint32_t)__shfl_down((int)c, 1u << k, 64);
+    if (lane == 0u) s.wave[wave] = c;
+    __syncthreads();                                  // (every strip has been read: the next tile may be staged)
+    uint32_t word = 0;
+    if (tid == 0u) {
+        const uint32_t lo = crc_mul(s.wave[0], XP2.v[16]) ^ s.wave[1], hi = crc_mul(s.wave[2], XP2.v[16]) ^ s.wave[3];
+        word = crc_mul(lo, XP2.v[17]) ^ hi;
+    }
+    return word;
+}
+
 // raw() of every 32 KiB tile of data[0 .. n) (the last one padded with zeros behind it) -> words[t], tiles blockIdx.x, + gridDim.x, ..
 // Launched with CRC_THREADS threads.  reads: data[0 .. n) only.  writes: words[0 .. ceil(n / 32768)).
 __device__ __forceinline__ void crc_tiles(const uint8_t* __restrict__ data, uint64_t n, uint32_t* __restrict__ words, CrcTileLds& s) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint64_t ntiles = (n + CRC_TILE - 1u) >> CRC_TILE_LOG2;
     uint64_t t = blockIdx.x;
     if (t >= ntiles) return;
@@ -184,28 +218,65 @@ __device__ __forceinline__ void crc_tiles(const uint8_t* __restrict__ data, uint
     };
     fetch(t);
     for (; t < ntiles; t += gridDim.x) {
-#pragma unroll
-        for (uint32_t k = 0; k < CRC_STEPS; k++) {
-            const uint32_t q = crc_piece_at(k);
-            uint32_t* d = &s.strip[(q >> 7) * CRC_STRIP_PITCH + ((q & 127u) >> 2)];
-            d[0] = piece[k].x; d[1] = piece[k].y; d[2] = piece[k].z; d[3] = piece[k].w;
-        }
+        crc_stage(s, piece);
         __syncthreads();                              // the tile is staged (and, the first time, the tables are built)
         if (t + gridDim.x < ntiles) fetch(t + gridDim.x);      // the next tile's loads fly while this one is computed
-        uint32_t c = 0;
-        const uint32_t* mine = &s.strip[tid * CRC_STRIP_PITCH];
-#pragma unroll 8
-        for (uint32_t w = 0; w < CRC_STRIP_WORDS; w++) c = crc_step(s, c, mine[w]);
-        // the wave's 64 strips: lane l keeps strips l .. l + 2^(k+1) - 1 after level k
-#pragma unroll
-        for (uint32_t k = 0; k < 6u; k++) c = crc_mul(c, XP2.v[10u + k]) ^ (uint32_t)__shfl_down((int)c, 1u << k, 64);
-        if (lane == 0u) s.wave[wave] = c;
-        __syncthreads();                              // (every strip has been read: the next tile may be staged)
-        if (tid == 0u) {
-            const uint32_t lo = crc_mul(s.wave[0], XP2.v[16]) ^ s.wave[1], hi = crc_mul(s.wave[2], XP2.v[16]) ^ s.wave[3];
-            words[t] = crc_mul(lo, XP2.v[17]) ^ hi;
-        }
+        const uint32_t word = crc_tile_word(s, 0u);
+        if (tid == 0u) words[t] = word;
     }
+}
+
+// crc32 of the L bytes at p (any alignment, L < 2^32) -> the return value of thread 0 (other threads: unspecified): ONE workgroup of
+// CRC_THREADS threads walks the block tile by tile (hdlz_crc32_batch_ws: a workgroup per block of a batch).  The first tile is the
+// PARTIAL one, r = L - 32768 (ntiles - 1) bytes placed RIGHT-ALIGNED: the pad = 32768 - r zero bytes stand in front of the data, where
+// they are free -- no un-padding product --, and a strip that lies wholly inside them is neither staged nor run.  Every further tile
+// is whole: one Horner step c * x^(8 * 32768) ^ tile (XP2[18]).  The initial register is a word in front, FFFFFFFF * x^(8 L) -- the
+// exponent reduced mod 2^32 - 1 (x^(2^32 - 1) = 1) and spread over 32 lanes as in crc_finish --, and the final xor comes last.
+// The tables must be built (crc_build_tables) in front of the call; the first synchronisation in here covers them.
+// reads: p[0 .. L) only.
+__device__ __forceinline__ uint32_t crc_block(const uint8_t* __restrict__ p, uint32_t L, CrcTileLds& s) {
+    const uint32_t tid = threadIdx.x;
+    if (L == 0u) return 0u;
+    const uint32_t ntiles = ((L - 1u) >> CRC_TILE_LOG2) + 1u;
+    const uint32_t r = L - ((ntiles - 1u) << CRC_TILE_LOG2), pad = CRC_TILE - r;      // r = 1 .. 32768
+    const uint32_t first_strip = pad / CRC_STRIP;      // strips in front of it hold padding only
+    uint32_t acc = 0;
+    crc_u32x4 piece[CRC_STEPS];
+    for (uint32_t t = 0; t < ntiles; t++) {
+        if (t == 0u) {
+#pragma unroll
+            for (uint32_t k = 0; k < CRC_STEPS; k++) {
+                const uint32_t q = crc_piece_at(k);
+                crc_u32x4 v = {0u, 0u, 0u, 0u};
+                if (q >= pad) v = *reinterpret_cast<const crc_u32x4u*>(p + (q - pad));      // (q + 16 <= 32768: the piece ends inside the data)
+                else if (q + 16u > pad) {              // the piece the data starts in: its bytes pad - q .. 15
+                    uint32_t d[4] = {0u, 0u, 0u, 0u};
+                    for (uint32_t i = pad - q; i < 16u; i++) d[i >> 2] |= (uint32_t)p[q + i - pad] << (8u * (i & 3u));
+                    v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
+                }
+                piece[k] = v;
+            }
+        } else {
+            const uint8_t* __restrict__ tp = p + r + ((uint64_t)(t - 1u) << CRC_TILE_LOG2);
+#pragma unroll
+            for (uint32_t k = 0; k < CRC_STEPS; k++) piece[k] = *reinterpret_cast<const crc_u32x4u*>(tp + crc_piece_at(k));
+        }
+        crc_stage(s, piece);
+        __syncthreads();
+        const uint32_t word = crc_tile_word(s, t == 0u ? first_strip : 0u);
+        if (tid == 0u) acc = t == 0u ? word : crc_mul(acc, XP2.v[CRC_TILE_LOG2 + 3u]) ^ word;
+    }
+    // FFFFFFFF * x^(8 L): 8 L = hi 2^32 + lo = hi + lo (mod 2^32 - 1)
+    uint32_t e = L << 3;
+    const uint32_t hi = L >> 29;
+    e += hi;
+    if (e < hi) e += 1u;
+    uint32_t f = tid < 32u && ((e >> tid) & 1u) ? XP2.v[tid & 31u] : CRC_ONE;
+    if (tid < 64u) {
+#pragma unroll
+        for (uint32_t o = 16u; o > 0u; o >>= 1) f = crc_mul(f, (uint32_t)__shfl_down((int)f, o, 64));
+    }
+    return acc ^ crc_mul(CRC_INIT, f) ^ CRC_INIT;
 }
 
 // crc32 of n bytes from their tile words -> the return value of thread 0 (other threads: unspecified).  Launched as ONE workgroup of

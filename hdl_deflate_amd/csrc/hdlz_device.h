@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
-#include "../../include/hdlz_gzip.h"      // (includes hdlz_unjoin.h, hdlz_join.h and hdlz.h)
+#include "../../include/hdlz_bgzf.h"      // (includes hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
 
 namespace hdlz {
 
@@ -51,13 +51,16 @@ struct MemberArgs : InflateArgs {
     const uint64_t* m_out_off;   // nullable: then member b decodes to out + b * m_out_len, m_out_len bytes
     uint32_t m_out_len;
     uint64_t m_out_cap;          // no store at or behind out + m_out_cap
+    uint32_t m_gap = 0;          // bytes at the end of [m_off[b], m_off[b + 1]) that are NOT the member's: 0 for a joined stream; 18 for BGZF
+                                 // (hdlz_bgzf_inflate_ws: m_off[b] = the member's start + 18, so the gap is the next member's header)
 };
 // the stream a decoder sees is in[m_off[b] - 2 .. m_off[b + 1]): it skips two bytes unvalidated (never loaded: the FF FF of the marker in
-// front, or 78 9C), and the member's own marker supplies the bytes the end-of-input rules want behind the end-of-block code
+// front, or 78 9C; BGZF: the BSIZE field), and the member's own marker (BGZF: its 8-byte trailer) supplies the bytes the end-of-input
+// rules want behind the end-of-block code
 __device__ __forceinline__ void member_view(const MemberArgs& a, uint64_t b, uint64_t& off, uint32_t& zn, uint64_t& o, uint32_t& cap) {
     const uint64_t lo = a.m_off[b];
     off = lo - 2u;
-    zn = (uint32_t)(a.m_off[b + 1] - lo) + 2u;
+    zn = (uint32_t)(a.m_off[b + 1] - lo) + 2u - a.m_gap;
     uint64_t n;
     if (a.m_out_off) { o = a.m_out_off[b]; n = a.m_out_off[b + 1] - o; }
     else { o = b * (uint64_t)a.m_out_len; n = a.m_out_len; }
@@ -195,6 +198,38 @@ hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len,
 hipError_t launch_join_gzip(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
                             const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* stream_out,
                             uint64_t cap, uint64_t* off, hdlz_join_gzip_result* result, void* work, hipStream_t stream);
+
+// ... -> a BGZF file (hdlz_bgzf_join_ws): k_join's other instance, the same scratch; `crc`: one word per block
+hipError_t launch_bgzf_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint32_t* status, const uint64_t* in_off,
+                            uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* file, uint64_t cap, uint64_t* off,
+                            hdlz_bgzf_join_result* result, void* work, hipStream_t stream);
+
+// hdlz_bgzf.hip: the CRC-32 of every block of a batch (`skip`: nullable, per block: a status that is not HDLZ_OK leaves the block
+// unread and its word unwritten), the member index of a BGZF file, and what runs around the member decode of hdlz_bgzf_inflate_ws
+hipError_t launch_crc32_batch(const uint8_t* data, const uint64_t* off, uint64_t pitch, uint32_t len, uint64_t nblocks, uint32_t* crc,
+                              const uint32_t* skip, hipStream_t stream);
+size_t bgzf_index_work_bytes(uint64_t file_len);
+hipError_t launch_bgzf_index(const uint8_t* file, uint64_t file_len, uint64_t member_cap, uint64_t* off, uint64_t* out_off,
+                             hdlz_bgzf_index_result* result, void* work, hipStream_t stream);
+struct BgzfArgs {
+    const uint8_t* in;
+    uint64_t in_len;
+    const uint64_t* off;
+    const uint64_t* out_off;
+    uint64_t nmembers;
+    uint8_t* out;
+    uint64_t out_cap;
+    uint32_t* member_status;     // nullable
+    hdlz_bgzf_inflate_result* result;
+    uint32_t* len;               // scratch, per member, as in UnjoinArgs: the decoded length / the workgroup's lowest failed member
+    uint32_t* status;
+    uint32_t* end_bit;
+    uint64_t* m_off;             // scratch, nmembers + 1 words: off[b] + 18 (MemberArgs::m_off with m_gap = 18)
+    uint64_t* m_out_off;         // scratch, nmembers + 1 words: out_off[b] - out_off[0]
+    uint32_t* crc;               // scratch, per member: the CRC-32 of its slot
+};
+hipError_t launch_bgzf_check(const BgzfArgs& a, hipStream_t stream);
+hipError_t launch_bgzf_judge(const BgzfArgs& a, hipStream_t stream);
 
 // hdlz_crc32.hip: CRC-32 of data[0 .. n) -> crc[0].  `words`: one word per 32 KiB tile (crc32_tiles(n) of them; null when n is 0).
 size_t crc32_tiles(uint64_t n);

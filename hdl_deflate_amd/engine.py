@@ -5,7 +5,7 @@ import functools
 import torch
 
 from . import _lib, host
-from .constants import OK, E_SHORT_INPUT, E_NO_EOF, E_BAD_CHECKSUM, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
+from .constants import OK, E_SHORT_INPUT, E_OUT_CAPACITY, E_NO_EOF, E_BAD_CHECKSUM, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
 from .session import CompressSession, InflateSession
 from .errors import Error, HdlzStatusError
 
@@ -256,6 +256,166 @@ class Engine(object):
             err.first_bad = rec.first_bad
             raise err
         return out[:rec.out_len]
+
+    # -- BGZF, the self-indexing blocked gzip (include/hdlz_bgzf.h): CRC-32 per block, the writer, the member index, the reader
+    @_on_device
+    def crc32_batch(self, d_buf, offsets=None, pitch=None, length=None, out=None):
+        """the CRC-32 (zlib.crc32) of every block of a batch -> uint32 device tensor[B] (hdlz_crc32_batch_ws; no scratch, no host sync).
+        d_buf: uint8 device tensor, any alignment.  offsets: int64[B + 1] on the device, ascending: block b is the flat
+        d_buf[offsets[b] - offsets[0] : offsets[b + 1] - offsets[0]]; else d_buf is [B, pitch] (or flat with pitch= and length=) and
+        block b the first `length` (default: pitch) bytes of row b."""
+        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous() and d_buf.device == self.device
+        if offsets is not None:
+            assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() >= 1
+            B, off_ptr, pitch, length = offsets.numel() - 1, offsets.data_ptr(), 0, 0
+        else:
+            if d_buf.dim() == 2:
+                B, pitch = d_buf.shape
+            else:
+                assert pitch, "a flat buffer needs offsets= or pitch="
+                B = d_buf.numel() // pitch
+            length = pitch if length is None else length
+            assert 0 <= length <= pitch
+            off_ptr = None
+        if out is None:
+            out = torch.empty(B, dtype=torch.uint32, device=d_buf.device)
+        assert out.is_cuda and out.dtype == torch.uint32 and out.numel() >= B and out.device == self.device
+        rc = self.lib.hdlz_crc32_batch_ws(d_buf.data_ptr() if d_buf.numel() else None, off_ptr, pitch, length, B,
+                                          out.data_ptr() if B else None, self._stream())
+        self._check(rc, "hdlz_crc32_batch_ws")
+        return out
+
+    @_on_device
+    def compress_bgzf(self, d_in, block=57344, cwindow=32, maxmatch=10, out=None):
+        """d_in: flat uint8 device tensor -> file uint8[file_len], a BGZF file (the blocked gzip of htslib and bgzip) that gzip -d,
+        Python's gzip and every htslib tool read back as d_in, and that carries its own member index (bgzf_index).  The input is cut
+        into blocks of `block` bytes (chain.plan_blocks), the CRC-32 of every block is taken (crc32_batch), the blocks are compressed
+        independently (hdlz_compress_batch) and framed as one gzip member each, with the EOF member behind them (hdlz_bgzf_join_ws).
+        block must be in [32, 65536]; a member holds at most 64 KiB, which blocks of up to 58230 bytes always fit -- a larger block of
+        bytes that do not compress fails with E_OUT_CAPACITY.  An empty input gives the 28-byte file (the EOF member alone); inputs of
+        1 to 4 bytes raise as compress_joined does.  One host sync (the result record); raises HdlzStatusError -- with .first_bad --
+        on a status that is not OK.  `out`: the file's buffer (default: hdlz_bgzf_bound(B, block) bytes)."""
+        from .chain import plan_blocks
+        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.dim() == 1 and d_in.is_contiguous() and d_in.device == self.device
+        if not 32 <= block <= 65536:
+            raise ValueError("block must be in [32, 65536]: a BGZF member holds at most 64 KiB")
+        n, dev = d_in.numel(), d_in.device
+        plan = plan_blocks(n, block) if n else []
+        B = len(plan)
+        if n:
+            slack = d_in.untyped_storage().nbytes() - d_in.storage_offset() - n
+            if d_in.data_ptr() % 16 or slack < 16:
+                d_in = self._stage(d_in)
+        in_off = torch.tensor([o for o, _ in plan] + [n], dtype=torch.int64).to(dev)
+        pitch = pitch_for(block)
+        rows, out_len, status = self._results(None, (B, pitch), B, dev)
+        if out is None:
+            out = torch.empty(self.lib.hdlz_bgzf_bound(B, block), dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+        offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        result = torch.empty(2, dtype=torch.int64, device=dev)                     # hdlz_bgzf_join_result: 16 bytes
+        work = torch.empty(max(8, self.lib.hdlz_bgzf_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)
+        crc = self.crc32_batch(d_in[:n], offsets=in_off)
+        if B:
+            rc = self.lib.hdlz_compress_batch(d_in.data_ptr(), in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
+                                              out_len.data_ptr(), status.data_ptr(), self._stream())
+            self._check(rc, "hdlz_compress_batch")
+        rc = self.lib.hdlz_bgzf_join_ws(rows.data_ptr() if B else None, pitch, out_len.data_ptr() if B else None,
+                                        status.data_ptr() if B else None, in_off.data_ptr(), block, B, crc.data_ptr() if B else None,
+                                        out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
+                                        work.data_ptr() if B else None, work.numel() * 8 if B else 0, self._stream())
+        self._check(rc, "hdlz_bgzf_join_ws")
+        rec = _lib.BgzfJoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+        if rec.status != OK:
+            err = HdlzStatusError(rec.status, "compress_bgzf")
+            err.first_bad = rec.first_bad
+            raise err
+        return out[:rec.file_len]
+
+    @_on_device
+    def bgzf_index(self, d_file, member_cap=None):
+        """d_file: flat uint8 device tensor, a BGZF file -> (member_offsets int64[M + 1], out_offsets int64[M + 1], record): member b is
+        d_file[member_offsets[b] : member_offsets[b + 1]] and holds bytes [out_offsets[b], out_offsets[b + 1]) of the data; the record
+        (a _lib.BgzfIndexResult: nmembers, total_out, file_used, status, eof_marker) is that of hdlz_bgzf_index_ws -- a status that is
+        not OK is returned, not raised: the M members in front of the failure stay valid and indexed.  The members are found on the
+        device; one host sync for the record.  member_cap: room for that many members (default: a guess, file_len // 4096 + 16); when
+        the file holds more, the call is made once more with the true count."""
+        assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.dim() == 1 and d_file.is_contiguous() and d_file.device == self.device
+        n, dev = d_file.numel(), d_file.device
+        cap = n // 4096 + 16 if member_cap is None else int(member_cap)
+        need = self.lib.hdlz_bgzf_index_work_bytes(n)
+        work = torch.empty(max(8, need) // 8, dtype=torch.int64, device=dev)
+        result = torch.empty(4, dtype=torch.int64, device=dev)                     # hdlz_bgzf_index_result: 32 bytes
+        while True:
+            off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            rc = self.lib.hdlz_bgzf_index_ws(d_file.data_ptr() if n else None, n, cap, off.data_ptr(), out_off.data_ptr(), result.data_ptr(),
+                                             work.data_ptr() if need else None, work.numel() * 8, self._stream())
+            self._check(rc, "hdlz_bgzf_index_ws")
+            rec = _lib.BgzfIndexResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+            if rec.status != E_OUT_CAPACITY or rec.nmembers <= cap:
+                return off[:rec.nmembers + 1], out_off[:rec.nmembers + 1], rec
+            cap = rec.nmembers
+
+    @_on_device
+    def inflate_bgzf(self, d_file, index=None, members=None, out=None, work=None):
+        """d_file: flat uint8 device tensor, a BGZF file of this or any other writer (stored, fixed and dynamic blocks) -> out uint8[n],
+        every member decoded in parallel and judged by its own trailer (CRC-32, ISIZE): hdlz_bgzf_inflate_ws.  index: the
+        (member_offsets, out_offsets) of bgzf_index (default: taken here; a file whose index stops with a status raises it, with
+        .first_bad = the number of sound members).  members=(b0, b1): only members b0 .. b1 - 1 are read and decoded -- the same bytes
+        as that slice of the whole output.  One host sync for the record (and one for the range's length); raises HdlzStatusError --
+        with .first_bad, counted from b0 -- on a status that is not OK.  `work`: the call's scratch, a uint8 device tensor of at
+        least hdlz_bgzf_inflate_work_bytes(b1 - b0, 0) bytes at a multiple of 256 (default: allocated here)."""
+        assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.dim() == 1 and d_file.is_contiguous() and d_file.device == self.device
+        dev = d_file.device
+        if index is None:
+            off, out_off, rec = self.bgzf_index(d_file)
+            if rec.status != OK:
+                err = HdlzStatusError(rec.status, "inflate_bgzf: the file's member index")
+                err.first_bad = rec.nmembers
+                raise err
+        else:
+            off, out_off = index[0], index[1]
+        assert off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and out_off.is_cuda and out_off.dtype == torch.int64 and \
+            out_off.is_contiguous() and off.numel() == out_off.numel() >= 1
+        M = off.numel() - 1
+        b0, b1 = (0, M) if members is None else (int(members[0]), int(members[1]))
+        if not 0 <= b0 <= b1 <= M:
+            raise ValueError("members=(%d, %d) is not a range of the file's %d members" % (b0, b1, M))
+        off, out_off, B = off[b0:b1 + 1], out_off[b0:b1 + 1], b1 - b0
+        total = int((out_off[B] - out_off[0]).item()) if B else 0
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.numel() >= total
+        need = self.lib.hdlz_bgzf_inflate_work_bytes(B, 0)
+        if work is None:
+            work = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
+        result = torch.empty(3, dtype=torch.int64, device=dev)                     # hdlz_bgzf_inflate_result: 24 bytes
+        rc = self.lib.hdlz_bgzf_inflate_ws(d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B, 0,
+                                           out.data_ptr() if total else None, total, None, result.data_ptr(),
+                                           work.data_ptr() if need else None, work.numel(), self._stream())
+        self._check(rc, "hdlz_bgzf_inflate_ws")
+        rec = _lib.BgzfInflateResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+        if rec.status != OK:
+            err = HdlzStatusError(rec.status, "inflate_bgzf")
+            err.first_bad = rec.first_bad
+            raise err
+        return out[:rec.out_len]
+
+    def compress_bgzf_bytes(self, data, block=57344, cwindow=32, maxmatch=10):
+        """host bytes -> the bytes of a BGZF file (compress_bgzf)"""
+        d = self._stage(data)[:len(data)]
+        return bytes(self.compress_bgzf(d, block=block, cwindow=cwindow, maxmatch=maxmatch).cpu().numpy().tobytes())
+
+    def inflate_bgzf_bytes(self, z):
+        """the bytes of a BGZF file -> (status, bytes): nothing but the file is needed -- no offsets, no block size, no capacity"""
+        d = self._stage(z)[:len(z)]
+        try:
+            out = self.inflate_bgzf(d)
+        except HdlzStatusError as e:
+            return e.status, b""
+        return OK, bytes(out.cpu().numpy().tobytes())
 
     # -- STARTC for ONE large stream, spread over the whole GPU (same bytes as compress_batch with one block)
     STREAM_MIN = 1 << 14          # measured crossover with the single-wave batch path: ~8 KiB
