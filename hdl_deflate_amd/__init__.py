@@ -11,6 +11,8 @@ from .constants import (IDLE, WRITE, READ, STARTC, STARTD, OK, E_SHORT_INPUT, E_
                         E_BAD_PARAM, E_HIP, E_BAD_TREE, E_BAD_HEADER, E_BAD_CHECKSUM, INFLATE_ASSUME_FIXED, INFLATE_LANE_PER_STREAM, INFLATE_WAVE_PER_STREAM, INFLATE_GROUP_PER_STREAM, INFLATE_ONEBLOCK, INFLATE_ONE_FIXED_BLOCK,
                         STATUS_NAMES, out_bound)
 from .port import Sig, DeflatePort, deflate                         # noqa: F401
+from . import bgzf                                                  # noqa: F401  (host-only: virtual offsets, .gzi files)
+from .bgzf import virtual_offset, split_virtual, gzi_dumps, gzi_loads   # noqa: F401
 
 
 def join_bound(nblocks, in_len):

@@ -77,6 +77,15 @@ BGZF_SIGNATURES = {
     "hdlz_bgzf_inflate_ws": (ci, [vp, u64, vp, vp, u64, u32, vp, u64, vp, vp, vp, sz, vp]),
 }
 BGZF_EXPORTS = tuple(BGZF_SIGNATURES)
+# ... and of include/hdlz_bgzf_range.h: batched range reads of a BGZF file by byte or virtual offset (tests/test_bgzf_range_cabi.py)
+BGZF_RANGE_SIGNATURES = {
+    "hdlz_bgzf_ranges_work_bytes": (sz, [u64, u64, u32]),
+    # d_file, file_len, d_off, d_out_off, nmembers, d_ranges, nranges, flags, d_out, out_cap, d_range_off, d_range_status, task_cap,
+    # d_result, d_work, work_bytes, stream
+    "hdlz_bgzf_read_ranges_ws": (ci, [vp, u64, vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, u64, vp, vp, sz, vp]),
+}
+BGZF_RANGE_EXPORTS = tuple(BGZF_RANGE_SIGNATURES)
+BGZF_RANGE_VIRTUAL = 1
 _lib = None
 
 
@@ -121,6 +130,11 @@ class BgzfInflateResult(ctypes.Structure):
     _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
 
 
+class BgzfRangesResult(ctypes.Structure):
+    """hdlz_bgzf_ranges_result: the result record of hdlz_bgzf_read_ranges_ws (32 bytes)"""
+    _fields_ = [("total_out", u64), ("ntasks", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -140,7 +154,7 @@ def load():
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
-            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()):
+            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

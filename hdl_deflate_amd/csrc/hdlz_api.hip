@@ -673,4 +673,49 @@ int hdlz_bgzf_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_
     return HDLZ_OK;
 }
 
+// ---- include/hdlz_bgzf_range.h: a batch of ranges of a BGZF file's data, by byte or virtual offset
+size_t hdlz_bgzf_ranges_work_bytes(uint64_t nranges, uint64_t task_cap, uint32_t flags) {
+    if (nranges > 0x7FFFFFFFull || task_cap > 0x7FFFFFFFull || (flags & ~HDLZ_BGZF_RANGE_VIRTUAL)) return 0;
+    return hdlz::bgzf_ranges_work_bytes(nranges, task_cap);
+}
+
+int hdlz_bgzf_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_off, const uint64_t* d_out_off, uint64_t nmembers,
+                             const uint64_t* d_ranges, uint64_t nranges, uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                             uint64_t* d_range_off, uint32_t* d_range_status, uint64_t task_cap, hdlz_bgzf_ranges_result* d_result,
+                             void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || !d_range_off || (nranges && (!d_ranges || !d_file || !d_off || !d_out_off)) || (out_cap && !d_out))
+        return fail_param("null device pointer");
+    if (nranges > 0x7FFFFFFFull || nmembers > 0x7FFFFFFFull || task_cap > 0x7FFFFFFFull)
+        return fail_param("nranges, nmembers and task_cap must be below 2^31");
+    if (flags & ~HDLZ_BGZF_RANGE_VIRTUAL) return fail_param("flags: only HDLZ_BGZF_RANGE_VIRTUAL is defined");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_ranges) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_range_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return fail_param("d_off / d_out_off / d_ranges / d_range_off / d_result must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_range_status) & 3u) return fail_param("d_range_status must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
+    const size_t need = hdlz::bgzf_ranges_work_bytes(nranges, task_cap);
+    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_bgzf_ranges_work_bytes(nranges, task_cap, flags)");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hdlz::RangeArgs u = hdlz::bgzf_ranges_args(d_work, nranges, task_cap);
+    u.in = d_file; u.in_len = file_len; u.off = d_off; u.out_off = d_out_off; u.nmembers = nmembers;
+    u.ranges = d_ranges; u.nranges = nranges; u.flags = flags; u.out = d_out; u.out_cap = out_cap;
+    u.range_off = d_range_off; u.range_status = d_range_status; u.task_cap = task_cap; u.result = d_result;
+    hipError_t e = hdlz::launch_bgzf_ranges_plan(u, st);
+    if (e != hipSuccess) return fail_hip(e, "launch the plan kernels (k_ranges_resolve, k_ranges_scan, k_ranges_expand)");
+    if (nranges && task_cap) {
+        hdlz::MemberArgs a;
+        a.in = d_file; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = task_cap;   // (slots behind ntasks are marked as refused)
+        a.flags = 0; a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.t_len; a.status = u.t_status; a.in_used = u.t_end_bit;
+        a.m_off = u.t_off; a.m_out_off = nullptr; a.m_out_len = 0; a.m_out_cap = 0; a.m_gap = 0;
+        a.m_end = u.t_end; a.m_dst = u.t_dst; a.m_dst_cap = u.t_cap;                               // the task view
+        e = hdlz::launch_inflate_dyn_members(a, st);
+        if (e != hipSuccess) return fail_hip(e, "launch the member decode");
+    }
+    e = hdlz::launch_bgzf_ranges_finish(u, st);
+    if (e != hipSuccess) return fail_hip(e, "launch the finish kernels (k_ranges_crc, k_ranges_judge, k_ranges_slice, k_ranges_finish, k_ranges_record)");
+    return HDLZ_OK;
+}
+
 }  // extern "C"

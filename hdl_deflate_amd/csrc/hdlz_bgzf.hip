@@ -20,19 +20,9 @@
 namespace hdlz {
 namespace bgzf {
 
-constexpr uint32_t HEAD = 18u, TAIL = 8u, MEMBER_MIN = HEAD + 2u + TAIL, MEMBER_MAX = 65536u, ISIZE_MAX = 65536u;
 constexpr uint32_t WIN_LOG2 = 16u, WIN = 1u << WIN_LOG2;
 constexpr uint64_t NONE64 = ~0ull;
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t JT = 256u;
-
-__device__ __forceinline__ uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t le32(const uint8_t* p) { return le16(p) | (le16(p + 2) << 16); }
-// the fixed bytes of a HEADER (MTIME, XFL and OS may be anything); the caller has checked that p[0 .. 18) lies inside the file
-__device__ __forceinline__ bool is_header(const uint8_t* p) {
-    return p[0] == 0x1Fu && p[1] == 0x8Bu && p[2] == 8u && p[3] == 4u && p[10] == 6u && p[11] == 0u && p[12] == 0x42u && p[13] == 0x43u &&
-           p[14] == 2u && p[15] == 0u;
-}
 
 // ---- hdlz_crc32_batch_ws
 __global__ __launch_bounds__(CRC_THREADS) void k_crc32_batch(const uint8_t* __restrict__ data, const uint64_t* __restrict__ off, uint64_t pitch,

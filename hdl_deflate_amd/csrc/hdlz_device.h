@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
-#include "../../include/hdlz_bgzf.h"      // (includes hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
+#include "../../include/hdlz_bgzf_range.h"   // (includes hdlz_bgzf.h, hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
 
 namespace hdlz {
 
@@ -53,6 +53,12 @@ struct MemberArgs : InflateArgs {
     uint64_t m_out_cap;          // no store at or behind out + m_out_cap
     uint32_t m_gap = 0;          // bytes at the end of [m_off[b], m_off[b + 1]) that are NOT the member's: 0 for a joined stream; 18 for BGZF
                                  // (hdlz_bgzf_inflate_ws: m_off[b] = the member's start + 18, so the gap is the next member's header)
+    // The TASK VIEW (hdlz_bgzf_read_ranges_ws): the members of a launch are not neighbours, and each has a destination
+    // of its own.  All three are null for every other caller, which the view then leaves exactly as it was.
+    const uint64_t* m_end = nullptr;      // nullable: member b is in[m_off[b] .. m_end[b]) -- m_off[b + 1] is not read
+    uint8_t* const* m_dst = nullptr;      // nullable, k_inflate_dyn<false, true> only: member b decodes to m_dst[b], m_dst_cap[b] bytes of room;
+    const uint32_t* m_dst_cap = nullptr;  //   out, m_out_off, m_out_len and m_out_cap are not used then.  The launchers of the other two
+                                          //   twins refuse a record with m_dst set (hipErrorInvalidValue): they would decode to out + 0
 };
 // the stream a decoder sees is in[m_off[b] - 2 .. m_off[b + 1]): it skips two bytes unvalidated (never loaded: the FF FF of the marker in
 // front, or 78 9C; BGZF: the BSIZE field), and the member's own marker (BGZF: its 8-byte trailer) supplies the bytes the end-of-input
@@ -60,7 +66,8 @@ struct MemberArgs : InflateArgs {
 __device__ __forceinline__ void member_view(const MemberArgs& a, uint64_t b, uint64_t& off, uint32_t& zn, uint64_t& o, uint32_t& cap) {
     const uint64_t lo = a.m_off[b];
     off = lo - 2u;
-    zn = (uint32_t)(a.m_off[b + 1] - lo) + 2u - a.m_gap;
+    zn = (uint32_t)((a.m_end ? a.m_end[b] : a.m_off[b + 1]) - lo) + 2u - a.m_gap;
+    if (a.m_dst) { o = 0; cap = a.m_dst_cap[b]; return; }     // (the task view: the caller takes m_dst[b]; its checks hold cap <= 65536)
     uint64_t n;
     if (a.m_out_off) { o = a.m_out_off[b]; n = a.m_out_off[b + 1] - o; }
     else { o = b * (uint64_t)a.m_out_len; n = a.m_out_len; }
@@ -230,6 +237,55 @@ struct BgzfArgs {
 };
 hipError_t launch_bgzf_check(const BgzfArgs& a, hipStream_t stream);
 hipError_t launch_bgzf_judge(const BgzfArgs& a, hipStream_t stream);
+
+// the format's constants and the header test, shared by hdlz_bgzf.hip and hdlz_bgzf_range.hip
+namespace bgzf {
+constexpr uint32_t HEAD = 18u, TAIL = 8u, MEMBER_MIN = HEAD + 2u + TAIL, MEMBER_MAX = 65536u, ISIZE_MAX = 65536u;
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+__device__ __forceinline__ uint32_t le32(const uint8_t* p) { return le16(p) | (le16(p + 2) << 16); }
+// the fixed bytes of a HEADER (MTIME, XFL and OS may be anything); the caller has checked that p[0 .. 18) lies inside the file
+__device__ __forceinline__ bool is_header(const uint8_t* p) {
+    return p[0] == 0x1Fu && p[1] == 0x8Bu && p[2] == 8u && p[3] == 4u && p[10] == 6u && p[11] == 0u && p[12] == 0x42u && p[13] == 0x43u &&
+           p[14] == 2u && p[15] == 0u;
+}
+}  // namespace bgzf
+
+// hdlz_bgzf_range.hip: hdlz_bgzf_read_ranges_ws (include/hdlz_bgzf_range.h).  The scratch, in this order -- every piece
+// a multiple of 256 bytes; R = nranges, T = task_cap:
+//   head      256 bytes: total_out, ntasks, the capacity flag (64 bits each), the lowest failed range (32 bits)
+//   per range p0, p1 (8 R each), tbase (8 (R + 1): the task counts, then their exclusive scan), lo, status, first (the lowest failed task,
+//             counted inside the range), edge[2] (the tasks that decode into the range's two slots) (4 R each)
+//   per task  off (the member's start + 18), end (the member's end), dst (8 T each), cap (its ISIZE), len, status, end_bit, crc,
+//             range (4 T each)
+//   slots     2 R slots of 65536 bytes: slot 2r holds range r's first member, slot 2r + 1 its last, when only a slice of it is delivered
+struct RangeArgs {
+    const uint8_t* in;
+    uint64_t in_len;
+    const uint64_t* off;
+    const uint64_t* out_off;
+    uint64_t nmembers;
+    const uint64_t* ranges;
+    uint64_t nranges;
+    uint32_t flags;
+    uint8_t* out;
+    uint64_t out_cap;
+    uint64_t* range_off;
+    uint32_t* range_status;      // nullable
+    uint64_t task_cap;
+    hdlz_bgzf_ranges_result* result;
+    uint64_t* head;
+    uint64_t *r_p0, *r_p1, *r_tbase;
+    uint32_t *r_lo, *r_status, *r_first, *r_edge;
+    uint64_t *t_off, *t_end;
+    uint8_t** t_dst;
+    uint32_t *t_cap, *t_len, *t_status, *t_end_bit, *t_crc, *t_range;
+    uint8_t* slots;
+};
+size_t bgzf_ranges_work_bytes(uint64_t nranges, uint64_t task_cap);
+RangeArgs bgzf_ranges_args(void* work, uint64_t nranges, uint64_t task_cap);       // the pieces of the scratch; the caller fills in the rest
+hipError_t launch_bgzf_ranges_plan(const RangeArgs& a, hipStream_t stream);        // resolve, scan, expand and check: in front of the decode
+hipError_t launch_bgzf_ranges_finish(const RangeArgs& a, hipStream_t stream);      // CRC words, judgement, edge slices, statuses, the record
 
 // hdlz_crc32.hip: CRC-32 of data[0 .. n) -> crc[0].  `words`: one word per 32 KiB tile (crc32_tiles(n) of them; null when n is 0).
 size_t crc32_tiles(uint64_t n);

@@ -202,7 +202,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             continue;
         }
         const uint8_t* __restrict__ z = a.in + off;
-        uint8_t* __restrict__ out = a.out + (MEMBERS ? m_o : sid * a.out_pitch);
+        uint8_t* out_base = a.out + (MEMBERS ? m_o : sid * a.out_pitch);
+        if constexpr (MEMBERS) { if (a.m_dst) out_base = a.m_dst[sid]; }    // the task view: a destination per member
+        uint8_t* __restrict__ out = out_base;
         const uint32_t cap0 = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)a.out_pitch;
         const uint32_t cap = STREAM ? (out_limit < cap0 ? out_limit : cap0) : cap0;      // STREAM: reaching it is a stop, not an error
         const uint32_t inbits = 8u * zn;                                                 // (zn < 2^28)

@@ -370,6 +370,7 @@ hipError_t launch_inflate_grp(const InflateArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_inflate_grp_members(const MemberArgs& a, hipStream_t stream) {
+    if (a.m_dst) return hipErrorInvalidValue;      // the task view's destinations: k_inflate_dyn<false, true> alone takes them
     if (a.nstreams == 0) return hipSuccess;
     const uint64_t per_wg = (uint64_t)grp::NS * grp::WAVES;
     hipLaunchKernelGGL(grp::k_inflate_grp<true>, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);

@@ -1081,6 +1081,7 @@ hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Wo
 
 // the member twin (hdlz_unjoin_ws): launch_inflate_tok with the lists ordered by the MEMBER lengths (a.m_off as in_off); no second pass
 hipError_t launch_inflate_tok_members(const MemberArgs& a, hipStream_t stream, const Work& w) {
+    if (a.m_dst) return hipErrorInvalidValue;      // the task view's destinations: k_inflate_dyn<false, true> alone takes them
     if (a.nstreams == 0) return hipSuccess;
     typedef tok::Lds<false, tok::CAP_FULL> L;
     const uint64_t per_wg = 64u * L::WAVES;

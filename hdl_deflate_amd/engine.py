@@ -417,6 +417,113 @@ class Engine(object):
             return e.status, b""
         return OK, bytes(out.cpu().numpy().tobytes())
 
+    # -- random access into a BGZF file (include/hdlz_bgzf_range.h): a batch of ranges by byte or virtual offset
+    def _read_ranges(self, d_file, off, out_off, ranges, flags, out, out_cap, task_cap, work):
+        """one hdlz_bgzf_read_ranges_ws call and its host sync -> (record, range_off int64[R + 1])"""
+        R, dev = ranges.shape[0], d_file.device
+        range_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        result = torch.empty(4, dtype=torch.int64, device=dev)                     # hdlz_bgzf_ranges_result: 32 bytes
+        need = self.lib.hdlz_bgzf_ranges_work_bytes(R, task_cap, flags)
+        assert work.numel() >= need, "the scratch holds %d bytes, the call needs %d" % (work.numel(), need)
+        rc = self.lib.hdlz_bgzf_read_ranges_ws(d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(),
+                                               off.numel() - 1, ranges.data_ptr() if R else None, R, flags,
+                                               out.data_ptr() if out_cap else None, out_cap, range_off.data_ptr(), None, task_cap,
+                                               result.data_ptr(), work.data_ptr() if need else None, work.numel(), self._stream())
+        self._check(rc, "hdlz_bgzf_read_ranges_ws")
+        return _lib.BgzfRangesResult.from_buffer_copy(result.cpu().numpy().tobytes()), range_off     # the one host sync
+
+    @_on_device
+    def read_bgzf(self, d_file, ranges, index=None, virtual=False, out=None, work=None, max_work_bytes=256 << 20):
+        """d_file: flat uint8 device tensor, a BGZF file; ranges: R pairs (begin, end) -- an int64 device tensor [R, 2] or a Python
+        sequence of pairs -> (out uint8[total], range_offsets int64[R + 1]), both on the device: range r's bytes are
+        out[range_offsets[r] : range_offsets[r + 1]].  The pairs are byte offsets into the data (clipped to it: reading past the end
+        is short), or with virtual=True virtual offsets, coffset << 16 | uoffset, as a .bai, .tbi or .csi index gives them
+        (hdl_deflate_amd.bgzf.virtual_offset; they fit int64 for files below 2^47 bytes).  Ranges may overlap, repeat and come in any
+        order.  Resolved, decoded, judged and trimmed on the device (hdlz_bgzf_read_ranges_ws): only the members the ranges touch are
+        decoded, each judged whole by its own trailer.  index: the (member_offsets, out_offsets) of bgzf_index (default: taken here;
+        a file whose index stops with a status raises it, as inflate_bgzf does).
+        The ranges are processed in groups so that no group's scratch exceeds max_work_bytes: 131072 bytes of slots per range and
+        48 bytes per touched member.  A group whose touched members do not fit is halved; a group of ONE range takes what it takes.
+        One host sync per call made.  Without `out`: two per group, the sizing call and the read.  With `out`, which must have room
+        for all the data: one per group when the guess of its touched members holds -- two per range and one per 256 bytes of room,
+        as far as max_work_bytes lets them fit --, else the call that missed was the sizing call and a second one follows.
+        `work`: the groups' scratch, a uint8 device tensor at a multiple of 256 whose size stands in for max_work_bytes.
+        Raises HdlzStatusError with .first_bad = the index of the lowest failed range over all groups."""
+        assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.dim() == 1 and d_file.is_contiguous() and d_file.device == self.device
+        dev = d_file.device
+        if index is None:
+            off, out_off, rec = self.bgzf_index(d_file)
+            if rec.status != OK:
+                err = HdlzStatusError(rec.status, "read_bgzf: the file's member index")
+                err.first_bad = rec.nmembers
+                raise err
+        else:
+            off, out_off = index[0], index[1]
+        assert off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and out_off.is_cuda and out_off.dtype == torch.int64 and \
+            out_off.is_contiguous() and off.numel() == out_off.numel() >= 1
+        if not torch.is_tensor(ranges):
+            pairs = [[int(v) - (1 << 64) if int(v) >= 1 << 63 else int(v) for v in pair] for pair in ranges]      # the words are unsigned
+            ranges = torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
+        assert ranges.is_cuda and ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2 and ranges.is_contiguous()
+        R, flags = ranges.shape[0], _lib.BGZF_RANGE_VIRTUAL if virtual else 0
+        query = self.lib.hdlz_bgzf_ranges_work_bytes
+        if work is not None:
+            assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
+            max_work_bytes = work.numel()
+        if out is not None:
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+        group = max(1, (max_work_bytes - 8192) // (131072 + 256))                  # ranges of two members each
+        while group > 1 and query(group, 2 * group, flags) > max_work_bytes:
+            group -= 1
+        todo = [(g, min(R, g + group)) for g in range(0, R, group)][::-1]          # a stack: the lowest group on top
+        pieces, offsets, pos = [], [], 0
+
+        def scratch(n, ntasks):
+            need = query(n, ntasks, flags)
+            return work if work is not None and work.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
+        while todo:
+            g0, g1 = todo.pop()
+            rg, n = ranges[g0:g1], g1 - g0
+            if out is None:
+                dst, ntasks = torch.empty(0, dtype=torch.uint8, device=dev), 0     # the sizing call
+            else:
+                dst = out[pos:]
+                fit = max(0, max_work_bytes - query(n, 0, flags) - 9 * 256) // 48  # task words that fit behind the group's slots
+                ntasks = min(fit, 2 * n + dst.numel() // 256)                      # the guess
+            rec, range_off = self._read_ranges(d_file, off, out_off, rg, flags, dst, dst.numel(), ntasks, scratch(n, ntasks))
+            if rec.status == E_OUT_CAPACITY:                                       # the sizing call, or a guess that did not hold
+                if rec.total_out == (1 << 64) - 1:
+                    raise ValueError("read_bgzf: the lengths of the ranges exceed 64 bits: the index is not ascending")
+                if out is not None and rec.total_out > dst.numel():
+                    raise ValueError("read_bgzf: `out` has room for %d bytes behind the earlier groups, this one holds %d" % (dst.numel(), rec.total_out))
+                if n > 1 and query(n, rec.ntasks, flags) > max_work_bytes:
+                    mid = g0 + n // 2
+                    todo += [(mid, g1), (g0, mid)]
+                    continue
+                if out is None:
+                    dst = torch.empty(rec.total_out, dtype=torch.uint8, device=dev)
+                rec, range_off = self._read_ranges(d_file, off, out_off, rg, flags, dst, dst.numel(), rec.ntasks, scratch(n, rec.ntasks))
+            if rec.status != OK:
+                err = HdlzStatusError(rec.status, "read_bgzf")
+                err.first_bad = g0 + rec.first_bad
+                raise err
+            pieces.append(dst[:rec.total_out])
+            offsets.append(range_off[:-1] + pos)
+            pos += rec.total_out
+        offsets.append(torch.tensor([pos], dtype=torch.int64, device=dev))
+        if out is None:
+            out = pieces[0] if len(pieces) == 1 else torch.cat(pieces) if pieces else torch.empty(0, dtype=torch.uint8, device=dev)
+        return out[:pos], torch.cat(offsets)
+
+    def read_bgzf_bytes(self, z, begin, end):
+        """the bytes of a BGZF file -> (status, bytes [begin, end) of its data), clipped to the data"""
+        d = self._stage(z)[:len(z)]
+        try:
+            out, _ = self.read_bgzf(d, [(begin, end)])
+        except HdlzStatusError as e:
+            return e.status, b""
+        return OK, bytes(out.cpu().numpy().tobytes())
+
     # -- STARTC for ONE large stream, spread over the whole GPU (same bytes as compress_batch with one block)
     STREAM_MIN = 1 << 14          # measured crossover with the single-wave batch path: ~8 KiB
     LARGE_BLOCK, MANY_WAVES = 1 << 16, 1200   # compress_batch: up to this many blocks of at least this size -> stream passes
