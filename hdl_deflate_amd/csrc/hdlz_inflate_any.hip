@@ -317,7 +317,7 @@ __global__ __launch_bounds__(FIND_T) void k_any_find(Args a) {
 }
 
 // one LANE per listed position: the code lengths, and the rest of the serial decoder's acceptance rules (hdlz_inflate_dyn.hip, "BL" ..
-// "canon_build": over-subscribed sets rejected, incomplete ones only with a single code -- for the distance code also with none --,
+// "canon_build": over-subscribed sets rejected, incomplete ones only with exactly one code of length 1 -- for the distance code also with none --,
 // an end-of-block code must exist, the header must leave room for the reference's end-of-input margin)
 // the code-length code of the header at bit p into a 7-bit table (symbol << 3 | length by the next 7 stream bits; stride: elements between
 // entries -- the lanes of k_any_headers interleave theirs); -> the reader behind the 3-bit lengths, HLIT + 257, HDIST + 1, BFINAL
@@ -407,8 +407,8 @@ __global__ __launch_bounds__(64) void k_any_headers(Args a) {
             }
         }
         if (eob_len == 0u) ok = false;                                                        // no end-of-block code
-        if (kr1 < 32768u && nz1 != 1u) ok = false;                                            // incomplete: only with a single code
-        if (kr2 < 32768u && nz2 > 1u) ok = false;                                             // ... the distance code also with none
+        if (kr1 < 32768u && !(nz1 == 1u && kr1 == 16384u)) ok = false;                        // incomplete: only as one code of length 1 (Kraft sum 1/2)
+        if (kr2 < 32768u && !(nz2 == 0u || (nz2 == 1u && kr2 == 16384u))) ok = false;         // ... the distance code also with none
         if ((int32_t)(r.pos >> 3) > isize - 3) ok = false;                                    // (the serial decoder's NO EOF at the end of a header)
         if (ok) {
             const uint32_t slot = atomicAdd(&v.ctl[A_NBLK], 1u);

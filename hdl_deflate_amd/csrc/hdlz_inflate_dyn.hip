@@ -14,7 +14,7 @@
 // The reference's table layout (10-bit instant table + incremental-mask retry) is FPGA-specific; a
 // canonical count/offset decoder returns the same symbols for every valid code.  Invalid code
 // descriptions are HDLZ_E_BAD_TREE (zlib's acceptance rules: over-subscribed sets rejected, incomplete
-// sets only with a single code -- or, for the distance code, with none at all).
+// sets only with exactly one code of length 1 -- or, for the distance code, with none at all).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
@@ -431,10 +431,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                 __syncthreads();
                 {
                     const int l1 = L.left[1], l2 = L.left[2];
-                    if (l1 < 0 || (l1 > 0 && (int)nlen - (int)L.cnt[1][0] != 1)) FAIL(HDLZ_E_BAD_TREE);
+                    // an incomplete set only as exactly one code of length 1 (zlib inflate_table: max == 1; puff: count[0] + count[1] == n)
+                    if (l1 < 0 || (l1 > 0 && !((int)nlen - (int)L.cnt[1][0] == 1 && L.cnt[1][1] == 1))) FAIL(HDLZ_E_BAD_TREE);
                     // an EMPTY distance set (a block of literals only) is legal, RFC1951 3.2.7 -- zlib's inflate_table (max == 0)
                     // and puff accept it; a distance symbol met later then finds no code (dlen > 15 -> BAD_SYMBOL)
-                    if (l2 < 0 || (l2 > 0 && (int)ndist - (int)L.cnt[2][0] > 1)) FAIL(HDLZ_E_BAD_TREE);
+                    if (l2 < 0 || (l2 > 0 && !((int)ndist == (int)L.cnt[2][0] || ((int)ndist - (int)L.cnt[2][0] == 1 && L.cnt[2][1] == 1)))) FAIL(HDLZ_E_BAD_TREE);
                 }
                 if (sfinal && (int32_t)(BITPOS() >> 3) > isize - 3) FAIL(HDLZ_E_NO_EOF);
                 if (STREAM) {                                        // the block's code lengths travel with the session

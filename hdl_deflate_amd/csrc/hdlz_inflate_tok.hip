@@ -526,9 +526,10 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
             x_build<15>(XL, [&](int l) { return nL.at(l); }, l1, c1);
             x_build<15>(XD, [&](int l) { return nD.at(l); }, l2, c2);
             if (hm == 2u) {
-                // incomplete sets only with a single code -- or, for the distance code, with none at all (RFC1951 3.2.7)
-                if (l1 < 0 || (l1 > 0 && c1 != 1u)) return HDLZ_E_BAD_TREE;
-                if (l2 < 0 || (l2 > 0 && c2 > 1u)) return HDLZ_E_BAD_TREE;
+                // incomplete sets only with exactly one code of length 1 (zlib inflate_table: max == 1) -- or, for the distance code,
+                // with none at all (RFC1951 3.2.7)
+                if (l1 < 0 || (l1 > 0 && !(c1 == 1u && nL.at(1) == 1u))) return HDLZ_E_BAD_TREE;
+                if (l2 < 0 || (l2 > 0 && !(c2 == 0u || (c2 == 1u && nD.at(1) == 1u)))) return HDLZ_E_BAD_TREE;
                 if (c1 > CAP) return HDLZ_E_DYNAMIC_UNSUPPORTED;       // (only CAP_SMALL: at most 286 symbols are coded)
                 {                                      // counts -> first slot per length
                     F16 fL, fD;

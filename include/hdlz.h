@@ -65,7 +65,8 @@ enum {
     HDLZ_E_BAD_PARAM = 8,
     HDLZ_E_HIP = 9,                 /* HIP runtime error / no device; see hdlz_last_error() */
     HDLZ_E_BAD_TREE = 10            /* dynamic block header does not describe a valid prefix code (the reference
-                                       builds garbage tables there, deflate.py:1204-1400; zlib's rules are used) */
+                                       builds garbage tables there, deflate.py:1204-1400; zlib's rules are used: no over-subscribed set,
+                                       an incomplete one only as exactly one code of length 1 -- or no distance code at all) */
 };
 /* ... and the two verdicts only hdlz_inflate_checked gives (the reference verifies neither, so no other call returns them) */
 #define HDLZ_E_BAD_HEADER   11   /* checked call: CMF/FLG is not a zlib header this library reads */

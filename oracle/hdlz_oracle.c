@@ -276,7 +276,7 @@ static void adv(bitr* r, unsigned width) { /* deflate.py:521-533 */
  * count/offset decoder yields the same symbols for every VALID code.  For code descriptions that are
  * not valid prefix codes the reference's behaviour is undefined table garbage; here they are errors
  * (HDLZ_E_BAD_TREE), using zlib's acceptance rules: over-subscribed sets are rejected, incomplete sets
- * only allowed when they hold a single code. */
+ * only allowed when they hold exactly one code OF LENGTH 1 (zlib inflate_table: max == 1; puff: nlen != count[0] + count[1]). */
 static const uint8_t code_length_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15}; /* :97-98 */
 
 typedef struct {
@@ -408,10 +408,11 @@ int hdlz_oracle_inflate(const uint8_t* z, size_t zn, unsigned flags, uint32_t ob
             }
             if (lengths[256] == 0) return HDLZ_E_BAD_TREE; /* no end-of-block code */
             int err = canon_build(&lencode, lengths, nlen);
-            if (err < 0 || (err > 0 && nlen - lencode.count[0] != 1)) return HDLZ_E_BAD_TREE;
+            if (err < 0 || (err > 0 && !(nlen - lencode.count[0] == 1 && lencode.count[1] == 1))) return HDLZ_E_BAD_TREE;
             err = canon_build(&distcode, lengths + nlen, ndist);
             /* an empty distance set (literals only) is legal (RFC1951 3.2.7; zlib inflate_table max == 0, puff) */
-            if (err < 0 || (err > 0 && ndist - distcode.count[0] > 1)) return HDLZ_E_BAD_TREE;
+            if (err < 0 || (err > 0 && !(ndist == distcode.count[0] || (ndist - distcode.count[0] == 1 && distcode.count[1] == 1))))
+                return HDLZ_E_BAD_TREE;
             if (r.di > isize - 3) return HDLZ_E_NO_EOF; /* header ran into the trailer / past the end */
         }
         /* NEXT / INFLATE loop */

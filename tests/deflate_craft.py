@@ -1,0 +1,553 @@
+"""Hand-crafted dynamic (BTYPE = 2) deflate blocks, bit by bit (a helper module like checked_ref.py, not a conftest).
+
+Stock zlib's encoder covers a small corner of the headers a decoder must accept -- no 15-bit codes on small inputs, no 7-bit
+code-length code, no one-code distance set at symbol 29, never 258 as symbol 284 + 31 extra -- and none of those it must reject.
+This module writes such blocks in pure Python: `emit_block` takes the code lengths, the tokens and, if wanted, the exact sequence of
+code-length-code operations; `catalogue()` is a list of named cases with their expectation (the plain bytes, computed here from the
+tokens, or the status of the rejection); `random_stream()` draws whole streams; `header_flips()` damages a stream inside a block header.
+Nothing here looks at a decoder: tests/test_crafted_trees_cpu.py holds all of it against stock zlib and the C oracle."""
+import functools
+import random
+import zlib
+
+OK, E_BAD_DISTANCE, E_BAD_SYMBOL, E_BAD_TREE = 0, 4, 7, 10
+ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)       # RFC1951 3.2.7
+LBASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+LEXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+DEXTRA = tuple(0 if c < 2 else c // 2 - 1 for c in range(30))
+DBASE = tuple(1 + sum(1 << DEXTRA[k] for k in range(c)) for c in range(30))
+assert DBASE[29] + (1 << DEXTRA[29]) - 1 == 32768 and LBASE[27] + 31 == 258
+
+
+class Bits(object):
+    """LSB-first bit writer; Huffman codes go in MSB first (RFC1951 3.1.1)"""
+
+    def __init__(self):
+        self.out, self.acc, self.n, self.pos = bytearray(), 0, 0, 0
+
+    def put(self, v, nb):
+        self.acc |= (v & ((1 << nb) - 1)) << self.n
+        self.n += nb
+        self.pos += nb
+        while self.n >= 8:
+            self.out.append(self.acc & 255)
+            self.acc >>= 8
+            self.n -= 8
+
+    def code(self, cl):
+        self.put(cl[0], cl[1])                         # (canonical() hands the codes out bit-reversed)
+
+    def bytes(self):
+        return bytes(self.out) + (bytes([self.acc]) if self.n else b"")
+
+
+def kraft(lengths, unit=15):
+    """the code space the lengths take, in units of 2^-unit: 2^unit = complete"""
+    return sum(1 << (unit - l) for l in lengths if l)
+
+
+def canonical(lengths):
+    """symbol -> (code with its bits reversed: as Bits.put takes it, length), RFC1951 3.2.2; for a set that is no prefix code the same
+    arithmetic, truncated to the length"""
+    count = [0] * 17
+    for l in lengths:
+        count[l] += 1
+    count[0] = 0
+    nxt, code = [0] * 17, 0
+    for b in range(1, 16):
+        code = (code + count[b - 1]) << 1
+        nxt[b] = code
+    out = {}
+    for s, l in enumerate(lengths):
+        if l:
+            out[s] = (int(format(nxt[l] & ((1 << l) - 1), "0%db" % l)[::-1], 2), l)
+            nxt[l] += 1
+    return out
+
+
+def complete_code(n, rng, max_len, shuffle=True):
+    """n code lengths with Kraft sum exactly 1 whose longest is exactly max_len where n allows it (n > max_len; for more than 2^max_len
+    codes the longest is as short as n allows): the chain 1, 2, .., max_len, max_len with random leaves shorter than max_len split"""
+    if n == 1:
+        return [1]                                     # (the one incomplete set a decoder accepts)
+    max_len = min(max_len, n - 1)
+    while (1 << max_len) < n:
+        max_len += 1
+    cnt = [0] * (max_len + 2)
+    for l in range(1, max_len + 1):
+        cnt[l] = 1
+    cnt[max_len] = 2
+    for _ in range(n - (max_len + 1)):
+        open_ = [l for l in range(1, max_len) if cnt[l]]
+        l = rng.choices(open_, [cnt[l] for l in open_])[0]
+        cnt[l] -= 1
+        cnt[l + 1] += 2
+    lens = [l for l in range(1, max_len + 1) for _ in range(cnt[l])]
+    assert len(lens) == n and kraft(lens) == 1 << 15 and max(lens) == max_len
+    if shuffle:
+        rng.shuffle(lens)
+    return lens
+
+
+def rle_ops(lengths):
+    """the run-length form of a length list: 0..15 as ints, repeats as (16 | 17 | 18, value of the extra field)"""
+    ops, i, n = [], 0, len(lengths)
+    while i < n:
+        v, j = lengths[i], i
+        while j < n and lengths[j] == v:
+            j += 1
+        run = j - i
+        if v == 0:
+            while run >= 11:
+                k = min(run, 138)
+                ops.append((18, k - 11))
+                run -= k
+            if run >= 3:
+                ops.append((17, run - 3))
+                run = 0
+            ops += [0] * run
+        else:
+            ops.append(v)
+            run -= 1
+            while run >= 3:
+                k = min(run, 6)
+                ops.append((16, k - 3))
+                run -= k
+            ops += [v] * run
+        i = j
+    return ops
+
+
+def op_sym(op):
+    return op[0] if isinstance(op, tuple) else op
+
+
+def op_rep(op):
+    return 1 if not isinstance(op, tuple) else op[1] + (11 if op[0] == 18 else 3)
+
+
+def balanced(n):
+    """n lengths of a complete code, as even as possible (shortest first)"""
+    if n == 1:
+        return [1]
+    k = n.bit_length() - 1
+    if 1 << k == n:
+        return [k] * n
+    return [k] * ((2 << k) - n) + [k + 1] * (2 * (n - (1 << k)))
+
+
+def default_cl_lens(ops):
+    """19 lengths of a complete code-length code over the symbols the operations use (the more frequent, the shorter)"""
+    freq = {}
+    for op in ops:
+        freq[op_sym(op)] = freq.get(op_sym(op), 0) + 1
+    if len(freq) == 1:                                 # a code-length code of one code is incomplete: a second, unused one
+        freq[0 if 0 not in freq else 1] = 0
+    syms = sorted(freq, key=lambda s: (-freq[s], s))
+    cl = [0] * 19
+    for s, l in zip(syms, balanced(len(syms))):
+        cl[s] = l
+    return cl
+
+
+def length_symbol(length):
+    s = max(k for k in range(29) if LBASE[k] <= length)
+    return 257 + (28 if length == 258 else s)
+
+
+def distance_symbol(dist):
+    return max(k for k in range(30) if DBASE[k] <= dist)
+
+
+def emit_block(w, ll, dl, tokens, final, ops=None, cl_lens=None, hclen=None, rle=True, eob=True):
+    """one dynamic block into the Bits `w`.  ll: HLIT + 257 literal/length code lengths, dl: HDIST + 1 distance code lengths (the counts
+    written are the lists' lengths, whatever they are); tokens: ints (literals) and (length, distance[, length symbol]);
+    ops: the code-length-code operations (default: rle_ops or one per length); cl_lens: the 19 code-length-code lengths by symbol
+    (default: a complete code over the used symbols); hclen: how many of them are written (default: as few as a header may).
+    -> dict: span = (first bit, end bit) of the header, and what the coverage assertions ask about"""
+    lengths = list(ll) + list(dl)
+    if ops is None:
+        ops = rle_ops(lengths) if rle else list(lengths)
+    if cl_lens is None:
+        cl_lens = default_cl_lens(ops)
+    assert len(cl_lens) == 19 and max(cl_lens) <= 7
+    if hclen is None:
+        hclen = max([4] + [i + 1 for i in range(19) if cl_lens[ORDER[i]]])
+    assert 4 <= hclen <= 19 and all(cl_lens[ORDER[i]] == 0 for i in range(hclen, 19))
+    start = w.pos
+    w.put(1 if final else 0, 1)
+    w.put(2, 2)
+    w.put(len(ll) - 257, 5)
+    w.put(len(dl) - 1, 5)
+    w.put(hclen - 4, 4)
+    for i in range(hclen):
+        w.put(cl_lens[ORDER[i]], 3)
+    cc = canonical(cl_lens)
+    idx, cross = 0, False
+    for op in ops:
+        w.code(cc[op_sym(op)])
+        if isinstance(op, tuple):
+            w.put(op[1], {16: 2, 17: 3, 18: 7}[op[0]])
+            cross = cross or idx < len(ll) < idx + op_rep(op)
+        idx += op_rep(op)
+    end = w.pos
+    lc, dc = canonical(ll), canonical(dl)
+    for t in tokens:
+        if isinstance(t, int):
+            w.code(lc[t])
+            continue
+        length, dist = t[0], t[1]
+        ls = t[2] if len(t) > 2 else length_symbol(length)
+        w.code(lc[ls])
+        assert 0 <= length - LBASE[ls - 257] < (1 << LEXTRA[ls - 257]) or length == LBASE[ls - 257]
+        w.put(length - LBASE[ls - 257], LEXTRA[ls - 257])
+        ds = distance_symbol(dist)
+        w.code(dc[ds])
+        w.put(dist - DBASE[ds], DEXTRA[ds])
+    if eob and 256 in lc:
+        w.code(lc[256])
+    return dict(span=(start, end), offset=start & 7, ncoded=sum(1 for l in ll if l), ndcoded=sum(1 for l in dl if l),
+                max_ll=max(ll), max_dl=max(dl), max_cl=max(cl_lens), cross=cross, hclen=hclen,
+                rle=any(isinstance(op, tuple) for op in ops))
+
+
+def emit_fixed_prefix(w, m):
+    """a fixed-Huffman block (not final) of m nine-bit literals: 10 + 9 m bits, so the next header starts at bit (2 + m) mod 8 behind
+    a byte-aligned start -> the literals"""
+    w.put(0, 1)
+    w.put(1, 2)
+    lits = [144 + (7 * k) % 112 for k in range(m)]
+    for v in lits:
+        w.put(int(format(0b110010000 + (v - 144), "09b")[::-1], 2), 9)
+    w.put(0, 7)
+    return bytes(lits)
+
+
+PREFIX_FOR_OFFSET = {(2 + m) % 8: m for m in range(8)}           # m literals in front -> bit offset of the next header
+
+
+def apply_tokens(out, tokens):
+    """the plain bytes of the tokens appended to the bytearray `out` (None when a distance reaches before the start)"""
+    for t in tokens:
+        if isinstance(t, int):
+            out.append(t)
+            continue
+        length, dist = t[0], t[1]
+        if dist > len(out):
+            return None
+        if dist >= length:
+            out += out[len(out) - dist:len(out) - dist + length]
+        else:
+            pat = bytes(out[len(out) - dist:])
+            out += (pat * (length // dist + 1))[:length]
+    return out
+
+
+def wrap(body, plain):
+    return b"\x78\x9c" + body + zlib.adler32(plain).to_bytes(4, "big")
+
+
+class Case(object):
+    """name; z: the zlib-framed stream; raw: the deflate stream alone; plain (None for a rejected one) and status; blocks: emit_block's
+    records, their spans in bits of z"""
+
+    def __init__(self, name, w, plain, status, blocks):
+        self.name, self.raw, self.status = name, w.bytes(), status
+        self.plain = bytes(plain) if status == OK else None
+        self.z = wrap(self.raw, self.plain or b"")
+        self.blocks = blocks
+        self.spans = [(b["span"][0] + 16, b["span"][1] + 16) for b in blocks]
+
+    def __repr__(self):
+        return "Case(%s)" % self.name
+
+
+def one_block(name, ll, dl, tokens, status=OK, prefix_offset=None, **kw):
+    """a stream of one final crafted block, behind a fixed block that puts its header at the given bit offset if one is asked for"""
+    w, out = Bits(), bytearray()
+    if prefix_offset is not None:
+        out += emit_fixed_prefix(w, PREFIX_FOR_OFFSET[prefix_offset])
+        assert w.pos & 7 == prefix_offset
+    b = emit_block(w, ll, dl, tokens, True, **kw)
+    plain = apply_tokens(out, tokens) if status == OK else None
+    assert status != OK or plain is not None
+    return Case(name, w, plain, status, [b])
+
+
+def sparse(n, lens):
+    """n lengths, zero but for the dict"""
+    out = [0] * n
+    for s, l in lens.items():
+        out[s] = l
+    return out
+
+
+def all_symbols_tokens():
+    """every literal, > 32 KiB of them; every length symbol and every distance symbol at its lowest and highest extra value; 258 as
+    symbol 285 and as 284 + 31"""
+    toks = [(k * 167 + (k >> 8)) & 255 for k in range(32768 + 256)]
+    assert set(toks) == set(range(256))
+    lens = []
+    for s in range(29):
+        lens += [(LBASE[s], 257 + s), (LBASE[s] + (1 << LEXTRA[s]) - 1, 257 + s)]
+    assert (258, 284) in lens and (258, 285) in lens
+    dists = []
+    for c in range(30):
+        dists += [DBASE[c], DBASE[c] + (1 << DEXTRA[c]) - 1]
+    for k in range(max(len(lens), len(dists))):
+        ln, ls = lens[k % len(lens)]
+        toks.append((ln, dists[(k * 7) % len(dists)], ls))
+        toks.append((k * 31) & 255)
+        ln, ls = lens[(k * 11) % len(lens)]
+        toks.append((ln, dists[k % len(dists)], ls))
+    return toks
+
+
+def tokens_for(rng, ll, dl, n, produced):
+    """n random tokens that only use coded symbols and distances that reach no further back than `produced` bytes + their own output"""
+    lits = [s for s in range(256) if s < len(ll) and ll[s]]
+    lsyms = [s for s in range(257, min(len(ll), 286)) if ll[s]]
+    dsyms = [c for c in range(min(len(dl), 30)) if dl[c]]
+    toks = []
+    for _ in range(n):
+        reach = [c for c in dsyms if DBASE[c] <= produced]
+        if lsyms and reach and (not lits or rng.random() < 0.18):
+            ls, c = rng.choice(lsyms), rng.choice(reach)
+            length = LBASE[ls - 257] + rng.choice((0, (1 << LEXTRA[ls - 257]) - 1, rng.randrange(1 << LEXTRA[ls - 257])))
+            dist = min(produced, DBASE[c] + rng.choice((0, (1 << DEXTRA[c]) - 1, rng.randrange(1 << DEXTRA[c]))))
+            toks.append((length, dist, ls))
+            produced += length
+        elif lits:
+            toks.append(rng.choice(lits))
+            produced += 1
+        else:
+            break
+    return toks
+
+
+def random_block_lengths(rng, count=None, max_len=None, dist_kind=None):
+    """(ll, dl) of one random block: HLIT and HDIST, `count` coded literal/length symbols among them (256 always), a complete code"""
+    if count is None:
+        count = rng.choice((2, 10, 143, 144, 145, 285, 286, rng.randint(2, 286), rng.randint(2, 60)))
+    if max_len is None:
+        max_len = rng.choice((7, 9, 12, 15))
+    coded = [256] + rng.sample([s for s in range(286) if s != 256], count - 1)
+    nlen = rng.randint(max(257, max(coded) + 1), 286)
+    ll = [0] * nlen
+    for s, l in zip(coded, complete_code(count, rng, max_len)):
+        ll[s] = l
+    kind = dist_kind or rng.choice(("none", "one", "several", "several"))
+    if kind == "none":
+        dl = [0] * rng.randint(1, 30)
+    elif kind == "one":
+        c = rng.randrange(30)
+        dl = sparse(rng.randint(c + 1, 30), {c: 1})
+    else:
+        k = rng.randint(2, 30)
+        dsy = rng.sample(range(30), k)
+        dl = [0] * rng.randint(max(dsy) + 1, 30)
+        for c, l in zip(dsy, complete_code(k, rng, rng.choice((5, 7, 9, 12, 15)))):
+            dl[c] = l
+    return ll, dl
+
+
+SPOILS = ("hlit_288", "hdist_32", "single_distance_code_of_length_5")
+
+
+def random_stream(seed, nblocks, tokens_per_block, spoil=None):
+    """-> Case: nblocks random crafted blocks (see random_block_lengths, tokens_for), half of the streams behind a fixed block that
+    moves the first header off the byte boundary.  spoil = (k, one of SPOILS): block k's header is one a decoder must reject although
+    everything in the block can be decoded -- the counts raised over 286 / 30 with zero lengths, or a distance set (unused: the block
+    has literals only) of one 5-bit code; the blocks in front of it are those of the unspoiled stream"""
+    rng = random.Random(seed)
+    w, out, blocks = Bits(), bytearray(), []
+    if rng.random() < 0.5:
+        out += emit_fixed_prefix(w, rng.randrange(8))
+    for k in range(nblocks):
+        ll, dl = random_block_lengths(rng)
+        if spoil and spoil[0] == k and spoil[1] == "single_distance_code_of_length_5":
+            dl = [0] * len(dl)
+        toks = tokens_for(rng, ll, dl, tokens_per_block, len(out))
+        if spoil and spoil[0] == k:
+            if spoil[1] == "hlit_288":
+                ll = ll + [0] * (288 - len(ll))
+            elif spoil[1] == "hdist_32":
+                dl = dl + [0] * (32 - len(dl))
+            else:
+                dl[len(dl) // 2] = 5
+        kw = {}
+        if rng.random() < 0.15:                        # a code-length code of all 19 symbols, up to 7 bits
+            kw["cl_lens"] = complete_code(19, rng, 7)
+        blocks.append(emit_block(w, ll, dl, toks, k == nblocks - 1, rle=rng.random() < 0.6, **kw))
+        assert apply_tokens(out, toks) is not None
+    if spoil:
+        return Case("random_%d %s in block %d" % (seed, spoil[1], spoil[0]), w, None, E_BAD_TREE, blocks)
+    return Case("random_%d" % seed, w, out, OK, blocks)
+
+
+def _alternating(offset, rng):
+    """six blocks, a 286-symbol 15-bit tree and a two-symbol tree in turn, the first header at bit `offset` of its byte"""
+    w, out, blocks = Bits(), bytearray(), []
+    if offset:
+        out += emit_fixed_prefix(w, PREFIX_FOR_OFFSET[offset])
+    assert w.pos & 7 == offset
+    for k in range(6):
+        if k % 2 == 0:
+            ll, dl = complete_code(286, rng, 15), complete_code(30, rng, 15)
+        else:
+            ll, dl = sparse(257, {97 + k: 1, 256: 1}), [0]
+        toks = tokens_for(rng, ll, dl, 40, len(out))
+        blocks.append(emit_block(w, ll, dl, toks, k == 5, rle=k != 2))
+        apply_tokens(out, toks)
+    assert blocks[0]["offset"] == offset
+    return Case("alternating_offset%d" % offset, w, out, OK, blocks)
+
+
+def catalogue():
+    """-> [Case]: the named headers, valid (status OK, .plain) and rejected (.status)"""
+    rng = random.Random(20261019)
+    cs = []
+    # ---- valid
+    ll, dl = sorted(complete_code(286, rng, 15)), sorted(complete_code(30, rng, 15))
+    ll, dl = ll[100:] + ll[:100], dl[7:] + dl[:7]          # (runs of equal lengths, so that the run-length form has something to do)
+    toks = all_symbols_tokens()
+    cs.append(one_block("all_symbols_rle", ll, dl, toks, rle=True))
+    cs.append(one_block("all_symbols_plain", ll, dl, toks, rle=False))
+    assert cs[0].blocks[0]["rle"] and not cs[1].blocks[0]["rle"] and cs[0].plain == cs[1].plain and len(cs[0].plain) < 65536 - 16
+    cs.append(one_block("eob_only", sparse(257, {256: 1}), [0], []))
+    small = sparse(260, {97: 2, 98: 3, 99: 3, 256: 3, 257: 3, 258: 3, 259: 3})
+    assert kraft(small) == 1 << 15
+    for c in (0, 3, 29):
+        lits = [97 + (k * k) % 3 for k in range(DBASE[c] + 5)]
+        far = DBASE[c] + (1 << DEXTRA[c]) - 1
+        toks = lits + [(3, DBASE[c]), 98, (5, DBASE[c] + 1 if DEXTRA[c] else DBASE[c]), (4, min(far, len(lits) + 9)), 99, (5, DBASE[c])]
+        cs.append(one_block("one_distance_code_at_%d" % c, small, sparse(c + 1, {c: 1}), toks))
+    b = one_block("repeat16_crosses", sparse(260, {97: 2, 98: 2, 256: 3, 257: 3, 258: 3, 259: 3}), [3] * 8,
+                  [97, 98, 97, 97, (3, 2), (4, 1), 98, (5, 7), (5, 5), (3, 16)], prefix_offset=5)
+    assert b.blocks[0]["cross"] and (16, 3) in rle_ops(sparse(260, {97: 2, 98: 2, 256: 3, 257: 3, 258: 3, 259: 3}) + [3] * 8)
+    cs.append(b)
+    b = one_block("repeat18_crosses", sparse(270, {97: 2, 98: 2, 256: 2, 257: 2}), sparse(13, {12: 1}),
+                  [97 + (k & 1) * (k % 3 == 0) for k in range(70)] + [(3, 65), 98, (3, 70)], prefix_offset=3)
+    assert b.blocks[0]["cross"]
+    cs.append(b)
+    ll, dl = random_block_lengths(random.Random(7), count=40, max_len=9, dist_kind="several")
+    ops = rle_ops(ll + dl)
+    freq = {}
+    for op in ops:
+        freq[op_sym(op)] = freq.get(op_sym(op), 0) + 1
+    cl = [0] * 19                                          # all 19 symbols coded, the most frequent with the LONGEST codes
+    for s, l in zip(sorted(range(19), key=lambda s: (-freq.get(s, 0), s)), sorted(complete_code(19, rng, 7), reverse=True)):
+        cl[s] = l
+    b = one_block("code_length_code_7_bits", ll, dl, tokens_for(random.Random(8), ll, dl, 60, 0), ops=ops, cl_lens=cl, hclen=19)
+    assert b.blocks[0]["max_cl"] == 7 and min(cl) > 0
+    cs.append(b)
+    # HCLEN = 5 -- 16, 17, 18, 0, 8 -- is the least that gives any symbol a length: 256 codes of 8 bits
+    b = one_block("hclen_smallest", [8] * 255 + [0, 8], [0], [k * 3 & 255 if k * 3 & 255 != 255 else 1 for k in range(50)],
+                  cl_lens=sparse(19, {8: 1, 0: 2, 16: 3, 18: 3}), prefix_offset=7)
+    assert b.blocks[0]["hclen"] == 5
+    cs.append(b)
+    flat = [8] * 226 + [9] * 60
+    assert kraft(flat) == 1 << 15
+    dl = [4, 4] + [5] * 28
+    cs.append(one_block("flat_8_9", flat, dl, tokens_for(random.Random(9), flat, dl, 80, 0), prefix_offset=1))
+    for n in (143, 144, 145, 286):
+        r = random.Random(n)
+        ll, dl = random_block_lengths(r, count=n, max_len=15, dist_kind="several")
+        b = one_block("coded_%d" % n, ll, dl, tokens_for(r, ll, dl, 120, 0), prefix_offset=(n % 7) + 1)
+        assert b.blocks[0]["ncoded"] == n
+        cs.append(b)
+    for offset in range(8):
+        cs.append(_alternating(offset, rng))
+    # ---- rejected in the header: HDLZ_E_BAD_TREE
+    good, gd = sparse(258, {97: 1, 256: 2, 257: 2}), [1, 1]
+
+    def bad(name, ll=good, dl=gd, status=E_BAD_TREE, toks=(), **kw):
+        cs.append(one_block(name, ll, dl, list(toks), status=status, **kw))
+    bad("first_op_is_16", ops=[(16, 0)] + (good + gd)[3:], cl_lens=sparse(19, {0: 1, 1: 2, 2: 3, 16: 3}))
+    bad("repeat_overruns", ops=(good + gd)[:-2] + [(16, 0)], cl_lens=sparse(19, {0: 1, 1: 2, 2: 3, 16: 3}))
+    bad("repeat18_overruns", ops=(good + gd)[:-2] + [(18, 0)], cl_lens=sparse(19, {0: 1, 1: 2, 2: 3, 18: 3}))
+    bad("no_end_of_block", ll=sparse(258, {97: 1, 98: 2, 257: 2}))
+    bad("literals_oversubscribed", ll=sparse(258, {97: 1, 256: 1, 257: 1}))
+    bad("literals_incomplete_two_codes", ll=sparse(258, {97: 2, 256: 2}))
+    bad("literals_incomplete_2_2_2_15", ll=sparse(258, {97: 2, 98: 2, 256: 2, 257: 15}))
+    bad("distances_oversubscribed", dl=[1, 1, 1])
+    bad("distances_incomplete_two_codes", dl=[2, 2])
+    bad("distances_30_of_5_bits", dl=[5] * 30)
+    bad("single_distance_code_of_length_5", dl=[0, 0, 5])
+    bad("single_distance_code_of_length_2_at_0", dl=[2])
+    bad("end_of_block_only_length_3", ll=sparse(257, {256: 3}), dl=[0])
+    bad("end_of_block_only_length_15", ll=sparse(257, {256: 15}), dl=[0])
+    bad("code_length_code_incomplete", cl_lens=sparse(19, {0: 2, 1: 2, 2: 2}), rle=False)
+    bad("code_length_code_oversubscribed", cl_lens=sparse(19, {0: 1, 1: 1, 2: 1}), rle=False)
+    bad("hlit_287", ll=good + [0] * 29)
+    bad("hlit_288", ll=good + [0] * 30)
+    bad("hdist_31", dl=gd + [0] * 29)
+    bad("hdist_32", dl=gd + [0] * 30)
+    # ---- rejected in the block body
+    w = Bits()
+    b = emit_block(w, small, [1], [97, 98, 99], True, eob=False)
+    w.code(canonical(small)[257])
+    w.put(1, 1)                                            # the unused code of the one-code distance set
+    w.code(canonical(small)[256])
+    cs.append(Case("unused_code_of_one_distance_code", w, None, E_BAD_SYMBOL, [b]))
+    w = Bits()
+    b = emit_block(w, sparse(257, {256: 1}), [0], [], True, eob=False)
+    w.put(1, 1)                                            # the unused code of the one-code literal/length set
+    w.put(0, 1)
+    cs.append(Case("unused_code_of_one_literal_code", w, None, E_BAD_SYMBOL, [b]))
+    bad("distance_before_the_start", ll=small, dl=[2, 2, 2, 2], status=E_BAD_DISTANCE, toks=[97, 98, (3, 3)])
+    assert len(set(c.name for c in cs)) == len(cs)
+    return cs
+
+
+def truncations(case):
+    """the stream cut at every byte length from 5 up to (not including) its own"""
+    return [case.z[:n] for n in range(5, len(case.z))]
+
+
+def header_flips(z, spans, rng, k):
+    """k copies of z, each with one bit flipped inside a block header (spans: the headers' bit ranges in z)"""
+    out = []
+    for _ in range(k):
+        a, b = spans[rng.randrange(len(spans))]
+        bit = rng.randrange(a, b)
+        m = bytearray(z)
+        m[bit >> 3] ^= 1 << (bit & 7)
+        out.append(bytes(m))
+    return out
+
+
+def random_small(n=300):
+    """the n small random streams of the suite: 1 to 4 blocks of 40 tokens"""
+    return [random_stream(1000 + s, 1 + s % 4, 40) for s in range(n)]
+
+
+TRUNCATED = ("repeat18_crosses", "code_length_code_7_bits")     # the small valid streams that are cut at every byte
+
+
+@functools.lru_cache(None)
+def suite():
+    """what both test files run, built once per process -> dict: catalogue [Case], random [Case] (300 small streams), cuts [bytes] (the
+    TRUNCATED streams at every length: stock zlib gives no verdict on a cut stream, so only the oracle judges them), flips [bytes]
+    (three header flips of each of 40 random streams)"""
+    cat, rnd = catalogue(), random_small()
+    by_name = dict((c.name, c) for c in cat)
+    rng = random.Random(40)
+    flips = [m for c in rnd[3::7][:40] for m in header_flips(c.z, c.spans, rng, 3)]
+    assert len(flips) == 120
+    return dict(catalogue=cat, random=rnd, cuts=[z for n in TRUNCATED for z in truncations(by_name[n])], flips=flips)
+
+
+@functools.lru_cache(None)
+def large():
+    """the streams of the whole-GPU test -> [(label, stream, plain or None)]: six random streams of 40 blocks x 1500 tokens, the
+    all-symbols catalogue stream, eight header flips of each, and three of the random streams with a spoiled header in the middle"""
+    valid = [random_stream(7000 + k, 40, 1500) for k in range(6)] + [suite()["catalogue"][0]]
+    rng = random.Random(41)
+    out = [(c.name, c.z, c.plain) for c in valid]
+    for k, kind in enumerate(SPOILS):
+        c = random_stream(7000 + k, 40, 1500, spoil=(17 + k, kind))
+        out.append((c.name, c.z, None))
+    for c in valid:
+        out += [("%s flip %d" % (c.name, k), m, None) for k, m in enumerate(header_flips(c.z, c.spans, rng, 8))]
+    return out

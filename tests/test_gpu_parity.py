@@ -606,6 +606,9 @@ def test_inflate_host_pipelined(engine, oracle):
     pitch = 608
     ref, rl, rs = oracle.inflate_batch(flat, off.astype(np.uint64), pitch, flags=0, nthreads=8)
     m = np.arange(pitch)[None, :] < rl[:, None]
+    # stream 2619: the flipped bit leaves a distance set of ONE code whose length is not 1 -- zlib's "invalid distances set", BAD_TREE
+    # here since an incomplete set is only taken as one code of length 1 (it used to pass the header and end as BAD_SYMBOL in the body)
+    assert rs[2619] == oracle.E_BAD_TREE and rl[2619] == 0
     for chunk, d2h in ((1000, "copy"), (896, "kernel"), (5000, "copy"), (None, "kernel"), (1000, "kernel")):
         # (d2h = "kernel": the rows reach pinned host memory through hdlz_compact_batch / k_compact_host -- ADVICE r4)
         h_out, h_len, h_st = engine.inflate_host(h_z, torch.from_numpy(off), pitch, chunk_streams=chunk, d2h=d2h)
