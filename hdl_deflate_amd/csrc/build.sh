@@ -14,6 +14,12 @@ fi
 if [ "${1:-}" = "keys" ]; then
   HDLZ_VARIANT=keys HDLZ_DEFS="-DHDLZ_SEARCH_KEYS" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
 fi
+# `build.sh alllive` builds lib/libhdlz_alllive.so: the one-tile kernel that skips neither a constant bit plane nor the extension,
+# parse and chain of a match-free tile (tests/test_gpu_dead_work.py runs its blocks through both forms; tools/ab.sh and
+# tools/probe_dead_work.py time them against each other)
+if [ "${1:-}" = "alllive" ]; then
+  HDLZ_VARIANT=alllive HDLZ_DEFS="-DHDLZ_PLANES_ALL_LIVE -DHDLZ_NO_LITERAL_TILE" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
+fi
 # `build.sh crcbank` builds lib/libhdlz_crcbank.so: the CRC-32 tile kernels with the bank-private table layout (hdlz_crc32.h;
 # tools/probe_gzip.py times and counts it against the sliced tables)
 if [ "${1:-}" = "crcbank" ]; then

@@ -3,7 +3,8 @@
 // Replaces the reference's compress FSM (/root/reference/deflate.py:734-1082 + :407-515 +
 // :535-567) with a data-parallel formulation.  Rule names R0..R9 are SURVEY.md 8(a)'s.
 //
-// Mapping: persistent single-wave workgroups; a wave takes blocks blockIdx.x, +gridDim.x, ... and
+// Mapping: persistent single-wave workgroups; a wave takes blocks blockIdx.x, +gridDim.x, ... (the one-tile
+// kernels with the bit search: one column further in every row of the grid, see next_block) and
 // walks each block in tiles of 2048 positions; lane l owns the RUN of 32 consecutive positions
 // [32l, 32l+32) of the tile.  Per tile:
 //   1. tile + 256-byte look-back halo + 16-byte look-ahead staged in LDS (coalesced 16-B loads)
@@ -149,8 +150,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
         lds_dma16(t + 1024u, lut_base + 1024u);
     };
 
+    // Which blocks a wave takes: block w of every row of gridDim.x blocks (the plain stride).  BITS: the column moves on by one per row --
+    // wave w takes block k G + (w + k) mod G of row k, a bijection in every row.  With the plain stride a wave of a batch whose kinds of
+    // data alternate with a period that divides the grid (the bench's four families) compresses ONE kind, and since a tile's time now
+    // depends on its data (dead planes, match-free tiles) the waves' lifetimes differ by the factor the kinds do: measured, the work that
+    // the fast kinds save then does not shorten the launch (profiles/dead_work.txt: -0.9 % with the plain stride, -11 % with the blocks
+    // in random order).  With the moving column every wave meets every kind.  (-DHDLZ_STRIDE_PLAIN: off; the -DHDLZ_TILE_TIMING build keeps
+    // the plain stride, its report lives in the out_len of the wave's own column.)
+#if defined(HDLZ_STRIDE_PLAIN) || defined(HDLZ_TILE_TIMING)
+    constexpr bool MOVING_COLUMN = false;
+#else
+    constexpr bool MOVING_COLUMN = BITS;
+#endif
+    [[maybe_unused]] uint64_t row0 = 0;
+    [[maybe_unused]] uint32_t col = blockIdx.x;
+    auto next_block = [&](uint64_t& blk) {
+        if constexpr (MOVING_COLUMN) {
+            row0 += gridDim.x;
+            col = col + 1u == gridDim.x ? 0u : col + 1u;
+            blk = row0 + col;
+        } else blk += gridDim.x;
+    };
     TT_DECL();
-    for (uint64_t blk = blockIdx.x; blk < a.nblocks; blk += gridDim.x) {
+    for (uint64_t blk = blockIdx.x; blk < a.nblocks; next_block(blk)) {
         const uint8_t* src;
         uint32_t n;
         const uint32_t bst = block_params(blk, src, n);
@@ -205,6 +227,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             const uint32_t nrem = n - min(p_run, n);                  // positions of the block from p_run on
             uint32_t best[RUN], tok[RUN], code[RUN];
             [[maybe_unused]] uint32_t oww[12];                    // BITS: the own bytes, in registers from here to the extension
+            // BITS: false = no position of the tile has a match candidate (match_search_bits): every token is a literal, whatever the
+            // extension, the parse and the skip chain would compute -- they do not run (wave-uniform; every other kernel: constant true)
+            [[maybe_unused]] bool any = true;
+            [[maybe_unused]] uint32_t planes[7];                  // BITS: the search's result as bit planes (search_result_bytes -> best[])
             if constexpr (BITS) {
                 load_own(lds.in, run_dw, oww);                    // `in` is dead from here on: every lane's reads have returned before
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the search writes the first row of NEQ over it
@@ -225,7 +251,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             }
 #ifndef HDLZ_SEARCH_KEYS                                                                           // (-DHDLZ_SEARCH_KEYS: the key form, for A/B)
             else if constexpr (BITS)                                                               // 2. R3/R4 (a one-tile block: bit planes, history by DPP)
-                match_search_bits<true>(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], best, lds.neq + lane);
+                any = match_search_bits<true>(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], planes, lds.neq + lane);
 #endif
             else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                    // 2. R3/R4 (a one-tile block: candidate keys by DPP)
             {
@@ -252,8 +278,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 else __builtin_amdgcn_s_setprio(HDLZ_HP_EXTEND);
                 HDLZ_MARK("extend");
                 if constexpr (BITS) {
-                    wave_lds_order();                             // (every lane's rows are written)
-                    make_tokens_bits<FULLWIN>(lds.neq, lane, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5, from NEQ
+                    if (any) {
+                        search_result_bytes(planes, best);
+                        wave_lds_order();                         // (every lane's rows are written)
+                        make_tokens_bits<FULLWIN>(lds.neq, lane, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5, from NEQ
+                    } else {
+                        literal_tokens(ow, tok);
+                        // nothing here reads NEQ, so nothing waits for the search's row stores: they must have been performed before
+                        // the LUT's LDS-DMA and the zeroing of the bit buffer reuse that memory (normal path: implied by the reads)
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        wave_lds_order();
+                    }
                 } else
                 make_tokens<NCH, FULLWIN, true>(lds.in, HALO + lane * RUN, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5
             }
@@ -268,10 +303,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             }
             if constexpr (HASH) __builtin_amdgcn_s_setprio(HDLZ_HP_REST);
             HDLZ_MARK("parse");
-            const uint64_t P = run_transfer(tok);                                                  // 4. greedy parse
-            TT(5);
-            HDLZ_MARK("chain");
-            uint32_t myskip = chain_skips(P, lane, skip_in);          // (skip_in: carried into the next tile)
+            uint32_t myskip = 0;                                  // (a match-free tile: every run function is "-> 0", every entry skip 0)
+            if (!BITS || any) {
+                const uint64_t P = run_transfer(tok);                                              // 4. greedy parse
+                TT(5);
+                HDLZ_MARK("chain");
+                myskip = chain_skips(P, lane, skip_in);           // (skip_in: carried into the next tile)
+            }
             pin(tok); asm volatile("" : "+v"(myskip));
             PHASE_FENCE();
             TT(6);
@@ -388,7 +426,8 @@ hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
         return launch_compress_small(a, stream, ncu);
     // (round 5: 256 waves queued per CU instead of 64 -- a wave's blocks all belong to one family when the families alternate with a
     //  period that divides the grid, and waves of different families differ 3x in their run time (profiles/r05_tile_timing.txt); the
-    //  shorter a wave lives, the shorter the tail in which the GPU drains: 4.585 -> 4.475 ms on configs[1], 128: 4.515, 512: 4.475, 1024: 4.51)
+    //  shorter a wave lives, the shorter the tail in which the GPU drains: 4.585 -> 4.475 ms on configs[1], 128: 4.515, 512: 4.475, 1024: 4.51;
+    //  the one-tile kernels with the bit search have since moved to a column that advances with the row -- next_block in k_compress)
     uint64_t g = (uint64_t)ncu * 256u;
     if (g > a.nblocks) g = a.nblocks;
     const dim3 grid((unsigned)g), block(64);

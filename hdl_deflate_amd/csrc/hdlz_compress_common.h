@@ -343,27 +343,68 @@ __device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uin
 // (x0 .. x7: the lane's own 32 bytes as dwords, in registers)
 // KEEP: neq_d of every distance goes to neq_col[(d & 31) * 64] (neq_col = NEQ + lane: one ds_write_b32 at a fixed address register +
 // immediate offset, where neq is complete and before the DPP for nx) -- what make_tokens_bits reads instead of comparing bytes again
+// WORK THE DATA DOES NOT NEED is skipped by wave-uniform branches (the result is the same bit for bit):
+//   a DEAD PLANE  O_b is the same word s = 0 or 0xFFFFFFFF in all 64 lanes (bit 7 of ASCII text; three planes of decimal digits; seven of
+//           '0' / '1' text): then P_b = s and every candidate word C_b = s, so the plane adds nothing to any neq.  The planes are the
+//           OUTER loop -- the 32 mismatch words accumulate in registers, plane 0 starts them -- and a plane b >= 1 is tested first (one
+//           v_readfirstlane, one compare + ballot) and its 31 v_alignbit + 32 v_bitop3 jumped over; P_b is fetched inside the live
+//           branch.  A second pass over the distances does what follows neq: row store, n3, D, G.  (-DHDLZ_PLANES_ALL_LIVE: no test.)
+//   a MATCH-FREE TILE  G is all ones in every lane (random, compressed or encrypted bytes): every result byte would be 0xFF and every
+//           token a literal.  The function returns false; the kernel then does not transpose the result, forms the literal tokens
+//           itself and runs neither the extension nor the parse nor the skip chain.  Lane 0's false history and lane 63's zero bits
+//           32, 33 can only CLEAR bits of G: such a tile takes the normal path, which rejects them.  (-DHDLZ_NO_LITERAL_TILE: always true.)
+constexpr bool skip_dead_planes() {
+#ifdef HDLZ_PLANES_ALL_LIVE
+    return false;
+#else
+    return true;
+#endif
+}
+constexpr bool literal_tiles() {
+#ifdef HDLZ_NO_LITERAL_TILE
+    return false;
+#else
+    return true;
+#endif
+}
+// R: the result as planes -- R[0] = G, R[1 + k] = D_k; search_result_bytes() turns them into best[], inside the branch that reads it (as
+// one function with a branch of its own around the transposition, best[] was live across both arms of the extension's branch: 26 spills)
+// returns: some position of the tile has a candidate
 template <bool KEEP>
-__device__ __forceinline__ void match_search_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t x5, uint32_t x6,
-                                                  uint32_t x7, uint32_t (&best)[RUN], [[maybe_unused]] uint32_t* neq_col = nullptr) {
-    uint32_t O[8], P[8];
+__device__ __forceinline__ bool match_search_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t x5, uint32_t x6,
+                                                  uint32_t x7, uint32_t (&R)[7], [[maybe_unused]] uint32_t* neq_col = nullptr) {
+    uint32_t O[8];
     // O[k] byte m = own byte k + 8 m (k = 0..7): bytes k, k + 8, k + 16, k + 24 are byte k & 3 of dwords k >> 2, +2, +4, +6
     transpose4x4_bytes(x0, x2, x4, x6, O[0], O[1], O[2], O[3]);
     transpose4x4_bytes(x1, x3, x5, x7, O[4], O[5], O[6], O[7]);
     exchange8(O);                                             // O[b] bit i = bit b of own byte i
-#pragma unroll
-    for (int b = 0; b < 8; b++) P[b] = (uint32_t)__builtin_amdgcn_mov_dpp((int)O[b], 0x13C, 0xF, 0xF, false);      // wave_ror:1
-    pin(O); pin(P);
+    pin(O);
     PHASE_FENCE();
+    uint32_t nq[RUN];                                         // nq[d - 1] = neq_d, over the planes seen so far
+    static_for<0, 8>([&](auto B) {
+        constexpr int b = decltype(B)::value;
+        bool live = true;
+        if constexpr (b != 0 && skip_dead_planes()) {
+            const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)O[b]);
+            live = !((s0 == 0u || s0 == 0xFFFFFFFFu) && ballot64(O[b] != s0) == 0ull);
+        }
+        if (live) {
+            const uint32_t Pb = (uint32_t)__builtin_amdgcn_mov_dpp((int)O[b], 0x13C, 0xF, 0xF, false);                // wave_ror:1
+            static_for<1, RUN + 1>([&](auto Dd) {
+                constexpr int d = decltype(Dd)::value;
+                const uint32_t c = d == 32 ? Pb : __builtin_amdgcn_alignbit(O[b], Pb, (uint32_t)(32 - d));
+                if constexpr (b == 0) nq[d - 1] = O[0] ^ c;
+                else nq[d - 1] = bitop3<B3_OR_XOR>(nq[d - 1], O[b], c);
+                if constexpr ((d & 3) == 0) { pin_range<d - 4, d>(nq); PHASE_FENCE(); }       // (else hipcc hoists the alignbits of all distances)
+            });
+        }
+        pin(nq);
+        PHASE_FENCE();
+    });
     uint32_t G = 0xFFFFFFFFu, D[6] = {0, 0, 0, 0, 0, 0};
     static_for<1, RUN + 1>([&](auto Dd) {
         constexpr int d = decltype(Dd)::value;
-        uint32_t neq = 0;
-        static_for<0, 8>([&](auto B) {
-            constexpr int b = decltype(B)::value;
-            const uint32_t c = d == 32 ? P[b] : __builtin_amdgcn_alignbit(O[b], P[b], (uint32_t)(32 - d));
-            neq = b == 0 ? O[0] ^ c : bitop3<B3_OR_XOR>(neq, O[b], c);
-        });
+        const uint32_t neq = nq[d - 1];
         if constexpr (KEEP) neq_col[(d & (NEQ_ROWS - 1)) * 64] = neq;
         const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)neq, 0x130, 0xF, 0xF, true);                      // wave_shl:1 (lane 63: 0)
         const uint32_t n3 = bitop3<B3_OR3>(neq, __builtin_amdgcn_alignbit(nx, neq, 1u), __builtin_amdgcn_alignbit(nx, neq, 2u));
@@ -372,10 +413,19 @@ __device__ __forceinline__ void match_search_bits(uint32_t x0, uint32_t x1, uint
             if constexpr ((d >> k) & 1) D[k] = bitop3<B3_OR_ANDN>(D[k], G, n3);
         });
         G &= n3;
-        if constexpr ((d & 3) == 0) { pin(D); asm volatile("" : "+v"(G)); PHASE_FENCE(); }     // (else hipcc hoists the alignbits of all distances)
+        if constexpr ((d & 3) == 0) { pin(D); asm volatile("" : "+v"(G)); PHASE_FENCE(); }
     });
+    R[0] = G;
+#pragma unroll
+    for (int k = 0; k < 6; k++) R[k + 1] = D[k];
+    if constexpr (literal_tiles()) return ballot64(G != 0xFFFFFFFFu) != 0ull;
+    else return true;
+}
+// the search's result planes -> best[] (not for a match-free tile: nothing would read it)
+__device__ __forceinline__ void search_result_bytes(const uint32_t (&R)[7], uint32_t (&best)[RUN]) {
     // planes of the result byte: bits 0, 1 = none, bits 2..7 = d | none
-    uint32_t Q[8] = {G, G, D[0] | G, D[1] | G, D[2] | G, D[3] | G, D[4] | G, D[5] | G};
+    const uint32_t G = R[0];
+    uint32_t Q[8] = {G, G, R[1] | G, R[2] | G, R[3] | G, R[4] | G, R[5] | G, R[6] | G};
     exchange8(Q);                                             // Q[k] byte m = result byte of own position k + 8 m
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -744,6 +794,17 @@ __device__ __forceinline__ void make_tokens(const uint32_t* in, uint32_t lds_run
 // Lane 0's bits j < d compare against lane 63's bytes (the search's rotate): a position i of lane 0 is eligible only for d <= i, and its
 // bits j >= i + 3 > d look at the block's own bytes.  12 VALU instructions per position (13 for i >= 23) against 22, one or two
 // conflict-free ds_read_b32 (bank = column, whatever the row) against three gathered dwords.
+// token word of the literal at own position I: the LUT offset 4 * byte (upper half 0: length 1)
+template <int I>
+__device__ __forceinline__ uint32_t literal_token(const uint32_t (&ow)[12]) {
+    constexpr int bsh = 8 * (I & 3);
+    if constexpr (bsh == 0) return (ow[I >> 2] << 2) & 0x3FCu;
+    else return (ow[I >> 2] >> (bsh - 2)) & 0x3FCu;
+}
+// a match-free tile (match_search_bits returned false): every token is its literal
+__device__ __forceinline__ void literal_tokens(const uint32_t (&ow)[12], uint32_t (&tok)[RUN]) {
+    static_for<0, RUN>([&](auto I) { tok[decltype(I)::value] = literal_token<decltype(I)::value>(ow); });
+}
 template <bool FULLWIN>
 __device__ __forceinline__ void make_tokens_bits(const uint32_t* neq, uint32_t lane, uint32_t (&ow)[12], uint32_t (&best)[RUN], uint32_t cw4,
                                                  uint32_t kmax, uint32_t p4_run, uint32_t nrem, uint32_t (&tok)[RUN], int32_t tile_rem) {
@@ -774,10 +835,7 @@ __device__ __forceinline__ void make_tokens_bits(const uint32_t* neq, uint32_t l
         uint32_t z;                                              // v_ffbl_b32(0) = 0xFFFFFFFF: "no difference in sight"
         asm("v_ffbl_b32 %0, %1" : "=v"(z) : "v"(x));             // (asm: hipcc turns ffs()-1 + min into a compare and a select)
         const uint32_t l3 = umin3(z, kmax_m3, nrem_m5 - (uint32_t)i);
-        constexpr int bsh = 8 * (i & 3);                         // literal byte -> LUT offset 4*byte
-        uint32_t lit;
-        if constexpr (bsh == 0) lit = (ow[i >> 2] << 2) & 0x3FCu;
-        else lit = (ow[i >> 2] >> (bsh - 2)) & 0x3FCu;
+        const uint32_t lit = literal_token<i>(ow);
         uint32_t mt;     // l3 * tok_mul + d4 + tok_k  (hipcc folds the C form into a quarter-rate v_mul_lo_u32)
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(mt) : "v"(l3), "s"(tok_mul), "v"(d4 + tok_k));
         asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(tok[i]) : "v"(lit), "v"(mt), "s"(okm));      // tok = ok ? mt : lit
