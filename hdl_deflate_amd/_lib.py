@@ -86,6 +86,15 @@ BGZF_RANGE_SIGNATURES = {
 }
 BGZF_RANGE_EXPORTS = tuple(BGZF_RANGE_SIGNATURES)
 BGZF_RANGE_VIRTUAL = 1
+# ... and of include/hdlz_bgzf_stored.h: the BGZF writer that falls back to a stored member (tests/test_bgzf_stored_cabi.py)
+BGZF_STORED_SIGNATURES = {
+    "hdlz_bgzf_stored_bound": (sz, [u64, u32]),
+    "hdlz_bgzf_join_stored_work_bytes": (sz, [u64]),
+    # d_in, d_in_off, in_pitch, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file, file_cap, d_off, d_kind, d_result,
+    # d_work, work_bytes, stream
+    "hdlz_bgzf_join_stored_ws": (ci, [vp, vp, u64, u32, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, sz, vp]),
+}
+BGZF_STORED_EXPORTS = tuple(BGZF_STORED_SIGNATURES)
 _lib = None
 
 
@@ -118,6 +127,11 @@ class UnjoinGzipResult(ctypes.Structure):
 class BgzfJoinResult(ctypes.Structure):
     """hdlz_bgzf_join_result: the result record of hdlz_bgzf_join_ws (16 bytes)"""
     _fields_ = [("file_len", u64), ("status", u32), ("first_bad", u32)]
+
+
+class BgzfStoredResult(ctypes.Structure):
+    """hdlz_bgzf_stored_result: the result record of hdlz_bgzf_join_stored_ws (24 bytes)"""
+    _fields_ = [("file_len", u64), ("nstored", u64), ("status", u32), ("first_bad", u32)]
 
 
 class BgzfIndexResult(ctypes.Structure):
@@ -154,7 +168,7 @@ def load():
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
-            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()):
+            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

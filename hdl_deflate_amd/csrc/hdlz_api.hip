@@ -612,6 +612,34 @@ int hdlz_bgzf_join_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t*
     return HDLZ_OK;
 }
 
+// ---- include/hdlz_bgzf_stored.h: the BGZF writer that falls back to a stored member
+size_t hdlz_bgzf_stored_bound(uint64_t nblocks, uint32_t in_len) {
+    const size_t fixed = hdlz_out_bound(in_len) + 20u, stored = (size_t)in_len + 31u;
+    return 28u + (size_t)nblocks * (fixed < stored ? fixed : stored);
+}
+
+size_t hdlz_bgzf_join_stored_work_bytes(uint64_t nblocks) { return hdlz_join_work_bytes(nblocks); }
+
+int hdlz_bgzf_join_stored_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len, const uint8_t* d_rows,
+                             uint64_t row_pitch, const uint32_t* d_len, const uint32_t* d_status, uint64_t nblocks, const uint32_t* d_crc,
+                             uint8_t* d_file, uint64_t file_cap, uint64_t* d_off, uint8_t* d_kind, hdlz_bgzf_stored_result* d_result,
+                             void* d_work, size_t work_bytes, void* stream) {
+    if (!d_file || !d_off || !d_result || (nblocks && (!d_in || !d_rows || !d_len || !d_status || !d_crc))) return fail_param("null device pointer");
+    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");
+    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks)))
+        return fail_param("d_work smaller than hdlz_bgzf_join_stored_work_bytes(nblocks)");
+    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_in_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return fail_param("d_off / d_in_off / d_result must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
+    int rc = check_device();
+    if (rc != HDLZ_OK) return rc;
+    const hipError_t e = hdlz::launch_bgzf_join_stored(d_in, d_in_off, in_pitch, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file,
+                                                       file_cap, d_off, d_kind, d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_join_stored");
+    return HDLZ_OK;
+}
+
 size_t hdlz_bgzf_index_work_bytes(uint64_t file_len) { return hdlz::bgzf_index_work_bytes(file_len); }
 
 int hdlz_bgzf_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off,

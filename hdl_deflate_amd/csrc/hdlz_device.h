@@ -5,6 +5,7 @@
 #include <type_traits>
 #include <utility>
 #include "../../include/hdlz_bgzf_range.h"   // (includes hdlz_bgzf.h, hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
+#include "../../include/hdlz_bgzf_stored.h"
 
 namespace hdlz {
 
@@ -210,6 +211,13 @@ hipError_t launch_join_gzip(const uint8_t* rows, uint64_t pitch, const uint32_t*
 hipError_t launch_bgzf_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint32_t* status, const uint64_t* in_off,
                             uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* file, uint64_t cap, uint64_t* off,
                             hdlz_bgzf_join_result* result, void* work, hipStream_t stream);
+
+// hdlz_bgzf_stored.hip: ... -> a BGZF file whose members are fixed or stored, whichever is shorter (hdlz_bgzf_join_stored_ws): a kernel
+// of its own on the same scratch; `in` ...: the input as the compress call was given it; `kind`: nullable, one byte per block
+hipError_t launch_bgzf_join_stored(const uint8_t* in, const uint64_t* in_off, uint64_t in_pitch, uint32_t in_len, const uint8_t* rows,
+                                   uint64_t pitch, const uint32_t* len, const uint32_t* status, uint64_t nblocks, const uint32_t* crc,
+                                   uint8_t* file, uint64_t cap, uint64_t* off, uint8_t* kind, hdlz_bgzf_stored_result* result, void* work,
+                                   hipStream_t stream);
 
 // hdlz_bgzf.hip: the CRC-32 of every block of a batch (`skip`: nullable, per block: a status that is not HDLZ_OK leaves the block
 // unread and its word unwritten), the member index of a BGZF file, and what runs around the member decode of hdlz_bgzf_inflate_ws

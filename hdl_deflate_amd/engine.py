@@ -286,7 +286,7 @@ class Engine(object):
         return out
 
     @_on_device
-    def compress_bgzf(self, d_in, block=57344, cwindow=32, maxmatch=10, out=None):
+    def compress_bgzf(self, d_in, block=57344, cwindow=32, maxmatch=10, out=None, stored=False):
         """d_in: flat uint8 device tensor -> file uint8[file_len], a BGZF file (the blocked gzip of htslib and bgzip) that gzip -d,
         Python's gzip and every htslib tool read back as d_in, and that carries its own member index (bgzf_index).  The input is cut
         into blocks of `block` bytes (chain.plan_blocks), the CRC-32 of every block is taken (crc32_batch), the blocks are compressed
@@ -294,13 +294,20 @@ class Engine(object):
         block must be in [32, 65536]; a member holds at most 64 KiB, which blocks of up to 58230 bytes always fit -- a larger block of
         bytes that do not compress fails with E_OUT_CAPACITY.  An empty input gives the 28-byte file (the EOF member alone); inputs of
         1 to 4 bytes raise as compress_joined does.  One host sync (the result record); raises HdlzStatusError -- with .first_bad --
-        on a status that is not OK.  `out`: the file's buffer (default: hdlz_bgzf_bound(B, block) bytes)."""
+        on a status that is not OK.  `out`: the file's buffer (default: hdlz_bgzf_bound(B, block) bytes).
+        stored=True (include/hdlz_bgzf_stored.h): a block whose fixed-Huffman member would be longer than the block stored verbatim is
+        written as a stored member (hdlz_bgzf_join_stored_ws), so no member exceeds its block by more than 31 bytes and no block fails
+        for its content.  block must then be in [32, 65505] -- 65280 is the block size of bgzip and htslib --, inputs of 1 to 4 bytes
+        give a valid file of two members, and the default `out` is hdlz_bgzf_stored_bound(B, block) bytes.  The blocks and the rows
+        are the same either way, so an input whose blocks all compress gives the same file with and without it."""
         from .chain import plan_blocks
         assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.dim() == 1 and d_in.is_contiguous() and d_in.device == self.device
+        if stored and not 32 <= block <= 65505:
+            raise ValueError("block must be in [32, 65505]: a stored BGZF member holds at most 65505 bytes")
         if not 32 <= block <= 65536:
             raise ValueError("block must be in [32, 65536]: a BGZF member holds at most 64 KiB")
         n, dev = d_in.numel(), d_in.device
-        plan = plan_blocks(n, block) if n else []
+        plan = [(0, n)] if stored and 0 < n < 5 else plan_blocks(n, block) if n else []      # (below 5 bytes the compressor never starts)
         B = len(plan)
         if n:
             slack = d_in.untyped_storage().nbytes() - d_in.storage_offset() - n
@@ -310,16 +317,28 @@ class Engine(object):
         pitch = pitch_for(block)
         rows, out_len, status = self._results(None, (B, pitch), B, dev)
         if out is None:
-            out = torch.empty(self.lib.hdlz_bgzf_bound(B, block), dtype=torch.uint8, device=dev)
+            out = torch.empty((self.lib.hdlz_bgzf_stored_bound if stored else self.lib.hdlz_bgzf_bound)(B, block), dtype=torch.uint8, device=dev)
         assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
         offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        result = torch.empty(2, dtype=torch.int64, device=dev)                     # hdlz_bgzf_join_result: 16 bytes
+        result = torch.empty(3 if stored else 2, dtype=torch.int64, device=dev)    # hdlz_bgzf_stored_result: 24 bytes; hdlz_bgzf_join_result: 16
         work = torch.empty(max(8, self.lib.hdlz_bgzf_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)
         crc = self.crc32_batch(d_in[:n], offsets=in_off)
         if B:
             rc = self.lib.hdlz_compress_batch(d_in.data_ptr(), in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
                                               out_len.data_ptr(), status.data_ptr(), self._stream())
             self._check(rc, "hdlz_compress_batch")
+        if stored:
+            rc = self.lib.hdlz_bgzf_join_stored_ws(d_in.data_ptr() if B else None, in_off.data_ptr(), 0, block, rows.data_ptr() if B else None, pitch,
+                                                   out_len.data_ptr() if B else None, status.data_ptr() if B else None, B,
+                                                   crc.data_ptr() if B else None, out.data_ptr(), out.numel(), offsets.data_ptr(), None,
+                                                   result.data_ptr(), work.data_ptr() if B else None, work.numel() * 8 if B else 0, self._stream())
+            self._check(rc, "hdlz_bgzf_join_stored_ws")
+            rec = _lib.BgzfStoredResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+            if rec.status != OK:
+                err = HdlzStatusError(rec.status, "compress_bgzf")
+                err.first_bad = rec.first_bad
+                raise err
+            return out[:rec.file_len]
         rc = self.lib.hdlz_bgzf_join_ws(rows.data_ptr() if B else None, pitch, out_len.data_ptr() if B else None,
                                         status.data_ptr() if B else None, in_off.data_ptr(), block, B, crc.data_ptr() if B else None,
                                         out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
@@ -403,10 +422,10 @@ class Engine(object):
             raise err
         return out[:rec.out_len]
 
-    def compress_bgzf_bytes(self, data, block=57344, cwindow=32, maxmatch=10):
+    def compress_bgzf_bytes(self, data, block=57344, cwindow=32, maxmatch=10, stored=False):
         """host bytes -> the bytes of a BGZF file (compress_bgzf)"""
         d = self._stage(data)[:len(data)]
-        return bytes(self.compress_bgzf(d, block=block, cwindow=cwindow, maxmatch=maxmatch).cpu().numpy().tobytes())
+        return bytes(self.compress_bgzf(d, block=block, cwindow=cwindow, maxmatch=maxmatch, stored=stored).cpu().numpy().tobytes())
 
     def inflate_bgzf_bytes(self, z):
         """the bytes of a BGZF file -> (status, bytes): nothing but the file is needed -- no offsets, no block size, no capacity"""

@@ -17,8 +17,8 @@
  * subfield and nothing else -- what bgzip, htslib and this writer make; MTIME, XFL and OS may be anything.  Any other header is
  * HDLZ_E_BAD_HEADER.  The writer emits MTIME = 0, XFL = 0, OS = FF and closes the file with the standard 28-byte EOF member
  *   1F 8B 08 04 00 00 00 00 00 FF 06 00 42 43 02 00 1B 00 03 00 00 00 00 00 00 00 00 00
- * Out of scope: .gzi index files, headers with other extra subfields, a stored-block fallback for incompressible blocks, the lane and
- * group mappings in the reader, the whole-GPU chains, the port adapter.
+ * Out of scope: .gzi index files, headers with other extra subfields, a stored-block fallback for incompressible blocks (taken up by
+ * hdlz_bgzf_stored.h), the lane and group mappings in the reader, the whole-GPU chains, the port adapter.
  */
 #ifndef HDLZ_BGZF_H
 #define HDLZ_BGZF_H
