@@ -20,6 +20,12 @@ fi
 if [ "${1:-}" = "alllive" ]; then
   HDLZ_VARIANT=alllive HDLZ_DEFS="-DHDLZ_PLANES_ALL_LIVE -DHDLZ_NO_LITERAL_TILE" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
 fi
+# `build.sh dword` builds lib/libhdlz_dword.so: the one-tile kernel whose extension extracts the search's result bytes into registers
+# and uses plain operands instead of the sub-dword (SDWA) forms (tests/test_gpu_wave_groups.py runs its blocks through both;
+# tools/ab.sh times them against each other)
+if [ "${1:-}" = "dword" ]; then
+  HDLZ_VARIANT=dword HDLZ_DEFS="-DHDLZ_EXT_SDWA=0" HDLZ_ONLY="hdlz_compress" exec "${BASH_SOURCE[0]}"
+fi
 # `build.sh crcbank` builds lib/libhdlz_crcbank.so: the CRC-32 tile kernels with the bank-private table layout (hdlz_crc32.h;
 # tools/probe_gzip.py times and counts it against the sliced tables)
 if [ "${1:-}" = "crcbank" ]; then

@@ -19,8 +19,9 @@
 //      per compare, no branches (-DHDLZ_SEARCH_KEYS: the one-tile kernels too, for A/B).
 //   3. extension (R5): 8-byte LDS gather at p-d+3, xor with the own bytes, count-trailing-zeros.  The one-tile kernels with the bit
 //      search compare nothing again: the search keeps its mismatch word of every distance in LDS (NEQ[d & 31][lane], WaveLdsBits), and
-//      the length is the run of zero bits from bit i + 3 of the chosen distance's word (make_tokens_bits: one or two conflict-free
-//      ds_read_b32 and 12 VALU instructions per position).  NEQ is the wave's whole LDS: it overlays the staged tile (the own bytes of
+//      the length is the run of zero bits from bit i + 3 of the chosen distance's word (make_tokens_bits_packed: one or two conflict-free
+//      ds_read_b32 and 10 VALU instructions per position; the block's end is a bit of those words, the search's result bytes are read
+//      in place by sub-dword operands).  NEQ is the wave's whole LDS: it overlays the staged tile (the own bytes of
 //      the search, the Adler sums and the literals stay in registers), and behind the extension the bit buffer and the LUT -- a constant
 //      table, fetched per tile by LDS-DMA under the parse -- take its place.
 //   4. greedy parse ("di += m / di += 1", deflate.py:960,1008): every lane folds its run into a
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             }
 #ifndef HDLZ_SEARCH_KEYS                                                                           // (-DHDLZ_SEARCH_KEYS: the key form, for A/B)
             else if constexpr (BITS)                                                               // 2. R3/R4 (a one-tile block: bit planes, history by DPP)
-                any = match_search_bits<true>(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], planes, lds.neq + lane);
+                any = match_search_bits<true>(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], planes, lds.neq + lane, end_cap_word((int32_t)(n - t0) - 2, lane * (uint32_t)RUN));
 #endif
             else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                    // 2. R3/R4 (a one-tile block: candidate keys by DPP)
             {
@@ -279,9 +280,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 HDLZ_MARK("extend");
                 if constexpr (BITS) {
                     if (any) {
+#if HDLZ_EXT_SDWA
+                        uint32_t Q[8];                            // the result bytes, four to a register: read in place (sub-dword operands)
+                        search_result_packed(planes, Q);
+                        wave_lds_order();                         // (every lane's rows are written)
+                        make_tokens_bits_packed<FULLWIN>(lds.neq, lane, ow, Q, cw4, kmax, tok, (int32_t)(n - t0));   // 3. R5, from NEQ
+#else
                         search_result_bytes(planes, best);
                         wave_lds_order();                         // (every lane's rows are written)
-                        make_tokens_bits<FULLWIN>(lds.neq, lane, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5, from NEQ
+                        make_tokens_bits<FULLWIN>(lds.neq, lane, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), tok, (int32_t)(n - t0));   // 3. R5, from NEQ
+#endif
                     } else {
                         literal_tokens(ow, tok);
                         // nothing here reads NEQ, so nothing waits for the search's row stores: they must have been performed before
@@ -406,8 +414,8 @@ template __global__ void k_compress<8, false, false, true>(CompressArgs);
 
 hipError_t launch_compress(const CompressArgs& a, hipStream_t stream) {
     if (a.nblocks == 0) return hipSuccess;
-    // persistent single-wave workgroups: 256 per CU queued (20 resident at 5 waves/SIMD) so that the
-    // hardware dispatcher balances uneven blocks; each wave strides over the batch
+    // persistent single-wave workgroups: 256 per CU queued (resident: 5 waves/SIMD by the registers; with 8192 bytes of LDS per wave, 18
+    // per CU -- profiles/wave_groups.txt) so that the hardware dispatcher balances uneven blocks; each wave strides over the batch
     // (the CU count is cached per DEVICE: a process may drive several GPUs)
     static int ncu_of[64] = {0};
     int dev = 0;

@@ -51,7 +51,10 @@ static_assert(sizeof(WaveLds) >= GATHER_SPAN, "make_tokens: masked gather inside
 // the word of the position's distance back (column = lane: bank = lane, conflict-free whatever the rows) instead of gathering and
 // comparing bytes.  d = 32 aliases row 0 (no distance 0 exists); "none" (result byte 0xFF) reads row 31, inside the array, and is discarded.
 // The LDS timeline of a tile:   stage: in | own bytes -> registers | search: NEQ | extend: NEQ | fixed LUT -> lut (LDS-DMA), zero: out |
-// parse, chain | codes: lut | scatter, flush: out.   NEQ is the whole LDS budget of a wave (8192 bytes: 20 waves per CU), so the staged
+// parse, chain | codes: lut | scatter, flush: out.   NEQ is the whole LDS budget of a wave (8192 bytes.  A CU holds 18 such waves, not the 20 its
+// registers allow: the LDS of a workgroup is granted in steps of 1280 bytes, 8192 occupy 8960 and 18 x 8960 fill the 160 KB.  7680 bytes
+// would give 20; workgroups of five or ten waves, whose LDS is a whole number of steps, hold 12 and 10 -- tools/ubench/wave_launch.hip,
+// profiles/wave_groups.txt), so the staged
 // tile in front of the search and the bit buffer + the LUT behind the extension share its memory.
 constexpr int NEQ_ROWS = 32;                              // row = d & 31
 constexpr int NEQ_WORDS = NEQ_ROWS * 64;                  // [row][lane]
@@ -77,7 +80,7 @@ struct __attribute__((aligned(16))) WaveLdsBits {
 // make_tokens_bits reads byte (d4 & 0x7C) * 64 + 4 * column, d4 = 4 d (d = 1 .. 32) or 0xFF, column = lane or min(lane + 1, 63)
 static_assert((0x7C << 6) + 4 * 63 + 4 <= 4 * NEQ_WORDS && ((0xFF & 0x7C) << 6) == 4 * 64 * 31, "every read of the extension inside NEQ; none -> row 31");
 static_assert(((4 * 32) & 0x7C) == 0 && (31 * 64 + 63) < NEQ_WORDS, "d = 32 aliases row 0; the search's last row ends inside NEQ");
-static_assert(sizeof(WaveLdsBits) == 8192 && 4 * NEQ_WORDS >= IN_BYTES, "20 waves per CU; the staged tile inside the block");
+static_assert(sizeof(WaveLdsBits) == 8192 && 4 * NEQ_WORDS >= IN_BYTES, "seven allocation steps of 1280 bytes: 18 waves per CU; the staged tile inside the block");
 static_assert(offsetof(WaveLdsBits, lut) >= 4 * OUT_WORDS && offsetof(WaveLdsBits, lut) % 16 == 0 && 4 * FIXED_LUT_WORDS == 2 * 64 * 16,
               "zero_bit_buffer leaves the LUT alone; the LUT is two 16-byte LDS-DMA requests per lane");
 
@@ -352,7 +355,8 @@ __device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uin
 //   a MATCH-FREE TILE  G is all ones in every lane (random, compressed or encrypted bytes): every result byte would be 0xFF and every
 //           token a literal.  The function returns false; the kernel then does not transpose the result, forms the literal tokens
 //           itself and runs neither the extension nor the parse nor the skip chain.  Lane 0's false history and lane 63's zero bits
-//           32, 33 can only CLEAR bits of G: such a tile takes the normal path, which rejects them.  (-DHDLZ_NO_LITERAL_TILE: always true.)
+//           32, 33 can only CLEAR bits of G: such a tile takes the normal path, which rejects them.  A short block is no exception: the
+//           end cap (below) keeps the zero bytes behind its end from matching each other.  (-DHDLZ_NO_LITERAL_TILE: always true.)
 constexpr bool skip_dead_planes() {
 #ifdef HDLZ_PLANES_ALL_LIVE
     return false;
@@ -367,12 +371,23 @@ constexpr bool literal_tiles() {
     return true;
 #endif
 }
+// THE END OF THE BLOCK is part of the mismatch words: E (end_cap_word) has bit j set for every position j of the run at or behind N - 2 and is
+// OR-ed into every neq_d with plane 0's xor.  Read from bit i + 3 on, such a word shows a difference at bit N - 2 - p_run at the latest,
+// that is after at most N - 5 - p equal bytes: R5's "a match ends at N - 2" needs no minimum of its own in make_tokens_bits.  Nothing
+// else changes: the forced bits reach n3 only at positions >= N - 4, which R3 never makes eligible (make_tokens_bits' okm rejects them), and
+// they only SET bits of G -- the zero bytes behind the end no longer match each other at distance 1, so a short block without a
+// candidate is a match-free tile like a full one.
 // R: the result as planes -- R[0] = G, R[1 + k] = D_k; search_result_bytes() turns them into best[], inside the branch that reads it (as
 // one function with a branch of its own around the transposition, best[] was live across both arms of the extension's branch: 26 spills)
 // returns: some position of the tile has a candidate
+// bit j = position p_run + j lies at or behind N - 2: the bits from N - 2 - p_run on, all of them when that is <= 0, none when it is >= 32
+__device__ __forceinline__ uint32_t end_cap_word(int32_t n_m2, uint32_t p_run) {
+    const int32_t first = min(max(n_m2 - (int32_t)p_run, 0), 32);      // (v_med3_i32)
+    return (uint32_t)(~0ull << first);
+}
 template <bool KEEP>
 __device__ __forceinline__ bool match_search_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, uint32_t x5, uint32_t x6,
-                                                  uint32_t x7, uint32_t (&R)[7], [[maybe_unused]] uint32_t* neq_col = nullptr) {
+                                                  uint32_t x7, uint32_t (&R)[7], [[maybe_unused]] uint32_t* neq_col = nullptr, uint32_t E = 0u) {
     uint32_t O[8];
     // O[k] byte m = own byte k + 8 m (k = 0..7): bytes k, k + 8, k + 16, k + 24 are byte k & 3 of dwords k >> 2, +2, +4, +6
     transpose4x4_bytes(x0, x2, x4, x6, O[0], O[1], O[2], O[3]);
@@ -393,7 +408,7 @@ __device__ __forceinline__ bool match_search_bits(uint32_t x0, uint32_t x1, uint
             static_for<1, RUN + 1>([&](auto Dd) {
                 constexpr int d = decltype(Dd)::value;
                 const uint32_t c = d == 32 ? Pb : __builtin_amdgcn_alignbit(O[b], Pb, (uint32_t)(32 - d));
-                if constexpr (b == 0) nq[d - 1] = O[0] ^ c;
+                if constexpr (b == 0) nq[d - 1] = bitop3<B3_OR_XOR>(E, O[0], c);        // (the end cap rides along: as cheap as the xor)
                 else nq[d - 1] = bitop3<B3_OR_XOR>(nq[d - 1], O[b], c);
                 if constexpr ((d & 3) == 0) { pin_range<d - 4, d>(nq); PHASE_FENCE(); }       // (else hipcc hoists the alignbits of all distances)
             });
@@ -421,12 +436,19 @@ __device__ __forceinline__ bool match_search_bits(uint32_t x0, uint32_t x1, uint
     if constexpr (literal_tiles()) return ballot64(G != 0xFFFFFFFFu) != 0ull;
     else return true;
 }
-// the search's result planes -> best[] (not for a match-free tile: nothing would read it)
-__device__ __forceinline__ void search_result_bytes(const uint32_t (&R)[7], uint32_t (&best)[RUN]) {
+// the search's result planes -> Q[k] byte m = result byte of own position k + 8 m (not for a match-free tile: nothing would read it)
+__device__ __forceinline__ void search_result_packed(const uint32_t (&R)[7], uint32_t (&Q)[8]) {
     // planes of the result byte: bits 0, 1 = none, bits 2..7 = d | none
     const uint32_t G = R[0];
-    uint32_t Q[8] = {G, G, R[1] | G, R[2] | G, R[3] | G, R[4] | G, R[5] | G, R[6] | G};
-    exchange8(Q);                                             // Q[k] byte m = result byte of own position k + 8 m
+    Q[0] = G; Q[1] = G;
+#pragma unroll
+    for (int k = 2; k < 8; k++) Q[k] = R[k - 1] | G;
+    exchange8(Q);
+}
+// ... -> best[], one register per position
+__device__ __forceinline__ void search_result_bytes(const uint32_t (&R)[7], uint32_t (&best)[RUN]) {
+    uint32_t Q[8];
+    search_result_packed(R, Q);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         best[k] = Q[k] & 0xFFu;
@@ -788,11 +810,15 @@ __device__ __forceinline__ void make_tokens(const uint32_t* in, uint32_t lds_run
 //   word   NEQ[(d & 31) * 64 + l]: byte offset (d4 & 0x7C) << 6 + 4 l.  d = 32 reads row 0, "none" (0xFF) row 31 (discarded)
 //   i <= 22: bits i + 3 .. i + 9 lie in the lane's own word -- a plain shift (at most Kmax - 3 <= 7 bits count);  i = 23 .. 28: the
 //          next lane's word of the same row too, one v_alignbit;  i >= 29: bit i + 3 is bit i - 29 of the next lane's word -- that word
-//          alone, a plain shift.  Lane 63 has no next lane: it reads its own word in that place (col_hi = 4 * min(l + 1, 63)), and
-//          N - 5 - p <= 27 - i caps what those bits could add (i + 3 + 27 - i <= 31: inside the own word; i >= 28 is not eligible there)
-//   l3     min3(ffbl(x), Kmax - 3, N - 5 - p): v_ffbl_b32(0) = 0xFFFFFFFF needs no sentinel under the cap
+//          alone, a plain shift.  Lane 63 has no next lane: it reads its own word in that place (col_hi = 4 * min(l + 1, 63)); its own
+//          word has the end cap's bit at N - 2 - p_run <= 30, so the count stops inside the own word before those bits are reached
+//          (i >= 28 is not eligible there)
+//   l3     min(ffbl(x), Kmax - 3): v_ffbl_b32(0) = 0xFFFFFFFF needs no sentinel under the cap; the block's end is a set bit of the
+//          words themselves (end_cap_word: bit N - 2 - p_run of the lane that holds it, so ffbl(x) <= N - 5 - p wherever p is eligible;
+//          a lane whose word has no such bit has N - 2 - p_run >= 32 and N - 5 - p >= 7 >= Kmax - 3 for its i <= 22, and its i >= 23
+//          read on into the next lane's word, which carries the bit or leaves at least 7 again)
 // Lane 0's bits j < d compare against lane 63's bytes (the search's rotate): a position i of lane 0 is eligible only for d <= i, and its
-// bits j >= i + 3 > d look at the block's own bytes.  12 VALU instructions per position (13 for i >= 23) against 22, one or two
+// bits j >= i + 3 > d look at the block's own bytes.  11 VALU instructions per position (12 for i >= 23) against 22, one or two
 // conflict-free ds_read_b32 (bank = column, whatever the row) against three gathered dwords.
 // token word of the literal at own position I: the LUT offset 4 * byte (upper half 0: length 1)
 template <int I>
@@ -805,12 +831,108 @@ __device__ __forceinline__ uint32_t literal_token(const uint32_t (&ow)[12]) {
 __device__ __forceinline__ void literal_tokens(const uint32_t (&ow)[12], uint32_t (&tok)[RUN]) {
     static_for<0, RUN>([&](auto I) { tok[decltype(I)::value] = literal_token<decltype(I)::value>(ow); });
 }
+// SUB-DWORD OPERANDS (-DHDLZ_EXT_SDWA=0: off, for A/B).  The result byte of a position has three readers -- the eligibility compare, the row
+// mask and the token's distance term -- and the literal's LUT offset is one byte of the own bytes times four.  The SDWA forms of v_cmp,
+// v_and, v_add and v_lshlrev take a byte of a register as their operand.  Measured (tools/ubench/valu_cycles4.hip, profiles/
+// wave_groups.txt): the compare and the shift cost what their plain forms cost (3.1 / 3.25 cycles), v_and and v_add move from the 1.97- to
+// the 3.25-cycle class -- 2.6 cycles more per position, which is what the extract (v_bfe 3.25, v_and / v_lshr 1.97) cost: even in cycles,
+// one instruction and one live register per position less.  What the packed form GAINS comes with it: thresholds packed like the result
+// bytes (one v_add per four positions instead of one v_or each) and a literal that needs no mask in byte 0 either.  (Inline asm with whole-dword destinations: no instruction here writes part of a register,
+// which is the one SDWA case with a read-after-write rule of its own.)
+#ifndef HDLZ_EXT_SDWA
+#define HDLZ_EXT_SDWA 1
+#endif
+#define HDLZ_SDWA_SRC0_BYTE(op, M) op " %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_" #M " src1_sel:DWORD"
+template <int M> __device__ __forceinline__ uint32_t and_byte(uint32_t q, uint32_t s) {             // ((q >> 8 M) & 0xFF) & s
+    uint32_t r;
+    if constexpr (M == 0) asm(HDLZ_SDWA_SRC0_BYTE("v_and_b32_sdwa", 0) : "=v"(r) : "v"(q), "s"(s));
+    else if constexpr (M == 1) asm(HDLZ_SDWA_SRC0_BYTE("v_and_b32_sdwa", 1) : "=v"(r) : "v"(q), "s"(s));
+    else if constexpr (M == 2) asm(HDLZ_SDWA_SRC0_BYTE("v_and_b32_sdwa", 2) : "=v"(r) : "v"(q), "s"(s));
+    else asm(HDLZ_SDWA_SRC0_BYTE("v_and_b32_sdwa", 3) : "=v"(r) : "v"(q), "s"(s));
+    return r;
+}
+template <int M> __device__ __forceinline__ uint32_t add_byte(uint32_t q, uint32_t s) {             // ((q >> 8 M) & 0xFF) + s
+    uint32_t r;
+    if constexpr (M == 0) asm(HDLZ_SDWA_SRC0_BYTE("v_add_u32_sdwa", 0) : "=v"(r) : "v"(q), "s"(s));
+    else if constexpr (M == 1) asm(HDLZ_SDWA_SRC0_BYTE("v_add_u32_sdwa", 1) : "=v"(r) : "v"(q), "s"(s));
+    else if constexpr (M == 2) asm(HDLZ_SDWA_SRC0_BYTE("v_add_u32_sdwa", 2) : "=v"(r) : "v"(q), "s"(s));
+    else asm(HDLZ_SDWA_SRC0_BYTE("v_add_u32_sdwa", 3) : "=v"(r) : "v"(q), "s"(s));
+    return r;
+}
+#define HDLZ_SDWA_CMP_BYTE(M, S1) "v_cmp_le_u32_sdwa %0, %1, %2 src0_sel:BYTE_" #M " src1_sel:" S1
+template <int M, bool BOTH> __device__ __forceinline__ uint64_t le_byte(uint32_t q, uint32_t s) {   // lanes with byte M of q <= s (BOTH: <= byte M of s)
+    uint64_t r;
+    if constexpr (BOTH) {
+        if constexpr (M == 0) asm(HDLZ_SDWA_CMP_BYTE(0, "BYTE_0") : "=s"(r) : "v"(q), "v"(s));
+        else if constexpr (M == 1) asm(HDLZ_SDWA_CMP_BYTE(1, "BYTE_1") : "=s"(r) : "v"(q), "v"(s));
+        else if constexpr (M == 2) asm(HDLZ_SDWA_CMP_BYTE(2, "BYTE_2") : "=s"(r) : "v"(q), "v"(s));
+        else asm(HDLZ_SDWA_CMP_BYTE(3, "BYTE_3") : "=s"(r) : "v"(q), "v"(s));
+    } else {
+        if constexpr (M == 0) asm(HDLZ_SDWA_CMP_BYTE(0, "DWORD") : "=s"(r) : "v"(q), "s"(s));
+        else if constexpr (M == 1) asm(HDLZ_SDWA_CMP_BYTE(1, "DWORD") : "=s"(r) : "v"(q), "s"(s));
+        else if constexpr (M == 2) asm(HDLZ_SDWA_CMP_BYTE(2, "DWORD") : "=s"(r) : "v"(q), "s"(s));
+        else asm(HDLZ_SDWA_CMP_BYTE(3, "DWORD") : "=s"(r) : "v"(q), "s"(s));
+    }
+    return r;
+}
+#define HDLZ_SDWA_SHL_BYTE(M) "v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_" #M
+template <int M> __device__ __forceinline__ uint32_t shl_byte(uint32_t sh, uint32_t w) {            // ((w >> 8 M) & 0xFF) << sh
+    uint32_t r;
+    if constexpr (M == 0) asm(HDLZ_SDWA_SHL_BYTE(0) : "=v"(r) : "s"(sh), "v"(w));
+    else if constexpr (M == 1) asm(HDLZ_SDWA_SHL_BYTE(1) : "=v"(r) : "s"(sh), "v"(w));
+    else if constexpr (M == 2) asm(HDLZ_SDWA_SHL_BYTE(2) : "=v"(r) : "s"(sh), "v"(w));
+    else asm(HDLZ_SDWA_SHL_BYTE(3) : "=v"(r) : "s"(sh), "v"(w));
+    return r;
+}
+// make_tokens_bits on the packed result bytes (a ONE-TILE block: the tile starts at position 0).  Position i = k + 8 m reads byte m of
+// Q[k]; the positions are taken register by register (k outer) -- tok[] does not care about the order -- so that the eligibility
+// thresholds can be packed the same way: d4 <= 4 p is  d4 <= 4 i  in lane 0 and "d4 is a distance at all" (d4 <= 128 < 0xFF) in every
+// other lane, where ANY threshold in [128, 254] will do.  T_k byte m = 4 (k + 8 m) in lane 0, 0x80 + 32 m + 4 k elsewhere (at most 0xFC):
+// T_k = T_0 + 0x04040404 k without a carry between the bytes, one v_add per FOUR positions, compared byte against byte.
+template <bool FULLWIN>
+__device__ __forceinline__ void make_tokens_bits_packed(const uint32_t* neq, uint32_t lane, uint32_t (&ow)[12], uint32_t (&Q)[8], uint32_t cw4,
+                                                        uint32_t kmax, uint32_t (&tok)[RUN], int32_t tile_rem) {
+    pin(Q);
+    PHASE_FENCE();
+    const uint32_t kmax_m3 = min(kmax - 3u, 7u);              // (MAXMATCH is 5 or 10: the clamp keeps the single-word shift exact whatever comes in)
+    const int32_t rem5 = tile_rem - 5;                        // R3's "p <= N - 5" as lane masks: see make_tokens (SCALAR_TAIL)
+    const uint32_t thr = rem5 >= 0 ? ((uint32_t)rem5 & 31u) : 0u;
+    const int32_t cnt_hi = rem5 >= 0 ? (rem5 >> 5) + 1 : 0, cnt_lo = rem5 >= 0 ? (rem5 >> 5) : 0;
+    const uint64_t m_hi = cnt_hi >= 64 ? ~0ull : ((1ull << cnt_hi) - 1ull), m_lo = cnt_lo >= 64 ? ~0ull : ((1ull << cnt_lo) - 1ull);
+    const uint32_t tok_mul = 4u * 65536u + 128u;
+    const uint8_t* neq8 = reinterpret_cast<const uint8_t*>(neq);
+    const uint32_t col_lo = 4u * lane, dcol = min(252u - col_lo, 4u);                 // col_hi = col_lo + dcol = 4 * min(lane + 1, 63)
+    // the constant operands of the sub-dword forms live in SGPRs (they take no literal constant)
+    const uint32_t tok_k = sconst((2u << 18) + LUT_MATCH_BYTE - 4u), row_mask = sconst(0x7Cu), two = sconst(2u), cw4v = cw4;
+    uint32_t T = lane == 0u ? 0x60402000u : 0xE0C0A080u;
+    asm volatile("" : "+v"(T));
+    static_for<0, RUN>([&](auto J) {
+        constexpr int k = decltype(J)::value >> 2, m = decltype(J)::value & 3, i = k + 8 * m;
+        if constexpr (m == 0 && k != 0) T += 0x04040404u;
+        uint64_t okm = le_byte<m, true>(Q[k], T);
+        if constexpr (!FULLWIN) okm &= le_byte<m, false>(Q[k], cw4v);
+        okm &= ((uint32_t)i <= thr ? m_hi : m_lo);
+        uint32_t a0;     // ((d4 & 0x7C) << 6) + col_lo
+        asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(a0) : "v"(and_byte<m>(Q[k], row_mask)), "v"(col_lo));
+        uint32_t x;      // (next lane's word : own word) >> (i + 3)
+        if constexpr (i + 3 + 7 <= 32) x = *reinterpret_cast<const uint32_t*>(neq8 + a0) >> (i + 3);
+        else if constexpr (i + 3 >= 32) x = *reinterpret_cast<const uint32_t*>(neq8 + (a0 + dcol)) >> (i + 3 - 32);      // (v_alignbit shifts by 0 .. 31)
+        else x = __builtin_amdgcn_alignbit(*reinterpret_cast<const uint32_t*>(neq8 + (a0 + dcol)), *reinterpret_cast<const uint32_t*>(neq8 + a0), (uint32_t)(i + 3));
+        uint32_t z;
+        asm("v_ffbl_b32 %0, %1" : "=v"(z) : "v"(x));
+        const uint32_t l3 = min(z, kmax_m3);                     // (N - 5 - p: the end cap in the word)
+        const uint32_t lit = shl_byte<(i & 3)>(two, ow[i >> 2]); // the LUT offset 4 * byte
+        uint32_t mt;     // l3 * tok_mul + d4 + tok_k
+        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(mt) : "v"(l3), "s"(tok_mul), "v"(add_byte<m>(Q[k], tok_k)));
+        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(tok[i]) : "v"(lit), "v"(mt), "s"(okm));      // tok = ok ? mt : lit
+        if constexpr (m == 3) { asm volatile("" : "+v"(tok[k]), "+v"(tok[k + 8]), "+v"(tok[k + 16]), "+v"(tok[k + 24]), "+v"(T)); PHASE_FENCE(); }
+    });
+}
 template <bool FULLWIN>
 __device__ __forceinline__ void make_tokens_bits(const uint32_t* neq, uint32_t lane, uint32_t (&ow)[12], uint32_t (&best)[RUN], uint32_t cw4,
-                                                 uint32_t kmax, uint32_t p4_run, uint32_t nrem, uint32_t (&tok)[RUN], int32_t tile_rem) {
+                                                 uint32_t kmax, uint32_t p4_run, uint32_t (&tok)[RUN], int32_t tile_rem) {
     pin(best); pin_range<0, 8>(ow);
     PHASE_FENCE();
-    const uint32_t nrem_m5 = nrem - 5u;                       // (wraps when nrem < 5: then nothing is eligible)
     const uint32_t kmax_m3 = min(kmax - 3u, 7u);              // (MAXMATCH is 5 or 10: the clamp keeps the single-word shift exact whatever comes in)
     const int32_t rem5 = tile_rem - 5;                        // R3's "p <= N - 5" as lane masks: see make_tokens (SCALAR_TAIL)
     const uint32_t thr = rem5 >= 0 ? ((uint32_t)rem5 & 31u) : 0u;
@@ -834,7 +956,7 @@ __device__ __forceinline__ void make_tokens_bits(const uint32_t* neq, uint32_t l
         else x = __builtin_amdgcn_alignbit(*reinterpret_cast<const uint32_t*>(neq8 + (a0 + dcol)), *reinterpret_cast<const uint32_t*>(neq8 + a0), (uint32_t)(i + 3));
         uint32_t z;                                              // v_ffbl_b32(0) = 0xFFFFFFFF: "no difference in sight"
         asm("v_ffbl_b32 %0, %1" : "=v"(z) : "v"(x));             // (asm: hipcc turns ffs()-1 + min into a compare and a select)
-        const uint32_t l3 = umin3(z, kmax_m3, nrem_m5 - (uint32_t)i);
+        const uint32_t l3 = min(z, kmax_m3);                     // (N - 5 - p: the end cap in the word, see above)
         const uint32_t lit = literal_token<i>(ow);
         uint32_t mt;     // l3 * tok_mul + d4 + tok_k  (hipcc folds the C form into a quarter-rate v_mul_lo_u32)
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(mt) : "v"(l3), "s"(tok_mul), "v"(d4 + tok_k));
