@@ -210,8 +210,8 @@ int hdlz_join_batch_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t
     if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u)) return fail_param("d_off / d_result must be 8-byte aligned");
     int rc = check_device();
     if (rc != HDLZ_OK) return rc;
-    hipError_t e = hdlz::launch_join(d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off,
-                                     d_result, d_work, static_cast<hipStream_t>(stream));
+    const hdlz::JoinArgs a{d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off, d_result, {}};
+    hipError_t e = hdlz::launch_join(a, d_work, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(e, "launch k_join");
     return HDLZ_OK;
 }
@@ -570,8 +570,8 @@ int hdlz_join_gzip_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t*
     if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
     int rc = check_device();
     if (rc != HDLZ_OK) return rc;
-    hipError_t e = hdlz::launch_join_gzip(d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_crc, d_stream, stream_cap,
-                                          d_off, d_result, d_work, static_cast<hipStream_t>(stream));
+    const hdlz::JoinArgs a{d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off, nullptr, {}};
+    hipError_t e = hdlz::launch_join_gzip(a, d_crc, d_result, d_work, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(e, "launch k_join");
     return HDLZ_OK;
 }
@@ -606,9 +606,9 @@ int hdlz_bgzf_join_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t*
     if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
     int rc = check_device();
     if (rc != HDLZ_OK) return rc;
-    const hipError_t e = hdlz::launch_bgzf_join(d_rows, row_pitch, d_len, d_status, d_in_off, in_len, nblocks, d_crc, d_file, file_cap, d_off,
-                                                d_result, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_join<bgzf>");
+    const hdlz::BgzfJoinArgs a{nullptr, d_in_off, 0u, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file, file_cap, d_off, nullptr, {}};
+    const hipError_t e = hdlz::launch_bgzf_join(a, d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_join<fixed>");
     return HDLZ_OK;
 }
 
@@ -634,9 +634,9 @@ int hdlz_bgzf_join_stored_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint
     if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
     int rc = check_device();
     if (rc != HDLZ_OK) return rc;
-    const hipError_t e = hdlz::launch_bgzf_join_stored(d_in, d_in_off, in_pitch, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file,
-                                                       file_cap, d_off, d_kind, d_result, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_join_stored");
+    const hdlz::BgzfJoinArgs a{d_in, d_in_off, in_pitch, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file, file_cap, d_off, d_kind, {}};
+    const hipError_t e = hdlz::launch_bgzf_join_stored(a, d_result, d_work, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_join<stored>");
     return HDLZ_OK;
 }
 

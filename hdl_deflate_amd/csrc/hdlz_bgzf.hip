@@ -1,6 +1,7 @@
 // hdlz_bgzf.hip -- the kernels of include/hdlz_bgzf.h that are not another kernel's instance: the CRC-32 of every
 // block of a batch, the member index of a BGZF file, and what hdlz_bgzf_inflate_ws runs around the member decode.  (The writer is
-// k_join<true>, hdlz_join.hip; the decode is k_inflate_dyn<false, true>, hdlz_inflate_dyn.hip, through MemberArgs with m_gap = 18.)
+// k_bgzf_join, hdlz_bgzf_stored.hip; the decode is k_inflate_dyn<false, true>, hdlz_inflate_dyn.hip, through MemberArgs with m_gap = 18.
+// The format's constants, the header bytes and is_header stand in hdlz_frame.h.)
 //
 // k_crc32_batch     a workgroup per block: crc_block of hdlz_crc32.h (first tile right-aligned, Horner over the further tiles).
 // k_bgzf_scan       a workgroup per 64 KiB window: the first header-shaped 16 bytes, taken for a member start, and the hops from it
@@ -10,19 +11,22 @@
 //                   sums are scanned on the way.  Writes the record and the two arrays' last words.
 // k_bgzf_emit       a thread per confirmed window: hops again and writes d_off / d_out_off.
 // k_bgzf_check      a thread per member: the index checks of hdlz_bgzf_inflate_ws and the decoder's private offsets.
-// k_bgzf_judge / k_bgzf_finish   the verdict per member from the decoder's results, the CRC words and the trailer; the record --
-//                   the reduction of k_unjoin_judge / k_unjoin_finish (hdlz_unjoin.hip).
+// k_bgzf_judge / k_bgzf_finish   the verdict per member from the decoder's results, the CRC words and the trailer; the record.  The
+//                   lowest failed member travels as in hdlz_unjoin.hip: per workgroup into word 256 g, then lowest_word (hdlz_frame.h).
+// The member check (k_bgzf_check, and per task k_ranges_expand), the verdict (k_bgzf_judge, k_ranges_judge) and the step into word
+// 256 g (k_bgzf_judge, k_unjoin_judge) stand written out in each kernel: as functions of hdlz_frame.h they gave every one of these
+// kernels another instruction sequence (profiles/framing_shared.txt, section 3).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
 #include "hdlz_crc32.h"
+#include "hdlz_frame.h"
 
 namespace hdlz {
 namespace bgzf {
 
 constexpr uint32_t WIN_LOG2 = 16u, WIN = 1u << WIN_LOG2;
 constexpr uint64_t NONE64 = ~0ull;
-constexpr uint32_t JT = 256u;
 
 // ---- hdlz_crc32_batch_ws
 __global__ __launch_bounds__(CRC_THREADS) void k_crc32_batch(const uint8_t* __restrict__ data, const uint64_t* __restrict__ off, uint64_t pitch,
@@ -225,7 +229,7 @@ __global__ __launch_bounds__(JT) void k_bgzf_check(BgzfArgs a) {
 }
 
 // ---- behind the decode and the CRC words: one thread per member; per workgroup the lowest failed member, in the length word of the
-// workgroup's first member (as k_unjoin_judge leaves it)
+// workgroup's first member, which every thread has read by then
 __global__ __launch_bounds__(JT) void k_bgzf_judge(BgzfArgs a) {
     __shared__ uint32_t s_first[JT / 64u];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -257,9 +261,7 @@ __global__ __launch_bounds__(JT) void k_bgzf_judge(BgzfArgs a) {
 __global__ __launch_bounds__(256) void k_bgzf_finish(BgzfArgs a, uint32_t ngroups) {
     __shared__ uint32_t s_f[256];
     const uint32_t tid = threadIdx.x;
-    uint32_t f = NONE;
-    for (uint32_t g = tid; g < ngroups; g += 256u) f = min(f, a.len[(size_t)g * JT]);
-    s_f[tid] = f;
+    s_f[tid] = lowest_word(a.len, ngroups, tid, 256u);
     __syncthreads();
     for (uint32_t o = 128u; o > 0u; o >>= 1) {
         if (tid < o) s_f[tid] = min(s_f[tid], s_f[tid + o]);
@@ -299,19 +301,15 @@ hipError_t launch_bgzf_index(const uint8_t* file, uint64_t file_len, uint64_t me
         return hipGetLastError();
     }
     const IndexWork w = index_work(work, W);
-    hipLaunchKernelGGL(k_bgzf_scan, dim3((unsigned)W), dim3(256), 0, stream, file, file_len, w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bgzf_seam, dim3(1), dim3(64), 0, stream, file, file_len, W, member_cap, off, out_off, result, w);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bgzf_emit, dim3((unsigned)((W + 255u) / 256u)), dim3(256), 0, stream, file, W, member_cap, off, out_off, w);
-    return hipGetLastError();
+    hipError_t e = launch(k_bgzf_scan, dim3((unsigned)W), dim3(256), stream, file, file_len, w);
+    if (e == hipSuccess) e = launch(k_bgzf_seam, dim3(1), dim3(64), stream, file, file_len, W, member_cap, off, out_off, result, w);
+    if (e == hipSuccess) e = launch(k_bgzf_emit, dim3((unsigned)((W + 255u) / 256u)), dim3(256), stream, file, W, member_cap, off, out_off, w);
+    return e;
 }
 
 hipError_t launch_bgzf_check(const BgzfArgs& a, hipStream_t stream) {
     if (a.nmembers == 0) return hipSuccess;
-    hipLaunchKernelGGL(bgzf::k_bgzf_check, dim3((unsigned)((a.nmembers + bgzf::JT - 1u) / bgzf::JT)), dim3(bgzf::JT), 0, stream, a);
+    hipLaunchKernelGGL(bgzf::k_bgzf_check, dim3((unsigned)((a.nmembers + JT - 1u) / JT)), dim3(JT), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -9,13 +9,14 @@
 //                    member's file span and its destination -- d_out when the range covers it whole, else one of the range's two slots.
 // k_ranges_crc       a workgroup per task: crc_block of hdlz_crc32.h over the decoded member (k_crc32_batch with a pointer per block).
 // k_ranges_judge     a thread per task: the verdict of k_bgzf_judge; the lowest failed task of every range (atomicMin).
-// k_ranges_slice     a workgroup per slot: the delivered slice of an edge member, slot -> d_out.
+// k_ranges_slice     a workgroup per slot: the delivered slice of an edge member, slot -> d_out (copy_to_aligned16, hdlz_frame.h).
 // k_ranges_finish    a thread per range: its status; the lowest failed range (atomicMin).
 // k_ranges_record    one thread: the record.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
 #include "hdlz_crc32.h"
+#include "hdlz_frame.h"
 
 namespace hdlz {
 namespace bgzf {
@@ -190,8 +191,6 @@ __global__ __launch_bounds__(RT) void k_ranges_judge(RangeArgs a) {
 }
 
 __global__ __launch_bounds__(RT) void k_ranges_slice(RangeArgs a) {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-    typedef v4 __attribute__((aligned(1))) v4u;
     const uint32_t tid = threadIdx.x;
     for (uint64_t slot = blockIdx.x; slot < 2u * a.nranges; slot += gridDim.x) {
         const uint32_t t = a.r_edge[slot];
@@ -203,14 +202,7 @@ __global__ __launch_bounds__(RT) void k_ranges_slice(RangeArgs a) {
         if (s1 <= s0) continue;
         const uint8_t* __restrict__ src = a.slots + slot * SLOT + (s0 - o);
         uint8_t* __restrict__ dst = a.out + (a.range_off[r] + (s0 - p0));
-        const uint32_t n = (uint32_t)(s1 - s0);
-        uint32_t head = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
-        head = head < n ? head : n;
-        const uint32_t body = (n - head) >> 4, tail = head + 16u * body;
-        if (tid < head) dst[tid] = src[tid];
-        for (uint32_t i = tid; i < body; i += RT)
-            *reinterpret_cast<v4*>(dst + head + 16u * i) = *reinterpret_cast<const v4u*>(src + head + 16u * i);
-        if (tail + tid < n) dst[tail + tid] = src[tail + tid];
+        copy_to_aligned16(dst, src, (uint32_t)(s1 - s0), tid, RT);
     }
 }
 
@@ -274,37 +266,30 @@ RangeArgs bgzf_ranges_args(void* work, uint64_t R, uint64_t T) {
     return a;
 }
 
-#define HDLZ_RANGES_LAUNCH(kernel, grid, block)                                  \
-    do {                                                                         \
-        hipLaunchKernelGGL(bgzf::kernel, dim3(grid), dim3(block), 0, stream, a); \
-        const hipError_t e_ = hipGetLastError();                                 \
-        if (e_ != hipSuccess) return e_;                                         \
-    } while (0)
+static inline dim3 capped(uint64_t n) { return dim3((unsigned)(n < (1u << 20) ? n : (1u << 20))); }
+static inline dim3 groups_of(uint64_t n) { return dim3((unsigned)((n + bgzf::RT - 1u) / bgzf::RT)); }
 
 hipError_t launch_bgzf_ranges_plan(const RangeArgs& a, hipStream_t stream) {
     using namespace bgzf;
-    if (a.nranges == 0) {
-        hipLaunchKernelGGL(k_ranges_empty, dim3(1), dim3(1), 0, stream, a.range_off, a.result);
-        return hipGetLastError();
-    }
-    HDLZ_RANGES_LAUNCH(k_ranges_resolve, (unsigned)((a.nranges + RT - 1u) / RT), RT);
-    HDLZ_RANGES_LAUNCH(k_ranges_scan, 1, RT);
-    if (a.task_cap) HDLZ_RANGES_LAUNCH(k_ranges_expand, (unsigned)((a.task_cap + RT - 1u) / RT), RT);
-    return hipSuccess;
+    if (a.nranges == 0) return launch(k_ranges_empty, dim3(1), dim3(1), stream, a.range_off, a.result);
+    hipError_t e = launch(k_ranges_resolve, groups_of(a.nranges), dim3(RT), stream, a);
+    if (e == hipSuccess) e = launch(k_ranges_scan, dim3(1), dim3(RT), stream, a);
+    if (e == hipSuccess && a.task_cap) e = launch(k_ranges_expand, groups_of(a.task_cap), dim3(RT), stream, a);
+    return e;
 }
 
 hipError_t launch_bgzf_ranges_finish(const RangeArgs& a, hipStream_t stream) {
     using namespace bgzf;
     if (a.nranges == 0) return hipSuccess;
+    hipError_t e = hipSuccess;
     if (a.task_cap) {
-        HDLZ_RANGES_LAUNCH(k_ranges_crc, (unsigned)(a.task_cap < (1u << 20) ? a.task_cap : (1u << 20)), CRC_THREADS);
-        HDLZ_RANGES_LAUNCH(k_ranges_judge, (unsigned)((a.task_cap + RT - 1u) / RT), RT);
-        HDLZ_RANGES_LAUNCH(k_ranges_slice, (unsigned)(2u * a.nranges < (1u << 20) ? 2u * a.nranges : (1u << 20)), RT);
+        e = launch(k_ranges_crc, capped(a.task_cap), dim3(CRC_THREADS), stream, a);
+        if (e == hipSuccess) e = launch(k_ranges_judge, groups_of(a.task_cap), dim3(RT), stream, a);
+        if (e == hipSuccess) e = launch(k_ranges_slice, capped(2u * a.nranges), dim3(RT), stream, a);
     }
-    HDLZ_RANGES_LAUNCH(k_ranges_finish, (unsigned)((a.nranges + RT - 1u) / RT), RT);
-    HDLZ_RANGES_LAUNCH(k_ranges_record, 1, 1);
-    return hipSuccess;
+    if (e == hipSuccess) e = launch(k_ranges_finish, groups_of(a.nranges), dim3(RT), stream, a);
+    if (e == hipSuccess) e = launch(k_ranges_record, dim3(1), dim3(1), stream, a);
+    return e;
 }
-#undef HDLZ_RANGES_LAUNCH
 
 }  // namespace hdlz

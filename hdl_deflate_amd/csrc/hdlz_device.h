@@ -197,27 +197,54 @@ hipError_t launch_compact(const uint8_t* rows, uint64_t pitch, const uint32_t* l
 hipError_t launch_archive(const uint8_t* rows, uint64_t pitch, const uint32_t* len, uint64_t nblocks, uint8_t* archive, uint64_t cap,
                           uint64_t* off, hipStream_t stream, const Work& w);
 
-// hdlz_join.hip: the rows of hdlz_compress_batch_bits -> one zlib stream.  `work`: join_work_bytes(nblocks) bytes (null when that is 0).
+// The tile joins (hdlz_join.hip, hdlz_bgzf_stored.hip; hdlz_frame.h has their shared steps).  `work`: join_work_bytes(nblocks) bytes
+// (null when that is 0), carved into a JoinWork by the launcher; the entry point fills in the rest of the record.
+struct JoinWork {
+    uint32_t* ticket;            // ticket (+ pad), ...
+    unsigned long long* desc;    // ... one look-back word per tile, ...
+    uint32_t* part;              // ... PARTS words per tile
+};
 size_t join_work_bytes(uint64_t nblocks);
-hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
-                       const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, uint8_t* stream_out, uint64_t cap, uint64_t* off,
-                       hdlz_join_result* result, void* work, hipStream_t stream);
-// ... -> one gzip member (hdlz_join_gzip_ws): the same scratch; `crc`: the device word that holds CRC-32 of the input
-hipError_t launch_join_gzip(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
-                            const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* stream_out,
-                            uint64_t cap, uint64_t* off, hdlz_join_gzip_result* result, void* work, hipStream_t stream);
-
-// ... -> a BGZF file (hdlz_bgzf_join_ws): k_join's other instance, the same scratch; `crc`: one word per block
-hipError_t launch_bgzf_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint32_t* status, const uint64_t* in_off,
-                            uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* file, uint64_t cap, uint64_t* off,
-                            hdlz_bgzf_join_result* result, void* work, hipStream_t stream);
-
-// hdlz_bgzf_stored.hip: ... -> a BGZF file whose members are fixed or stored, whichever is shorter (hdlz_bgzf_join_stored_ws): a kernel
-// of its own on the same scratch; `in` ...: the input as the compress call was given it; `kind`: nullable, one byte per block
-hipError_t launch_bgzf_join_stored(const uint8_t* in, const uint64_t* in_off, uint64_t in_pitch, uint32_t in_len, const uint8_t* rows,
-                                   uint64_t pitch, const uint32_t* len, const uint32_t* status, uint64_t nblocks, const uint32_t* crc,
-                                   uint8_t* file, uint64_t cap, uint64_t* off, uint8_t* kind, hdlz_bgzf_stored_result* result, void* work,
-                                   hipStream_t stream);
+// the rows of hdlz_compress_batch_bits -> one zlib stream (hdlz_join_batch_ws) or one gzip member (hdlz_join_gzip_ws)
+struct JoinArgs {
+    const uint8_t* rows;
+    uint64_t pitch;
+    const uint32_t* len;
+    const uint64_t* end_bits;
+    const uint32_t* status;
+    const uint64_t* in_off;      // nullable: then every block has in_len bytes
+    uint32_t in_len;
+    uint64_t nblocks;
+    uint8_t* stream;
+    uint64_t cap;
+    uint64_t* off;
+    hdlz_join_result* result;    // the zlib form's record (the gzip form has its own)
+    JoinWork w;
+};
+hipError_t launch_join(JoinArgs a, void* work, hipStream_t stream);
+// `crc`: the device word that holds the CRC-32 of the input; a.stream / a.cap: the whole gzip stream
+hipError_t launch_join_gzip(JoinArgs a, const uint32_t* crc, hdlz_join_gzip_result* result, void* work, hipStream_t stream);
+// the rows of hdlz_compress_batch -> a BGZF file: every member the row's fixed block (hdlz_bgzf_join_ws), or fixed or stored, whichever
+// is shorter (hdlz_bgzf_join_stored_ws: `in` ... as the compress call was given them, `kind`)
+struct BgzfJoinArgs {
+    const uint8_t* in;           // the stored form only
+    const uint64_t* in_off;      // nullable: then block b is the in_len bytes at in + b * in_pitch
+    uint64_t in_pitch;           // the stored form only
+    uint32_t in_len;
+    const uint8_t* rows;
+    uint64_t pitch;
+    const uint32_t* len;
+    const uint32_t* status;
+    uint64_t nblocks;
+    const uint32_t* crc;         // the CRC-32 of every input block
+    uint8_t* file;
+    uint64_t cap;
+    uint64_t* off;
+    uint8_t* kind;               // nullable; the stored form only
+    JoinWork w;
+};
+hipError_t launch_bgzf_join(BgzfJoinArgs a, hdlz_bgzf_join_result* result, void* work, hipStream_t stream);
+hipError_t launch_bgzf_join_stored(BgzfJoinArgs a, hdlz_bgzf_stored_result* result, void* work, hipStream_t stream);
 
 // hdlz_bgzf.hip: the CRC-32 of every block of a batch (`skip`: nullable, per block: a status that is not HDLZ_OK leaves the block
 // unread and its word unwritten), the member index of a BGZF file, and what runs around the member decode of hdlz_bgzf_inflate_ws
@@ -245,19 +272,6 @@ struct BgzfArgs {
 };
 hipError_t launch_bgzf_check(const BgzfArgs& a, hipStream_t stream);
 hipError_t launch_bgzf_judge(const BgzfArgs& a, hipStream_t stream);
-
-// the format's constants and the header test, shared by hdlz_bgzf.hip and hdlz_bgzf_range.hip
-namespace bgzf {
-constexpr uint32_t HEAD = 18u, TAIL = 8u, MEMBER_MIN = HEAD + 2u + TAIL, MEMBER_MAX = 65536u, ISIZE_MAX = 65536u;
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t le32(const uint8_t* p) { return le16(p) | (le16(p + 2) << 16); }
-// the fixed bytes of a HEADER (MTIME, XFL and OS may be anything); the caller has checked that p[0 .. 18) lies inside the file
-__device__ __forceinline__ bool is_header(const uint8_t* p) {
-    return p[0] == 0x1Fu && p[1] == 0x8Bu && p[2] == 8u && p[3] == 4u && p[10] == 6u && p[11] == 0u && p[12] == 0x42u && p[13] == 0x43u &&
-           p[14] == 2u && p[15] == 0u;
-}
-}  // namespace bgzf
 
 // hdlz_bgzf_range.hip: hdlz_bgzf_read_ranges_ws (include/hdlz_bgzf_range.h).  The scratch, in this order -- every piece
 // a multiple of 256 bytes; R = nranges, T = task_cap:

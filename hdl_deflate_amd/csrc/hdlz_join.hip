@@ -8,12 +8,13 @@
 //     member = row[2 .. nbytes) with bit 0 of its first byte cleared, then 00 00 FF FF when p >= 3 (the stored block's three header
 //              bits fall inside the padding), else 00 00 00 FF FF
 //     stream = 78 9C, the members, 03 00 (a final empty fixed block), Adler-32 of the whole input, big-endian.
-// k_join is k_archive's pattern (hdlz_compact.hip; restated here, not shared: as a shared inline function the look-back changed
-// k_archive's instruction schedule): a workgroup takes a TILE of 256 consecutive rows by a ticket, scans the 256 member lengths,
-// publishes its sum as one 64-bit word {state, value} and finds its base by a decoupled look-back over the tiles in front of it; then
-// it writes the 256 offsets and copies its members, a wave per row, with 16-byte stores to 16-byte aligned destinations.  The same
-// pass reads every row's trailer and leaves the tile's three Adler sums and its worst status in the scratch; k_join_finish (one
-// workgroup) reduces them and writes the header, the final block, the checksum and the result record.
+// k_join is a tile join (hdlz_frame.h: tile_scan, tile_lookback, the scratch and launch_tile_join, shared with the BGZF writer of
+// hdlz_bgzf_stored.hip; k_archive of hdlz_compact.hip keeps a look-back of its own): a workgroup takes a TILE of 256
+// consecutive rows by a ticket, scans the 256 member lengths, publishes its sum as one 64-bit word {state, value} and finds its base
+// by a decoupled look-back over the tiles in front of it; then it writes the 256 offsets and copies its members, a wave per row, with
+// 16-byte stores to 16-byte aligned destinations (its own loop, not copy_to_aligned16: BFINAL is cleared and the marker appended on the
+// way).  The same pass reads every row's trailer and leaves the tile's three Adler sums and its worst status in the scratch;
+// k_join_finish (one workgroup) reduces them and writes the header, the final block, the checksum and the result record.
 //
 // The Adler-32 of the concatenation X (N bytes) from the blocks' own: with A_b = s1_b - 1 (the block's byte sum), n_b its length and e_b
 // its END offset in X, s2(X) = N + sum_p (N - p) x_p and N - p = (N - e_b) + (n_b - q) for byte q of block b, so (all mod 65521)
@@ -23,91 +24,30 @@
 #include <stdint.h>
 #include "hdlz_device.h"
 #include "hdlz_compress_common.h"                        // the framing constants: HEADER_WORD, HEADER_BITS, block_nbytes; hdlz_adler.h: ADLER_MOD
+#include "hdlz_frame.h"                                  // the tile's scan and look-back, the wave reductions, the scratch and the launch
 
 namespace hdlz {
 
-constexpr uint32_t JT = 256;                             // rows per tile
-constexpr uint64_t J_AGG = 1ull << 62, J_PFX = 2ull << 62, J_MASK = 3ull << 62;
-constexpr uint32_t PARTS = 4;                            // words a tile leaves for k_join_finish: sum A, sum e A, sum (s2 - n), worst status
 constexpr uint64_t STREAM_HEAD = 2;                      // 78 9C: the first member starts here
 constexpr uint32_t HEAD0 = HEADER_WORD & 0xFFu, HEAD1 = (HEADER_WORD >> 8) & 0xFFu;      // 78 9C
 constexpr uint32_t FINAL_EMPTY = HEADER_WORD >> 16;      // 03 (+ 00): BFINAL = 1, BTYPE = 01 and the seven zero bits of the end-of-block code
 constexpr uint32_t STREAM_TAIL = 6;                      // 03 00 + Adler-32
 
-struct JoinArgs {
-    const uint8_t* rows;
-    uint64_t pitch;
-    const uint32_t* len;
-    const uint64_t* end_bits;
-    const uint32_t* status;
-    const uint64_t* in_off;      // nullable: then every block has in_len bytes
-    uint32_t in_len;
-    uint64_t nblocks;
-    uint8_t* stream;
-    uint64_t cap;
-    uint64_t* off;
-    hdlz_join_result* result;
-    uint32_t* ticket;            // scratch: ticket (+ pad), ...
-    unsigned long long* desc;    // ... one look-back word per tile, ...
-    uint32_t* part;              // ... PARTS words per tile
-    const uint32_t* crc = nullptr;      // BGZF only: the CRC-32 of every input block
-};
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor(v, o, 64));
-    return v;
-}
-
-// BGZF = true (hdlz_bgzf_join_ws; include/hdlz_bgzf.h) is the same scan and gather for another member: the row's block
-// as it is (BFINAL stays 1: every member is a gzip member of its own) between an 18-byte header that carries the member's size and
-// the trailer CRC-32, ISIZE.  The first member starts at 0, a.end_bits is not read, and of the tile's PARTS words the first holds
-// the lowest failed row (NONE_BAD: none) in place of an Adler sum; the others but the status are not used.
-constexpr uint32_t BGZF_HEAD = 18, BGZF_TAIL = 8, BGZF_MAX = 65536, NONE_BAD = 0xFFFFFFFFu;
-__constant__ const uint8_t BGZF_HEADER[16] = {0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF, 6, 0, 0x42, 0x43, 2, 0};
-__constant__ const uint8_t BGZF_EOF[28] = {0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF, 6, 0, 0x42, 0x43, 2, 0, 0x1B, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-template <bool BGZF>
 __global__ __launch_bounds__(256) void k_join(JoinArgs a) {
-    constexpr uint64_t HEAD = BGZF ? 0u : STREAM_HEAD;   // where the first member starts
     __shared__ uint32_t s_tile;
     __shared__ uint64_t s_wsum[4], s_base;
     __shared__ uint64_t s_off[JT];
     __shared__ uint32_t s_body[JT];                      // bytes of the member that come from the row (0: no member)
     __shared__ uint32_t s_part[4][PARTS];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid == 0u) s_tile = atomicAdd(a.ticket, 1u);
+    if (tid == 0u) s_tile = atomicAdd(a.w.ticket, 1u);
     __syncthreads();
     const uint32_t tile = s_tile;
     const uint64_t b = (uint64_t)tile * JT + tid;
 
     // ---- the row's member length, and its share of the three Adler sums
     uint32_t m = 0, body_len = 0, st = HDLZ_OK, pa = 0, pe = 0, ps = 0;
-    if constexpr (BGZF) {
-        pa = NONE_BAD;
-        if (b < a.nblocks) {
-            st = a.status[b];
-            const uint32_t n = a.len[b];
-            const uint64_t nb = a.in_off ? a.in_off[b + 1] - a.in_off[b] : (uint64_t)a.in_len;
-            if (st == HDLZ_OK && (n < 8u || (uint64_t)n > a.pitch)) st = HDLZ_E_BAD_PARAM;      // 78 9C, at least 03 00, Adler-32: what is read below lies inside the row
-            else if (st == HDLZ_OK && (n > BGZF_MAX - 20u || nb > BGZF_MAX)) st = HDLZ_E_OUT_CAPACITY;
-            if (st == HDLZ_OK) {
-                body_len = n - 6u;
-                m = body_len + BGZF_HEAD + BGZF_TAIL;
-            } else pa = tid;
-        }
-    } else if (b < a.nblocks) {
+    if (b < a.nblocks) {
         st = a.status[b];
         const uint32_t n = a.len[b];
         const uint64_t E = a.end_bits[b];
@@ -136,56 +76,24 @@ __global__ __launch_bounds__(256) void k_join(JoinArgs a) {
     }
     s_body[tid] = body_len;
     {   // (256 residues below 65521: the sums stay below 2^24)
-        const uint32_t ra = BGZF ? wave_min(pa) : wave_add(pa), re = wave_add(pe), rs = wave_add(ps), rt = wave_max(st);
+        const uint32_t ra = wave_add(pa), re = wave_add(pe), rs = wave_add(ps), rt = wave_max(st);
         if (lane == 0u) { s_part[wave][0] = ra; s_part[wave][1] = re; s_part[wave][2] = rs; s_part[wave][3] = rt; }
     }
-    // ---- exclusive scan of the tile's member lengths
-    uint64_t v = m;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v += t;
-    }
-    if (lane == 63u) s_wsum[wave] = v;
-    __syncthreads();
-    const uint64_t w0 = s_wsum[0], w1 = s_wsum[1], w2 = s_wsum[2], w3 = s_wsum[3];
-    const uint64_t local = v - m + (wave > 0u ? w0 : 0ull) + (wave > 1u ? w1 : 0ull) + (wave > 2u ? w2 : 0ull);
-    const uint64_t tsum = w0 + w1 + w2 + w3;
+    uint64_t tsum;
+    const uint64_t local = tile_scan(m, lane, wave, s_wsum, tsum);
     if (tid < PARTS) {
         const uint32_t x0 = s_part[0][tid], x1 = s_part[1][tid], x2 = s_part[2][tid], x3 = s_part[3][tid];
-        if (BGZF && tid == 0u) {
-            const uint32_t f = min(min(x0, x1), min(x2, x3));
-            a.part[(size_t)PARTS * tile] = f == NONE_BAD ? NONE_BAD : tile * JT + f;
-        } else a.part[(size_t)PARTS * tile + tid] = tid == 3u ? max(max(x0, x1), max(x2, x3)) : x0 + x1 + x2 + x3;
+        a.w.part[(size_t)PARTS * tile + tid] = tid == 3u ? max(max(x0, x1), max(x2, x3)) : x0 + x1 + x2 + x3;
     }
     if (wave == 0u) {
-        uint64_t base = 0;
-        if (tile != 0u) {
-            if (lane == 0u) __hip_atomic_store(&a.desc[tile], J_AGG | tsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int64_t t = (int64_t)tile - 1 - (int64_t)lane;        // lane 0 looks at the nearest tile
-            for (;;) {
-                uint64_t d = J_PFX;                                // (tiles in front of tile 0: an empty prefix)
-                if (t >= 0) {
-                    do { d = __hip_atomic_load(&a.desc[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((d & J_MASK) == 0ull);
-                }
-                const uint64_t pm = ballot64((d & J_MASK) == J_PFX);
-                const uint32_t first = pm ? (uint32_t)__builtin_ctzll(pm) : 64u;      // the nearest published prefix among these 64
-                uint64_t x = lane <= first ? (d & ~J_MASK) : 0ull;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-                base += x;
-                if (pm) break;
-                t -= 64;
-            }
-        }
+        const uint64_t base = tile_lookback(a.w.desc, tile, tsum, lane);
         if (lane == 0u) {
-            __hip_atomic_store(&a.desc[tile], J_PFX | (base + tsum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s_base = base;
-            if ((uint64_t)(tile + 1u) * JT >= a.nblocks) a.off[a.nblocks] = HEAD + base + tsum;      // the last tile: where 03 00 (BGZF: the EOF member) goes
+            if ((uint64_t)(tile + 1u) * JT >= a.nblocks) a.off[a.nblocks] = STREAM_HEAD + base + tsum;      // the last tile: where 03 00 goes
         }
     }
     __syncthreads();
-    const uint64_t mine = HEAD + s_base + local;
+    const uint64_t mine = STREAM_HEAD + s_base + local;
     if (b < a.nblocks) a.off[b] = mine;
     s_off[tid] = mine;
     __syncthreads();
@@ -194,30 +102,10 @@ __global__ __launch_bounds__(256) void k_join(JoinArgs a) {
         const uint64_t rb = (uint64_t)tile * JT + r;
         if (rb >= a.nblocks) break;
         const uint64_t o0 = s_off[r];
-        const uint32_t rn = (uint32_t)((r + 1u < JT ? s_off[r + 1u] : HEAD + s_base + tsum) - o0);      // the member's length
+        const uint32_t rn = (uint32_t)((r + 1u < JT ? s_off[r + 1u] : STREAM_HEAD + s_base + tsum) - o0);      // the member's length
         if (rn == 0u || o0 + rn > a.cap) continue;            // a failed row / a member that would end beyond the capacity
         typedef uint32_t v4 __attribute__((ext_vector_type(4)));
         typedef v4 __attribute__((aligned(1))) v4u;
-        if constexpr (BGZF) {
-            const uint32_t bl = s_body[r];                    // rn = 18 + bl + 8
-            const uint8_t* src = a.rows + rb * a.pitch + 2u;  // row[2 .. 2 + bl): the block
-            uint8_t* dst = a.stream + o0;
-            if (lane < 16u) dst[lane] = BGZF_HEADER[lane];
-            else if (lane < BGZF_HEAD) dst[lane] = (uint8_t)((rn - 1u) >> (8u * (lane - 16u)));      // BSIZE
-            else if (lane < BGZF_HEAD + BGZF_TAIL) {
-                const uint32_t k = lane - BGZF_HEAD;
-                const uint32_t isize = a.in_off ? (uint32_t)(a.in_off[rb + 1] - a.in_off[rb]) : a.in_len;
-                dst[BGZF_HEAD + bl + k] = (uint8_t)((k < 4u ? a.crc[rb] : isize) >> (8u * (k & 3u)));
-            }
-            uint8_t* d2 = dst + BGZF_HEAD;
-            const uint32_t head = min(bl, (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(d2) & 15u)) & 15u));
-            if (lane < head) d2[lane] = src[lane];
-            const uint32_t body = (bl - head) >> 4;           // whole 16-byte chunks: no load leaves row[2 .. 2 + bl)
-            for (uint32_t k = lane; k < body; k += 64u) *reinterpret_cast<v4*>(d2 + head + 16u * k) = *reinterpret_cast<const v4u*>(src + head + 16u * k);
-            const uint32_t done = head + 16u * body;          // at most 15 bytes are left
-            if (done + lane < bl) d2[done + lane] = src[done + lane];
-            continue;
-        }
         const uint32_t bl = s_body[r], mark0 = rn - 2u;      // [0, bl): from the row; [bl, mark0): 00; [mark0, rn): FF
         const uint8_t* src = a.rows + rb * a.pitch + STREAM_HEAD;
         uint8_t* dst = a.stream + o0;
@@ -246,7 +134,7 @@ __global__ __launch_bounds__(256) void k_join_finish(JoinArgs a, uint32_t ntiles
     uint64_t sa = 0, se = 0, ss = 0;
     uint32_t st = HDLZ_OK;
     for (uint32_t t = tid; t < ntiles; t += 256u) {          // (up to 2^23 tiles of sums below 2^24)
-        const uint32_t* q = a.part + (size_t)PARTS * t;
+        const uint32_t* q = a.w.part + (size_t)PARTS * t;
         sa += q[0]; se += q[1]; ss += q[2]; st = max(st, q[3]);
     }
     s_sum[tid][0] = sa; s_sum[tid][1] = se; s_sum[tid][2] = ss; s_st[tid] = st;
@@ -297,7 +185,7 @@ __global__ __launch_bounds__(256) void k_join_gzip_finish(JoinArgs a, uint32_t n
     for (uint64_t b = (uint64_t)blockIdx.x * 256u + tid; b < a.nblocks; b += (uint64_t)gridDim.x * 256u) a.off[b] += GZ_LIFT;
     if (blockIdx.x != 0u) return;
     uint32_t st = HDLZ_OK;
-    for (uint32_t t = tid; t < ntiles; t += 256u) st = max(st, a.part[(size_t)PARTS * t + 3u]);
+    for (uint32_t t = tid; t < ntiles; t += 256u) st = max(st, a.w.part[(size_t)PARTS * t + 3u]);
     s_st[tid] = st;
     __syncthreads();
     for (uint32_t o = 128u; o > 0u; o >>= 1) {
@@ -326,95 +214,26 @@ __global__ __launch_bounds__(256) void k_join_gzip_finish(JoinArgs a, uint32_t n
     }
 }
 
-// ---- the BGZF form: one workgroup behind k_join<true>: the tiles' worst status and lowest failed row, the EOF member, the record
-__global__ __launch_bounds__(256) void k_bgzf_join_finish(JoinArgs a, uint32_t ntiles, hdlz_bgzf_join_result* result) {
-    __shared__ uint32_t s_st[256], s_f[256];
-    const uint32_t tid = threadIdx.x;
-    uint32_t st = HDLZ_OK, f = NONE_BAD;
-    for (uint32_t t = tid; t < ntiles; t += 256u) {
-        const uint32_t* q = a.part + (size_t)PARTS * t;
-        st = max(st, q[3]); f = min(f, q[0]);
-    }
-    s_st[tid] = st; s_f[tid] = f;
-    __syncthreads();
-    for (uint32_t o = 128u; o > 0u; o >>= 1) {
-        if (tid < o) { s_st[tid] = max(s_st[tid], s_st[tid + o]); s_f[tid] = min(s_f[tid], s_f[tid + o]); }
-        __syncthreads();
-    }
-    st = s_st[0];
-    if (a.nblocks == 0 && tid == 0u) a.off[0] = 0u;
-    const uint64_t end = a.nblocks ? a.off[a.nblocks] : 0u;      // (k_join's last tile wrote it, in front of this launch)
-    const uint64_t total = end + sizeof(BGZF_EOF);
-    if (st == HDLZ_OK && total <= a.cap && tid < sizeof(BGZF_EOF)) a.stream[end + tid] = BGZF_EOF[tid];
-    if (tid != 0u) return;
-    hdlz_bgzf_join_result res;
-    res.file_len = st != HDLZ_OK ? 0u : total;
-    res.status = st != HDLZ_OK ? st : total > a.cap ? (uint32_t)HDLZ_E_OUT_CAPACITY : (uint32_t)HDLZ_OK;
-    res.first_bad = s_f[0];
-    *result = res;
+size_t join_work_bytes(uint64_t nblocks) {
+    const uint64_t ntiles = join_tiles(nblocks);
+    return ntiles ? round256(sizeof(uint32_t) * (join_zeroed_words(ntiles) + PARTS * (size_t)ntiles)) : 0u;
 }
 
-static inline uint64_t join_tiles(uint64_t nblocks) { return (nblocks + JT - 1u) / JT; }
-
-size_t join_work_bytes(uint64_t nblocks) {                     // ticket (+ pad), one 64-bit look-back word and PARTS words per tile
-    const uint64_t ntiles = join_tiles(nblocks);
-    return ntiles ? round256(sizeof(uint32_t) * (2u + (2u + PARTS) * (size_t)ntiles)) : 0u;
+hipError_t launch_join(JoinArgs a, void* work, hipStream_t stream) {
+    a.w = join_work(work, a.nblocks);
+    return launch_tile_join(k_join, a, stream, [&](uint32_t ntiles) { return launch(k_join_finish, dim3(1), dim3(256), stream, a, ntiles); });
 }
 
-hipError_t launch_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
-                       const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, uint8_t* stream_out, uint64_t cap, uint64_t* off,
-                       hdlz_join_result* result, void* work, hipStream_t stream) {
-    const uint64_t ntiles = join_tiles(nblocks);
-    uint32_t* ws = static_cast<uint32_t*>(work);
-    JoinArgs a{rows, pitch, len, end_bits, status, in_off, in_len, nblocks, stream_out, cap, off, result, ws,
-               reinterpret_cast<unsigned long long*>(ws + 2), ws + 2u + 2u * (size_t)ntiles};
-    if (ntiles) {
-        const hipError_t e = zero_words(ws, (uint32_t)(2u + 2u * ntiles), stream);      // the ticket and the look-back words
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_join<false>, dim3((unsigned)ntiles), dim3(256), 0, stream, a);
-        const hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) return e2;
-    }
-    hipLaunchKernelGGL(k_join_finish, dim3(1), dim3(256), 0, stream, a, (uint32_t)ntiles);
-    return hipGetLastError();
-}
-
-hipError_t launch_join_gzip(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint64_t* end_bits, const uint32_t* status,
-                            const uint64_t* in_off, uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* stream_out,
-                            uint64_t cap, uint64_t* off, hdlz_join_gzip_result* result, void* work, hipStream_t stream) {
-    const uint64_t ntiles = join_tiles(nblocks);
-    uint32_t* ws = static_cast<uint32_t*>(work);
+hipError_t launch_join_gzip(JoinArgs a, const uint32_t* crc, hdlz_join_gzip_result* result, void* work, hipStream_t stream) {
+    uint8_t* gz = a.stream;
+    const uint64_t gz_cap = a.cap;
     // k_join's view: the stream from byte 8 on (a capacity below 8 leaves it no room at all: it then writes no byte)
-    JoinArgs a{rows, pitch, len, end_bits, status, in_off, in_len, nblocks, stream_out + GZ_LIFT, cap > GZ_LIFT ? cap - GZ_LIFT : 0u, off,
-               nullptr, ws, reinterpret_cast<unsigned long long*>(ws + 2), ws + 2u + 2u * (size_t)ntiles};
-    if (ntiles) {
-        const hipError_t e = zero_words(ws, (uint32_t)(2u + 2u * ntiles), stream);      // the ticket and the look-back words
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_join<false>, dim3((unsigned)ntiles), dim3(256), 0, stream, a);
-        const hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) return e2;
-    }
-    const unsigned grid = (unsigned)(ntiles < 1024u ? (ntiles ? ntiles : 1u) : 1024u);
-    hipLaunchKernelGGL(k_join_gzip_finish, dim3(grid), dim3(256), 0, stream, a, (uint32_t)ntiles, crc, stream_out, cap, result);
-    return hipGetLastError();
-}
-
-hipError_t launch_bgzf_join(const uint8_t* rows, uint64_t pitch, const uint32_t* len, const uint32_t* status, const uint64_t* in_off,
-                            uint32_t in_len, uint64_t nblocks, const uint32_t* crc, uint8_t* file, uint64_t cap, uint64_t* off,
-                            hdlz_bgzf_join_result* result, void* work, hipStream_t stream) {
-    const uint64_t ntiles = join_tiles(nblocks);
-    uint32_t* ws = static_cast<uint32_t*>(work);
-    JoinArgs a{rows, pitch, len, nullptr, status, in_off, in_len, nblocks, file, cap, off, nullptr, ws,
-               reinterpret_cast<unsigned long long*>(ws + 2), ws + 2u + 2u * (size_t)ntiles, crc};
-    if (ntiles) {
-        const hipError_t e = zero_words(ws, (uint32_t)(2u + 2u * ntiles), stream);      // the ticket and the look-back words
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_join<true>, dim3((unsigned)ntiles), dim3(256), 0, stream, a);
-        const hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) return e2;
-    }
-    hipLaunchKernelGGL(k_bgzf_join_finish, dim3(1), dim3(256), 0, stream, a, (uint32_t)ntiles, result);
-    return hipGetLastError();
+    a.stream = gz + GZ_LIFT; a.cap = gz_cap > GZ_LIFT ? gz_cap - GZ_LIFT : 0u;
+    a.w = join_work(work, a.nblocks);
+    return launch_tile_join(k_join, a, stream, [&](uint32_t ntiles) {
+        const unsigned grid = ntiles < 1024u ? (ntiles ? ntiles : 1u) : 1024u;
+        return launch(k_join_gzip_finish, dim3(grid), dim3(256), stream, a, ntiles, crc, gz, gz_cap, result);
+    });
 }
 
 }  // namespace hdlz

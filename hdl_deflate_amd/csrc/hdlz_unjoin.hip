@@ -14,12 +14,11 @@
 #include "hdlz_device.h"
 #include "hdlz_adler.h"
 #include "hdlz_crc32.h"
+#include "hdlz_frame.h"
 
 namespace hdlz {
 namespace unj {
 
-constexpr uint32_t JT = 256u;                 // members per workgroup of the index checks and of the judge
-constexpr uint32_t NONE = 0xFFFFFFFFu;        // a workgroup without a failed member
 constexpr uint64_t MEMBER_MAX = 1ull << 28;   // bit positions are 32-bit in the decoders
 
 // member b's slot of the output: [o, e) -- the caller checks what it relies on
@@ -136,8 +135,7 @@ __global__ __launch_bounds__(256) void k_unjoin_finish(UnjoinArgs a, uint32_t nt
         const uint2 s = a.tiles[t];
         fold_tile(A64, C64, t, s.x, s.y);
     }
-    uint32_t f = NONE;
-    for (uint32_t g = tid; g < ngroups; g += 256u) f = min(f, a.len[(size_t)g * JT]);
+    const uint32_t f = lowest_word(a.len, ngroups, tid, 256u);
     s_a[tid] = A64 % ADLER_MOD; s_c[tid] = C64 % ADLER_MOD; s_f[tid] = f;
     __syncthreads();
     for (uint32_t o = 128u; o > 0u; o >>= 1) {
@@ -182,18 +180,12 @@ __global__ __launch_bounds__(CRC_THREADS) void k_unjoin_gzip_tiles(UnjoinArgs a)
     crc_tiles(a.out, total_of(a), reinterpret_cast<uint32_t*>(a.tiles), s);
 }
 
-__device__ __forceinline__ uint32_t load_le32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
 // one workgroup of CRC_FIN_THREADS: the tile words -> the CRC-32, the verdicts -> the first failure; the gzip frame; the record
 __global__ __launch_bounds__(CRC_FIN_THREADS) void k_unjoin_gzip_finish(UnjoinArgs a, uint32_t ngroups) {
     __shared__ uint32_t s_fin[CRC_FIN_THREADS], s_f[CRC_FIN_THREADS];
     const uint32_t tid = threadIdx.x;
     const uint64_t total = total_of(a);
-    uint32_t f = NONE;
-    for (uint32_t g = tid; g < ngroups; g += CRC_FIN_THREADS) f = min(f, a.len[(size_t)g * JT]);
-    s_f[tid] = f;
+    s_f[tid] = lowest_word(a.len, ngroups, tid, CRC_FIN_THREADS);
     const uint32_t crc = crc_finish(reinterpret_cast<const uint32_t*>(a.tiles), total, s_fin);      // (synchronises: s_f is written)
     for (uint32_t o = CRC_FIN_THREADS / 2u; o > 0u; o >>= 1) {
         if (tid < o) s_f[tid] = min(s_f[tid], s_f[tid + o]);
@@ -209,7 +201,7 @@ __global__ __launch_bounds__(CRC_FIN_THREADS) void k_unjoin_gzip_finish(UnjoinAr
         const bool head = a.off[0] == 10u && a.in_len >= 10u && a.in[0] == 0x1Fu && a.in[1] == 0x8Bu && a.in[2] == 8u && a.in[3] == 0u;
         if (!head) res.status = HDLZ_E_BAD_HEADER;
         else if (end > a.in_len - 10u || a.in[end] != 3u || a.in[end + 1u] != 0u) res.status = HDLZ_E_NO_EOF;
-        else if (load_le32(a.in + end + 2u) != crc || load_le32(a.in + end + 6u) != (uint32_t)total) res.status = HDLZ_E_BAD_CHECKSUM;
+        else if (le32(a.in + end + 2u) != crc || le32(a.in + end + 6u) != (uint32_t)total) res.status = HDLZ_E_BAD_CHECKSUM;
         if (res.status != HDLZ_OK) res.first_bad = a.nmembers;
     }
     if (res.status != HDLZ_OK) res.out_len = 0u;
@@ -222,7 +214,7 @@ size_t unjoin_tiles(uint64_t total_out) { return (size_t)((total_out + ADLER_TIL
 
 hipError_t launch_unjoin_index(const UnjoinArgs& a, hipStream_t stream) {
     if (a.nmembers == 0) return hipSuccess;
-    hipLaunchKernelGGL(unj::k_unjoin_index, dim3((unsigned)((a.nmembers + unj::JT - 1u) / unj::JT)), dim3(unj::JT), 0, stream, a);
+    hipLaunchKernelGGL(unj::k_unjoin_index, dim3((unsigned)((a.nmembers + JT - 1u) / JT)), dim3(JT), 0, stream, a);
     return hipGetLastError();
 }
 

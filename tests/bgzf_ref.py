@@ -93,6 +93,22 @@ def data(n, seed):
     return text[:n // 2] + bytes(r.integers(0, 256, n - n // 2, dtype=np.uint8))
 
 
+def many_members(count=600):
+    """`count` members of 1 to 64 data bytes and the EOF member -> (file, the members' data): more members than one wave and than two
+    workgroups of the per-member kernels hold"""
+    r = np.random.default_rng(count)
+    parts = [data(int(n), 1000 + k) for k, n in enumerate(r.integers(1, 65, count))]
+    return b"".join(member(p, 6) for p in parts) + EOF, parts
+
+
+def with_crc_flipped(f, off, members):
+    """the file with a byte of the CRC word flipped in each of `members` (off: the index of the serial walk)"""
+    z = bytearray(f)
+    for b in members:
+        z[off[b + 1] - 8] ^= 0x10
+    return bytes(z)
+
+
 def damaged_files():
     """(label, file, what the walk must say) -- also the cut and garbage cases of tests/test_gpu_bgzf.py"""
     parts = [data(n, 50 + n) for n in (300, 0, 5000, 65280, 12)]

@@ -370,6 +370,17 @@ def test_damage_in_one_member(engine, k):
     assert verdict(g, off=w.off[:k + 1] + [o + 1 for o in w.off[k + 1:]]) == E_NO_EOF
 
 
+@pytest.mark.parametrize("bad", [(70, 300, 570), (570,), (300,)], ids=["70-300-570", "570", "300"])
+def test_failed_members_beyond_the_first_wave_and_workgroup(engine, bad):
+    """600 members: the failing ones sit in other waves and other workgroups of the judge than member 0 -- the lowest one is reported"""
+    f, parts = bgzf_ref.many_members()
+    w = bgzf_ref.walk(f)
+    assert w.status == OK and w.nmembers == 601
+    r = Read(engine.lib, bgzf_ref.with_crc_flipped(f, w.off, bad), w.off, w.out_off)
+    assert r.rec == (E_BAD_CHECKSUM, bad[0], 0), r.rec
+    assert [(b, s) for b, s in enumerate(r.members) if s] == [(b, E_BAD_CHECKSUM) for b in bad]      # exactly those members are marked
+
+
 def test_sub_ranges_and_a_short_capacity(engine):
     f, parts = base_file()
     w = bgzf_ref.walk(f)

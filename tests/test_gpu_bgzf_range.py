@@ -8,7 +8,7 @@ import torch
 
 import bgzf_ref
 import bgzf_range_ref as ref
-from bgzf_ref import OK, E_OUT_CAPACITY, E_BAD_PARAM, E_BAD_HEADER
+from bgzf_ref import OK, E_OUT_CAPACITY, E_BAD_PARAM, E_BAD_HEADER, E_BAD_CHECKSUM
 from hdl_deflate_amd import _lib
 from hdl_deflate_amd.errors import HdlzStatusError
 
@@ -247,6 +247,20 @@ def test_damage_in_member_3(engine, files_a, kind):
     assert len(touching) > 10 and [r for r, st in enumerate(e.status) if st != OK] == touching
     assert {g.status[r] for r in touching} == {ms[3]} and (g.rec.status, g.rec.first_bad) == (ms[3], touching[0])
     assert batch.index((out_off[4] - 1, out_off[4])) in touching        # the range that delivers member 3's last byte alone
+
+
+def test_failed_tasks_beyond_the_first_workgroup(engine):
+    """600 members under one range: its tasks span three workgroups of the per-task kernels, the failing ones sit in the second and the
+    third; a second range in front of them is delivered"""
+    f, parts = bgzf_ref.many_members()
+    w = bgzf_ref.walk(f)
+    F = File(bgzf_ref.with_crc_flipped(f, w.off, (300, 570)), index=(w.off, w.out_off))
+    ms = member_statuses(engine.lib, F)
+    assert [(b, st) for b, st in enumerate(ms) if st != OK] == [(300, E_BAD_CHECKSUM), (570, E_BAD_CHECKSUM)]
+    ranges = [(0, w.total_out), (0, w.out_off[70])]
+    g, e = sized_read(engine.lib, F, ranges, member_status=ms)
+    assert e.ntasks == 600 + 70 and g.status == [ms[300], OK] and (g.rec.status, g.rec.first_bad) == (ms[300], 0)
+    assert g.out[g.range_off[1]:g.range_off[2]] == b"".join(parts[:70])
 
 
 def test_an_index_from_elsewhere_with_one_word_moved(engine, files_a):

@@ -355,6 +355,28 @@ def test_round_trip_under_every_mapping(engine, flags):
     assert len(e.stream) == 20 and (r.rec.status, r.rec.first_bad, r.rec.out_len, r.rec.crc) == (OK, NOBODY, 0, 0)
 
 
+_many = {}
+
+
+@pytest.mark.parametrize("flags", [LANE, WAVE, GROUP])
+def test_failed_members_beyond_the_first_wave_and_workgroup(engine, flags):
+    """600 members of 5 to 64 bytes: the failing ones sit in other waves and other workgroups of the judge than member 0 -- the lowest
+    one is reported"""
+    if not _many:
+        r = random.Random(600)
+        blocks = blocks_of([4 * r.randint(2, 16) for _ in range(599)] + [5], seed=6)
+        _many["g"], _many["oo"] = gzip_ref.expected_gzip(blocks, 32, 10), offsets_of(blocks)
+    g, oo = _many["g"], _many["oo"]
+    for bad in ((300, 570), (570,)):
+        z = g.stream
+        for k in bad:                                                                       # a member's FF FF -> FF FE
+            assert z[g.offsets[k + 1] - 2:g.offsets[k + 1]] == b"\xff\xff"
+            z = flipped(z, g.offsets[k + 1] - 1, 0x01)
+        r = Run(engine.lib, z, g.offsets, oo, flags=flags)
+        assert (r.rec.status, r.rec.first_bad, r.rec.out_len, r.rec.crc) == (E_NO_EOF, bad[0], 0, 0), (bad, r.rec.status, r.rec.first_bad)
+        assert [(b, s) for b, s in enumerate(r.members) if s] == [(k, E_NO_EOF) for k in bad]
+
+
 @pytest.mark.parametrize("flags", HINTS)
 def test_damaged_frame(engine, flags):
     g, oo = damage_base()

@@ -223,6 +223,25 @@ def test_damaged_members(engine, flags):
         assert r.rec.status != OK and r.rec.first_bad in (k - 1, k) and r.rec.out_len == 0, (k, r.rec.status, r.rec.first_bad)
 
 
+@pytest.mark.parametrize("flags", [LANE, WAVE, GROUP])
+def test_failed_members_beyond_the_first_wave_and_workgroup(engine, flags):
+    """600 members of 5 to 64 bytes: the failing ones sit in other waves and other workgroups of the judge than member 0 -- the lowest
+    one is reported"""
+    if "many" not in _damage:
+        r = random.Random(600)
+        blocks = blocks_of([4 * r.randint(2, 16) for _ in range(599)] + [5], seed=6)
+        _damage["many"] = (joined_ref.expected_joined(blocks, 32, 10), offsets_of(blocks))
+    j, oo = _damage["many"]
+    for bad in ((300, 570), (570,)):
+        z = j.stream
+        for k in bad:                                                                       # a member's FF FF -> FF FE
+            assert z[j.offsets[k + 1] - 2:j.offsets[k + 1]] == b"\xff\xff"
+            z = flipped(z, j.offsets[k + 1] - 1, 0x01)
+        r = Run(engine.lib, z, j.offsets, oo, flags=flags)
+        assert (r.rec.status, r.rec.first_bad, r.rec.out_len, r.rec.adler) == (E_NO_EOF, bad[0], 0, 0), (bad, r.rec.status, r.rec.first_bad)
+        assert [(b, s) for b, s in enumerate(r.members) if s] == [(k, E_NO_EOF) for k in bad]
+
+
 @pytest.mark.parametrize("flags", HINTS)
 def test_wrong_output_slots(engine, flags):
     j, oo = damage_base()

@@ -15,8 +15,14 @@ replaces its own sections of --out and leaves the others:
                             4. without a bar: hdlz_bgzf_inflate_ws of the all-stored file against the all-fixed 57344-byte file
                             5. file sizes: the older writer at 57344 against this one at 65280
 
+  framing --parent LIB      the bar of section 2 for a change that leaves every entry point's bytes alone: hdlz_join_batch_ws,
+                            hdlz_bgzf_join_ws and hdlz_bgzf_join_stored_ws of this build against the same call of the PARENT library,
+                            at section 2's two shapes, from the same rows; both sides' outputs must be identical.  Writes
+                            section 2 of profiles/framing_shared.txt (or --out).
+
     python tools/probe_bgzf_stored.py codeobj --parent <csrc/_obj of a build of the parent commit>
-    python tools/probe_bgzf_stored.py time --parent <libhdlz.so of a build of the parent commit>"""
+    python tools/probe_bgzf_stored.py time --parent <libhdlz.so of a build of the parent commit>
+    python tools/probe_bgzf_stored.py framing --parent <libhdlz.so of a build of the parent commit>"""
 import argparse
 import ctypes
 import gzip
@@ -59,8 +65,10 @@ def cmd_codeobj(args):
 def _bind(path):
     from hdl_deflate_amd import _lib
     L = ctypes.CDLL(path)
-    for t in (_lib.SIGNATURES, _lib.JOIN_SIGNATURES, _lib.UNJOIN_SIGNATURES, _lib.GZIP_SIGNATURES, _lib.BGZF_SIGNATURES):
+    for t in (_lib.SIGNATURES, _lib.JOIN_SIGNATURES, _lib.UNJOIN_SIGNATURES, _lib.GZIP_SIGNATURES, _lib.BGZF_SIGNATURES, _lib.BGZF_STORED_SIGNATURES):
         for name, (restype, argtypes) in t.items():
+            if not hasattr(L, name):                            # (a parent older than the stored writer)
+                continue
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
     return L
@@ -251,16 +259,78 @@ def cmd_time(args):
     return 0
 
 
+def cmd_framing(args):
+    import torch
+    import hdl_deflate_amd
+    from hdl_deflate_amd import _lib
+    from hdl_deflate_amd.data import make_blocks
+    assert torch.cuda.is_available(), "the probe needs a HIP device: there is nothing to time without one"
+    assert args.repeats >= 10
+    eng = hdl_deflate_amd.Engine()
+    L, P = eng.lib, _bind(args.parent)
+    nbytes = 1 << args.log2_bytes
+    lines = ["%s, median of %d after %d warm-up repeats, HIP events around each call, ms; every call in turn within a repeat." %
+             (torch.cuda.get_device_name(0), args.repeats, args.warmup),
+             "command: python tools/probe_bgzf_stored.py framing --parent <libhdlz.so of the parent commit> --log2-bytes %d" % args.log2_bytes, ""]
+    missed = 0
+    for n, fam, label in ((57344, None, "the four bench families"), (2048, (1, 2, 4), "the three bench families that compress")):
+        data = (make_blocks(nbytes // 2048, 2048, "cuda", seed=5, families=fam) if fam else make_blocks(nbytes // 2048, 2048, "cuda", seed=5)).reshape(-1)
+        b = Batch(L, data, n)
+        del data
+        bits = torch.empty(b.B, dtype=torch.int64, device="cuda")
+        zcap = L.hdlz_join_bound(b.B, n)
+        assert zcap <= b.cap
+        zres = torch.zeros(2, dtype=torch.int64, device="cuda")
+        assert b.crc() == 0 and L.hdlz_compress_batch_bits(b.data.data_ptr(), None, n, n, b.B, 32, 10, b.rows.data_ptr(), b.pitch, b.out_len.data_ptr(),
+                                                           b.status.data_ptr(), bits.data_ptr(), b.st) == 0, L.hdlz_last_error()
+        # every call writes into file / off / res of its side: (file, off, res) for this build, (old_file, old_off, res2) for the parent
+        res2 = torch.zeros(3, dtype=torch.int64, device="cuda")
+        side = {L: (b.file, b.off, b.res), P: (b.old_file, b.old_off, res2)}
+        zlib_join = lambda lib: lib.hdlz_join_batch_ws(b.rows.data_ptr(), b.pitch, b.out_len.data_ptr(), bits.data_ptr(), b.status.data_ptr(), None, n, b.B,
+                                                       side[lib][0].data_ptr(), zcap, side[lib][1].data_ptr(), zres.data_ptr(), b.work.data_ptr(), b.wb, b.st)
+        fixed = lambda lib: lib.hdlz_bgzf_join_ws(b.rows.data_ptr(), b.pitch, b.out_len.data_ptr(), b.status.data_ptr(), None, n, b.B, b.crcs.data_ptr(),
+                                                  side[lib][0].data_ptr(), b.cap, side[lib][1].data_ptr(), side[lib][2].data_ptr(), b.work.data_ptr(), b.wb, b.st)
+        stored = lambda lib: lib.hdlz_bgzf_join_stored_ws(b.data.data_ptr(), None, n, n, b.rows.data_ptr(), b.pitch, b.out_len.data_ptr(), b.status.data_ptr(),
+                                                          b.B, b.crcs.data_ptr(), side[lib][0].data_ptr(), b.cap, side[lib][1].data_ptr(), None,
+                                                          side[lib][2].data_ptr(), b.work.data_ptr(), b.wb, b.st)
+        lines.append("%d blocks of %d bytes (%s), %d bytes of input" % (b.B, n, label, b.total))
+        for name, call, words in (("hdlz_join_batch_ws", zlib_join, 0), ("hdlz_bgzf_join_ws", fixed, 2), ("hdlz_bgzf_join_stored_ws", stored, 3)):
+            for lib in (P, L):
+                side[lib][0].zero_()
+                assert call(lib) == 0, lib.hdlz_last_error()
+            rec = (zres if words == 0 else b.res).cpu().numpy()
+            assert int(rec[words - 1 if words else 1]) & 0xFFFFFFFF == 0, (name, rec)          # the status word
+            size = int(rec[0])
+            assert torch.equal(b.file[:size], b.old_file[:size]) and torch.equal(b.off, b.old_off), name      # identical on both sides
+            if words:
+                assert torch.equal(b.res[:words], side[P][2][:words]), name
+            t = timed([("(p) parent " + name, lambda: call(P)), ("(n) " + name, lambda: call(L))], args.repeats, args.warmup, L.hdlz_last_error)
+            vp, vn = t["(p) parent " + name], t["(n) " + name]
+            mp, mn = statistics.median(vp), statistics.median(vn)
+            allowed = max(max(vp) - min(vp), max(vn) - min(vn))
+            held = mn - mp <= allowed
+            missed += not held
+            lines += [row(k, v, b.total) for k, v in t.items()]
+            lines.append("  output %d bytes, identical on both sides; (n) / (p) = %.4f   excess %.4f ms, allowed %.4f ms (spreads: parent %.4f, new %.4f): "
+                         "the bar is %s" % (size, mn / mp, mn - mp, allowed, max(vp) - min(vp), max(vn) - min(vn), "HELD" if held else "MISSED"))
+        lines.append("")
+        del b
+    put_section(args.out, "2. the bar of profiles/bgzf_stored.txt, section 2, for the three tile joins against the parent's", lines)
+    return 1 if missed else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("cmd", choices=("codeobj", "time"))
+    ap.add_argument("cmd", choices=("codeobj", "time", "framing"))
     ap.add_argument("--parent", required=True)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_stored.txt"))
     ap.add_argument("--log2-bytes", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     args = ap.parse_args()
-    return {"codeobj": cmd_codeobj, "time": cmd_time}[args.cmd](args)
+    if args.cmd == "framing" and args.out == ap.get_default("out"):
+        args.out = os.path.join(ROOT, "profiles", "framing_shared.txt")
+    return {"codeobj": cmd_codeobj, "time": cmd_time, "framing": cmd_framing}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,9 @@
   codeobj --parent OBJDIR   (no GPU) the code-object metadata of every kernel in hdlz_inflate_tok / _grp / _dyn / hdlz_checksum (or of
                             --sources A,B,...) of a build of the parent commit (its csrc/_obj) beside this build's: the existing
                             instantiations must be the same, the member twins are listed next to them.  Each kernel's instructions
-                            (llvm-objdump -d) are compared too: identical / same opcodes, registers renamed / differs.
+                            (llvm-objdump -d) are compared too: identical / same opcodes, registers renamed / differs.  With
+                            hdlz_join and hdlz_bgzf_stored among the sources, the kernels of MOVED are listed against the parent's
+                            kernels they took the place of; a pair that differs there is settled by its timing and not counted.
   time                      (a) hdlz_inflate_checked of the per-block rows as a ragged archive, forced to the mapping (b) chooses,
                             (b) hdlz_unjoin_ws of the joined stream; 2 GiB of the four bench families as 2 KiB and as 64 KiB blocks,
                             HIP events, calls alternated in one process.  Yardstick: (b) <= 1.15 x (a).
@@ -63,6 +65,8 @@ def kernels_of(obj):
         name = subprocess.check_output(["c++filt", sym]).decode().strip()
         k = out[re.sub(r"\(.*", "", name).replace("void ", "")] = {f: int(re.search(r"(?m)^\s*%s:\s*(\d+)" % re.escape(f), blk).group(1)) for f in FIELDS}
         k["code"] = code[sym]
+        while k["code"] and k["code"][-1].split()[0] in ("s_nop", "s_code_end", "..."):      # the padding behind a kernel
+            k["code"].pop()
     return out
 
 
@@ -73,6 +77,9 @@ def code_tag(old, new):
     blank = lambda seq: [re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", i) for i in seq]
     if blank(old) == blank(new):
         return "same opcodes, registers renamed (%d instructions)" % len(new)
+    args = lambda seq: [re.sub(r"^(s_load_dword\w* .*), 0x[0-9a-f]+$", r"\1, #", i) for i in seq]
+    if args(old) == args(new):
+        return "identical but for the offsets of scalar loads: the argument record changed (%d instructions)" % len(new)
     return "differs (%d -> %d instructions)" % (len(old), len(new))
 
 
@@ -84,20 +91,44 @@ def canon(name):
     return name.replace("k_inflate_grp<false>", "k_inflate_grp")
 
 
+# the one BGZF writer (hdlz_bgzf_stored.hip) against the kernels it took the place of, which stood in two files: this build's name ->
+# (the parent's source, the parent's names); the zlib/gzip join keeps its file and lost its template flag
+MOVED = {"hdlz::k_bgzf_join<false>": ("hdlz_join", ["hdlz::k_join<true>"]),
+         "hdlz::k_bgzf_join<true>": ("hdlz_bgzf_stored", ["hdlz::k_bgzf_join_stored"]),
+         "hdlz::k_bgzf_join_finish": ("hdlz_join", ["hdlz::k_bgzf_join_finish"]),
+         "hdlz::k_bgzf_join_finish ": ("hdlz_bgzf_stored", ["hdlz::k_bgzf_join_stored_finish"]),
+         "hdlz::k_join": ("hdlz_join", ["hdlz::k_join<false>"])}
+
+
+def moved_lines(parent, new_dir, fmt):
+    """the kernels of MOVED, each against its parent: a pair that differs is a different function now and is settled by its timing"""
+    lines, objs = ["moved or merged kernels (this build | the parent's kernel it is compared with):"], {}
+    load = lambda d, src: objs.setdefault((d, src), kernels_of(os.path.join(d, src + ".o")))
+    for name, (src, olds) in sorted(MOVED.items()):
+        n = load(new_dir, "hdlz_join" if name == "hdlz::k_join" else "hdlz_bgzf_stored")[name.strip()]
+        for old in olds:
+            o = load(parent, src)[old]
+            lines.append("  %-28s %-24s | %-34s %-24s %s" % (name.strip(), fmt(n), old, fmt(o), code_tag(o["code"], n["code"])))
+    return lines
+
+
 def cmd_codeobj(args):
     new_dir = os.path.join(ROOT, "hdl_deflate_amd", "csrc", "_obj")
     lines = ["code-object metadata, parent build | this build (%s)" % ", ".join(f[1:] for f in FIELDS),
              "command: python tools/probe_unjoin.py codeobj --parent <csrc/_obj of a build of the parent commit>" +
              (" --sources " + args.sources if args.sources else ""), ""]
     differ, notes = 0, []
+    fmt = lambda v: "-" if v is None else " ".join("%d" % v[f] for f in FIELDS)
+    gone = {(src, old) for src, olds in MOVED.values() for old in olds}
     for src in (args.sources.split(",") if args.sources else SOURCES):
         old = {canon(k): v for k, v in kernels_of(os.path.join(args.parent, src + ".o")).items()}
         new = {canon(k): (k, v) for k, v in kernels_of(os.path.join(new_dir, src + ".o")).items()}
         lines.append(src + ":")
         for name in sorted(set(old) | set(new)):
+            if (src, name) in gone or name in MOVED:
+                continue
             o = old.get(name)
             full, n = new.get(name, (name, None))
-            fmt = lambda v: "-" if v is None else " ".join("%d" % v[f] for f in FIELDS)
             tag = "twin (new)" if o is None else "MISSING" if n is None else "same" if fmt(o) == fmt(n) else "DIFFERS"
             code = code_tag(o["code"], n["code"]) if o and n else ""
             differ += tag in ("MISSING", "DIFFERS") or code.startswith("differs")
@@ -106,6 +137,8 @@ def cmd_codeobj(args):
                 notes.append("  finding: %s -- scratch %d bytes, %d VGPRs and %d SGPRs spilled" %
                              (full, n[".private_segment_fixed_size"], n[".vgpr_spill_count"], n[".sgpr_spill_count"]))
     lines.append("")
+    if {"hdlz_join", "hdlz_bgzf_stored"} <= set(args.sources.split(",") if args.sources else SOURCES):
+        lines += moved_lines(args.parent, new_dir, fmt) + [""]
     lines.append("existing instantiations that differ or are missing: %d" % differ)
     lines.extend(notes or ["  no twin uses scratch or spills"])
     put_section(args.out, "1. code objects of the existing kernels (no GPU)", lines)
