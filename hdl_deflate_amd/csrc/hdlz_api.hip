@@ -51,6 +51,59 @@ int check_device() {
     }
     return HDLZ_OK;
 }
+
+// ---- The vocabulary of the parameter checks.  Every entry point states its OWN sequence of checks, one `if (...) return ...;` line
+// each, in front of check_device(); what a check tests and how its refusal reads is written here once.
+template <class... P>
+bool any_null(const P*... p) { return (... || !p); }
+// is one of the pointers off a multiple of k (a power of two)?  A null pointer is aligned.
+template <class... P>
+bool misaligned(uintptr_t k, const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & (k - 1u)) != 0u; }
+int fail_align(unsigned k, const char* names) {           // names: "a / b / c"
+    snprintf(g_err, sizeof(g_err), "bad parameter: %s must be %u-byte aligned", names, k);
+    return HDLZ_E_BAD_PARAM;
+}
+// the hipError_t of a launcher -> the call's status
+int launched(hipError_t e, const char* where) { return e == hipSuccess ? HDLZ_OK : fail_hip(e, where); }
+// the two knobs of the three compress entry points; false: refused, the message is set
+bool window_ok(int cwindow, int maxmatch) {
+    if (cwindow < 1 || cwindow > 256) fail_param("cwindow must be in [1,256]");
+    else if (maxmatch != 5 && maxmatch != 10) fail_param("maxmatch must be 5 (MATCH10=False) or 10 (MATCH10=True)");
+    else return true;
+    return false;
+}
+// is the caller's scratch short of `need` bytes (0: none is needed and d_work may be null)?  true: refused, the message names the query
+bool work_too_small(size_t need, const void* d_work, size_t work_bytes, const char* query) {
+    if (need == 0u || (d_work && work_bytes >= need)) return false;
+    snprintf(g_err, sizeof(g_err), "bad parameter: d_work smaller than %s", query);
+    return true;
+}
+// The checks the four joins share, in their order (hdlz_join_batch_ws, hdlz_join_gzip_ws, hdlz_bgzf_join_ws, hdlz_bgzf_join_stored_ws).
+// null_pointer: the entry point's own list of required pointers has a null in it; query: its size query, for the message; d_in_off:
+// the BGZF forms hold it to 8 bytes as well (the other two pass null); d_crc: null where the form has none.
+int join_checks(bool null_pointer, uint64_t nblocks, const void* d_off, const void* d_in_off, const void* d_result, const void* d_crc,
+                const void* d_work, size_t work_bytes, const char* query, bool bgzf) {
+    if (null_pointer) return fail_param("null device pointer");
+    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");   // (32-bit tile and word counts)
+    if (work_too_small(hdlz::join_work_bytes(nblocks), d_work, work_bytes, query)) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_work)) return fail_align(8, "d_work");
+    if (misaligned(8, d_off, d_result) || (bgzf && misaligned(8, d_in_off))) return fail_align(8, bgzf ? "d_off / d_in_off / d_result" : "d_off / d_result");
+    if (misaligned(4, d_crc)) return fail_align(4, "d_crc");
+    return HDLZ_OK;
+}
+// the scratch of a call: the caller's buffer (the _ws entry points), or the library's stream-ordered pool
+hdlz::Work caller_work(void* d_work, size_t work_bytes) { return hdlz::Work{static_cast<uint8_t*>(d_work), d_work ? work_bytes : 0u, true}; }
+hdlz::Work pooled_work() { return hdlz::Work{nullptr, 0u, false}; }
+// The member view of one flat input (hdlz::MemberArgs): n members at m_off, decoded into `out`, the three result arrays in scratch.
+// What the three callers differ in stays with them: m_out_off / m_out_len / m_out_cap, m_gap, the task view.
+hdlz::MemberArgs member_args(const uint8_t* in, uint64_t n, uint32_t flags, uint8_t* out, uint32_t* len, uint32_t* status, uint32_t* end_bit,
+                             const uint64_t* m_off) {
+    hdlz::MemberArgs a;
+    a.in = in; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = n; a.flags = flags; a.obsize = 0;
+    a.out = out; a.out_pitch = 0; a.out_len = len; a.status = status; a.in_used = end_bit;
+    a.m_off = m_off; a.m_out_off = nullptr; a.m_out_len = 0; a.m_out_cap = 0;
+    return a;
+}
 }  // namespace
 
 namespace hdlz {
@@ -154,28 +207,21 @@ int hdlz_device_count(void) {
 size_t hdlz_out_bound(size_t n) { return 6 + (9 * n + 10 + 7) / 8; }
 
 int hdlz_release_scratch(void) {
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    const hipError_t e = hdlz::scratch_release();
-    if (e != hipSuccess) return fail_hip(e, "hipMemPoolTrimTo");
-    return HDLZ_OK;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::scratch_release(), "hipMemPoolTrimTo");
 }
 
 static int compress_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
                                uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
                                uint32_t* d_out_len, uint32_t* d_status, uint64_t* d_end_bits, void* stream) {
-    if (cwindow < 1 || cwindow > 256) return fail_param("cwindow must be in [1,256]");
-    if (maxmatch != 5 && maxmatch != 10) return fail_param("maxmatch must be 5 (MATCH10=False) or 10 (MATCH10=True)");
+    if (!window_ok(cwindow, maxmatch)) return HDLZ_E_BAD_PARAM;
     if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch");
-    if (nblocks && (!d_in || !d_out || !d_out_len || !d_status)) return fail_param("null device pointer");
-    if ((out_pitch & 3u) || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return fail_param("d_out / out_pitch must be 4-byte aligned");
+    if (nblocks && any_null(d_in, d_out, d_out_len, d_status)) return fail_param("null device pointer");
+    if ((out_pitch & 3u) || misaligned(4, d_out)) return fail_align(4, "d_out / out_pitch");
     if (!d_in_off && in_len >= 0x80000000u) return fail_param("in_len too large");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hdlz::CompressArgs a{d_in, d_in_off, in_pitch, in_len, nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status, d_end_bits};
-    hipError_t e = hdlz::launch_compress(a, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_compress");
-    return HDLZ_OK;
+    return launched(hdlz::launch_compress(a, static_cast<hipStream_t>(stream)), "launch k_compress");
 }
 
 int hdlz_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
@@ -190,7 +236,7 @@ int hdlz_compress_batch_bits(const uint8_t* d_in, const uint64_t* d_in_off, uint
                              uint64_t nblocks, int cwindow, int maxmatch, uint8_t* d_out, uint64_t out_pitch,
                              uint32_t* d_out_len, uint32_t* d_status, uint64_t* d_end_bits, void* stream) {
     if (!d_end_bits) return fail_param("d_end_bits is required");
-    if (reinterpret_cast<uintptr_t>(d_end_bits) & 7u) return fail_param("d_end_bits must be 8-byte aligned");
+    if (misaligned(8, d_end_bits)) return fail_align(8, "d_end_bits");
     return compress_batch_impl(d_in, d_in_off, in_pitch, in_len, nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status,
                                d_end_bits, stream);
 }
@@ -203,17 +249,11 @@ int hdlz_join_batch_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t
                        const uint32_t* d_status, const uint64_t* d_in_off, uint32_t in_len, uint64_t nblocks,
                        uint8_t* d_stream, uint64_t stream_cap, uint64_t* d_off, hdlz_join_result* d_result, void* d_work,
                        size_t work_bytes, void* stream) {
-    if (!d_stream || !d_off || !d_result || (nblocks && (!d_rows || !d_len || !d_end_bits || !d_status))) return fail_param("null device pointer");
-    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");   // (32-bit tile and word counts)
-    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_join_work_bytes(nblocks)");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u)) return fail_param("d_off / d_result must be 8-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    const bool null_pointer = any_null(d_stream, d_off, d_result) || (nblocks && any_null(d_rows, d_len, d_end_bits, d_status));
+    if (const int rc = join_checks(null_pointer, nblocks, d_off, nullptr, d_result, nullptr, d_work, work_bytes, "hdlz_join_work_bytes(nblocks)", false); rc != HDLZ_OK) return rc;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     const hdlz::JoinArgs a{d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off, d_result, {}};
-    hipError_t e = hdlz::launch_join(a, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_join");
-    return HDLZ_OK;
+    return launched(hdlz::launch_join(a, d_work, static_cast<hipStream_t>(stream)), "launch k_join");
 }
 
 #ifndef HDLZ_PAR_BATCH_SHORT_MAX
@@ -258,7 +298,7 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
                        uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
                        uint32_t* d_out_len, uint32_t* d_status, const hdlz::Work& w, void* stream, uint32_t* d_in_used = nullptr) {
     if (nstreams > 0x7FFFFFFFull * 32) return fail_param("nstreams too large for one launch");
-    if (nstreams && (!d_in || !d_out || !d_out_len || !d_status)) return fail_param("null device pointer");
+    if (nstreams && any_null(d_in, d_out, d_out_len, d_status)) return fail_param("null device pointer");
     if (flags & ~INFLATE_FLAGS) return fail_param("unknown flag");
     // the kernels keep stream lengths and bit positions in 32 bits (8 * length must not wrap)
     if (!d_in_off && in_len >= 0x10000000u) return fail_param("in_len too large (streams are limited to 256 MiB - 1)");
@@ -268,10 +308,9 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
         const uint32_t mf = flags & MAPPING_HINTS;
         if (mf & (mf - 1u)) return fail_param("contradictory mapping flags");
     }
-    if ((out_pitch & 3u) || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return fail_param("d_out / out_pitch must be 4-byte aligned");
-    if (w.caller && w.base && (reinterpret_cast<uintptr_t>(w.base) & 255u)) return fail_param("d_work must be 256-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    if ((out_pitch & 3u) || misaligned(4, d_out)) return fail_align(4, "d_out / out_pitch");
+    if (w.caller && misaligned(256, w.base)) return fail_align(256, "d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     if (nstreams == 0) return HDLZ_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hdlz::InflateArgs a{d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, d_in_used};
@@ -279,24 +318,17 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
     const Mapping map = mapping_of(nstreams, flags);
     if (par_applies(nstreams, in_len, flags)) {
         bool used = false;
-        hipError_t e = hdlz::launch_inflate_par(a, st, &used, w);
-        if (e != hipSuccess) return fail_hip(e, "launch the whole-GPU inflate (k_par_*)");
-        if (used) return HDLZ_OK;
+        const int rc = launched(hdlz::launch_inflate_par(a, st, &used, w), "launch the whole-GPU inflate (k_par_*)");
+        if (rc != HDLZ_OK || used) return rc;
         // (no scratch, or a shape the path leaves alone: the batch kernels below)
     }
-    if (map == Mapping::wave) {
-        hipError_t e = hdlz::launch_inflate_dyn(a, st, true);
-        if (e != hipSuccess) return fail_hip(e, "launch k_inflate_dyn");
-        return HDLZ_OK;
-    }
+    if (map == Mapping::wave) return launched(hdlz::launch_inflate_dyn(a, st, true), "launch k_inflate_dyn");
     // lane per stream, one TOKEN group per round (k_inflate_tok), or 16 lanes per stream
-    hipError_t e = map == Mapping::group ? hdlz::launch_inflate_grp(a, st) : hdlz::launch_inflate_tok(a, st, w);
-    if (e != hipSuccess) return fail_hip(e, "launch k_inflate");
+    if (const int rc = launched(map == Mapping::group ? hdlz::launch_inflate_grp(a, st) : hdlz::launch_inflate_tok(a, st, w), "launch k_inflate"); rc != HDLZ_OK) return rc;
     // second pass, same stream: streams in which pass 1 met a dynamic-tree block (status 6) are redone, again one lane each
     // (k_inflate_tok<true>); everything else is left untouched
-    e = nstreams > 0xFFFFFFFFull ? hdlz::launch_inflate_dyn(a, st, false) : hdlz::launch_inflate_tok_dyn(a, st, false, w);
-    if (e != hipSuccess) return fail_hip(e, "launch the dynamic-tree pass");
-    return HDLZ_OK;
+    return launched(nstreams > 0xFFFFFFFFull ? hdlz::launch_inflate_dyn(a, st, false) : hdlz::launch_inflate_tok_dyn(a, st, false, w),
+                    "launch the dynamic-tree pass");
 }
 }  // namespace
 
@@ -316,16 +348,15 @@ size_t hdlz_inflate_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_
 int hdlz_inflate_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
                           uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
                           uint32_t* d_out_len, uint32_t* d_status, void* d_work, size_t work_bytes, void* stream) {
-    const hdlz::Work w{static_cast<uint8_t*>(d_work), d_work ? work_bytes : 0u, true};
-    return inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, w, stream);
+    return inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status,
+                              caller_work(d_work, work_bytes), stream);
 }
 
 int hdlz_inflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len,
                        uint64_t nstreams, uint32_t flags, uint32_t obsize, uint8_t* d_out, uint64_t out_pitch,
                        uint32_t* d_out_len, uint32_t* d_status, void* stream) {
-    if (nstreams) { const int rc = refuse_capture(stream, "hdlz_inflate_batch_ws"); if (rc != HDLZ_OK) return rc; }
-    const hdlz::Work w{nullptr, 0u, false};                  // scratch from the library's stream-ordered pool
-    return inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, w, stream);
+    if (const int rc = nstreams ? refuse_capture(stream, "hdlz_inflate_batch_ws") : HDLZ_OK; rc != HDLZ_OK) return rc;
+    return inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, pooled_work(), stream);
 }
 
 size_t hdlz_inflate_checked_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_pitch, uint32_t flags, int ragged) {
@@ -343,54 +374,44 @@ int hdlz_inflate_checked(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t
     if (flags & ~INFLATE_FLAGS) return fail_param("unknown flag");
     if (flags & HDLZ_INFLATE_ONEBLOCK) return fail_param("HDLZ_INFLATE_ONEBLOCK: a stream cut at its first block has no trailer behind it");
     const size_t share = hdlz::judge_work_bytes(nstreams, out_pitch);
-    if (share != 0u && (!d_work || work_bytes < share)) return fail_param("d_work smaller than the judging pass's share (hdlz_inflate_checked_work_bytes - hdlz_inflate_work_bytes)");
+    if (work_too_small(share, d_work, work_bytes, "the judging pass's share (hdlz_inflate_checked_work_bytes - hdlz_inflate_work_bytes)")) return HDLZ_E_BAD_PARAM;
     uint8_t* wbase = static_cast<uint8_t*>(d_work);
-    const hdlz::Work w{wbase ? wbase + share : nullptr, wbase ? work_bytes - share : 0u, true};
+    const hdlz::Work w = caller_work(wbase ? wbase + share : nullptr, work_bytes - share);
     const int rc = inflate_batch_impl(d_in, d_in_off, in_pitch, in_len, nstreams, flags, obsize, d_out, out_pitch, d_out_len, d_status, w, stream, d_in_used);
     if (rc != HDLZ_OK || nstreams == 0) return rc;
     const hdlz::JudgeArgs j{d_in, d_in_off, in_pitch, in_len, nstreams, d_out, out_pitch, d_out_len, d_status, d_in_used, d_adler,
                             share ? reinterpret_cast<uint2*>(wbase) : nullptr};
-    const hipError_t e = hdlz::launch_judge(j, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch the judging pass (k_adler_*)");
-    return HDLZ_OK;
+    return launched(hdlz::launch_judge(j, static_cast<hipStream_t>(stream)), "launch the judging pass (k_adler_*)");
 }
 
 int hdlz_compact_batch(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_off,
                        uint64_t nblocks, uint8_t* d_archive, void* stream) {
-    if (nblocks && (!d_rows || !d_len || !d_off || !d_archive)) return fail_param("null device pointer");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    hipError_t e = hdlz::launch_compact(d_rows, row_pitch, d_len, d_off, nblocks, d_archive, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_compact");
-    return HDLZ_OK;
+    if (nblocks && any_null(d_rows, d_len, d_off, d_archive)) return fail_param("null device pointer");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_compact(d_rows, row_pitch, d_len, d_off, nblocks, d_archive, static_cast<hipStream_t>(stream)), "launch k_compact");
 }
 
 static int archive_impl(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, uint64_t nblocks,
                         uint8_t* d_archive, uint64_t archive_cap, uint64_t* d_off, const hdlz::Work& w, void* stream) {
-    if (!d_off || (nblocks && (!d_rows || !d_len || !d_archive))) return fail_param("null device pointer");
+    if (!d_off || (nblocks && any_null(d_rows, d_len, d_archive))) return fail_param("null device pointer");
     if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");   // (32-bit tile and word counts)
-    if (w.caller && nblocks && (!w.base || w.bytes < hdlz::archive_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_archive_work_bytes(nblocks)");
-    if (w.caller && (reinterpret_cast<uintptr_t>(w.base) & 7u)) return fail_param("d_work must be 8-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    hipError_t e = hdlz::launch_archive(d_rows, row_pitch, d_len, nblocks, d_archive, archive_cap, d_off, static_cast<hipStream_t>(stream), w);
-    if (e != hipSuccess) return fail_hip(e, "launch k_archive");
-    return HDLZ_OK;
+    if (w.caller && work_too_small(hdlz::archive_work_bytes(nblocks), w.base, w.bytes, "hdlz_archive_work_bytes(nblocks)")) return HDLZ_E_BAD_PARAM;
+    if (w.caller && misaligned(8, w.base)) return fail_align(8, "d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_archive(d_rows, row_pitch, d_len, nblocks, d_archive, archive_cap, d_off, static_cast<hipStream_t>(stream), w), "launch k_archive");
 }
 
 size_t hdlz_archive_work_bytes(uint64_t nblocks) { return nblocks > 0x7FFFFFFFull ? 0u : hdlz::archive_work_bytes(nblocks); }
 
 int hdlz_archive_batch_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, uint64_t nblocks,
                           uint8_t* d_archive, uint64_t archive_cap, uint64_t* d_off, void* d_work, size_t work_bytes, void* stream) {
-    const hdlz::Work w{static_cast<uint8_t*>(d_work), d_work ? work_bytes : 0u, true};
-    return archive_impl(d_rows, row_pitch, d_len, nblocks, d_archive, archive_cap, d_off, w, stream);
+    return archive_impl(d_rows, row_pitch, d_len, nblocks, d_archive, archive_cap, d_off, caller_work(d_work, work_bytes), stream);
 }
 
 int hdlz_archive_batch(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, uint64_t nblocks,
                        uint8_t* d_archive, uint64_t archive_cap, uint64_t* d_off, void* stream) {
-    if (nblocks) { const int rc = refuse_capture(stream, "hdlz_archive_batch_ws"); if (rc != HDLZ_OK) return rc; }
-    const hdlz::Work w{nullptr, 0u, false};
-    return archive_impl(d_rows, row_pitch, d_len, nblocks, d_archive, archive_cap, d_off, w, stream);
+    if (const int rc = nblocks ? refuse_capture(stream, "hdlz_archive_batch_ws") : HDLZ_OK; rc != HDLZ_OK) return rc;
+    return archive_impl(d_rows, row_pitch, d_len, nblocks, d_archive, archive_cap, d_off, pooled_work(), stream);
 }
 
 size_t hdlz_stream_work_bytes(size_t in_len) { return hdlz_streams_work_bytes(in_len, 1); }
@@ -411,19 +432,17 @@ int hdlz_compress_stream(const uint8_t* d_in, uint32_t in_len, int cwindow, int 
 int hdlz_compress_streams(const uint8_t* d_in, uint64_t in_pitch, uint32_t in_len, uint64_t nblocks, int cwindow,
                           int maxmatch, uint8_t* d_out, uint64_t out_pitch, uint32_t* d_out_len, uint32_t* d_status,
                           void* d_work, size_t work_bytes, void* stream) {
-    if (cwindow < 1 || cwindow > 256) return fail_param("cwindow must be in [1,256]");
-    if (maxmatch != 5 && maxmatch != 10) return fail_param("maxmatch must be 5 (MATCH10=False) or 10 (MATCH10=True)");
+    if (!window_ok(cwindow, maxmatch)) return HDLZ_E_BAD_PARAM;
     if (nblocks == 0) return HDLZ_OK;
-    if (!d_in || !d_out || !d_out_len || !d_status || !d_work) return fail_param("null device pointer");
+    if (any_null(d_in, d_out, d_out_len, d_status, d_work)) return fail_param("null device pointer");
     if (in_len >= 0x80000000u) return fail_param("in_len too large");
-    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail_param("d_out must be 4-byte aligned");
+    if (misaligned(4, d_out)) return fail_align(4, "d_out");
     if (nblocks > 1 && (out_pitch & 3u)) return fail_param("out_pitch must be a multiple of 4");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
+    if (misaligned(8, d_work)) return fail_align(8, "d_work");
     const size_t need_work = hdlz_streams_work_bytes(in_len, nblocks);
     if (need_work == 0) return fail_param("in_len x nblocks too large for one call");
-    if (work_bytes < need_work) return fail_param("d_work smaller than hdlz_streams_work_bytes(in_len, nblocks)");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    if (work_too_small(need_work, d_work, work_bytes, "hdlz_streams_work_bytes(in_len, nblocks)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint64_t need = ((uint64_t)hdlz::out_bound(in_len) + 3u) & ~3ull;
     if (in_len < 5u || out_pitch < need) {            // R0 / capacity: same per-stream status as the batch call
@@ -431,53 +450,54 @@ int hdlz_compress_streams(const uint8_t* d_in, uint64_t in_pitch, uint32_t in_le
         // (a kernel, not hipMemsetD32Async: 32-bit memsets did not survive HIP-graph capture on this stack)
         hipLaunchKernelGGL(k_set_result, dim3(1), dim3(1), 0, st, d_out_len, d_status,
                            in_len < 5u ? (uint32_t)HDLZ_E_SHORT_INPUT : (uint32_t)HDLZ_E_OUT_CAPACITY);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail_hip(e, "launch k_set_result");
-        return HDLZ_OK;
+        return launched(hipGetLastError(), "launch k_set_result");
     }
-    hipError_t e = hdlz::launch_compress_streams(d_in, in_pitch, in_len, (uint32_t)nblocks, cwindow, maxmatch, d_out, out_pitch,
-                                                 d_out_len, d_status, d_work, st);
-    if (e != hipSuccess) return fail_hip(e, "launch k_stream_*");
-    return HDLZ_OK;
+    return launched(hdlz::launch_compress_streams(d_in, in_pitch, in_len, (uint32_t)nblocks, cwindow, maxmatch, d_out, out_pitch, d_out_len, d_status,
+                                                  d_work, st), "launch k_stream_*");
 }
 
 int hdlz_compress_chunk(const uint8_t* d_in, uint32_t in_len, uint32_t q_end, int final, int cwindow, int maxmatch,
                         uint8_t* d_out, uint64_t out_cap, void* d_state, void* stream) {
-    if (cwindow < 1 || cwindow > 256) return fail_param("cwindow must be in [1,256]");
-    if (maxmatch != 5 && maxmatch != 10) return fail_param("maxmatch must be 5 (MATCH10=False) or 10 (MATCH10=True)");
-    if (!d_in || !d_out || !d_state) return fail_param("null device pointer");
+    if (!window_ok(cwindow, maxmatch)) return HDLZ_E_BAD_PARAM;
+    if (any_null(d_in, d_out, d_state)) return fail_param("null device pointer");
     if (in_len >= 0x80000000u) return fail_param("in_len too large");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 3u) || (reinterpret_cast<uintptr_t>(d_state) & 3u)) return fail_param("d_out / d_state must be 4-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    hipError_t e = hdlz::launch_compress_chunk(d_in, in_len, q_end, final, cwindow, maxmatch, d_out, out_cap, d_state,
-                                               static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_compress_chunk");
-    return HDLZ_OK;
+    if (misaligned(4, d_out, d_state)) return fail_align(4, "d_out / d_state");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_compress_chunk(d_in, in_len, q_end, final, cwindow, maxmatch, d_out, out_cap, d_state, static_cast<hipStream_t>(stream)),
+                    "launch k_compress_chunk");
 }
 
 int hdlz_inflate_chunk(const uint8_t* d_in, uint32_t in_len, int final, uint32_t flags, uint32_t obsize, uint8_t* d_out,
                        uint64_t out_cap, uint32_t out_limit, void* d_state, void* stream) {
     if (flags & ~(HDLZ_INFLATE_ASSUME_FIXED | HDLZ_INFLATE_ONEBLOCK)) return fail_param("unknown flag");
-    if (!d_in || !d_out || !d_state) return fail_param("null device pointer");
+    if (any_null(d_in, d_out, d_state)) return fail_param("null device pointer");
     if (in_len >= 0x10000000u) return fail_param("in_len too large (streams are limited to 256 MiB - 1)");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 3u) || (reinterpret_cast<uintptr_t>(d_state) & 3u)) return fail_param("d_out / d_state must be 4-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    hipError_t e = hdlz::launch_inflate_chunk(d_in, in_len, final, flags, obsize, d_out, out_cap, out_limit, d_state,
-                                              static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_inflate_dyn<stream>");
-    return HDLZ_OK;
+    if (misaligned(4, d_out, d_state)) return fail_align(4, "d_out / d_state");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_inflate_chunk(d_in, in_len, final, flags, obsize, d_out, out_cap, out_limit, d_state, static_cast<hipStream_t>(stream)),
+                    "launch k_inflate_dyn<stream>");
 }
 
 // ---- include/hdlz_unjoin.h: a joined stream read back member by member (the member view of the batch decoders; hdlz_unjoin.hip)
 // (and include/hdlz_gzip.h: the gzip form differs in the checksum's share of the scratch and in what runs behind the decode)
-static size_t unjoin_tile_bytes(uint64_t total_out, bool gzip) {
-    return gzip ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(total_out)) : hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(total_out));
+// The scratch of hdlz_unjoin_ws / hdlz_unjoin_gzip_ws, laid out ONCE for the size query and the call: three words per member (length,
+// status, end bit), the checksum's words per 32 KiB tile of the output (gzip: one CRC word; zlib: an (A, C) pair), the decoder's share.
+struct UnjoinScratch {
+    uint32_t *len, *status, *end_bit;
+    uint2* tiles;
+    size_t decode;               // the offset of the decoder's share: it takes what is left from there
+    size_t bytes;
+};
+static UnjoinScratch unjoin_scratch(void* base, uint64_t nmembers, uint64_t total_out, uint32_t flags, bool gzip) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);       // (integer arithmetic: the size query lays out from a null base)
+    const size_t per = hdlz::round256(12u * (size_t)nmembers);
+    const size_t tiles = gzip ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(total_out)) : hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(total_out));
+    auto words = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * nmembers)); };
+    return {words(0), words(1), words(2), reinterpret_cast<uint2*>(b + per), per + tiles,
+            per + tiles + hdlz::round256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1))};
 }
 static size_t unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags, bool gzip) {
-    if (nmembers > 0x7FFFFFFFull) return 0;
-    return hdlz::round256(12u * (size_t)nmembers) + unjoin_tile_bytes(total_out, gzip) + hdlz::round256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1));
+    return nmembers > 0x7FFFFFFFull ? 0u : unjoin_scratch(nullptr, nmembers, total_out, flags, gzip).bytes;
 }
 size_t hdlz_unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) { return unjoin_work_bytes(nmembers, total_out, flags, false); }
 size_t hdlz_unjoin_gzip_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) { return unjoin_work_bytes(nmembers, total_out, flags, true); }
@@ -485,43 +505,32 @@ size_t hdlz_unjoin_gzip_work_bytes(uint64_t nmembers, uint64_t total_out, uint32
 static int unjoin_impl(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
                        uint64_t nmembers, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status,
                        hdlz_unjoin_result* d_result, void* d_work, size_t work_bytes, void* stream, bool gzip) {
-    if (!d_stream || !d_off || !d_result || (out_cap && !d_out)) return fail_param("null device pointer");
+    if (any_null(d_stream, d_off, d_result) || (out_cap && !d_out)) return fail_param("null device pointer");
     if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
     if (flags & ~MAPPING_HINTS) return fail_param("unknown flag (hdlz_unjoin_ws and hdlz_unjoin_gzip_ws take the three mapping hints only)");
     if (flags & (flags - 1u)) return fail_param("contradictory mapping flags");
-    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail_param("d_out must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
-        return fail_param("d_off / d_out_off / d_result must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
-    const size_t need = unjoin_work_bytes(nmembers, out_cap, flags, gzip);
-    if (need != 0u && (!d_work || work_bytes < need))
-        return fail_param(gzip ? "d_work smaller than hdlz_unjoin_gzip_work_bytes(nmembers, out_cap, flags)" : "d_work smaller than hdlz_unjoin_work_bytes(nmembers, out_cap, flags)");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    if (misaligned(4, d_out)) return fail_align(4, "d_out");
+    if (misaligned(8, d_off, d_out_off, d_result)) return fail_align(8, "d_off / d_out_off / d_result");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    const UnjoinScratch s = unjoin_scratch(d_work, nmembers, out_cap, flags, gzip);
+    if (work_too_small(s.bytes, d_work, work_bytes, gzip ? "hdlz_unjoin_gzip_work_bytes(nmembers, out_cap, flags)" : "hdlz_unjoin_work_bytes(nmembers, out_cap, flags)"))
+        return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t* wb = static_cast<uint8_t*>(d_work);
-    uint32_t* words = reinterpret_cast<uint32_t*>(wb);
-    const size_t per = hdlz::round256(12u * (size_t)nmembers), tiles = unjoin_tile_bytes(out_cap, gzip);
     const hdlz::UnjoinArgs u{d_stream, stream_len, d_off, d_out_off, out_len, nmembers, d_out, out_cap, d_member_status, d_result,
-                             words, words + nmembers, words + 2u * nmembers, reinterpret_cast<uint2*>(wb + per)};
-    hipError_t e = hdlz::launch_unjoin_index(u, st);
-    if (e != hipSuccess) return fail_hip(e, "launch k_unjoin_index");
+                             s.len, s.status, s.end_bit, s.tiles};
+    if (const int rc = launched(hdlz::launch_unjoin_index(u, st), "launch k_unjoin_index"); rc != HDLZ_OK) return rc;
     if (nmembers) {
-        hdlz::MemberArgs a;
-        a.in = d_stream; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = nmembers;
-        a.flags = HDLZ_INFLATE_ONEBLOCK;                       // BFINAL is not read: a member is one block
-        a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.len; a.status = u.status; a.in_used = u.end_bit;
-        a.m_off = d_off; a.m_out_off = d_out_off; a.m_out_len = out_len; a.m_out_cap = out_cap;
+        hdlz::MemberArgs a = member_args(d_stream, nmembers, HDLZ_INFLATE_ONEBLOCK, d_out, u.len, u.status, u.end_bit, d_off);   // (BFINAL is not read: a member is one block)
+        a.m_out_off = d_out_off; a.m_out_len = out_len; a.m_out_cap = out_cap;
         // the mapping: the thresholds of hdlz_inflate_batch_ws, or the hint; never the whole-GPU chains
         const Mapping map = mapping_of(nmembers, flags);
-        const hdlz::Work w{wb + per + tiles, work_bytes - per - tiles, true};
-        e = map == Mapping::wave ? hdlz::launch_inflate_dyn_members(a, st) : map == Mapping::group ? hdlz::launch_inflate_grp_members(a, st)
-                                                                                                 : hdlz::launch_inflate_tok_members(a, st, w);
-        if (e != hipSuccess) return fail_hip(e, "launch the member decode");
+        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
+        if (const int rc = launched(map == Mapping::wave ? hdlz::launch_inflate_dyn_members(a, st) : map == Mapping::group ? hdlz::launch_inflate_grp_members(a, st)
+                                                                                                            : hdlz::launch_inflate_tok_members(a, st, w),
+                      "launch the member decode"); rc != HDLZ_OK) return rc;
     }
-    e = gzip ? hdlz::launch_unjoin_gzip_judge(u, st) : hdlz::launch_unjoin_judge(u, st);
-    if (e != hipSuccess) return fail_hip(e, "launch k_unjoin_judge");
-    return HDLZ_OK;
+    return launched(gzip ? hdlz::launch_unjoin_gzip_judge(u, st) : hdlz::launch_unjoin_judge(u, st), "launch k_unjoin_judge");
 }
 
 int hdlz_unjoin_ws(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_off, const uint64_t* d_out_off, uint32_t out_len,
@@ -544,13 +553,10 @@ size_t hdlz_crc32_work_bytes(uint64_t n) { return hdlz::round256(sizeof(uint32_t
 int hdlz_crc32_ws(const uint8_t* d_data, uint64_t n, uint32_t* d_crc, void* d_work, size_t work_bytes, void* stream) {
     if (!d_crc || (n && !d_data)) return fail_param("null device pointer");
     const size_t need = hdlz_crc32_work_bytes(n);
-    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_crc32_work_bytes(n)");
-    if ((reinterpret_cast<uintptr_t>(d_crc) & 3u) || (reinterpret_cast<uintptr_t>(d_work) & 3u)) return fail_param("d_crc / d_work must be 4-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    const hipError_t e = hdlz::launch_crc32(d_data, n, d_crc, static_cast<uint32_t*>(d_work), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_crc32_tiles");
-    return HDLZ_OK;
+    if (work_too_small(need, d_work, work_bytes, "hdlz_crc32_work_bytes(n)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(4, d_crc, d_work)) return fail_align(4, "d_crc / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_crc32(d_data, n, d_crc, static_cast<uint32_t*>(d_work), static_cast<hipStream_t>(stream)), "launch k_crc32_tiles");
 }
 
 size_t hdlz_join_gzip_bound(uint64_t nblocks, uint32_t in_len) { return hdlz_join_bound(nblocks, in_len) + 12u; }
@@ -562,18 +568,11 @@ int hdlz_join_gzip_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t*
                       uint8_t* d_stream, uint64_t stream_cap, uint64_t* d_off, hdlz_join_gzip_result* d_result, void* d_work,
                       size_t work_bytes, void* stream) {
     if (!d_crc) return fail_param("d_crc is required");
-    if (!d_stream || !d_off || !d_result || (nblocks && (!d_rows || !d_len || !d_end_bits || !d_status))) return fail_param("null device pointer");
-    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");
-    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_join_gzip_work_bytes(nblocks)");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u)) return fail_param("d_off / d_result must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    const bool null_pointer = any_null(d_stream, d_off, d_result) || (nblocks && any_null(d_rows, d_len, d_end_bits, d_status));
+    if (const int rc = join_checks(null_pointer, nblocks, d_off, nullptr, d_result, d_crc, d_work, work_bytes, "hdlz_join_gzip_work_bytes(nblocks)", false); rc != HDLZ_OK) return rc;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     const hdlz::JoinArgs a{d_rows, row_pitch, d_len, d_end_bits, d_status, d_in_off, in_len, nblocks, d_stream, stream_cap, d_off, nullptr, {}};
-    hipError_t e = hdlz::launch_join_gzip(a, d_crc, d_result, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_join");
-    return HDLZ_OK;
+    return launched(hdlz::launch_join_gzip(a, d_crc, d_result, d_work, static_cast<hipStream_t>(stream)), "launch k_join");
 }
 
 // ---- include/hdlz_bgzf.h: the CRC-32 of every block of a batch, the BGZF writer, the member index and the reader
@@ -581,13 +580,10 @@ int hdlz_crc32_batch_ws(const uint8_t* d_data, const uint64_t* d_off, uint64_t p
                         void* stream) {
     if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one call (2^31 - 1 blocks)");
     if (nblocks && (!d_crc || (!d_data && (d_off || len)))) return fail_param("null device pointer");
-    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_off) & 7u) return fail_param("d_off must be 8-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    const hipError_t e = hdlz::launch_crc32_batch(d_data, d_off, pitch, len, nblocks, d_crc, nullptr, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_crc32_batch");
-    return HDLZ_OK;
+    if (misaligned(4, d_crc)) return fail_align(4, "d_crc");
+    if (misaligned(8, d_off)) return fail_align(8, "d_off");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_crc32_batch(d_data, d_off, pitch, len, nblocks, d_crc, nullptr, static_cast<hipStream_t>(stream)), "launch k_crc32_batch");
 }
 
 size_t hdlz_bgzf_bound(uint64_t nblocks, uint32_t in_len) { return 28u + (size_t)nblocks * (hdlz_out_bound(in_len) + 20u); }
@@ -597,19 +593,11 @@ size_t hdlz_bgzf_join_work_bytes(uint64_t nblocks) { return hdlz_join_work_bytes
 int hdlz_bgzf_join_ws(const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint32_t* d_status, const uint64_t* d_in_off,
                       uint32_t in_len, uint64_t nblocks, const uint32_t* d_crc, uint8_t* d_file, uint64_t file_cap, uint64_t* d_off,
                       hdlz_bgzf_join_result* d_result, void* d_work, size_t work_bytes, void* stream) {
-    if (!d_file || !d_off || !d_result || (nblocks && (!d_rows || !d_len || !d_status || !d_crc))) return fail_param("null device pointer");
-    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");
-    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks))) return fail_param("d_work smaller than hdlz_bgzf_join_work_bytes(nblocks)");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_in_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
-        return fail_param("d_off / d_in_off / d_result must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    const bool null_pointer = any_null(d_file, d_off, d_result) || (nblocks && any_null(d_rows, d_len, d_status, d_crc));
+    if (const int rc = join_checks(null_pointer, nblocks, d_off, d_in_off, d_result, d_crc, d_work, work_bytes, "hdlz_bgzf_join_work_bytes(nblocks)", true); rc != HDLZ_OK) return rc;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     const hdlz::BgzfJoinArgs a{nullptr, d_in_off, 0u, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file, file_cap, d_off, nullptr, {}};
-    const hipError_t e = hdlz::launch_bgzf_join(a, d_result, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_join<fixed>");
-    return HDLZ_OK;
+    return launched(hdlz::launch_bgzf_join(a, d_result, d_work, static_cast<hipStream_t>(stream)), "launch k_bgzf_join<fixed>");
 }
 
 // ---- include/hdlz_bgzf_stored.h: the BGZF writer that falls back to a stored member
@@ -624,81 +612,68 @@ int hdlz_bgzf_join_stored_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint
                              uint64_t row_pitch, const uint32_t* d_len, const uint32_t* d_status, uint64_t nblocks, const uint32_t* d_crc,
                              uint8_t* d_file, uint64_t file_cap, uint64_t* d_off, uint8_t* d_kind, hdlz_bgzf_stored_result* d_result,
                              void* d_work, size_t work_bytes, void* stream) {
-    if (!d_file || !d_off || !d_result || (nblocks && (!d_in || !d_rows || !d_len || !d_status || !d_crc))) return fail_param("null device pointer");
-    if (nblocks > 0x7FFFFFFFull) return fail_param("nblocks too large for one launch (2^31 - 1 rows)");
-    if (nblocks && (!d_work || work_bytes < hdlz::join_work_bytes(nblocks)))
-        return fail_param("d_work smaller than hdlz_bgzf_join_stored_work_bytes(nblocks)");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7u) return fail_param("d_work must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_in_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
-        return fail_param("d_off / d_in_off / d_result must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_crc) & 3u) return fail_param("d_crc must be 4-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    const bool null_pointer = any_null(d_file, d_off, d_result) || (nblocks && any_null(d_in, d_rows, d_len, d_status, d_crc));
+    if (const int rc = join_checks(null_pointer, nblocks, d_off, d_in_off, d_result, d_crc, d_work, work_bytes, "hdlz_bgzf_join_stored_work_bytes(nblocks)", true); rc != HDLZ_OK) return rc;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     const hdlz::BgzfJoinArgs a{d_in, d_in_off, in_pitch, in_len, d_rows, row_pitch, d_len, d_status, nblocks, d_crc, d_file, file_cap, d_off, d_kind, {}};
-    const hipError_t e = hdlz::launch_bgzf_join_stored(a, d_result, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_join<stored>");
-    return HDLZ_OK;
+    return launched(hdlz::launch_bgzf_join_stored(a, d_result, d_work, static_cast<hipStream_t>(stream)), "launch k_bgzf_join<stored>");
 }
 
 size_t hdlz_bgzf_index_work_bytes(uint64_t file_len) { return hdlz::bgzf_index_work_bytes(file_len); }
 
 int hdlz_bgzf_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off,
                        hdlz_bgzf_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
-    if (!d_off || !d_out_off || !d_result || (file_len && !d_file)) return fail_param("null device pointer");
+    if (any_null(d_off, d_out_off, d_result) || (file_len && !d_file)) return fail_param("null device pointer");
     if (member_cap >= (1ull << 40)) return fail_param("member_cap too large (below 2^40)");
     const size_t need = hdlz::bgzf_index_work_bytes(file_len);
-    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_bgzf_index_work_bytes(file_len)");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_work) & 7u))
-        return fail_param("d_off / d_out_off / d_result / d_work must be 8-byte aligned");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
-    const hipError_t e = hdlz::launch_bgzf_index(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_scan");
-    return HDLZ_OK;
+    if (work_too_small(need, d_work, work_bytes, "hdlz_bgzf_index_work_bytes(file_len)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_off, d_out_off, d_result, d_work)) return fail_align(8, "d_off / d_out_off / d_result / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_bgzf_index(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream)),
+                    "launch k_bgzf_scan");
 }
 
+// The scratch of hdlz_bgzf_inflate_ws, laid out once for the size query and the call: three words per member (length, status, end bit),
+// the two shifted offset arrays of nmembers + 1 words (BgzfArgs::m_off, m_out_off), one CRC word per member.  No members: no scratch.
+struct BgzfScratch {
+    uint32_t *len, *status, *end_bit;
+    uint64_t *m_off, *m_out_off;
+    uint32_t* crc;
+    size_t bytes;
+};
+static BgzfScratch bgzf_inflate_scratch(void* base, uint64_t nmembers) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const size_t per = hdlz::round256(12u * (size_t)nmembers), idx = hdlz::round256(16u * ((size_t)nmembers + 1u));
+    auto words = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * nmembers)); };
+    return {words(0), words(1), words(2), reinterpret_cast<uint64_t*>(b + per), reinterpret_cast<uint64_t*>(b + per + 8u * ((size_t)nmembers + 1u)),
+            reinterpret_cast<uint32_t*>(b + per + idx), nmembers ? per + idx + hdlz::round256(4u * (size_t)nmembers) : 0u};
+}
 size_t hdlz_bgzf_inflate_work_bytes(uint64_t nmembers, uint32_t flags) {
-    if (nmembers == 0 || nmembers > 0x7FFFFFFFull || flags != 0u) return 0;
-    return hdlz::round256(12u * (size_t)nmembers) + hdlz::round256(16u * ((size_t)nmembers + 1u)) + hdlz::round256(4u * (size_t)nmembers);
+    return nmembers > 0x7FFFFFFFull || flags != 0u ? 0u : bgzf_inflate_scratch(nullptr, nmembers).bytes;
 }
 
 int hdlz_bgzf_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_off, const uint64_t* d_out_off, uint64_t nmembers,
                          uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status, hdlz_bgzf_inflate_result* d_result,
                          void* d_work, size_t work_bytes, void* stream) {
-    if (!d_result || (nmembers && (!d_file || !d_off || !d_out_off)) || (out_cap && !d_out)) return fail_param("null device pointer");
+    if (!d_result || (nmembers && any_null(d_file, d_off, d_out_off)) || (out_cap && !d_out)) return fail_param("null device pointer");
     if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
     if (flags != 0u) return fail_param("flags must be 0 (hdlz_bgzf_inflate_ws decodes a wave per member: the mapping hints do not apply)");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
-        return fail_param("d_off / d_out_off / d_result must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
-    const size_t need = hdlz_bgzf_inflate_work_bytes(nmembers, flags);
-    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_bgzf_inflate_work_bytes(nmembers, flags)");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    if (misaligned(8, d_off, d_out_off, d_result)) return fail_align(8, "d_off / d_out_off / d_result");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    const BgzfScratch s = bgzf_inflate_scratch(d_work, nmembers);
+    if (work_too_small(s.bytes, d_work, work_bytes, "hdlz_bgzf_inflate_work_bytes(nmembers, flags)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t* wb = static_cast<uint8_t*>(d_work);
-    uint32_t* words = reinterpret_cast<uint32_t*>(wb);
-    const size_t per = hdlz::round256(12u * (size_t)nmembers), idx = hdlz::round256(16u * ((size_t)nmembers + 1u));
-    uint64_t* moff = reinterpret_cast<uint64_t*>(wb + per);
-    const hdlz::BgzfArgs u{d_file, file_len, d_off, d_out_off, nmembers, d_out, out_cap, d_member_status, d_result, words, words + nmembers,
-                           words + 2u * nmembers, moff, moff + nmembers + 1u, reinterpret_cast<uint32_t*>(wb + per + idx)};
-    hipError_t e = hdlz::launch_bgzf_check(u, st);
-    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_check");
+    const hdlz::BgzfArgs u{d_file, file_len, d_off, d_out_off, nmembers, d_out, out_cap, d_member_status, d_result, s.len, s.status, s.end_bit,
+                           s.m_off, s.m_out_off, s.crc};
+    if (const int rc = launched(hdlz::launch_bgzf_check(u, st), "launch k_bgzf_check"); rc != HDLZ_OK) return rc;
     if (nmembers) {
-        hdlz::MemberArgs a;
-        a.in = d_file; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = nmembers;
-        a.flags = 0;                                           // BFINAL is honoured: a member may hold any number of blocks of any type
-        a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.len; a.status = u.status; a.in_used = u.end_bit;
-        a.m_off = u.m_off; a.m_out_off = u.m_out_off; a.m_out_len = 0; a.m_out_cap = out_cap; a.m_gap = 18u;
-        e = hdlz::launch_inflate_dyn_members(a, st);
-        if (e != hipSuccess) return fail_hip(e, "launch the member decode");
-        e = hdlz::launch_crc32_batch(d_out, u.m_out_off, 0, 0, nmembers, u.crc, u.status, st);
-        if (e != hipSuccess) return fail_hip(e, "launch k_crc32_batch");
+        hdlz::MemberArgs a = member_args(d_file, nmembers, 0, d_out, u.len, u.status, u.end_bit, u.m_off);   // (BFINAL is honoured: a member may hold any number of blocks of any type)
+        a.m_out_off = u.m_out_off; a.m_out_cap = out_cap; a.m_gap = 18u;
+        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+        if (const int rc = launched(hdlz::launch_crc32_batch(d_out, u.m_out_off, 0, 0, nmembers, u.crc, u.status, st), "launch k_crc32_batch"); rc != HDLZ_OK) return rc;
     }
-    e = hdlz::launch_bgzf_judge(u, st);
-    if (e != hipSuccess) return fail_hip(e, "launch k_bgzf_judge");
-    return HDLZ_OK;
+    return launched(hdlz::launch_bgzf_judge(u, st), "launch k_bgzf_judge");
 }
 
 // ---- include/hdlz_bgzf_range.h: a batch of ranges of a BGZF file's data, by byte or virtual offset
@@ -711,39 +686,28 @@ int hdlz_bgzf_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uin
                              const uint64_t* d_ranges, uint64_t nranges, uint32_t flags, uint8_t* d_out, uint64_t out_cap,
                              uint64_t* d_range_off, uint32_t* d_range_status, uint64_t task_cap, hdlz_bgzf_ranges_result* d_result,
                              void* d_work, size_t work_bytes, void* stream) {
-    if (!d_result || !d_range_off || (nranges && (!d_ranges || !d_file || !d_off || !d_out_off)) || (out_cap && !d_out))
-        return fail_param("null device pointer");
+    if (any_null(d_result, d_range_off) || (nranges && any_null(d_ranges, d_file, d_off, d_out_off)) || (out_cap && !d_out)) return fail_param("null device pointer");
     if (nranges > 0x7FFFFFFFull || nmembers > 0x7FFFFFFFull || task_cap > 0x7FFFFFFFull)
         return fail_param("nranges, nmembers and task_cap must be below 2^31");
     if (flags & ~HDLZ_BGZF_RANGE_VIRTUAL) return fail_param("flags: only HDLZ_BGZF_RANGE_VIRTUAL is defined");
-    if ((reinterpret_cast<uintptr_t>(d_off) & 7u) || (reinterpret_cast<uintptr_t>(d_out_off) & 7u) || (reinterpret_cast<uintptr_t>(d_ranges) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_range_off) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
-        return fail_param("d_off / d_out_off / d_ranges / d_range_off / d_result must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_range_status) & 3u) return fail_param("d_range_status must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_work) & 255u) return fail_param("d_work must be 256-byte aligned");
-    const size_t need = hdlz::bgzf_ranges_work_bytes(nranges, task_cap);
-    if (need != 0u && (!d_work || work_bytes < need)) return fail_param("d_work smaller than hdlz_bgzf_ranges_work_bytes(nranges, task_cap, flags)");
-    int rc = check_device();
-    if (rc != HDLZ_OK) return rc;
+    if (misaligned(8, d_off, d_out_off, d_ranges, d_range_off, d_result)) return fail_align(8, "d_off / d_out_off / d_ranges / d_range_off / d_result");
+    if (misaligned(4, d_range_status)) return fail_align(4, "d_range_status");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    if (work_too_small(hdlz::bgzf_ranges_work_bytes(nranges, task_cap), d_work, work_bytes, "hdlz_bgzf_ranges_work_bytes(nranges, task_cap, flags)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hdlz::RangeArgs u = hdlz::bgzf_ranges_args(d_work, nranges, task_cap);
     u.in = d_file; u.in_len = file_len; u.off = d_off; u.out_off = d_out_off; u.nmembers = nmembers;
     u.ranges = d_ranges; u.nranges = nranges; u.flags = flags; u.out = d_out; u.out_cap = out_cap;
     u.range_off = d_range_off; u.range_status = d_range_status; u.task_cap = task_cap; u.result = d_result;
-    hipError_t e = hdlz::launch_bgzf_ranges_plan(u, st);
-    if (e != hipSuccess) return fail_hip(e, "launch the plan kernels (k_ranges_resolve, k_ranges_scan, k_ranges_expand)");
+    if (const int rc = launched(hdlz::launch_bgzf_ranges_plan(u, st), "launch the plan kernels (k_ranges_resolve, k_ranges_scan, k_ranges_expand)"); rc != HDLZ_OK) return rc;
     if (nranges && task_cap) {
-        hdlz::MemberArgs a;
-        a.in = d_file; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = task_cap;   // (slots behind ntasks are marked as refused)
-        a.flags = 0; a.obsize = 0; a.out = d_out; a.out_pitch = 0; a.out_len = u.t_len; a.status = u.t_status; a.in_used = u.t_end_bit;
-        a.m_off = u.t_off; a.m_out_off = nullptr; a.m_out_len = 0; a.m_out_cap = 0; a.m_gap = 0;
+        hdlz::MemberArgs a = member_args(d_file, task_cap, 0, d_out, u.t_len, u.t_status, u.t_end_bit, u.t_off);   // (slots behind ntasks are marked as refused)
         a.m_end = u.t_end; a.m_dst = u.t_dst; a.m_dst_cap = u.t_cap;                               // the task view
-        e = hdlz::launch_inflate_dyn_members(a, st);
-        if (e != hipSuccess) return fail_hip(e, "launch the member decode");
+        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
     }
-    e = hdlz::launch_bgzf_ranges_finish(u, st);
-    if (e != hipSuccess) return fail_hip(e, "launch the finish kernels (k_ranges_crc, k_ranges_judge, k_ranges_slice, k_ranges_finish, k_ranges_record)");
-    return HDLZ_OK;
+    return launched(hdlz::launch_bgzf_ranges_finish(u, st),
+                    "launch the finish kernels (k_ranges_crc, k_ranges_judge, k_ranges_slice, k_ranges_finish, k_ranges_record)");
 }
 
 }  // extern "C"

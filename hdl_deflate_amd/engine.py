@@ -1,5 +1,6 @@
 """Batch engine: thin Python over the C-ABI (include/hdlz.h).  torch is used for device memory and
 streams only.  All tensors live on the GPU; nothing here computes on the CPU."""
+import ctypes
 import functools
 
 import torch
@@ -15,6 +16,23 @@ def _container_is_gzip(container):
     if container not in ("zlib", "gzip"):
         raise ValueError("container must be \"zlib\" or \"gzip\", not %r" % (container,))
     return container == "gzip"
+
+
+def _raise_unless_ok(rec, what, base=0):
+    """a result record whose status is not OK -> HdlzStatusError, with .first_bad (counted from `base`) where the record has the word"""
+    if rec.status != OK:
+        raise HdlzStatusError(rec.status, what, first_bad=base + rec.first_bad if hasattr(rec, "first_bad") else None)
+
+
+def _is_index(t, count=None):
+    """an index array as the library reads it: int64, contiguous, on the device (and of `count` words)"""
+    assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and (count is None or t.numel() == count), \
+        "an index must be a contiguous int64 device tensor" + ("" if count is None else " of %d words" % count)
+
+
+def _block_offsets(plan, n, dev):
+    """the blocks of chain.plan_blocks over n bytes -> their offsets int64[B + 1] on the device"""
+    return torch.tensor([o for o, _ in plan] + [n], dtype=torch.int64).to(dev)
 
 
 def _on_device(fn):
@@ -50,11 +68,56 @@ class Engine(object):
     def _stream():
         return torch.cuda.current_stream().cuda_stream
 
+    def _is_bytes(self, t, name, flat=False, room=0):
+        """a buffer as the library reads or writes it: uint8, contiguous, on this engine's device (`flat`: one-dimensional; `room`: of at
+        least that many bytes)"""
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and (t.dim() == 1 or not flat) and t.numel() >= room, \
+            "%s must be a contiguous%s uint8 device tensor%s" % (name, " flat" if flat else "", " of at least %d bytes" % room if room else "")
+        assert t.device == self.device, "%s on %s, engine on %s" % (name, t.device, self.device)
+
+    def _scratch(self, need, work, dtype=None, full=False):
+        """the scratch of one library call -> (tensor, its pointer or None when it is empty, its bytes).  Default: `need` bytes from
+        torch's allocator, stream-ordered like every other tensor of the call (its blocks start at multiples of 512, which covers the
+        8 and the 256 bytes the calls ask for).  A caller's tensor: of `dtype` where the method states one; `full`: refused here when
+        it holds fewer than `need` bytes -- else the library decides, or takes a path that needs less."""
+        if work is None:
+            work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        assert work.is_cuda and work.is_contiguous() and work.device == self.device and (dtype is None or work.dtype == dtype)
+        nbytes = work.numel() * work.element_size()
+        assert nbytes >= need or not full, "the scratch holds %d bytes, the call needs %d" % (nbytes, need)
+        return work, (work.data_ptr() if nbytes else None), nbytes
+
+    def _record(self, fn, Struct, scratch, *args):
+        """a library call that ends (..., d_result, d_work, work_bytes, stream) -> its result record: the record's tensor sized by the
+        struct, the call with `scratch` (what _scratch returned) and its check, the record read back -- the one host sync"""
+        result = torch.empty(ctypes.sizeof(Struct) // 8, dtype=torch.int64, device=self.device)
+        self._check(getattr(self.lib, fn)(*args, result.data_ptr(), scratch[1], scratch[2], self._stream()), fn)
+        return Struct.from_buffer_copy(result.cpu().numpy().tobytes())
+
+    def _aligned_input(self, d_in, n):
+        """the compress kernels load whole 16-byte pieces: an input that does not start at a multiple of 16 or has fewer than 16 bytes
+        of its storage behind its n bytes is copied to a padded buffer first"""
+        slack = d_in.untyped_storage().nbytes() - d_in.storage_offset() - n
+        return self._stage(d_in) if d_in.data_ptr() % 16 or slack < 16 else d_in
+
+    def _file_index(self, d_file, index, what):
+        """the (member_offsets, out_offsets) of a BGZF file: the caller's, or taken here (bgzf_index) -- a file whose index stops with
+        a status raises it, with .first_bad = the number of sound members"""
+        if index is None:
+            off, out_off, rec = self.bgzf_index(d_file)
+            if rec.status != OK:
+                raise HdlzStatusError(rec.status, "%s: the file's member index" % what, first_bad=rec.nmembers)
+        else:
+            off, out_off = index[0], index[1]
+        _is_index(off)
+        _is_index(out_off, off.numel())
+        assert off.numel() >= 1
+        return off, out_off
+
     def _prep(self, d_in, in_off, in_len, nblocks):
-        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
-        assert d_in.device == self.device, "tensor on %s, engine on %s" % (d_in.device, self.device)
+        self._is_bytes(d_in, "d_in")
         if in_off is not None:
-            assert in_off.is_cuda and in_off.dtype == torch.int64 and in_off.is_contiguous()
+            _is_index(in_off)
             nb = in_off.numel() - 1
             return in_off.data_ptr(), 0, (0 if in_len is None else in_len), nb
         assert d_in.dim() == 2 or nblocks is not None
@@ -111,10 +174,9 @@ class Engine(object):
             # (a too small out_pitch stays on the batch path, which reports E_OUT_CAPACITY per block instead of failing the call)
             # few large blocks: one wave per block (hdlz_compress_batch) would leave the GPU idle (a 1 MiB block is 5.5 ms
             # on a wave); all tiles of all blocks go through the stream passes together instead (same bytes)
-            work = torch.empty((self.lib.hdlz_streams_work_bytes(ilen, nb) + 7) // 8, dtype=torch.int64, device=d_in.device)
+            work, wptr, wbytes = self._scratch(self.lib.hdlz_streams_work_bytes(ilen, nb), None)
             rc = self.lib.hdlz_compress_streams(d_in.data_ptr(), pitch, ilen, nb, cwindow, maxmatch, out.data_ptr(), out_pitch,
-                                                out_len.data_ptr(), status.data_ptr(), work.data_ptr(),
-                                                work.numel() * 8, self._stream())
+                                                out_len.data_ptr(), status.data_ptr(), wptr, wbytes, self._stream())
             self._check(rc, "hdlz_compress_streams")
             return out, out_len, status
         rc = self.lib.hdlz_compress_batch(d_in.data_ptr(), off_ptr, pitch, ilen, nb, cwindow, maxmatch,
@@ -129,17 +191,13 @@ class Engine(object):
         """d_buf: flat uint8 device tensor, any alignment -> uint32 device tensor[1] holding zlib.crc32 of its bytes (hdlz_crc32_ws).
         No host sync: the word is ready in stream order.  `out`: the tensor to write (default: allocated here); `work`: the call's
         scratch, a device tensor of at least hdlz_crc32_work_bytes(n) bytes (default: allocated here)."""
-        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.dim() == 1 and d_buf.is_contiguous() and d_buf.device == self.device
+        self._is_bytes(d_buf, "d_buf", flat=True)
         n, dev = d_buf.numel(), d_buf.device
         if out is None:
             out = torch.empty(1, dtype=torch.uint32, device=dev)
         assert out.is_cuda and out.dtype == torch.uint32 and out.numel() >= 1 and out.device == self.device
-        need = self.lib.hdlz_crc32_work_bytes(n)
-        if work is None:
-            work = torch.empty((need + 3) // 4, dtype=torch.int32, device=dev)
-        assert work.is_cuda and work.is_contiguous() and work.device == self.device and work.numel() * work.element_size() >= need
-        rc = self.lib.hdlz_crc32_ws(d_buf.data_ptr() if n else None, n, out.data_ptr(), work.data_ptr() if need else None,
-                                    work.numel() * work.element_size(), self._stream())
+        work, wptr, wbytes = self._scratch(self.lib.hdlz_crc32_work_bytes(n), work, full=True)
+        rc = self.lib.hdlz_crc32_ws(d_buf.data_ptr() if n else None, n, out.data_ptr(), wptr, wbytes, self._stream())
         self._check(rc, "hdlz_crc32_ws")
         return out
 
@@ -157,43 +215,31 @@ class Engine(object):
         on the same stream in front of the compression (hdlz_crc32_ws), `out` defaults to hdlz_join_gzip_bound(B, block) bytes."""
         from .chain import plan_blocks
         gz = _container_is_gzip(container)
-        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.dim() == 1 and d_in.is_contiguous() and d_in.device == self.device
+        bound, join, Result = (self.lib.hdlz_join_gzip_bound, "hdlz_join_gzip_ws", _lib.JoinGzipResult) if gz else \
+            (self.lib.hdlz_join_bound, "hdlz_join_batch_ws", _lib.JoinResult)
+        self._is_bytes(d_in, "d_in", flat=True)
         if not 32 <= block < (1 << 31):
             raise ValueError("block must be in [32, 2^31)")           # (plan_blocks may shorten a block by 16 bytes; a block is below 2 GiB)
         n = d_in.numel()
         plan = plan_blocks(n, block)
         B, dev = len(plan), d_in.device
-        slack = d_in.untyped_storage().nbytes() - d_in.storage_offset() - n
-        if d_in.data_ptr() % 16 or slack < 16:
-            d_in = self._stage(d_in)
-        in_off = torch.tensor([o for o, _ in plan] + [n], dtype=torch.int64).to(dev)
+        d_in = self._aligned_input(d_in, n)
+        in_off = _block_offsets(plan, n, dev)
         pitch = pitch_for(block)
         rows, out_len, status = self._results(None, (B, pitch), B, dev)
         end_bits = torch.empty(B, dtype=torch.int64, device=dev)
-        cap = self.lib.hdlz_join_gzip_bound(B, block) if gz else self.lib.hdlz_join_bound(B, block)
         if out is None:
-            out = torch.empty(cap, dtype=torch.uint8, device=dev)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+            out = torch.empty(bound(B, block), dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out")
         offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        result = torch.empty(2, dtype=torch.int64, device=dev)                     # hdlz_join_result: 16 bytes
-        work = torch.empty(max(8, self.lib.hdlz_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)      # (the gzip join asks for the same)
+        scratch = self._scratch(self.lib.hdlz_join_work_bytes(B), None)                    # (the gzip join asks for the same)
         crc = self.crc32(d_in[:n]) if gz else None
         rc = self.lib.hdlz_compress_batch_bits(d_in.data_ptr(), in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
                                                out_len.data_ptr(), status.data_ptr(), end_bits.data_ptr(), self._stream())
         self._check(rc, "hdlz_compress_batch_bits")
-        if gz:
-            rc = self.lib.hdlz_join_gzip_ws(rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(),
-                                            in_off.data_ptr(), block, B, crc.data_ptr(), out.data_ptr(), out.numel(), offsets.data_ptr(),
-                                            result.data_ptr(), work.data_ptr(), work.numel() * 8, self._stream())
-            self._check(rc, "hdlz_join_gzip_ws")
-        else:
-            rc = self.lib.hdlz_join_batch_ws(rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(),
-                                             in_off.data_ptr(), block, B, out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
-                                             work.data_ptr(), work.numel() * 8, self._stream())
-            self._check(rc, "hdlz_join_batch_ws")
-        rec = _lib.JoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
-        if rec.status != OK:
-            raise HdlzStatusError(rec.status, "compress_joined")
+        rec = self._record(join, Result, scratch, rows.data_ptr(), pitch, out_len.data_ptr(), end_bits.data_ptr(), status.data_ptr(), in_off.data_ptr(),
+                           block, B, *([crc.data_ptr()] if gz else []), out.data_ptr(), out.numel(), offsets.data_ptr())
+        _raise_unless_ok(rec, "compress_joined")
         return out[:rec.stream_len], offsets
 
     # -- STARTD for a joined stream, member by member in parallel (include/hdlz_unjoin.h)
@@ -212,10 +258,10 @@ class Engine(object):
         hdlz_unjoin_gzip_ws; its scratch is hdlz_unjoin_gzip_work_bytes(B, total, flags) bytes."""
         from .chain import plan_blocks
         gz = _container_is_gzip(container)
-        work_bytes, unjoin = (self.lib.hdlz_unjoin_gzip_work_bytes, self.lib.hdlz_unjoin_gzip_ws) if gz else \
-            (self.lib.hdlz_unjoin_work_bytes, self.lib.hdlz_unjoin_ws)
-        assert d_stream.is_cuda and d_stream.dtype == torch.uint8 and d_stream.dim() == 1 and d_stream.is_contiguous() and d_stream.device == self.device
-        assert member_offsets.is_cuda and member_offsets.dtype == torch.int64 and member_offsets.is_contiguous()
+        work_bytes, unjoin, Result = (self.lib.hdlz_unjoin_gzip_work_bytes, "hdlz_unjoin_gzip_ws", _lib.UnjoinGzipResult) if gz else \
+            (self.lib.hdlz_unjoin_work_bytes, "hdlz_unjoin_ws", _lib.UnjoinResult)
+        self._is_bytes(d_stream, "d_stream", flat=True)
+        _is_index(member_offsets)
         B, dev = member_offsets.numel() - 1, d_stream.device
         out_len = 0
         if block is not None:
@@ -230,31 +276,20 @@ class Engine(object):
             if B and all(ln == block for _, ln in plan):
                 out_len = block                                      # uniform: no offset array at all
             else:
-                out_offsets = torch.tensor([o for o, _ in plan] + [total], dtype=torch.int64).to(dev)
+                out_offsets = _block_offsets(plan, total, dev)
         elif out_offsets is None:
             raise ValueError("one of block= and out_offsets= says where the members go")
         if out_offsets is not None:
-            assert out_offsets.is_cuda and out_offsets.dtype == torch.int64 and out_offsets.numel() == B + 1 and out_offsets.is_contiguous()
+            _is_index(out_offsets, B + 1)
         if total is None:
             total = out.numel() if out is not None else int(out_offsets[B].item())
         if out is None:
             out = torch.empty(total, dtype=torch.uint8, device=dev)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.numel() >= total
-        need = work_bytes(B, total, flags)
-        if work is None:
-            work = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
-        result = torch.empty(3, dtype=torch.int64, device=dev)                     # hdlz_unjoin_result / hdlz_unjoin_gzip_result: 24 bytes
-        rc = unjoin(d_stream.data_ptr(), d_stream.numel(), member_offsets.data_ptr(),
-                    out_offsets.data_ptr() if out_offsets is not None else None, out_len, B, flags,
-                    out.data_ptr() if total else None, total, None, result.data_ptr(),
-                    work.data_ptr() if work.numel() else None, work.numel(), self._stream())
-        self._check(rc, "hdlz_unjoin_gzip_ws" if gz else "hdlz_unjoin_ws")
-        rec = _lib.UnjoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
-        if rec.status != OK:
-            err = HdlzStatusError(rec.status, "inflate_joined")
-            err.first_bad = rec.first_bad
-            raise err
+        self._is_bytes(out, "out", room=total)
+        rec = self._record(unjoin, Result, self._scratch(work_bytes(B, total, flags), work, torch.uint8), d_stream.data_ptr(), d_stream.numel(),
+                           member_offsets.data_ptr(), out_offsets.data_ptr() if out_offsets is not None else None, out_len, B, flags,
+                           out.data_ptr() if total else None, total, None)
+        _raise_unless_ok(rec, "inflate_joined")
         return out[:rec.out_len]
 
     # -- BGZF, the self-indexing blocked gzip (include/hdlz_bgzf.h): CRC-32 per block, the writer, the member index, the reader
@@ -264,9 +299,10 @@ class Engine(object):
         d_buf: uint8 device tensor, any alignment.  offsets: int64[B + 1] on the device, ascending: block b is the flat
         d_buf[offsets[b] - offsets[0] : offsets[b + 1] - offsets[0]]; else d_buf is [B, pitch] (or flat with pitch= and length=) and
         block b the first `length` (default: pitch) bytes of row b."""
-        assert d_buf.is_cuda and d_buf.dtype == torch.uint8 and d_buf.is_contiguous() and d_buf.device == self.device
+        self._is_bytes(d_buf, "d_buf")
         if offsets is not None:
-            assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() >= 1
+            _is_index(offsets)
+            assert offsets.numel() >= 1
             B, off_ptr, pitch, length = offsets.numel() - 1, offsets.data_ptr(), 0, 0
         else:
             if d_buf.dim() == 2:
@@ -301,54 +337,40 @@ class Engine(object):
         give a valid file of two members, and the default `out` is hdlz_bgzf_stored_bound(B, block) bytes.  The blocks and the rows
         are the same either way, so an input whose blocks all compress gives the same file with and without it."""
         from .chain import plan_blocks
-        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.dim() == 1 and d_in.is_contiguous() and d_in.device == self.device
+        self._is_bytes(d_in, "d_in", flat=True)
         if stored and not 32 <= block <= 65505:
             raise ValueError("block must be in [32, 65505]: a stored BGZF member holds at most 65505 bytes")
         if not 32 <= block <= 65536:
             raise ValueError("block must be in [32, 65536]: a BGZF member holds at most 64 KiB")
+        bound, join, Result = (self.lib.hdlz_bgzf_stored_bound, "hdlz_bgzf_join_stored_ws", _lib.BgzfStoredResult) if stored else \
+            (self.lib.hdlz_bgzf_bound, "hdlz_bgzf_join_ws", _lib.BgzfJoinResult)
         n, dev = d_in.numel(), d_in.device
         plan = [(0, n)] if stored and 0 < n < 5 else plan_blocks(n, block) if n else []      # (below 5 bytes the compressor never starts)
         B = len(plan)
         if n:
-            slack = d_in.untyped_storage().nbytes() - d_in.storage_offset() - n
-            if d_in.data_ptr() % 16 or slack < 16:
-                d_in = self._stage(d_in)
-        in_off = torch.tensor([o for o, _ in plan] + [n], dtype=torch.int64).to(dev)
+            d_in = self._aligned_input(d_in, n)
+        in_off = _block_offsets(plan, n, dev)
         pitch = pitch_for(block)
         rows, out_len, status = self._results(None, (B, pitch), B, dev)
         if out is None:
-            out = torch.empty((self.lib.hdlz_bgzf_stored_bound if stored else self.lib.hdlz_bgzf_bound)(B, block), dtype=torch.uint8, device=dev)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+            out = torch.empty(bound(B, block), dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out")
         offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        result = torch.empty(3 if stored else 2, dtype=torch.int64, device=dev)    # hdlz_bgzf_stored_result: 24 bytes; hdlz_bgzf_join_result: 16
-        work = torch.empty(max(8, self.lib.hdlz_bgzf_join_work_bytes(B)) // 8, dtype=torch.int64, device=dev)
+        scratch = self._scratch(self.lib.hdlz_bgzf_join_work_bytes(B), None)               # (no blocks: none; the stored join asks for the same)
         crc = self.crc32_batch(d_in[:n], offsets=in_off)
         if B:
             rc = self.lib.hdlz_compress_batch(d_in.data_ptr(), in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
                                               out_len.data_ptr(), status.data_ptr(), self._stream())
             self._check(rc, "hdlz_compress_batch")
-        if stored:
-            rc = self.lib.hdlz_bgzf_join_stored_ws(d_in.data_ptr() if B else None, in_off.data_ptr(), 0, block, rows.data_ptr() if B else None, pitch,
-                                                   out_len.data_ptr() if B else None, status.data_ptr() if B else None, B,
-                                                   crc.data_ptr() if B else None, out.data_ptr(), out.numel(), offsets.data_ptr(), None,
-                                                   result.data_ptr(), work.data_ptr() if B else None, work.numel() * 8 if B else 0, self._stream())
-            self._check(rc, "hdlz_bgzf_join_stored_ws")
-            rec = _lib.BgzfStoredResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
-            if rec.status != OK:
-                err = HdlzStatusError(rec.status, "compress_bgzf")
-                err.first_bad = rec.first_bad
-                raise err
-            return out[:rec.file_len]
-        rc = self.lib.hdlz_bgzf_join_ws(rows.data_ptr() if B else None, pitch, out_len.data_ptr() if B else None,
-                                        status.data_ptr() if B else None, in_off.data_ptr(), block, B, crc.data_ptr() if B else None,
-                                        out.data_ptr(), out.numel(), offsets.data_ptr(), result.data_ptr(),
-                                        work.data_ptr() if B else None, work.numel() * 8 if B else 0, self._stream())
-        self._check(rc, "hdlz_bgzf_join_ws")
-        rec = _lib.BgzfJoinResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
-        if rec.status != OK:
-            err = HdlzStatusError(rec.status, "compress_bgzf")
-            err.first_bad = rec.first_bad
-            raise err
+        ptr = lambda t: t.data_ptr() if B else None                                        # (no blocks: the per-block arrays are null)
+        row_args = (ptr(rows), pitch, ptr(out_len), ptr(status))
+        file_args = (ptr(crc), out.data_ptr(), out.numel(), offsets.data_ptr())
+        if stored:                                                                         # the input itself in front, d_kind (not asked for) behind
+            args = (ptr(d_in), in_off.data_ptr(), 0, block) + row_args + (B,) + file_args + (None,)
+        else:
+            args = row_args + (in_off.data_ptr(), block, B) + file_args
+        rec = self._record(join, Result, scratch, *args)
+        _raise_unless_ok(rec, "compress_bgzf")
         return out[:rec.file_len]
 
     @_on_device
@@ -359,19 +381,14 @@ class Engine(object):
         not OK is returned, not raised: the M members in front of the failure stay valid and indexed.  The members are found on the
         device; one host sync for the record.  member_cap: room for that many members (default: a guess, file_len // 4096 + 16); when
         the file holds more, the call is made once more with the true count."""
-        assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.dim() == 1 and d_file.is_contiguous() and d_file.device == self.device
+        self._is_bytes(d_file, "d_file", flat=True)
         n, dev = d_file.numel(), d_file.device
         cap = n // 4096 + 16 if member_cap is None else int(member_cap)
-        need = self.lib.hdlz_bgzf_index_work_bytes(n)
-        work = torch.empty(max(8, need) // 8, dtype=torch.int64, device=dev)
-        result = torch.empty(4, dtype=torch.int64, device=dev)                     # hdlz_bgzf_index_result: 32 bytes
+        scratch = self._scratch(self.lib.hdlz_bgzf_index_work_bytes(n), None)
         while True:
             off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
             out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
-            rc = self.lib.hdlz_bgzf_index_ws(d_file.data_ptr() if n else None, n, cap, off.data_ptr(), out_off.data_ptr(), result.data_ptr(),
-                                             work.data_ptr() if need else None, work.numel() * 8, self._stream())
-            self._check(rc, "hdlz_bgzf_index_ws")
-            rec = _lib.BgzfIndexResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
+            rec = self._record("hdlz_bgzf_index_ws", _lib.BgzfIndexResult, scratch, d_file.data_ptr() if n else None, n, cap, off.data_ptr(), out_off.data_ptr())
             if rec.status != E_OUT_CAPACITY or rec.nmembers <= cap:
                 return off[:rec.nmembers + 1], out_off[:rec.nmembers + 1], rec
             cap = rec.nmembers
@@ -385,18 +402,9 @@ class Engine(object):
         as that slice of the whole output.  One host sync for the record (and one for the range's length); raises HdlzStatusError --
         with .first_bad, counted from b0 -- on a status that is not OK.  `work`: the call's scratch, a uint8 device tensor of at
         least hdlz_bgzf_inflate_work_bytes(b1 - b0, 0) bytes at a multiple of 256 (default: allocated here)."""
-        assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.dim() == 1 and d_file.is_contiguous() and d_file.device == self.device
+        self._is_bytes(d_file, "d_file", flat=True)
         dev = d_file.device
-        if index is None:
-            off, out_off, rec = self.bgzf_index(d_file)
-            if rec.status != OK:
-                err = HdlzStatusError(rec.status, "inflate_bgzf: the file's member index")
-                err.first_bad = rec.nmembers
-                raise err
-        else:
-            off, out_off = index[0], index[1]
-        assert off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and out_off.is_cuda and out_off.dtype == torch.int64 and \
-            out_off.is_contiguous() and off.numel() == out_off.numel() >= 1
+        off, out_off = self._file_index(d_file, index, "inflate_bgzf")
         M = off.numel() - 1
         b0, b1 = (0, M) if members is None else (int(members[0]), int(members[1]))
         if not 0 <= b0 <= b1 <= M:
@@ -405,21 +413,11 @@ class Engine(object):
         total = int((out_off[B] - out_off[0]).item()) if B else 0
         if out is None:
             out = torch.empty(total, dtype=torch.uint8, device=dev)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.numel() >= total
-        need = self.lib.hdlz_bgzf_inflate_work_bytes(B, 0)
-        if work is None:
-            work = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
-        result = torch.empty(3, dtype=torch.int64, device=dev)                     # hdlz_bgzf_inflate_result: 24 bytes
-        rc = self.lib.hdlz_bgzf_inflate_ws(d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B, 0,
-                                           out.data_ptr() if total else None, total, None, result.data_ptr(),
-                                           work.data_ptr() if need else None, work.numel(), self._stream())
-        self._check(rc, "hdlz_bgzf_inflate_ws")
-        rec = _lib.BgzfInflateResult.from_buffer_copy(result.cpu().numpy().tobytes())   # the one host sync
-        if rec.status != OK:
-            err = HdlzStatusError(rec.status, "inflate_bgzf")
-            err.first_bad = rec.first_bad
-            raise err
+        self._is_bytes(out, "out", room=total)
+        rec = self._record("hdlz_bgzf_inflate_ws", _lib.BgzfInflateResult, self._scratch(self.lib.hdlz_bgzf_inflate_work_bytes(B, 0), work, torch.uint8),
+                           d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B, 0,
+                           out.data_ptr() if total else None, total, None)
+        _raise_unless_ok(rec, "inflate_bgzf")
         return out[:rec.out_len]
 
     def compress_bgzf_bytes(self, data, block=57344, cwindow=32, maxmatch=10, stored=False):
@@ -439,17 +437,13 @@ class Engine(object):
     # -- random access into a BGZF file (include/hdlz_bgzf_range.h): a batch of ranges by byte or virtual offset
     def _read_ranges(self, d_file, off, out_off, ranges, flags, out, out_cap, task_cap, work):
         """one hdlz_bgzf_read_ranges_ws call and its host sync -> (record, range_off int64[R + 1])"""
-        R, dev = ranges.shape[0], d_file.device
-        range_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
-        result = torch.empty(4, dtype=torch.int64, device=dev)                     # hdlz_bgzf_ranges_result: 32 bytes
-        need = self.lib.hdlz_bgzf_ranges_work_bytes(R, task_cap, flags)
-        assert work.numel() >= need, "the scratch holds %d bytes, the call needs %d" % (work.numel(), need)
-        rc = self.lib.hdlz_bgzf_read_ranges_ws(d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(),
-                                               off.numel() - 1, ranges.data_ptr() if R else None, R, flags,
-                                               out.data_ptr() if out_cap else None, out_cap, range_off.data_ptr(), None, task_cap,
-                                               result.data_ptr(), work.data_ptr() if need else None, work.numel(), self._stream())
-        self._check(rc, "hdlz_bgzf_read_ranges_ws")
-        return _lib.BgzfRangesResult.from_buffer_copy(result.cpu().numpy().tobytes()), range_off     # the one host sync
+        R = ranges.shape[0]
+        range_off = torch.empty(R + 1, dtype=torch.int64, device=d_file.device)
+        scratch = self._scratch(self.lib.hdlz_bgzf_ranges_work_bytes(R, task_cap, flags), work, torch.uint8, full=True)
+        rec = self._record("hdlz_bgzf_read_ranges_ws", _lib.BgzfRangesResult, scratch, d_file.data_ptr() if d_file.numel() else None, d_file.numel(),
+                           off.data_ptr(), out_off.data_ptr(), off.numel() - 1, ranges.data_ptr() if R else None, R, flags,
+                           out.data_ptr() if out_cap else None, out_cap, range_off.data_ptr(), None, task_cap)
+        return rec, range_off
 
     @_on_device
     def read_bgzf(self, d_file, ranges, index=None, virtual=False, out=None, work=None, max_work_bytes=256 << 20):
@@ -468,18 +462,9 @@ class Engine(object):
         as far as max_work_bytes lets them fit --, else the call that missed was the sizing call and a second one follows.
         `work`: the groups' scratch, a uint8 device tensor at a multiple of 256 whose size stands in for max_work_bytes.
         Raises HdlzStatusError with .first_bad = the index of the lowest failed range over all groups."""
-        assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.dim() == 1 and d_file.is_contiguous() and d_file.device == self.device
+        self._is_bytes(d_file, "d_file", flat=True)
         dev = d_file.device
-        if index is None:
-            off, out_off, rec = self.bgzf_index(d_file)
-            if rec.status != OK:
-                err = HdlzStatusError(rec.status, "read_bgzf: the file's member index")
-                err.first_bad = rec.nmembers
-                raise err
-        else:
-            off, out_off = index[0], index[1]
-        assert off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and out_off.is_cuda and out_off.dtype == torch.int64 and \
-            out_off.is_contiguous() and off.numel() == out_off.numel() >= 1
+        off, out_off = self._file_index(d_file, index, "read_bgzf")
         if not torch.is_tensor(ranges):
             pairs = [[int(v) - (1 << 64) if int(v) >= 1 << 63 else int(v) for v in pair] for pair in ranges]      # the words are unsigned
             ranges = torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
@@ -487,10 +472,10 @@ class Engine(object):
         R, flags = ranges.shape[0], _lib.BGZF_RANGE_VIRTUAL if virtual else 0
         query = self.lib.hdlz_bgzf_ranges_work_bytes
         if work is not None:
-            assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
+            self._is_bytes(work, "work")
             max_work_bytes = work.numel()
         if out is not None:
-            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+            self._is_bytes(out, "out")
         group = max(1, (max_work_bytes - 8192) // (131072 + 256))                  # ranges of two members each
         while group > 1 and query(group, 2 * group, flags) > max_work_bytes:
             group -= 1
@@ -522,10 +507,7 @@ class Engine(object):
                 if out is None:
                     dst = torch.empty(rec.total_out, dtype=torch.uint8, device=dev)
                 rec, range_off = self._read_ranges(d_file, off, out_off, rg, flags, dst, dst.numel(), rec.ntasks, scratch(n, rec.ntasks))
-            if rec.status != OK:
-                err = HdlzStatusError(rec.status, "read_bgzf")
-                err.first_bad = g0 + rec.first_bad
-                raise err
+            _raise_unless_ok(rec, "read_bgzf", base=g0)
             pieces.append(dst[:rec.total_out])
             offsets.append(range_off[:-1] + pos)
             pos += rec.total_out
@@ -552,14 +534,12 @@ class Engine(object):
     def compress_stream(self, d_in, n, cwindow=32, maxmatch=10, out=None, work=None):
         """d_in: flat uint8 device tensor, readable up to n rounded up to 16.
         Returns (out uint8[cap], out_len int32[1], status int32[1])."""
-        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous() and d_in.numel() >= (n + 15) // 16 * 16
+        self._is_bytes(d_in, "d_in", room=(n + 15) // 16 * 16)
         cap = pitch_for(n)
         out, out_len, status = self._results(out, cap, 1, d_in.device)
-        if work is None:
-            work = torch.empty((self.lib.hdlz_stream_work_bytes(n) + 7) // 8, dtype=torch.int64, device=d_in.device)
+        work, wptr, wbytes = self._scratch(self.lib.hdlz_stream_work_bytes(n), work)
         rc = self.lib.hdlz_compress_stream(d_in.data_ptr(), n, cwindow, maxmatch, out.data_ptr(), out.numel(),
-                                           out_len.data_ptr(), status.data_ptr(), work.data_ptr(),
-                                           work.numel() * work.element_size(), self._stream())
+                                           out_len.data_ptr(), status.data_ptr(), wptr, wbytes, self._stream())
         self._check(rc, "hdlz_compress_stream")
         return out, out_len, status
 
@@ -592,11 +572,10 @@ class Engine(object):
         off_ptr, pitch, ilen, nb = self._prep(d_in, in_off, in_len, nblocks)
         assert out_pitch is not None and out_pitch % 4 == 0
         res = self._results(out, (nb, out_pitch), nb, d_in.device, checked)
-        if work is None:
-            work = torch.empty(getattr(self.lib, sizer)(nb, ilen, out_pitch, flags, 0 if in_off is None else 1), dtype=torch.uint8, device=d_in.device)
-        assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.device == self.device
+        need = getattr(self.lib, sizer)(nb, ilen, out_pitch, flags, 0 if in_off is None else 1) if work is None else 0      # (a caller's: as it is)
+        work, wptr, wbytes = self._scratch(need, work, torch.uint8)
         rc = getattr(self.lib, call)(d_in.data_ptr(), off_ptr, pitch, ilen, nb, flags, obsize, res[0].data_ptr(), out_pitch,
-                                     *[t.data_ptr() for t in res[1:]], work.data_ptr() if work.numel() else None, work.numel(), self._stream())
+                                     *[t.data_ptr() for t in res[1:]], wptr, wbytes, self._stream())
         self._check(rc, call)
         return res
 
@@ -636,12 +615,12 @@ class Engine(object):
             archive = torch.empty(B * pitch, dtype=torch.uint8, device=rows.device)
         if offsets is None:
             offsets = torch.empty(B + 1, dtype=torch.int64, device=rows.device)
-        assert archive.is_cuda and archive.dtype == torch.uint8 and archive.is_contiguous()
-        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.numel() == B + 1 and offsets.is_contiguous()
-        if work is None:                 # the call's scratch (8 bytes per 256 rows), caller-owned like every other buffer of the call
-            work = torch.empty(max(8, self.lib.hdlz_archive_work_bytes(B)) // 8, dtype=torch.int64, device=rows.device)
+        self._is_bytes(archive, "archive")
+        _is_index(offsets, B + 1)
+        # the call's scratch (8 bytes per 256 rows), caller-owned like every other buffer of the call
+        work, wptr, wbytes = self._scratch(self.lib.hdlz_archive_work_bytes(B), work)
         rc = self.lib.hdlz_archive_batch_ws(rows.data_ptr(), pitch, lens.data_ptr(), B, archive.data_ptr(), archive.numel(),
-                                            offsets.data_ptr(), work.data_ptr(), work.numel() * work.element_size(), self._stream())
+                                            offsets.data_ptr(), wptr, wbytes, self._stream())
         self._check(rc, "hdlz_archive_batch_ws")
         return archive, offsets
 

@@ -4,9 +4,14 @@ class Error(Exception):
 
 
 class HdlzStatusError(Error):
-    def __init__(self, status, what=""):
+    """a result record whose status is not OK.  first_bad: the record's word (the lowest failed member, block or range) where the
+    call has one -- the attribute exists only then"""
+
+    def __init__(self, status, what="", first_bad=None):
         from .constants import STATUS_NAMES
         self.status = int(status)
+        if first_bad is not None:
+            self.first_bad = first_bad
         super().__init__("%s: status %d (%s)" % (what, self.status, STATUS_NAMES.get(self.status, "?")))
 
 

@@ -4,15 +4,13 @@ of the GPU tests (members from stock zlib, the serial walk of the index call), h
 trusted to it."""
 import ctypes
 import gzip
-import os
-import re
 import zlib
 
 import numpy as np
 import pytest
 
-from conftest import REPO
 import bgzf_ref
+from cabi_common import check_struct_mirror, declarations, header, host_buffer as _host_buffer, no_device as _no_device, r256
 from bgzf_ref import OK, E_NO_EOF, E_BAD_PARAM, E_BAD_HEADER
 
 E_HIP = 9
@@ -20,13 +18,11 @@ LEVELS = (0, 1, 6, 9)
 
 
 def _header():
-    return open(os.path.join(REPO, "include", "hdlz_bgzf.h")).read()
+    return header("hdlz_bgzf.h")
 
 
 def _declarations():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    return {name: 0 if args.strip() == "void" else args.count(",") + 1
-            for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src)}
+    return declarations(_header())
 
 
 def test_every_declaration_is_exported_and_bound():
@@ -63,21 +59,7 @@ def test_the_tables_in_front_of_it_are_as_they_were():
 ])
 def test_struct_mirrors_match_the_header(struct, mirror, want):
     from hdl_deflate_amd import _lib
-    R = getattr(_lib, mirror)
-    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (struct, struct), _header(), flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint64_t|uint32_t)\s+(\w+)\s*;", body)
-    assert fields == want
-    assert [f[0] for f in R._fields_] == [f[1] for f in fields]
-    offsets, o = [], 0
-    for t, _ in fields:
-        offsets.append(o)
-        o += 8 if t == "uint64_t" else 4
-    assert ctypes.sizeof(R) == o and [getattr(R, f[1]).offset for f in fields] == offsets
-
-
-def r256(x):
-    return (x + 255) // 256 * 256
+    check_struct_mirror(_header(), struct, getattr(_lib, mirror), want)
 
 
 def test_the_queries_are_their_closed_forms():
@@ -104,17 +86,6 @@ def test_blocks_of_58230_bytes_always_fit_a_member():
     L = _lib.load()
     assert L.hdlz_out_bound(58230) == 6 + ((9 * 58230 + 17) >> 3) == 65516
     assert L.hdlz_out_bound(58230) + 20 <= 65536 < L.hdlz_out_bound(58231) + 20
-
-
-def _host_buffer():
-    buf = (ctypes.c_uint8 * 16384)()
-    base = ctypes.addressof(buf)
-    return buf, base + (-base % 256)
-
-
-def _no_device():
-    import torch
-    return not torch.cuda.is_available()         # (with a device the good calls would run kernels on host buffers)
 
 
 def test_crc32_batch_parameter_errors_come_before_the_device():

@@ -3,14 +3,13 @@ work query equal to its closed form, parameter errors in front of the device, no
 reference of the GPU tests, held against a brute-force per-byte map; and the host module hdl_deflate_amd/bgzf.py (virtual offsets, the
 .gzi file) against hand-written bytes."""
 import ctypes
-import os
 import re
 import struct
 
 import pytest
 
-from conftest import REPO
 import bgzf_ref
+from cabi_common import check_struct_mirror, declarations, header, host_buffer, no_device as _no_device, r256
 import bgzf_range_ref as ref
 from bgzf_ref import OK, E_BAD_PARAM
 
@@ -18,13 +17,11 @@ E_HIP = 9
 
 
 def _header():
-    return open(os.path.join(REPO, "include", "hdlz_bgzf_range.h")).read()
+    return header("hdlz_bgzf_range.h")
 
 
 def _declarations():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    return {name: 0 if args.strip() == "void" else args.count(",") + 1
-            for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src)}
+    return declarations(_header())
 
 
 def test_every_declaration_is_exported_and_bound():
@@ -55,20 +52,9 @@ def test_the_tables_in_front_of_it_are_as_they_were():
 def test_the_struct_mirror_matches_the_header():
     from hdl_deflate_amd import _lib
     R = _lib.BgzfRangesResult
-    body = re.search(r"typedef\s+struct\s+hdlz_bgzf_ranges_result\s*\{(.*?)\}\s*hdlz_bgzf_ranges_result\s*;", _header(), flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint64_t|uint32_t)\s+(\w+)\s*;", body)
-    assert fields == [("uint64_t", "total_out"), ("uint64_t", "ntasks"), ("uint64_t", "first_bad"), ("uint32_t", "status"), ("uint32_t", "reserved")]
-    assert [f[0] for f in R._fields_] == [f[1] for f in fields]
-    offsets, o = [], 0
-    for t, _ in fields:
-        offsets.append(o)
-        o += 8 if t == "uint64_t" else 4
-    assert ctypes.sizeof(R) == o == 32 and [getattr(R, f[1]).offset for f in fields] == offsets
-
-
-def r256(x):
-    return (x + 255) // 256 * 256
+    check_struct_mirror(_header(), "hdlz_bgzf_ranges_result", R,
+                        [("uint64_t", "total_out"), ("uint64_t", "ntasks"), ("uint64_t", "first_bad"), ("uint32_t", "status"), ("uint32_t", "reserved")])
+    assert ctypes.sizeof(R) == 32
 
 
 def closed_form(R, T):
@@ -94,14 +80,7 @@ def test_the_work_query_is_its_closed_form():
 
 
 def _host_buffer():
-    buf = (ctypes.c_uint8 * (1 << 19))()
-    base = ctypes.addressof(buf)
-    return buf, base + (-base % 256)
-
-
-def _no_device():
-    import torch
-    return not torch.cuda.is_available()         # (with a device the good calls would run kernels on host buffers)
+    return host_buffer(1 << 19)
 
 
 def test_parameter_errors_come_before_the_device():

@@ -4,13 +4,11 @@ the reference of the GPU tests (the member rule on the CPU oracle's rows), held 
 the arithmetic of the rule on crafted blocks before any kernel is trusted to it."""
 import ctypes
 import gzip
-import os
-import re
 
 import numpy as np
 
-from conftest import REPO
 import bgzf_ref
+from cabi_common import check_struct_mirror, declarations as _declarations, header, host_buffer as _host_buffer, no_device as _no_device
 import bgzf_stored_ref as ref
 from bgzf_ref import OK, E_OUT_CAPACITY, E_BAD_PARAM
 from bgzf_stored_ref import FIXED, STORED, E_SHORT_INPUT
@@ -20,13 +18,7 @@ E_BAD_DISTANCE = 4
 
 
 def _header():
-    return open(os.path.join(REPO, "include", "hdlz_bgzf_stored.h")).read()
-
-
-def _declarations(text):
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return {name: 0 if args.strip() == "void" else args.count(",") + 1
-            for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src)}
+    return header("hdlz_bgzf_stored.h")
 
 
 def test_every_declaration_is_exported_and_bound():
@@ -52,17 +44,15 @@ def test_the_tables_in_front_of_it_are_as_they_were():
     assert len(_lib.BGZF_STORED_EXPORTS) == 3 and not set(_lib.BGZF_STORED_EXPORTS) & set().union(*older)
     assert _lib.load().hdlz_version() == 0x000600
     # the header it extends still declares its eight functions and nothing of this one
-    base = _declarations(open(os.path.join(REPO, "include", "hdlz_bgzf.h")).read())
+    base = _declarations(header("hdlz_bgzf.h"))
     assert len(base) == 8 and not set(base) & set(_lib.BGZF_STORED_EXPORTS)
 
 
 def test_struct_mirror_matches_the_header():
     from hdl_deflate_amd import _lib
     R = _lib.BgzfStoredResult
-    body = re.search(r"typedef\s+struct\s+hdlz_bgzf_stored_result\s*\{(.*?)\}\s*hdlz_bgzf_stored_result\s*;", _header(), flags=re.S).group(1)
-    fields = re.findall(r"(uint64_t|uint32_t)\s+(\w+)\s*;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
-    assert fields == [("uint64_t", "file_len"), ("uint64_t", "nstored"), ("uint32_t", "status"), ("uint32_t", "first_bad")]
-    assert [f[0] for f in R._fields_] == [f[1] for f in fields]
+    fields = [("uint64_t", "file_len"), ("uint64_t", "nstored"), ("uint32_t", "status"), ("uint32_t", "first_bad")]
+    check_struct_mirror(_header(), "hdlz_bgzf_stored_result", R, fields)
     assert [getattr(R, f[1]).offset for f in fields] == [0, 8, 16, 20] and ctypes.sizeof(R) == 24
 
 
@@ -78,17 +68,6 @@ def test_the_queries_are_their_closed_forms():
     # the bound never exceeds the older writer's
     assert L.hdlz_bgzf_stored_bound(1, 65280) == 28 + 65311 < L.hdlz_bgzf_bound(1, 65280)
     assert all(L.hdlz_bgzf_stored_bound(3, n) <= L.hdlz_bgzf_bound(3, n) for n in range(0, 300))
-
-
-def _host_buffer():
-    buf = (ctypes.c_uint8 * 16384)()
-    base = ctypes.addressof(buf)
-    return buf, base + (-base % 256)
-
-
-def _no_device():
-    import torch
-    return not torch.cuda.is_available()         # (with a device the good calls would run kernels on host buffers)
 
 
 def test_join_stored_parameter_errors_come_before_the_device():

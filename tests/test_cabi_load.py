@@ -5,11 +5,11 @@ import os
 import re
 
 from conftest import REPO
+from cabi_common import declarations, header
 
 
 def _header():
-    src = open(os.path.join(REPO, "include", "hdlz.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.sub(r"/\*.*?\*/", "", header("hdlz.h"), flags=re.S)
 
 
 def _declared():
@@ -29,8 +29,7 @@ def test_signature_table_matches_the_header():
     """every entry point has a restype and an argtypes list as long as its declaration's parameter list ((void) = 0), and load()
     puts exactly those on the library's functions"""
     from hdl_deflate_amd import _lib
-    params = {name: 0 if args.strip() == "void" else args.count(",") + 1
-              for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", _header())}
+    params = declarations(_header())
     assert len(params) == 22 and sorted(params) == sorted(_lib.EXPORTS) == sorted(_lib.SIGNATURES)
     assert sorted(set(params.values())) == [0, 1, 2, 5, 7, 8, 10, 11, 12, 13, 14, 16]
     L = _lib.load()

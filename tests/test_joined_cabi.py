@@ -2,22 +2,18 @@
 their closed forms, parameter errors in front of the device, no CPU path behind good parameters; and the reference side of the GPU
 tests (joined_ref.expected_joined) against stock zlib."""
 import ctypes
-import os
-import re
 import zlib
 
 import numpy as np
 
-from conftest import REPO
 import joined_ref
+from cabi_common import check_struct_mirror, declarations, header
 
 E_BAD_PARAM, E_HIP = 8, 9
 
 
 def _declarations():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "hdlz_join.h")).read(), flags=re.S)
-    return {name: 0 if args.strip() == "void" else args.count(",") + 1
-            for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src)}
+    return declarations(header("hdlz_join.h"))
 
 
 def test_every_declaration_is_exported_and_bound():
@@ -36,10 +32,7 @@ def test_every_declaration_is_exported_and_bound():
         assert fn.restype is restype and list(fn.argtypes) == argtypes, name
     assert L.hdlz_version() == 0x000600
     assert ctypes.sizeof(_lib.JoinResult) == 16 and _lib.JoinResult.status.offset == 8 and _lib.JoinResult.adler.offset == 12
-    hdr = open(os.path.join(REPO, "include", "hdlz_join.h")).read()
-    body = re.search(r"typedef\s+struct\s+hdlz_join_result\s*\{(.*?)\}\s*hdlz_join_result\s*;", hdr, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    assert re.findall(r"(uint64_t|uint32_t)\s+(\w+)\s*;", body) == [("uint64_t", "stream_len"), ("uint32_t", "status"), ("uint32_t", "adler")]
+    check_struct_mirror(header("hdlz_join.h"), "hdlz_join_result", _lib.JoinResult, [("uint64_t", "stream_len"), ("uint32_t", "status"), ("uint32_t", "adler")])
     assert [f[0] for f in _lib.JoinResult._fields_] == ["stream_len", "status", "adler"]
 
 

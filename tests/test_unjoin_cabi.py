@@ -3,26 +3,22 @@ scratch query equal to its closed form, parameter errors in front of the device,
 member rule (end bit -> three zero bits -> 00 00 FF FF -> the next offset) stated in Python and held against joined_ref before any
 kernel sees it."""
 import ctypes
-import os
-import re
 
 import numpy as np
 
-from conftest import REPO
 import joined_ref
+from cabi_common import check_struct_mirror, declarations, header, r256
 
 E_BAD_PARAM, E_HIP = 8, 9
 LANE, WAVE, GROUP = 2, 4, 64
 
 
 def _header():
-    return open(os.path.join(REPO, "include", "hdlz_unjoin.h")).read()
+    return header("hdlz_unjoin.h")
 
 
 def _declarations():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    return {name: 0 if args.strip() == "void" else args.count(",") + 1
-            for name, args in re.findall(r"\b(hdlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src)}
+    return declarations(_header())
 
 
 def test_every_declaration_is_exported_and_bound():
@@ -51,17 +47,8 @@ def test_the_tables_in_front_of_it_are_as_they_were():
 def test_struct_mirror_matches_the_header():
     from hdl_deflate_amd import _lib
     R = _lib.UnjoinResult
-    body = re.search(r"typedef\s+struct\s+hdlz_unjoin_result\s*\{(.*?)\}\s*hdlz_unjoin_result\s*;", _header(), flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint64_t|uint32_t)\s+(\w+)\s*;", body)
-    assert fields == [("uint64_t", "out_len"), ("uint64_t", "first_bad"), ("uint32_t", "status"), ("uint32_t", "adler")]
-    assert [f[0] for f in R._fields_] == [f[1] for f in fields]
-    assert [ctypes.sizeof(f[1]) for f in R._fields_] == [8 if t == "uint64_t" else 4 for t, _ in fields]
+    check_struct_mirror(_header(), "hdlz_unjoin_result", R, [("uint64_t", "out_len"), ("uint64_t", "first_bad"), ("uint32_t", "status"), ("uint32_t", "adler")])
     assert ctypes.sizeof(R) == 24 and (R.out_len.offset, R.first_bad.offset, R.status.offset, R.adler.offset) == (0, 8, 16, 20)
-
-
-def r256(x):
-    return (x + 255) // 256 * 256
 
 
 def test_the_work_size_is_its_closed_form():
