@@ -26,6 +26,12 @@ def unjoin_work_bytes(nmembers, total_out, flags=0):
     return _lib.load().hdlz_unjoin_work_bytes(nmembers, total_out, flags)
 
 
+def gunzip_work_bytes(nstreams, in_len, out_pitch, ragged=False):
+    """the scratch hdlz_gunzip_ws asks for (hdlz_gunzip_work_bytes: host arithmetic of the library) -- Engine.inflate_gzip's `work`"""
+    from . import _lib
+    return _lib.load().hdlz_gunzip_work_bytes(nstreams, in_len, out_pitch, 1 if ragged else 0)
+
+
 def Engine(*a, **kw):
     """The HIP batch engine (imports torch lazily)."""
     from .engine import Engine as _E

@@ -95,6 +95,13 @@ BGZF_STORED_SIGNATURES = {
     "hdlz_bgzf_join_stored_ws": (ci, [vp, vp, u64, u32, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, sz, vp]),
 }
 BGZF_STORED_EXPORTS = tuple(BGZF_STORED_SIGNATURES)
+# ... and of include/hdlz_gunzip.h: gzip members of any writer, one per stream (tests/test_gunzip_cabi.py)
+GUNZIP_SIGNATURES = {
+    "hdlz_gunzip_work_bytes": (sz, [u64, u32, u64, ci]),
+    # d_in, d_in_off, in_pitch, in_len, nstreams, d_out, out_pitch, d_out_len, d_status, d_in_used, d_crc, d_work, work_bytes, stream
+    "hdlz_gunzip_ws": (ci, _BATCH_IN + [vp, u64, vp, vp, vp, vp, vp, sz, vp]),
+}
+GUNZIP_EXPORTS = tuple(GUNZIP_SIGNATURES)
 _lib = None
 
 
@@ -168,7 +175,8 @@ def load():
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
-            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()):
+            list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
+            list(GUNZIP_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -710,4 +710,64 @@ int hdlz_bgzf_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uin
                     "launch the finish kernels (k_ranges_crc, k_ranges_judge, k_ranges_slice, k_ranges_finish, k_ranges_record)");
 }
 
+// ---- include/hdlz_gunzip.h: gzip members of any writer, one per stream (hdlz_gunzip.hip)
+// The scratch of hdlz_gunzip_ws, laid out once for the size query and the call: three words per stream (p, the header's verdict, the
+// CRC-32), the decoder's view of 2 nstreams offsets, one CRC word per 32 KiB tile of row capacity where the rows are tiled, and -- one
+// stream -- the share of the batch call's path, which takes what is left from `decode` on.
+struct GunzipScratch {
+    uint32_t *p, *verdict, *crcw;
+    uint64_t* idx;
+    uint32_t* tiles;
+    size_t decode;
+    size_t bytes;
+};
+static GunzipScratch gunzip_scratch(void* base, uint64_t nstreams, uint32_t in_len, uint64_t out_pitch) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const size_t per = hdlz::round256(12u * (size_t)nstreams), idx = hdlz::round256(16u * (size_t)nstreams);
+    const size_t words = hdlz::gunzip_tile_words(nstreams, out_pitch), tiles = hdlz::round256(sizeof(uint32_t) * words);
+    auto words_at = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * nstreams)); };
+    return {words_at(0), words_at(1), words_at(2), reinterpret_cast<uint64_t*>(b + per), words ? reinterpret_cast<uint32_t*>(b + per + idx) : nullptr,
+            per + idx + tiles, per + idx + tiles + (nstreams == 1 ? hdlz::round256(hdlz_inflate_work_bytes(1, in_len, out_pitch, 0, 1)) : 0u)};
+}
+size_t hdlz_gunzip_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_pitch, int ragged) {
+    if (nstreams == 0 || nstreams > 0x7FFFFFFFull || (!ragged && in_len >= 0x10000000u) || (nstreams > 1 && out_pitch > 0xFFFFFFFFull)) return 0;
+    return gunzip_scratch(nullptr, nstreams, in_len, out_pitch).bytes;
+}
+
+int hdlz_gunzip_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len, uint64_t nstreams, uint8_t* d_out,
+                   uint64_t out_pitch, uint32_t* d_out_len, uint32_t* d_status, uint32_t* d_in_used, uint32_t* d_crc, void* d_work,
+                   size_t work_bytes, void* stream) {
+    if (!d_in_used) return fail_param("d_in_used is required");
+    if (nstreams > 0x7FFFFFFFull) return fail_param("nstreams too large for one call (2^31 - 1 streams)");
+    if (nstreams && any_null(d_in, d_out, d_out_len, d_status)) return fail_param("null device pointer");
+    if (!d_in_off && in_len >= 0x10000000u) return fail_param("in_len too large (streams are limited to 256 MiB - 1)");
+    if (!d_in_off && nstreams > 1 && in_pitch < in_len) return fail_param("in_pitch < in_len");
+    if (nstreams > 1 && out_pitch > 0xFFFFFFFFull) return fail_param("out_pitch too large for more than one stream (below 2^32)");
+    if ((out_pitch & 3u) || misaligned(4, d_out)) return fail_align(4, "d_out / out_pitch");
+    if (misaligned(8, d_in_off)) return fail_align(8, "d_in_off");
+    if (misaligned(4, d_out_len, d_status, d_in_used, d_crc)) return fail_align(4, "d_out_len / d_status / d_in_used / d_crc");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    const GunzipScratch s = gunzip_scratch(d_work, nstreams, in_len, out_pitch);
+    if (nstreams && work_too_small(s.bytes, d_work, work_bytes, "hdlz_gunzip_work_bytes(nstreams, in_len, out_pitch, ragged)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    if (nstreams == 0) return HDLZ_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool single = nstreams == 1;
+    const hdlz::GunzipArgs g{d_in, d_in_off, in_pitch, in_len, nstreams, d_out, out_pitch, d_out_len, d_status, d_in_used, d_crc,
+                             s.p, s.verdict, s.crcw, s.idx, s.tiles, single};
+    if (const int rc = launched(hdlz::launch_gunzip_heads(g, st), "launch k_gunzip_heads"); rc != HDLZ_OK) return rc;
+    if (single) {
+        // the .gz file: the batch call's path over the two-word index the header walk left on the device -- the whole-GPU chains for
+        // a large stream, their fallbacks, the wave for a small one; in_len is the bound the call was given
+        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
+        if (const int rc = inflate_batch_impl(d_in, s.idx, 0, in_len, 1, 0, 0, d_out, out_pitch, d_out_len, d_status, w, stream, d_in_used); rc != HDLZ_OK) return rc;
+    } else {
+        hdlz::MemberArgs a = member_args(d_in, nstreams, 0, d_out, d_out_len, d_status, d_in_used, s.idx);   // (BFINAL is honoured)
+        a.m_end = s.idx + nstreams; a.m_out_len = (uint32_t)out_pitch; a.m_out_cap = nstreams * out_pitch;
+        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+    }
+    if (const int rc = launched(hdlz::launch_gunzip_crc(g, st), "launch k_gunzip_crc_*"); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_gunzip_judge(g, st), "launch k_gunzip_judge");
+}
+
 }  // extern "C"

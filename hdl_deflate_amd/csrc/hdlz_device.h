@@ -6,6 +6,7 @@
 #include <utility>
 #include "../../include/hdlz_bgzf_range.h"   // (includes hdlz_bgzf.h, hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
 #include "../../include/hdlz_bgzf_stored.h"
+#include "../../include/hdlz_gunzip.h"
 
 namespace hdlz {
 
@@ -312,5 +313,31 @@ hipError_t launch_bgzf_ranges_finish(const RangeArgs& a, hipStream_t stream);   
 // hdlz_crc32.hip: CRC-32 of data[0 .. n) -> crc[0].  `words`: one word per 32 KiB tile (crc32_tiles(n) of them; null when n is 0).
 size_t crc32_tiles(uint64_t n);
 hipError_t launch_crc32(const uint8_t* data, uint64_t n, uint32_t* crc, uint32_t* words, hipStream_t stream);
+
+// hdlz_gunzip.hip: hdlz_gunzip_ws (include/hdlz_gunzip.h) -- the header walk in front of the decode, the CRC-32 of the
+// rows and the verdict behind it.  The input and the five result arrays are the caller's; the rest is scratch.
+struct GunzipArgs {
+    const uint8_t* in;
+    const uint64_t* in_off;     // nullable, as in InflateArgs
+    uint64_t in_pitch;
+    uint32_t in_len;
+    uint64_t nstreams;
+    const uint8_t* out;
+    uint64_t out_pitch;
+    uint32_t* out_len;
+    uint32_t* status;
+    uint32_t* in_used;
+    uint32_t* crc;              // nullable
+    uint32_t* p;                // scratch, per stream: the offset of the first payload byte
+    uint32_t* verdict;          // ... the header's verdict
+    uint32_t* crcw;             // ... the CRC-32 of the row
+    uint64_t* idx;              // scratch, 2 nstreams words: MemberArgs::m_off, then m_end; single: the ragged index {start + p - 2, end}
+    uint32_t* tiles;            // scratch: gunzip_tile_words(nstreams, out_pitch) words (null when that is 0)
+    bool single;                // nstreams == 1: the decode is the batch call's, and in_used holds a byte where the member view stores a bit
+};
+size_t gunzip_tile_words(uint64_t nstreams, uint64_t out_pitch);
+hipError_t launch_gunzip_heads(const GunzipArgs& a, hipStream_t stream);
+hipError_t launch_gunzip_crc(const GunzipArgs& a, hipStream_t stream);
+hipError_t launch_gunzip_judge(const GunzipArgs& a, hipStream_t stream);
 
 }  // namespace hdlz

@@ -6,7 +6,7 @@ import functools
 import torch
 
 from . import _lib, host
-from .constants import OK, E_SHORT_INPUT, E_OUT_CAPACITY, E_NO_EOF, E_BAD_CHECKSUM, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
+from .constants import OK, E_SHORT_INPUT, E_OUT_CAPACITY, E_NO_EOF, E_BAD_HEADER, E_BAD_CHECKSUM, INFLATE_ONE_FIXED_BLOCK, inflate_cap, pitch_for
 from .session import CompressSession, InflateSession
 from .errors import Error, HdlzStatusError
 
@@ -578,6 +578,56 @@ class Engine(object):
                                      *[t.data_ptr() for t in res[1:]], wptr, wbytes, self._stream())
         self._check(rc, call)
         return res
+
+    # -- gzip members of any writer, one per stream (include/hdlz_gunzip.h)
+    @_on_device
+    def inflate_gzip(self, d_in, in_off=None, in_len=None, nblocks=None, out_pitch=None, out=None, work=None):
+        """d_in: as inflate_batch -- uint8 [B, pitch] or flat uint8 with in_off int64[B + 1] (then `in_len` is the bound on the lengths).
+        Every stream is ONE gzip member of any writer (FEXTRA, FNAME, FCOMMENT, FHCRC) followed by anything: the header is walked, the
+        payload decoded, CRC-32 and ISIZE verified on the device (hdlz_gunzip_ws; one stream per call: the whole-GPU decode).
+        -> (out uint8[B, out_pitch], out_len int32[B], status int32[B], in_used int32[B], crc int32[B]: the 32 bits of the checksum);
+        in_used is where the member ended -- the next member of a file starts there.  Per-stream failures are statuses.  `work`: the
+        call's scratch, a uint8 device tensor of at least hdlz_gunzip_work_bytes(...) bytes at a multiple of 256 (default: allocated here)."""
+        off_ptr, pitch, ilen, nb = self._prep(d_in, in_off, in_len, nblocks)
+        assert out_pitch is not None and out_pitch % 4 == 0
+        res = self._results(out, (nb, out_pitch), nb, d_in.device, True)
+        need = self.lib.hdlz_gunzip_work_bytes(nb, ilen, out_pitch, 0 if in_off is None else 1)
+        work, wptr, wbytes = self._scratch(need, work, torch.uint8, full=True)
+        rc = self.lib.hdlz_gunzip_ws(d_in.data_ptr(), off_ptr, pitch, ilen, nb, res[0].data_ptr(), out_pitch,
+                                     *[t.data_ptr() for t in res[1:]], wptr, wbytes, self._stream())
+        self._check(rc, "hdlz_gunzip_ws")
+        return res
+
+    @_on_device
+    def inflate_gzip_bytes(self, z, out_cap=None):
+        """the bytes of a .gz file -> (status, bytes), with gzip.decompress's acceptance: one or more members back to back, zero bytes
+        behind a member ignored, anything else behind a member E_BAD_HEADER, empty input (OK, b"").  z is staged once; every
+        member is one device call (inflate_gzip with one stream) and one host sync, the next one starts at in_used.  Capacity of a
+        call: out_cap when given; else the ISIZE word at the end of the remaining bytes when it does not exceed inflate_cap(remaining),
+        and once more with inflate_cap(remaining) after E_OUT_CAPACITY."""
+        n, pos, pieces = len(z), 0, []
+        d = self._stage(z)
+        while pos < n:
+            if pieces:                               # zero bytes behind a member are padding
+                pos = n - len(bytes(z[pos:]).lstrip(b"\0"))
+                if pos == n:
+                    break
+            rest = n - pos
+            bound = inflate_cap(rest)
+            isize = int.from_bytes(bytes(z[n - 4:n]), "little") if rest >= 4 else bound
+            caps = [out_cap] if out_cap is not None else [isize, bound] if isize < bound else [bound]
+            for cap in caps:
+                out, ol, st, used, _ = self.inflate_gzip(d[pos:pos + rest], in_len=rest, nblocks=1, out_pitch=max(16, (cap + 15) // 16 * 16))
+                st = int(st.item())
+                if st != E_OUT_CAPACITY:
+                    break
+            if st != OK:
+                if pieces and rest < 10 and not b"\x1f\x8b\x08".startswith(bytes(z[pos:pos + 3])):
+                    st = E_BAD_HEADER                # (too short for the device to look at the magic: what stands there is no member)
+                return st, b""
+            pieces.append(bytes(out[0, :int(ol.item())].cpu().numpy().tobytes()))
+            pos += int(used.item())
+        return OK, b"".join(pieces)
 
     # -- archive compaction (SURVEY 8(f) rank 2)
     @_on_device

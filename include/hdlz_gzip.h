@@ -14,7 +14,8 @@
  * stream_len is the zlib form's length plus 12; d_off[0] = 10 and d_off[B] is where 03 00 starts; B = 0: the header followed by
  * 03 00 00 00 00 00 00 00 00 00 (20 bytes).  The member bytes and the index are those of the zlib form, moved by 8.
  * Out of scope: gzip in hdlz_inflate_checked, headers of other writers (FEXTRA, FNAME, FCOMMENT, FHCRC), files of several gzip
- * members, the CRC-32 of a pitched or gapped batch.
+ * members, the CRC-32 of a pitched or gapped batch.  (hdlz_gunzip.h, the extension of this header, reads members with such headers and
+ * says where each one ended, which is what a file of several members needs.)
  */
 #ifndef HDLZ_GZIP_H
 #define HDLZ_GZIP_H
