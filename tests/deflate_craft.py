@@ -5,7 +5,10 @@ code-length code, no one-code distance set at symbol 29, never 258 as symbol 284
 This module writes such blocks in pure Python: `emit_block` takes the code lengths, the tokens and, if wanted, the exact sequence of
 code-length-code operations; `catalogue()` is a list of named cases with their expectation (the plain bytes, computed here from the
 tokens, or the status of the rejection); `random_stream()` draws whole streams; `header_flips()` damages a stream inside a block header.
-Nothing here looks at a decoder: tests/test_crafted_trees_cpu.py holds all of it against stock zlib and the C oracle."""
+Nothing here looks at a decoder: tests/test_crafted_trees_cpu.py holds all of it against stock zlib and the C oracle.
+The second half does for block BODIES what the first does for headers: `geometry_stream`, `geometry_mixed` and `geometry_rejected` put
+match distances and lengths on the ring thresholds of the inflate kernels, in fixed blocks (`emit_fixed_block`) and in dynamic ones whose
+code comes from the token frequencies (`frequency_lengths`); tests/test_match_geometry_cpu.py holds those against zlib and the oracle."""
 import functools
 import random
 import zlib
@@ -551,3 +554,258 @@ def large():
     for c in valid:
         out += [("%s flip %d" % (c.name, k), m, None) for k, m in enumerate(header_flips(c.z, c.spans, rng, 8))]
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ match geometry
+# Block BODIES: token lists whose distances and lengths sit on the comparisons by which every inflate decoder chooses between its LDS ring,
+# its own flushed output and a marker.  tests/test_match_geometry_cpu.py reads the kernels' constants and fails when a grid below no
+# longer holds a threshold and its two neighbours.
+FIXED_LL = (8,) * 144 + (9,) * 112 + (7,) * 24 + (8,) * 8            # RFC1951 3.2.6
+FIXED_DL = (5,) * 30
+
+GEO_DISTANCES = (
+    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14,    # periods below a 16-byte step: a copy that overlaps itself (every `i % D` arm; 3, 4, 5: a dword)
+    15, 16, 17,                                       # the 16 source bytes of a step (k_inflate_tok's far load, k_inflate_grp's lanes)
+    18, 19, 20,                                       # k_inflate_tok: a round advances the output by at most 19 bytes
+    31, 32, 33,                                       # k_inflate_grp: RB - NEAR = 32, two steps
+    47, 48, 49,                                       # k_inflate_tok with a 64-byte ring: NEAR = 64 - 16
+    63, 64, 65,                                       # CHUNK, DCHUNK: the 64-byte flush line; a wave's lanes
+    75, 76, 77,                                       # k_inflate_tok: URGENT = RINGB - 52
+    94, 95, 96,                                       # k_inflate_tok: URGENT + 19, the most unflushed bytes when a far load is issued
+    108, 109, 110,
+    111, 112, 113,                                    # k_inflate_tok: NEAR = RINGB - 16, ring or far load
+    114, 115, 116,                                    # k_inflate_tok: NEAR + 3, the dword alignment of the source
+    117, 118, 119, 120, 121, 122, 123, 124, 125, 126,
+    127, 128, 129,                                    # k_inflate_tok: RINGB
+    130, 131,
+    255, 256, 257,                                    # the longest match but one byte or two; a quarter of HRING
+    447, 448, 449,                                    # k_inflate_dyn: WCAP
+    511, 512, 513,                                    # k_inflate_dyn: the 512 of DRING - 512; half of FLUSH
+    767, 768, 769,                                    # k_par_emit: SPAN
+    895, 896, 897,                                    # k_par_emit, k_any_*: HREACH = HRING - 128, ring or marker
+    1023, 1024, 1025,                                 # HRING; k_inflate_grp: FLUSH
+    1277, 1278, 1279,                                 # k_inflate_dyn: DRING - 512 - 258
+    1280, 1281,                                       # HRING + 256
+    1471, 1472, 1473,                                 # k_inflate_dyn: DRING - 512 - 64
+    1519, 1520, 1521,                                 # k_inflate_dyn: DRING - 512 - 16
+    1532, 1533, 1534,                                 # k_inflate_dyn: DRING - 512 - 3
+    1535, 1536, 1537,                                 # k_inflate_dyn: DRING - 512, in the ring or out[src]
+    2015, 2016, 2017,                                 # k_inflate_grp: NEAR = RB - 32, ring or HBM
+    2031, 2032, 2033,                                 # k_inflate_grp: RB - 16, one step below the ring's size
+    2047, 2048, 2049,                                 # RB, DRING
+    4095, 4096, 4097,                                 # powers of two up to the window: the distance codes' bases + 1 ...
+    8191, 8192, 8193,
+    16383, 16384, 16385,
+    24576, 24577,                                     # ... the last distance code's base
+    32767, 32768)                                     # the window
+GEO_LENGTHS = (
+    3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14,          # the shortest matches: within one 16-byte step; k_inflate_tok's dwords
+    15, 16, 17,                                       # one step of 16 bytes and its neighbours
+    18, 19, 20,                                       # k_inflate_tok: the 19 bytes of a round
+    31, 32, 33, 34, 35,                               # two steps; k_inflate_grp: RB - NEAR
+    63, 64, 65, 66, 67,                               # CHUNK, DCHUNK: a flush line; a wave's lanes
+    127, 128, 129, 130, 131,                          # k_inflate_tok: RINGB; k_par_emit: HRING - HREACH
+    192, 227,                                         # three flush lines; the base of length symbol 284
+    255, 256, 257, 258)                               # 257 = symbol 284 + 30, 258 = symbol 285
+assert len(GEO_DISTANCES) == len(set(GEO_DISTANCES)) == 116 and len(GEO_LENGTHS) == len(set(GEO_LENGTHS)) == 39
+GEO_KINDS = ("fixed", "dynamic")
+
+
+def emit_fixed_block(w, tokens, final):
+    """one fixed-Huffman block (BTYPE = 1) into the Bits `w` from the token lists emit_block takes: the code of RFC1951 3.2.6 through
+    canonical(), 258 as symbol 285 unless the token names its length symbol, 5-bit distance codes, the end-of-block code
+    -> dict: span = (first bit, end bit) of the three header bits"""
+    start = w.pos
+    w.put(1 if final else 0, 1)
+    w.put(1, 2)
+    emit_tokens(w, FIXED_LL, FIXED_DL, tokens)
+    return dict(span=(start, start + 3), offset=start & 7)
+
+
+def emit_tokens(w, ll, dl, tokens):
+    """the tokens and an end-of-block code in the codes of the lengths ll / dl (what emit_block writes behind its header)"""
+    lc, dc = canonical(ll), canonical(dl)
+    for t in tokens:
+        if isinstance(t, int):
+            w.code(lc[t])
+            continue
+        ls = t[2] if len(t) > 2 else length_symbol(t[0])
+        w.code(lc[ls])
+        assert 0 <= t[0] - LBASE[ls - 257] < (1 << LEXTRA[ls - 257]) or t[0] == LBASE[ls - 257]
+        w.put(t[0] - LBASE[ls - 257], LEXTRA[ls - 257])
+        ds = distance_symbol(t[1])
+        w.code(dc[ds])
+        w.put(t[1] - DBASE[ds], DEXTRA[ds])
+    w.code(lc[256])
+
+
+def token_bits(ll, dl, tokens):
+    """the number of bits each token takes in the codes of the lengths ll / dl"""
+    out = []
+    for t in tokens:
+        if isinstance(t, int):
+            out.append(ll[t])
+            continue
+        ls, ds = t[2] if len(t) > 2 else length_symbol(t[0]), distance_symbol(t[1])
+        out.append(ll[ls] + LEXTRA[ls - 257] + dl[ds] + DEXTRA[ds])
+    return out
+
+
+def limited_lengths(freq, limit=15):
+    """symbol -> code length of a Huffman code for the frequencies (a dict), no code longer than `limit`: while the tree is too deep the
+    frequencies are halved (rounded up), which ends at the latest with all of them 1, a balanced tree.  One symbol: length 1"""
+    import heapq
+    syms = sorted(freq)
+    if len(syms) == 1:
+        return {syms[0]: 1}
+    f = dict(freq)
+    while True:
+        heap = [(f[s], s, (s,)) for s in syms]
+        heapq.heapify(heap)
+        depth = dict.fromkeys(syms, 0)
+        while len(heap) > 1:
+            a, b = heapq.heappop(heap), heapq.heappop(heap)
+            for s in a[2] + b[2]:
+                depth[s] += 1
+            heapq.heappush(heap, (a[0] + b[0], min(a[1], b[1]), a[2] + b[2]))
+        if max(depth.values()) <= limit:
+            return depth
+        f = dict((s, (v + 1) // 2) for s, v in f.items())
+
+
+def frequency_lengths(tokens):
+    """(ll, dl) of a length-limited (15 bits) Huffman code from the frequencies of the tokens' symbols, 256 always coded; a single used
+    distance symbol gets length 1, no match at all gives dl = [0].  Frequent matches get short codes this way, so that several of them
+    fall into one 64-bit decode window"""
+    lf, df = {256: 1}, {}
+    for t in tokens:
+        if isinstance(t, int):
+            lf[t] = lf.get(t, 0) + 1
+            continue
+        ls, ds = t[2] if len(t) > 2 else length_symbol(t[0]), distance_symbol(t[1])
+        lf[ls] = lf.get(ls, 0) + 1
+        df[ds] = df.get(ds, 0) + 1
+    ll = sparse(max(257, max(lf) + 1), limited_lengths(lf))
+    dl = sparse(max(df) + 1, limited_lengths(df)) if df else [0]
+    assert len(lf) == 1 or kraft(ll) == 1 << 15
+    assert len(df) <= 1 or kraft(dl) == 1 << 15
+    return ll, dl
+
+
+def geometry_case(name, blocks_of_tokens, kind, status=OK, **attrs):
+    """-> Case: one block per token list, all fixed or all dynamic with frequency_lengths of their own.  On top of Case's fields: tokens
+    (all of them), token_pos (the bit in .raw at which each begins; + 16: in .z), kind and whatever `attrs` name"""
+    w, out, blocks, pos, tokens = Bits(), bytearray(), [], [], []
+    for k, toks in enumerate(blocks_of_tokens):
+        final = k == len(blocks_of_tokens) - 1
+        if kind == "fixed":
+            ll, dl = FIXED_LL, FIXED_DL
+            blocks.append(emit_fixed_block(w, toks, final))
+        else:
+            assert kind == "dynamic"
+            ll, dl = frequency_lengths(toks)
+            blocks.append(emit_block(w, ll, dl, toks, final))
+        p = blocks[-1]["span"][1]
+        for nb in token_bits(ll, dl, toks):
+            pos.append(p)
+            p += nb
+        assert p + ll[256] == w.pos
+        tokens += toks
+        if out is not None:
+            out = apply_tokens(out, toks)
+    assert (out is not None) == (status == OK), name
+    c = Case(name, w, out, status, blocks)
+    c.tokens, c.token_pos, c.kind = tokens, pos, kind
+    for k, v in attrs.items():
+        setattr(c, k, v)
+    return c
+
+
+def geometry_stream(D, kind, long_preamble=False):
+    """-> Case (+ .D, .first_match: the number of literals in front of the first match): one block, seeded by D.  A preamble of
+    max(D, 64) + randrange(64) uniformly random literals -- a source that is off by one byte shows, and the first match starts at any
+    phase of a 64-byte line; long_preamble: at least 4400 of them, which is above HDLZ_INFLATE_PAR_MIN and ANY_MIN in both codings --,
+    then every length of GEO_LENGTHS once, in random order, at distance D, with 0 to 3 random literals behind each (the lane decoder's
+    groups of three literals and a match)"""
+    rng = random.Random(D)
+    npre = max(D, 64, 4400 if long_preamble else 0) + rng.randrange(64)
+    toks = [rng.randrange(256) for _ in range(npre)]
+    lens = list(GEO_LENGTHS)
+    rng.shuffle(lens)
+    for l in lens:
+        toks.append((l, D))
+        toks += [rng.randrange(256) for _ in range(rng.randrange(4))]
+    return geometry_case("geometry D=%d %s%s" % (D, kind, " long" if long_preamble else ""), [toks], kind, D=D, first_match=npre)
+
+
+def geometry_mixed(seed, kind, nbytes):
+    """-> Case: 33000 random literals, then random (length, distance) pairs from the two grids with 0 to 3 literals between them until
+    there are nbytes of output.  "fixed": one block; "dynamic": blocks of at most 30000 tokens, each with its own frequency_lengths"""
+    rng = random.Random(seed)
+    toks = [rng.randrange(256) for _ in range(33000)]
+    n = len(toks)
+    while n < nbytes:
+        l, d, k = rng.choice(GEO_LENGTHS), rng.choice(GEO_DISTANCES), rng.randrange(4)
+        toks.append((l, d))
+        toks += [rng.randrange(256) for _ in range(k)]
+        n += l + k
+    blocks = [toks] if kind == "fixed" else [toks[i:i + 30000] for i in range(0, len(toks), 30000)]
+    return geometry_case("geometry mixed %d %s" % (seed, kind), blocks, kind, first_match=33000)
+
+
+def window_stats(case):
+    """-> (the most matches whose codes begin within any 64 bits of the stream's body -- the tokens from the first match on --, the most
+    output bytes of the tokens that begin within any 64 bits)"""
+    body = [(p, t) for p, t in zip(case.token_pos, case.tokens)][case.first_match:]
+    best_m = best_b = m = b = j = 0
+    for i, (p, t) in enumerate(body):                      # a window of 64 bits that begins with token i
+        while j < len(body) and body[j][0] < p + 64:
+            m += 0 if isinstance(body[j][1], int) else 1
+            b += 1 if isinstance(body[j][1], int) else body[j][1][0]
+            j += 1
+        best_m, best_b = max(best_m, m), max(best_b, b)
+        m -= 0 if isinstance(t, int) else 1
+        b -= 1 if isinstance(t, int) else t[0]
+    return best_m, best_b
+
+
+REJECTED_D = (1, 2, 113, 1537, 2049, 32768)
+OBSIZE_D = (113, 512, 1537, 2049)
+
+
+def geometry_rejected():
+    """-> dict: reach [Case]: for D in REJECTED_D, both kinds, exactly D literals and then (258, D) -- the match reaches byte 0 and is
+    valid --; short [Case]: D - 1 literals in front of it (not for D = 1): E_BAD_DISTANCE; obsize [Case]: for D in OBSIZE_D a stream
+    whose only matches are (10, D), a literal, (10, D + 1), to be decoded with obsize in (D - 1, D, D + 1, 0): E_BAD_DISTANCE exactly
+    for a non-zero obsize below D + 1"""
+    reach, short, obs = [], [], []
+    for D in REJECTED_D:
+        rng = random.Random(100000 + D)
+        lits = [rng.randrange(256) for _ in range(D)]
+        for kind in GEO_KINDS:
+            reach.append(geometry_case("reach D=%d %s" % (D, kind), [lits + [(258, D)]], kind, D=D, first_match=D))
+            if D > 1:
+                short.append(geometry_case("short D=%d %s" % (D, kind), [lits[1:] + [(258, D)]], kind, status=E_BAD_DISTANCE, D=D,
+                                           first_match=D - 1))
+    for k, D in enumerate(OBSIZE_D):
+        rng = random.Random(200000 + D)
+        lits = [rng.randrange(256) for _ in range(D + 5 + rng.randrange(64))]
+        toks = lits + [(10, D), rng.randrange(256), (10, D + 1), rng.randrange(256)]
+        obs.append(geometry_case("obsize D=%d" % D, [toks], GEO_KINDS[k & 1], D=D, first_match=len(lits)))
+    return dict(reach=reach, short=short, obsize=obs)
+
+
+@functools.lru_cache(None)
+def geometry():
+    """what both match-geometry test files run, built once per process -> dict: short, long [Case]: geometry_stream of every distance in
+    both kinds (232 each: fixed, dynamic, fixed, ..), with the short and the long preamble; reach, short_by_one, obsize: geometry_rejected"""
+    rej = geometry_rejected()
+    return dict(short=[geometry_stream(D, kind) for D in GEO_DISTANCES for kind in GEO_KINDS],
+                long=[geometry_stream(D, kind, True) for D in GEO_DISTANCES for kind in GEO_KINDS],
+                reach=rej["reach"], short_by_one=rej["short"], obsize=rej["obsize"])
+
+
+@functools.lru_cache(None)
+def geometry_large():
+    """-> (fixed, dynamic): the two mixed streams of 1 MiB"""
+    return geometry_mixed(1, "fixed", 1 << 20), geometry_mixed(2, "dynamic", 1 << 20)
