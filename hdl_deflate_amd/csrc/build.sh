@@ -31,6 +31,12 @@ fi
 if [ "${1:-}" = "crcbank" ]; then
   HDLZ_VARIANT=crcbank HDLZ_DEFS="-DHDLZ_CRC_BANK_PRIVATE" HDLZ_ONLY="hdlz_crc32 hdlz_unjoin" exec "${BASH_SOURCE[0]}"
 fi
+# `build.sh dbg` builds lib/libhdlz_dbg.so: the same kernels plus the host-only debug exports (hdlz_debug_par_offsets: where the control
+# words of the two whole-GPU inflate chains lie in the caller's scratch; hdlz_debug_gunzip_crc).  tests/chain_verdict.py asks it for the
+# layout (tests/test_gpu_chain_verdicts.py, tools/dev_any.py, tools/fuzz_any.py, tools/probe_gunzip.py)
+if [ "${1:-}" = "dbg" ]; then
+  HDLZ_VARIANT=dbg HDLZ_DEFS="-DHDLZ_DEBUG_EXPORTS" HDLZ_ONLY="hdlz_inflate_par hdlz_gunzip" exec "${BASH_SOURCE[0]}"
+fi
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"

@@ -8,7 +8,10 @@ tokens, or the status of the rejection); `random_stream()` draws whole streams; 
 Nothing here looks at a decoder: tests/test_crafted_trees_cpu.py holds all of it against stock zlib and the C oracle.
 The second half does for block BODIES what the first does for headers: `geometry_stream`, `geometry_mixed` and `geometry_rejected` put
 match distances and lengths on the ring thresholds of the inflate kernels, in fixed blocks (`emit_fixed_block`) and in dynamic ones whose
-code comes from the token frequencies (`frequency_lengths`); tests/test_match_geometry_cpu.py holds those against zlib and the oracle."""
+code comes from the token frequencies (`frequency_lengths`); tests/test_match_geometry_cpu.py holds those against zlib and the oracle.
+The third part, `chain_cases`, puts whole streams on the limits of the two whole-GPU inflate chains -- list sizes, bit budgets, piece
+boundaries, false block headers written into the stream by literals -- with the verdict each must get; tests/test_chain_cases_cpu.py
+measures them, tests/test_gpu_chain_verdicts.py asserts the verdicts."""
 import functools
 import random
 import zlib
@@ -809,3 +812,586 @@ def geometry():
 def geometry_large():
     """-> (fixed, dynamic): the two mixed streams of 1 MiB"""
     return geometry_mixed(1, "fixed", 1 << 20), geometry_mixed(2, "dynamic", 1 << 20)
+
+
+# ------------------------------------------------------------------------------------------------ the limits of the whole-GPU chains
+# Streams that sit on each limit of hdlz_inflate_par.hip (k_par_*) and hdlz_inflate_any.hip (k_any_*): a case on the last value a chain
+# takes and one on the first it gives up, with the verdict it must get (tests/chain_verdict.py reads it from the chains' control words).
+# The sizes come from the constants in the kernels' sources (chain_verdict.source_constants, .lay); tests/test_chain_cases_cpu.py measures
+# every declared property again from the case's own records and fails when a constant moves a case off its limit.
+BULK_LL = (8,) * 226 + (9,) * 60                     # literals 0..225: 8 bits; 226..255, the end-of-block code and the lengths: 9 bits
+BULK_DL = (4, 4) + (5,) * 28
+WRITER_LL = (8,) * 255 + (9, 9)                      # literal v < 255: the eight bits of v, MSB first -- a run of literals WRITES chosen bits
+EOB15_LL = (8,) * 255 + (9, 15, 10, 11, 12, 13, 14, 15)      # the end-of-block code has 15 bits
+assert kraft(BULK_LL) == kraft(WRITER_LL) == kraft(EOB15_LL) == 1 << 15 and EOB15_LL[256] == 15
+ONE_BIT_LL = tuple(sparse(257, {97: 1, 256: 1}))    # 'a' = the bit 0, end of block = the bit 1: a token per bit
+
+
+def rev8(v):
+    return int(format(v, "08b")[::-1], 2)
+
+
+def header_image():
+    """-> (bytes, header bits): a complete, valid, FINAL dynamic block -- 101 header bits, eight literals, the end-of-block code -- as
+    whole bytes, none of them 255 (so that literals of WRITER_LL can write it)"""
+    w = Bits()
+    b = emit_block(w, list(ONE_BIT_LL), [0], [97] * 8, True)
+    img = w.bytes()
+    assert 255 not in img and zlib.decompressobj(-15).decompress(img) == b"a" * 8
+    return img, b["span"][1]
+
+
+def find_passes(z):
+    """the bit positions of z that pass the two tests of k_any_find (BTYPE = 10, HLIT <= 29, HDIST <= 29; a complete code-length code),
+    restated: what A_NCAND counts"""
+    nbits, zp, out = 8 * len(z), z + bytes(16), []
+    for B in range(2, len(z)):
+        w = int.from_bytes(zp[B:B + 13], "little")
+        for j in range(8):
+            x = w >> j
+            if 8 * B + j + 29 > nbits or (x >> 1) & 3 != 2 or (x >> 3) & 31 > 29 or (x >> 8) & 31 > 29:
+                continue
+            left, f = 128, x >> 17
+            for _ in range(((x >> 13) & 15) + 4):
+                left -= (128 >> (f & 7)) if f & 7 else 0
+                f >>= 3
+            if left == 0:
+                out.append(8 * B + j)
+    return out
+
+
+class ChainCase(object):
+    """name; z; plain (None: a damaged stream); expect: "any" | "fixed" | "serial", the verdict of the stream alone; evidence: for
+    "serial", names of which at least one must show -- a W_* bit of A_WHY, "A_OVER", "C_NCROSS" (the fixed chain's list of end-of-block
+    codes overflowed), "A_OPEN" (the gate stayed shut: the chain for any block types never ran); exactly / at_least: counters of the
+    Verdict; props: the measured properties that put the case on its side of its limit; ndyn: its own dynamic blocks; images: the bit
+    offsets in z of embedded header images; expect_at(lay): the verdict in a batch whose in_len gives the list sizes `lay`
+    (chain_verdict.lay) -- the lists of the chain for any block types are sized by the CALL's in_len, so a case on one of those limits
+    alone may be within it in a batch of longer streams; big: one of the two streams of 4 MiB"""
+
+    def __init__(self, name, z, plain, expect, evidence=(), exactly=None, at_least=None, props=None, ndyn=0, images=(), expect_at=None,
+                 big=False, records=()):
+        self.name, self.z, self.plain, self.expect, self.evidence = name, z, plain, expect, tuple(evidence)
+        self.exactly, self.at_least, self.props = exactly or {}, at_least or {}, props or {}
+        self.ndyn, self.images, self.big, self.records = ndyn, tuple(images), big, list(records)
+        self._expect_at = expect_at
+        assert expect in ("any", "fixed", "serial") and (expect == "serial") == bool(evidence), name
+
+    def expect_at(self, lay):
+        return self._expect_at(lay) if self._expect_at else self.expect
+
+    def __repr__(self):
+        return "ChainCase(%s)" % self.name
+
+
+class _Chain(object):
+    """a stream under construction: the writer, the plain bytes, a record per block with its bit positions in z (the zlib header's 16 bits
+    counted)"""
+
+    def __init__(self, seed):
+        self.w, self.out, self.rng, self.recs, self.ndyn, self.images = Bits(), bytearray(), random.Random(seed), [], 0, []
+
+    @property
+    def pos(self):
+        return 16 + self.w.pos
+
+    def dyn(self, ll, dl, toks, final=False, **kw):
+        start = self.pos
+        b = emit_block(self.w, list(ll), list(dl), toks, final, **kw)
+        assert apply_tokens(self.out, toks) is not None
+        self.ndyn += 1
+        self.recs.append(dict(kind="dynamic", hdr=start, pay=16 + b["span"][1], eob=self.pos - ll[256], end=self.pos, ll=ll, dl=dl, tokens=toks, block=b))
+        return self.recs[-1]
+
+    def fixed(self, toks, final=False):
+        start = self.pos
+        emit_fixed_block(self.w, toks, final)
+        assert apply_tokens(self.out, toks) is not None
+        self.recs.append(dict(kind="fixed", hdr=start, pay=start + 3, eob=self.pos - 7, end=self.pos, ll=FIXED_LL, dl=FIXED_DL, tokens=toks))
+        return self.recs[-1]
+
+    def stored(self, data, final=False):
+        start = self.pos
+        self.w.put(1 if final else 0, 1)
+        self.w.put(0, 2)
+        if self.w.n:
+            self.w.put(0, 8 - self.w.n)
+        self.w.put(len(data), 16)
+        self.w.put(len(data) ^ 0xFFFF, 16)
+        assert self.w.n == 0 and len(data) <= 65535
+        first = self.pos
+        self.w.out += data
+        self.w.pos += 8 * len(data)
+        self.out += data
+        self.recs.append(dict(kind="stored", hdr=start, data=first, length=len(data), end=self.pos))
+        return self.recs[-1]
+
+    def zseg(self, seg, data):
+        """a raw-deflate segment made by zlib and closed with a full flush, at a byte boundary"""
+        assert self.w.n == 0
+        self.recs.append(dict(kind="zlib", hdr=self.pos, end=self.pos + 8 * len(seg)))
+        self.w.out += seg
+        self.w.pos += 8 * len(seg)
+        self.out += data
+
+    def lits(self, n8, n9=0, lo=226):
+        """n8 random literals of 8 bits and n9 of 9 bits in BULK_LL (FIXED_LL: lo = 144), shuffled"""
+        t = [self.rng.randrange(lo) for _ in range(n8)] + [self.rng.randrange(lo, 256) for _ in range(n9)]
+        self.rng.shuffle(t)
+        return t
+
+    def bulk(self, ntok, final=False):
+        """a block of BULK_LL: random literals and a few short matches"""
+        toks, made = [], len(self.out)
+        for _ in range(ntok):
+            if made > 40 and self.rng.random() < 0.05:
+                toks.append((self.rng.randint(3, 40), self.rng.randint(1, min(made, 3000))))
+                made += toks[-1][0]
+            else:
+                toks.append(self.rng.randrange(256))
+                made += 1
+        return self.dyn(BULK_LL, BULK_DL, toks, final)
+
+    def fill_to(self, target):
+        """a block of BULK_LL, literals only, whose end-of-block code ends exactly at bit `target` of z"""
+        T = target - self.pos - _hdr_bits(BULK_LL, BULK_DL) - BULK_LL[256]
+        assert T >= 63, (target, self.pos)
+        return self.dyn(BULK_LL, BULK_DL, self.lits((T - 9 * (T % 8)) // 8, T % 8))
+
+    def next_at(self, residue, pb, ahead=0):
+        """the first bit t that fill_to can reach with (t + ahead) % pb == residue"""
+        t = self.pos + _hdr_bits(BULK_LL, BULK_DL) + BULK_LL[256] + 63
+        return t + (residue - t - ahead) % pb
+
+    def done(self, name, expect, **kw):
+        z = wrap(self.w.bytes(), bytes(self.out))
+        return ChainCase(name, z, bytes(self.out), expect, ndyn=self.ndyn, images=self.images, records=self.recs, **kw)
+
+
+@functools.lru_cache(None)
+def _hdr_bits(ll, dl):
+    w = Bits()
+    return emit_block(w, list(ll), list(dl), [], False)["span"][1]
+
+
+def _payload_to(s, ll, lo9, pay, target):
+    """literals of 8 bits (below lo9) and 9 bits that take the payload from bit `pay` exactly to bit `target`"""
+    T = target - pay
+    assert T >= 63
+    t = [s.rng.randrange(lo9) for _ in range((T - 9 * (T % 8)) // 8)] + [s.rng.randrange(lo9, 256) for _ in range(T % 8)]
+    s.rng.shuffle(t)
+    assert sum(ll[v] for v in t) == T
+    return t
+
+
+def _tree_kinds():
+    """the catalogue's kinds of tree as generators of (ll, dl, emit_block keywords) for block k"""
+    def bits15(rng, k):
+        return complete_code(286, rng, 15), complete_code(30, rng, 15), {}
+
+    def cl7(rng, k):
+        ll, dl = random_block_lengths(rng, count=40, max_len=9, dist_kind="several")
+        return ll, dl, dict(ops=rle_ops(ll + dl), cl_lens=complete_code(19, rng, 7), hclen=19)
+
+    def hlit257(rng, k):
+        ll = [0] * 257
+        for s_, l in zip([256] + rng.sample(range(256), 59), complete_code(60, rng, 9)):
+            ll[s_] = l
+        return ll, [1, 1], {}
+
+    def hlit286(rng, k):
+        ll = [0] * 286
+        for s_, l in zip([256, 285] + rng.sample([v for v in range(285) if v != 256], 98), complete_code(100, rng, 12)):
+            ll[s_] = l
+        return ll, complete_code(30, rng, 9), {}
+
+    def one_distance(rng, k):
+        ll, _ = random_block_lengths(rng, count=80, max_len=11, dist_kind="one")
+        c = (0, 3, 29, 12, 7)[k % 5]
+        return ll, sparse(c + 1 + k % 2, {c: 1}), {}
+
+    def no_distance(rng, k):
+        ll, _ = random_block_lengths(rng, count=90, max_len=12, dist_kind="none")
+        return ll, [0] * (1 + k % 3), {}
+
+    def repeat_crosses(rng, k):
+        a, b = rng.sample(range(256), 2)
+        return sparse(260, {a: 2, b: 2, 256: 3, 257: 3, 258: 3, 259: 3}), [3] * 8, dict(rle=True)
+    return (("15-bit codes", bits15), ("7-bit code-length code", cl7), ("HLIT 257", hlit257), ("HLIT 286", hlit286),
+            ("one-code distance set", one_distance), ("empty distance set", no_distance), ("repeat crosses into the distances", repeat_crosses))
+
+
+def _tree_cases(K):
+    out = []
+    for n, (name, gen) in enumerate(_tree_kinds()):
+        s = _Chain(9100 + n)
+        k = 0
+        while True:
+            last = k >= 2 and len(s.w.out) >= K["ANY_MIN"] + 300
+            ll, dl, kw = gen(s.rng, k)
+            r = s.dyn(ll, dl, tokens_for(s.rng, ll, dl, 1200, len(s.out)), last, **kw)
+            b = r["block"]
+            if name == "15-bit codes":
+                assert b["max_ll"] == 15 and b["max_dl"] == 15
+            elif name == "7-bit code-length code":
+                assert b["max_cl"] == 7 and b["hclen"] == 19
+            elif name.startswith("HLIT"):
+                assert len(ll) == int(name[5:]) and (len(ll) == 257 or ll[285])
+            elif name == "one-code distance set":
+                assert b["ndcoded"] == 1
+            elif name == "empty distance set":
+                assert b["ndcoded"] == 0
+            else:
+                assert b["cross"] and b["rle"]
+            k += 1
+            if last:
+                break
+        out.append(s.done("trees: " + name, "any", at_least=dict(nblk=s.ndyn)))
+    return out
+
+
+def _position_stream(s, pb, tag):
+    """into s: a block whose payload starts at bit = 0, 1 and pb - 1 mod pb, and one whose header's first bit is the last bit of a piece
+    -> props"""
+    props, H = {}, _hdr_bits(BULK_LL, BULK_DL)
+    for what, residue in (("pay", 0), ("pay", 1), ("pay", pb - 1), ("hdr", pb - 1)):
+        s.fill_to(s.next_at(residue, pb, H if what == "pay" else 0))
+        r = s.bulk(700)
+        props["%s %s = %d mod pb" % (tag, what, residue)] = (r[what], "pb", residue)
+        assert r[what] % pb == residue
+    return props
+
+
+def _position_cases(K):
+    out = []
+    for what, residue in (("pay", 0), ("pay", 1), ("pay", 1023), ("hdr", 1023)):
+        s = _Chain(9200 + residue + (what == "hdr"))
+        s.bulk(1500)
+        s.fill_to(s.next_at(residue, 1024, _hdr_bits(BULK_LL, BULK_DL) if what == "pay" else 0))
+        r = s.bulk(1500)
+        s.bulk(1500, True)
+        out.append(s.done("position: %s at %d mod 1024" % ("payload" if what == "pay" else "header", residue), "any", at_least=dict(nblk=3),
+                          props={"%s mod pb" % what: (r[what], "pb", residue)}))
+    return out
+
+
+def _eob_edge_cases(K):
+    out = []
+    for residue in (1023, 0):
+        s = _Chain(9300 + residue)
+        s.bulk(2200)
+        pay = s.pos + _hdr_bits(EOB15_LL, (1, 1))
+        target = pay + 4000 + (residue - (pay + 4000)) % 1024
+        r = s.dyn(EOB15_LL, (1, 1), _payload_to(s, EOB15_LL, 255, pay, target))
+        assert r["pay"] == pay and r["eob"] == target and r["end"] - r["eob"] == 15
+        s.bulk(2200, True)
+        out.append(s.done("end-of-block: a 15-bit code that starts at %d mod 1024" % residue, "any", at_least=dict(nblk=3),
+                          props={"end-of-block code mod pb": (r["eob"], "pb", residue)}))
+    return out
+
+
+def _writer_block(s, nimg, lead, gap, tail, final=False):
+    """a block of WRITER_LL whose literals write `nimg` header images into the stream, `gap` random literals (8 bits each) behind each"""
+    img, _ = header_image()
+    toks, at = [s.rng.randrange(255) for _ in range(lead)], []
+    for _ in range(nimg):
+        at.append(len(toks))
+        toks += [rev8(v) for v in img] + [s.rng.randrange(255) for _ in range(gap)]
+    toks += [s.rng.randrange(255) for _ in range(tail)]
+    r = s.dyn(WRITER_LL, (0,), toks, final)
+    s.images += [r["pay"] + 8 * k for k in at]
+    return r
+
+
+def _false_positive_cases(K):
+    out = []
+    for nimg in (1, 2, 3):
+        s = _Chain(9400 + nimg)
+        s.bulk(1500)
+        r = _writer_block(s, nimg, 300, 512, 600)
+        s.bulk(1500, True)
+        taken = nimg < K["WALK_ROUNDS"]
+        out.append(s.done("false positives: %d in a row inside one block" % nimg, "any" if taken else "serial",
+                          evidence=() if taken else ("W_WALK_OWNER",), at_least=dict(nblk=3 + nimg, nreq=nimg if taken else 0),
+                          props={"images in a row": (nimg, "WALK", ("below", "last", "first")[nimg - 1]),
+                                 "whole pieces between the images and behind the last": (512 * 8 // 1024, "ONE", "above")}))
+    # a request of more than REQ_MAX pieces: the rest is asked for in the next round
+    s = _Chain(9410)
+    s.bulk(1500)
+    r = _writer_block(s, 1, 300, 0, (K["REQ_MAX"] + 16) * 128)
+    s.bulk(1500, True)
+    asked = -(-s.recs[-1]["pay"] // 1024) + (s.images[0] + header_image()[1]) // -1024        # from the image's first whole piece to the next block's payload
+    c = s.done("false positives: a request longer than REQ_MAX pieces", "any", at_least=dict(nblk=4, nreq=2, reqp=K["REQ_MAX"] + 1),
+               props={"pieces asked for": (asked, "REQ_MAX", "above"), "pieces asked for, of the list": (asked, "mapcap", "below")})
+    out.append(c)
+    return out
+
+
+def _list_cases(K, lay):
+    out = []
+    img, _ = header_image()
+    # ---- maxb: the true blocks and the images in a stored block together, one below the list's size, on it, one above
+    for total in (63, 64, 65):
+        s = _Chain(9500 + total)
+        data = b"".join(img + bytes(64 - len(img)) for _ in range(total - 1)) + bytes(200)
+        r = s.stored(data)
+        s.images += [r["data"] + 512 * k for k in range(total - 1)]
+        s.bulk(1500, True)
+        c = s.done("lists: %d candidate blocks" % total, "any", exactly=dict(nblk=total))
+        maxb = lay(len(c.z)).maxb
+        c.props = {"candidate blocks": (total, "maxb", ("below", "last", "first")[total - 63])}
+        if total > maxb:
+            c.expect, c.evidence = "serial", ("A_OVER",)
+        c._expect_at = lambda L, total=total: "any" if total <= L.maxb else "serial"
+        out.append(c)
+    # ---- candcap: a stored block of a four-byte period that passes k_any_find's tests (no position of it is a header), zero bytes
+    # behind it that add to the list's size and not to the list
+    period = (4 | 1 << 17 | 1 << 20).to_bytes(4, "little")           # BTYPE = 10, HLIT = HDIST = HCLEN = 0, the lengths 1, 1, 0, 0
+    def build(m, zeros, seed=9600):
+        s = _Chain(seed)
+        s.stored(period * m + bytes(16 * zeros))
+        s.bulk(1200, True)
+        return s
+    m = 1400
+    while True:
+        s = build(m, 0)
+        z = wrap(s.w.bytes(), bytes(s.out))
+        d = len(find_passes(z)) - lay(len(z)).candcap
+        if d >= 2:
+            break
+        m += 40
+    for over in (0, 1):
+        s = build(m, d - over)
+        c = s.done("lists: %s than candcap positions pass the search" % ("one more" if over else "no more"), "serial" if over else "any",
+                   evidence=("A_OVER",) if over else ())
+        n = len(find_passes(c.z))
+        assert n == lay(len(c.z)).candcap + over, (n, lay(len(c.z)).candcap, over)
+        c.exactly, c.props = dict(ncand=n), {"positions that pass the search": (n, "candcap", "first" if over else "last")}
+        c._expect_at = lambda L, n=n: "any" if n <= L.candcap else "serial"
+        out.append(c)
+    return out
+
+
+def _stored_cases(K, lay):
+    out = []
+    # ---- maxs: small non-empty stored blocks, a run of empty ones among them (they take no entry of the list)
+    def build(n):
+        s = _Chain(9700)
+        for k in range(n):
+            if k == n // 2:
+                for _ in range(20):
+                    s.stored(b"")
+            s.stored(bytes((k * 7 + j) & 31 for j in range(16)), k == n - 1)
+        return s
+    n, want = 256, [0, 1]
+    while want:
+        s = build(n)
+        zn = len(s.w.bytes()) + 6
+        if n - lay(zn).maxs == want[0]:
+            over = want.pop(0)
+            c = s.done("stored: %s non-empty stored blocks than maxs" % ("one more" if over else "no more"), "serial" if over else "any",
+                       evidence=("A_OVER",) if over else (), exactly=dict(ns=n, ncand=0), props={"non-empty stored blocks": (n, "maxs", "first" if over else "last")})
+            assert len(c.z) == zn and not find_passes(c.z)
+            c._expect_at = lambda L, n=n: "any" if n <= L.maxs else "serial"
+            out.append(c)
+        n += 1
+        assert n < 400
+    # ---- a final stored block whose data ends exactly at the trailer, its header at each bit offset
+    for offset in range(8):
+        s = _Chain(9710 + offset)
+        s.bulk(1200)
+        s.fill_to(s.next_at(0, 8))
+        start = s.pos
+        lits = emit_fixed_prefix(s.w, PREFIX_FOR_OFFSET[offset])
+        s.out += lits
+        s.recs.append(dict(kind="fixed", hdr=start, pay=start + 3, eob=s.pos - 7, end=s.pos, ll=FIXED_LL, dl=FIXED_DL, tokens=list(lits)))
+        r = s.stored(bytes(s.rng.randrange(256) for _ in range(3000)), True)
+        assert r["hdr"] % 8 == offset
+        c = s.done("stored: the last block ends at the trailer, header at bit %d" % offset, "any", exactly=dict(ns=1),
+                   props={"header bit": (r["hdr"], "byte", offset)})
+        assert r["data"] // 8 + r["length"] == len(c.z) - 4
+        out.append(c)
+    return out
+
+
+def fixed_walk_starts(pay, bits, pb):
+    """where k_any_walk begins an item while it follows a fixed block whose payload starts at bit `pay` (bits: the tokens' sizes, the
+    end-of-block code last): the payload's first bit, then the first token boundary at or behind every piece boundary"""
+    starts, pos, limit = [pay], pay, (pay // pb + 1) * pb
+    for nb in bits[:-1]:
+        pos += nb
+        if pos >= limit:
+            starts.append(pos)
+            limit = (pos // pb + 1) * pb
+    return starts
+
+
+def _fixed_cases(K):
+    out = []
+    F = K["FIX_MAX_BITS"]
+    # ---- a fixed block behind a dynamic one, its payload on a piece boundary: the walk takes it while its end-of-block code starts within
+    # FIX_MAX_BITS of the payload's first bit
+    for over in (0, 1):
+        s = _Chain(9800 + over)
+        s.bulk(1500)
+        s.fill_to(s.next_at(1024 - 3, 1024))
+        pay = s.pos + 3
+        r = s.fixed(_payload_to(s, FIXED_LL, 144, pay, pay + F - 1 + over))
+        s.bulk(1500, True)
+        starts = fixed_walk_starts(pay, token_bits(FIXED_LL, FIXED_DL, r["tokens"]) + [7], 1024)
+        assert pay % 1024 == 0 and (max(starts) >= pay + F or r["eob"] >= max(starts) + 1024) == bool(over)
+        out.append(s.done("fixed: a block of %d bits behind a dynamic one" % (r["end"] - r["hdr"]), "serial" if over else "any",
+                          evidence=("W_WALK_FIX",) if over else (), at_least=dict(nblk=3),
+                          props={"end-of-block code - payload": (r["eob"] - pay, "FIX", "first" if over else "last"), "payload mod pb": (pay, "pb", 0)}))
+    # ---- a FIRST block that is fixed: the gate opens when its end-of-block code starts within FIRST_FIX_BITS and another type follows
+    G = K["FIRST_FIX_BITS"]
+    for over in (0, 1):
+        for follow in ("dynamic", "stored"):
+            s = _Chain(9810 + 2 * over + (follow == "stored"))
+            r = s.fixed(_payload_to(s, FIXED_LL, 144, 19, 19 + G - 1 + over))
+            assert r["pay"] == 19 and r["eob"] - 19 == G - 1 + over
+            if follow == "dynamic":
+                s.bulk(2200)
+                s.bulk(2200, True)
+            else:
+                s.stored(bytes(s.rng.randrange(256) for _ in range(4200)), True)
+            out.append(s.done("fixed first: its end-of-block code %d bits in, a %s block behind it" % (G - 1 + over, follow),
+                              "serial" if over else "any", evidence=("A_OPEN",) if over else (),
+                              exactly=dict(open=0 if over else 1), props={"end-of-block code - payload": (r["eob"] - 19, "FIRST_FIX", "first" if over else "last")}))
+    s = _Chain(9820)
+    s.fixed(s.lits(2400, 100, 144))
+    s.fixed(s.lits(2400, 100, 144), True)
+    out.append(s.done("fixed first: another fixed block behind it", "fixed", exactly=dict(open=0)))
+    # ---- the fixed-block chain lists MAXCROSS end-of-block codes
+    for over in (0, 1):
+        s = _Chain(9830 + over)
+        n = K["MAXCROSS"] + over
+        for k in range(n):
+            s.fixed([s.rng.randrange(144)] if k < n - 1 else [200], k == n - 1)
+        assert (-s.w.pos) % 8 >= 3                     # (three zero bits behind the last end-of-block code: no fixed header, the chain of pieces ends)
+        out.append(s.done("fixed chain: %d short fixed blocks" % n, "serial" if over else "fixed", evidence=("C_NCROSS",) if over else (),
+                          props={"fixed blocks": (n, "MAXCROSS", "first" if over else "last")}))
+    return out
+
+
+def _token_cases(K, lay):
+    out = []
+    # ---- a token per bit: 1024 tokens in a piece, a list holds tcap.  One dense stretch ...
+    s = _Chain(9900)
+    s.bulk(1500)
+    r = s.dyn(ONE_BIT_LL, (0,), [97] * (16 * 1024))
+    s.bulk(1500, True)
+    c = s.done("tokens: one stretch of 16 pieces with a token per bit", "any", at_least=dict(nblk=3, nx=3 + 1))
+    L = lay(len(c.z))
+    c.props = {"tokens per piece": (1024, "tcap", "above"), "lists wanted beyond the pieces' own": (3 * 16 + 8, "maxx", "below")}
+    assert 1024 > L.tcap and 3 * 16 + 8 <= L.maxx
+    out.append(c)
+    # ... and a stream that is dense throughout: more lists than the budget of extra items (k_any_tokens: W_TCAP)
+    s = _Chain(9901)
+    b = emit_block(s.w, list(ONE_BIT_LL), [0], [], True, eob=False)
+    n = 1000 * 1024
+    s.w.put(0, n)
+    s.w.put(1, 1)
+    s.out += b"a" * n
+    s.ndyn = 1
+    s.recs.append(dict(kind="dynamic", hdr=16, pay=16 + b["span"][1], eob=s.pos - 1, end=s.pos, ll=ONE_BIT_LL, dl=(0,), tokens=None, ntokens=n))
+    c = s.done("tokens: a token per bit throughout", "serial", evidence=("W_TCAP",), at_least=dict(nblk=1))
+    want = lambda L: sum(-(-min(1024, s.recs[0]["eob"] - max(q * 1024, s.recs[0]["pay"])) // L.tcap) - 1
+                         for q in range(s.recs[0]["pay"] // 1024, s.recs[0]["eob"] // 1024 + 1)) + 1
+    L = lay(len(c.z))
+    c.props = {"tokens per piece": (1024, "tcap", "above"), "lists wanted beyond the pieces' own": (want(L), "maxx", "above")}
+    assert want(L) > L.maxx
+    c._expect_at = lambda L_: "serial" if want(L_) > L_.maxx else "any"
+    out.append(c)
+    return out
+
+
+@functools.lru_cache(None)
+def _zlib_bulk():
+    """-> (segment, data): 4.3 MB of raw deflate made by zlib (dynamic blocks of 6-bit random bytes), closed with a full flush"""
+    import numpy as np
+    data = np.random.default_rng(77).integers(0, 64, 5900000, dtype=np.uint8).tobytes()
+    co = zlib.compressobj(1, zlib.DEFLATED, -15)
+    seg = co.compress(data) + co.flush(zlib.Z_FULL_FLUSH)
+    assert len(seg) >= (4 << 20) + 4096 and (seg[0] >> 1) & 3 == 2
+    return seg, data
+
+
+def _big_cases(K, lay):
+    seg, data = _zlib_bulk()
+    s = _Chain(9950)
+    s.zseg(seg, data)
+    props = _position_stream(s, 2048, "behind 4 MiB:")
+    s.bulk(1500, True)
+    a = s.done("pb = 2048: positions of headers and payloads", "any", at_least=dict(nblk=s.ndyn), props=props, big=True)
+    s = _Chain(9951)
+    s.zseg(seg, data)
+    s.bulk(1500)
+    r = _writer_block(s, 2, 600, 2048, 2048)
+    s.bulk(1500, True)
+    b = s.done("pb = 2048: two false positives in a row", "any", at_least=dict(nblk=s.ndyn + 2, nreq=2), big=True,
+               props={"images in a row": (2, "WALK", "last"), "whole pieces between the images and behind the last": (2048 * 8 // 2048, "ONE", "above")})
+    for c in (a, b):
+        assert lay(len(c.z)).pb == 2048
+    return [a, b]
+
+
+def _damaged(case, rec, what):
+    """-> ChainCase: `case` with one bit flipped -- "header": BTYPE 10 -> 11 in the block of `rec`; "payload": the first bit behind the
+    payload's 200th after which stock zlib no longer finds the stream's end"""
+    z = bytearray(case.z)
+    if what == "header":
+        bit = rec["hdr"] + 1
+    else:
+        for bit in range(rec["pay"] + 200, rec["eob"]):
+            m = bytearray(case.z)
+            m[bit >> 3] ^= 1 << (bit & 7)
+            d = zlib.decompressobj(-15)                  # (the raw stream: a flip that only changes a literal is no damage to a decoder)
+            try:
+                d.decompress(bytes(m[2:]))
+                bad = not d.eof
+            except zlib.error:
+                bad = True
+            if bad:
+                break
+        else:
+            raise AssertionError("no flip found")
+    z[bit >> 3] ^= 1 << (bit & 7)
+    c = ChainCase("damaged (%s): %s" % (what, case.name), bytes(z), None, "serial", evidence=("damaged",))
+    c.neighbour, c.bit = case, bit
+    return c
+
+
+def chain_limits(K, L):
+    """the largest value each limit of the chains TAKES, from the constants K (chain_verdict.source_constants) and the list sizes L
+    (chain_verdict.lay of the stream's length) -- and the two moduli of the position properties"""
+    return dict(pb=L.pb, byte=8, ONE=1, FIX=K["FIX_MAX_BITS"] - 1, FIRST_FIX=K["FIRST_FIX_BITS"] - 1, WALK=K["WALK_ROUNDS"] - 1,
+                MAXCROSS=K["MAXCROSS"], REQ_MAX=K["REQ_MAX"], maxb=L.maxb, maxs=L.maxs, candcap=L.candcap, mapcap=L.mapcap, tcap=L.tcap, maxx=L.maxx)
+
+
+def off_limit(case, K, L):
+    """the declared properties of `case` that do not hold under the constants K and list sizes L -> [text]: (measured, limit, side) with
+    side "last" (the largest value taken), "first" (one more), "below", "above", or a residue of a bit position modulo the limit"""
+    lim, out = chain_limits(K, L), []
+    for what, (m, key, side) in sorted(case.props.items()):
+        v = lim[key]
+        ok = m % v == side if isinstance(side, int) else {"last": m == v, "first": m == v + 1, "below": m < v, "above": m > v}[side]
+        if not ok:
+            out.append("%s: %s = %d is not %s %s = %d" % (case.name, what, m, "%d modulo" % side if isinstance(side, int) else side, key, v))
+    return out
+
+
+@functools.lru_cache(None)
+def chain_cases():
+    """-> [ChainCase]: every limit of the two whole-GPU inflate chains, the last value taken and the first given up"""
+    import chain_verdict as V
+    K = V.source_constants()
+    cs = _tree_cases(K) + _position_cases(K) + _eob_edge_cases(K) + _false_positive_cases(K) + _list_cases(K, V.lay) + \
+        _stored_cases(K, V.lay) + _fixed_cases(K) + _token_cases(K, V.lay) + _big_cases(K, V.lay)
+    by = dict((c.name, c) for c in cs)
+    a, b = by["position: payload at 0 mod 1024"], by["end-of-block: a 15-bit code that starts at 1023 mod 1024"]
+    cs += [_damaged(a, a.records[2], "header"), _damaged(b, b.records[1], "payload")]
+    assert len(set(c.name for c in cs)) == len(cs)
+    for c in cs:
+        assert len(c.z) >= K["ANY_MIN"], c.name
+    return cs

@@ -5,8 +5,11 @@ import ctypes, os, random, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import hdl_deflate_amd
 from hdl_deflate_amd.data import make_blocks
+import chain_verdict                             # the control words' indices, read from the kernels' sources
+K = chain_verdict.source_constants()
 
 eng = hdl_deflate_amd.Engine()
 L = eng.lib
@@ -41,10 +44,12 @@ def run(name, z, want, reps=3):
         oc, oa = ctypes.c_size_t(0), ctypes.c_size_t(0)
         L.hdlz_debug_par_offsets(len(z), 1, cap, 0, ctypes.byref(oc), ctypes.byref(oa))
         w32 = work.view(torch.int32)
-        cf = w32[oc.value // 4: oc.value // 4 + 64].cpu().tolist()
-        ca = w32[oa.value // 4: oa.value // 4 + 64].cpu().tolist()
+        cf = w32[oc.value // 4: oc.value // 4 + K["C_WORDS"]].cpu().tolist()
+        ca = w32[oa.value // 4: oa.value // 4 + K["C_WORDS"]].cpu().tolist()
         info = " F[fallback %d notfixed %d ok %d] ANY[fallback %d ok %d total %d nused %d mark %d | ncand %d nblk %d nx %d ns %d over %d why %#x nreq %d reqp %d dbg %s] scratch %.1f MB" % (
-            cf[0], cf[7], cf[3], ca[0], ca[3], ca[2], ca[1], ca[4], ca[40], ca[41], ca[42], ca[43], ca[44], ca[45], ca[46], ca[47], ca[48:54], wb / 1e6)
+            cf[K["C_FALLBACK"]], cf[K["C_NOTFIXED"]], cf[K["C_OK"]], ca[K["C_FALLBACK"]], ca[K["C_OK"]], ca[K["C_TOTAL"]], ca[K["C_NUSED"]], ca[K["C_MARK"]],
+            ca[K["A_NCAND"]], ca[K["A_NBLK"]], ca[K["A_NX"]], ca[K["A_NS"]], ca[K["A_OVER"]], ca[K["A_WHY"]], ca[K["A_NREQ"]], ca[K["A_NREQP"]],
+            ca[K["A_OPEN"]:K["A_OPEN"] + 6], wb / 1e6)
     print("%-34s z %9d -> %10d  %s  %8.3f ms  %8.1f MB/s%s" % (name, len(z), n, "OK " if ok else "BAD", min(ts) * 1e3, n / min(ts) / 1e6, info), flush=True)
     return ok
 

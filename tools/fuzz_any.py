@@ -11,8 +11,9 @@ import zlib
 
 import numpy as np
 
-sys.path.insert(0, ".")
+sys.path[:0] = [".", "tests"]
 import torch                                   # noqa: E402
+import chain_verdict                           # noqa: E402  (the control words' indices and the list sizes, read from the kernels' sources)
 import hdl_deflate_amd                         # noqa: E402
 from oracle import oracle as O                 # noqa: E402
 
@@ -135,15 +136,16 @@ def main():
             if dbg and not ragged:
                 oc, oa = ctypes.c_size_t(0), ctypes.c_size_t(0)
                 L.hdlz_debug_par_offsets(len(zs[0]), 1, cap, 0, ctypes.byref(oc), ctypes.byref(oa))
-                ca = work.view(torch.int32)[oa.value // 4: oa.value // 4 + 64].cpu().tolist()
-                zn_ = len(zs[0])
+                K = chain_verdict.source_constants()
+                ca = work.view(torch.int32)[oa.value // 4: oa.value // 4 + K["C_WORDS"]].cpu().tolist()
+                lay = chain_verdict.lay(len(zs[0]))
                 over = []
-                if ca[44]:
-                    if ca[40] > 8 * zn_ // 128 + 1024: over.append("cand")
-                    if ca[41] > min(8000, max(64, zn_ // 1024)): over.append("blocks")
-                    if ca[43] > zn_ // 512 + 256: over.append("stored")
-                    if not over: over.append("items/queue nx=%d" % ca[42])
-                whys[(ca[0], hex(ca[45]), "+".join(over))] += 1          # fallback flag, why bits, which list overflowed
+                if ca[K["A_OVER"]]:
+                    if ca[K["A_NCAND"]] > lay.candcap: over.append("cand")
+                    if ca[K["A_NBLK"]] > lay.maxb: over.append("blocks")
+                    if ca[K["A_NS"]] > lay.maxs: over.append("stored")
+                    if not over: over.append("items/queue nx=%d" % ca[K["A_NX"]])
+                whys[(ca[K["C_FALLBACK"]], hex(ca[K["A_WHY"]]), "+".join(over))] += 1          # fallback flag, why bits, which list overflowed
     print("fuzz_any seed %d: %d cases, %d damaged or cut streams, %.1f MB inflated, all equal to the oracle; %d of %d large good single "
           "streams at whole-GPU speed" % (a.seed, it, damaged, nbytes / 1e6, taken, big), flush=True)
     if dbg:
