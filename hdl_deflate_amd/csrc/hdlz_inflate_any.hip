@@ -45,6 +45,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "hdlz_device.h"
+#include "hdlz_inflate_rules.h"
 #include "hdlz_inflate_tables.h"
 #include "hdlz_inflate_par.h"
 
@@ -236,7 +237,8 @@ __device__ __forceinline__ Token token_at(const Tab* t, Bits& r) {
 // ================================================================================================ 1. the candidates
 // the cheap part of the test: BTYPE = 10, HLIT <= 29, HDIST <= 29 (22 % of all positions pass)
 __device__ __forceinline__ bool header_fields_ok(uint32_t x) {
-    return ((x >> 1) & 3u) == 2u && ((x >> 3) & 31u) <= 29u && ((x >> 8) & 31u) <= 29u;
+    uint32_t nlen, ndist, ncode;
+    return ((x >> 1) & 3u) == 2u && rules::dyn_header_fields(x >> 3, nlen, ndist, ncode);
 }
 // ... and the rest: a COMPLETE code-length code (lo: the 64 stream bits from the header's first bit on, hi: the 32 behind them)
 __device__ __forceinline__ bool header_precode_ok(uint64_t lo, uint32_t hi) {
@@ -248,7 +250,7 @@ __device__ __forceinline__ bool header_precode_ok(uint64_t lo, uint32_t hi) {
         f >>= 3;
         left -= l ? (int32_t)(128u >> l) : 0;
     }
-    return left == 0;
+    return rules::cl_code_ok(left);
 }
 constexpr uint32_t FIND_T = 256, FIND_CAP = 2048, FIND_Q = 640;
 __global__ __launch_bounds__(FIND_T) void k_any_find(Args a) {
@@ -316,18 +318,17 @@ __global__ __launch_bounds__(FIND_T) void k_any_find(Args a) {
     flush();
 }
 
-// one LANE per listed position: the code lengths, and the rest of the serial decoder's acceptance rules (hdlz_inflate_dyn.hip, "BL" ..
-// "canon_build": over-subscribed sets rejected, incomplete ones only with exactly one code of length 1 -- for the distance code also with none --,
-// an end-of-block code must exist, the header must leave room for the reference's end-of-input margin)
+// one LANE per listed position: the code lengths, and the rest of the acceptance rules (hdlz_inflate_rules.h: over-subscribed sets
+// rejected, incomplete ones only with exactly one code of length 1 -- for the distance code also with none --, an end-of-block code
+// must exist, the header must leave room for the reference's end-of-input margin)
 // the code-length code of the header at bit p into a 7-bit table (symbol << 3 | length by the next 7 stream bits; stride: elements between
 // entries -- the lanes of k_any_headers interleave theirs); -> the reader behind the 3-bit lengths, HLIT + 257, HDIST + 1, BFINAL
-static __device__ const uint8_t CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 __device__ __forceinline__ void read_precode(Bits& r, uint8_t* clut, uint8_t* cl, uint32_t stride, uint32_t& nlen, uint32_t& ndist, uint32_t& fin) {
     fin = (uint32_t)r.bb & 1u;
     r.take(3u);
     r.refill();
-    nlen = ((uint32_t)r.bb & 31u) + 257u; ndist = (((uint32_t)r.bb >> 5) & 31u) + 1u;
-    const uint32_t ncode = (((uint32_t)r.bb >> 10) & 15u) + 4u;
+    uint32_t ncode;
+    rules::dyn_header_fields((uint32_t)r.bb, nlen, ndist, ncode);     // (legal counts: k_any_find checked)
     r.take(14u);
     for (uint32_t k = 0; k < 19u; k++) cl[k * stride] = 0;
     uint64_t cnt8 = 0;                                              // counts of the lengths 1..7, 8 bits each
@@ -336,7 +337,7 @@ __device__ __forceinline__ void read_precode(Bits& r, uint8_t* clut, uint8_t* cl
             r.refill();
             const uint32_t l = (uint32_t)r.bb & 7u;
             r.take(3u);
-            cl[CL_ORDER[k] * stride] = (uint8_t)l;
+            cl[rules::CL_ORDER[k] * stride] = (uint8_t)l;
             cnt8 += l ? (1ull << (8u * l)) : 0ull;
         }
     }
@@ -363,6 +364,7 @@ __device__ __forceinline__ void read_length(Bits& r, const uint8_t* clut, uint32
     const uint32_t e = clut[((uint32_t)r.bb & 127u) * stride], l = e & 7u;
     sy = e >> 3;
     r.take(l);
+    // (rules::cl_extra_bits / cl_repeat / cl_value, spelled out per symbol: through the calls k_any_tables needs 2 to 6 VGPRs more)
     rep = 1u; val = sy;
     if (sy == 16u) { rep = 3u + ((uint32_t)r.bb & 3u); r.take(2u); val = prev; }
     else if (sy == 17u) { rep = 3u + ((uint32_t)r.bb & 7u); r.take(3u); val = 0u; }
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(64) void k_any_headers(Args a) {
     if (v.ctl[A_OVER] != 0u) { if (threadIdx.x == 0u && blockIdx.x == 0u) give_up(v); return; }
     const uint32_t lane = threadIdx.x, ncand = min(v.ctl[A_NCAND], a.candcap);
     const uint32_t nbits = 8u * v.zn;
-    const int32_t isize = (int32_t)v.zn - 1;
+    const int32_t isize = rules::isize_of(v.zn);
     for (uint32_t c0 = blockIdx.x * 64u; c0 < ncand; c0 += gridDim.x * 64u) {
         const uint32_t i = c0 + lane;
         bool ok = i < ncand;
@@ -397,19 +399,20 @@ __global__ __launch_bounds__(64) void k_any_headers(Args a) {
             if (ok && idx < total) {
                 uint32_t val, rep, sy;
                 read_length(r, &L.clut[0][lane], 64u, prev, val, rep, sy);
-                if ((sy == 16u && idx == 0u) || idx + rep > total || r.pos > nbits) ok = false;
+                if (!rules::cl_step_ok(sy, idx, rep, total) || r.pos > nbits) ok = false;
                 const uint32_t n1 = idx < nlen ? min(rep, nlen - idx) : 0u, n2 = rep - n1;
                 if (val) { kr1 += n1 << (15u - val); kr2 += n2 << (15u - val); nz1 += n1; nz2 += n2; }
                 if (kr1 > 32768u || kr2 > 32768u) ok = false;                                // over-subscribed
-                if (idx <= 256u && 256u < idx + rep) eob_len = val;
+                if (rules::cl_run_covers_eob(idx, rep)) eob_len = val;
                 prev = val;
                 idx += rep;
             }
         }
         if (eob_len == 0u) ok = false;                                                        // no end-of-block code
-        if (kr1 < 32768u && !(nz1 == 1u && kr1 == 16384u)) ok = false;                        // incomplete: only as one code of length 1 (Kraft sum 1/2)
-        if (kr2 < 32768u && !(nz2 == 0u || (nz2 == 1u && kr2 == 16384u))) ok = false;         // ... the distance code also with none
-        if ((int32_t)(r.pos >> 3) > isize - 3) ok = false;                                    // (the serial decoder's NO EOF at the end of a header)
+        // (a single code has length 1 when its Kraft sum is 1/2; over-subscribed sets were dropped above)
+        if (!rules::code_set_ok((int32_t)(32768u - kr1), nz1, kr1 == 16384u ? 1u : 0u, false)) ok = false;
+        if (!rules::code_set_ok((int32_t)(32768u - kr2), nz2, kr2 == 16384u ? 1u : 0u, true)) ok = false;
+        if (rules::no_eof_behind_code(r.pos, isize)) ok = false;                              // (the serial decoder's NO EOF at the end of a header)
         if (ok) {
             const uint32_t slot = atomicAdd(&v.ctl[A_NBLK], 1u);
             if (slot < a.maxb) v.blk[slot] = Blk{p, r.pos, fin, nlen};
@@ -769,8 +772,8 @@ __global__ __launch_bounds__(64) void k_any_walk(Args a, uint32_t round) {
 __device__ __forceinline__ void walk_node(const Args& a, const View& v, uint32_t round, uint32_t n, uint32_t i, uint32_t lane, uint32_t* smap, uint32_t* sown, Tab* ltp) {
     Tab& lt = *ltp;
     const uint32_t nbits = 8u * v.zn;
-    const int32_t isize = (int32_t)v.zn - 1;
-    const uint32_t len_mask = a.obsize ? ((1u << (31u - (uint32_t)__builtin_clz(a.obsize))) - 1u) : 0xFFFFu;     // deflate.py:329,:714
+    const int32_t isize = rules::isize_of(v.zn);
+    const uint32_t len_mask = rules::stored_len_mask(a.obsize);
     const uint32_t node_id = i < n ? i : a.maxb;
     if (round != 0u && v.node[node_id].ok != 3u) return;              // later rounds: the walks that wait for pieces of their own
     uint64_t nb = 0;                      // bytes of this node so far
@@ -887,9 +890,7 @@ __device__ __forceinline__ void walk_node(const Args& a, const View& v, uint32_t
         if (ty == 3u) { ok = false; why |= W_WALK_HDR; break; }
         if (ty == 0u) {
             // stored (deflate.py:709-717, :1603-1626): LEN sits `skip` bits behind the header's first bit, NLEN is not checked (D2)
-            const uint32_t dio = ebit & 7u;
-            uint32_t skip = 8u - dio;
-            if (skip <= 2u) skip = 16u - dio;
+            const uint32_t skip = rules::stored_len_skip(ebit & 7u);
             const uint32_t length = (uint32_t)(rd.bb >> skip) & 0xFFFFu & len_mask;
             const uint32_t p0 = (ebit + skip + 32u) >> 3;
             const uint32_t i_noeof = (int32_t)p0 >= isize ? 0u : (uint32_t)isize - p0;
@@ -1026,7 +1027,7 @@ __global__ __launch_bounds__(64) void k_any_tokens(Args a) {
     __shared__ Tab lt;                       // the tables of the wave's items when they all belong to one block (most waves: 64 consecutive pieces)
     if (!v.run || v.ctl[C_OK] == 0u) return;
     const uint32_t nitems = v.ctl[C_NUSED];
-    const int32_t isize = (int32_t)v.zn - 1;
+    const int32_t isize = rules::isize_of(v.zn);
     const uint32_t obsize = a.obsize ? a.obsize : 32768u;
     const uint32_t lane = threadIdx.x;
     bool bad = false;
@@ -1074,11 +1075,11 @@ __global__ __launch_bounds__(64) void k_any_tokens(Args a) {
             while (have && rd.pos < limit) {
                 const uint32_t p0 = rd.pos;
                 const Token k = token_at(t, rd);
-                bool f = k.kind == 3u || (int32_t)((p0 + k.nb) >> 3) > isize - 3;                  // no code; NO EOF (deflate.py:1535-1539)
+                bool f = k.kind == 3u || rules::no_eof_behind_code(p0 + k.nb, isize);              // no code; NO EOF (deflate.py:1535-1539)
                 if (k.kind == 2u) { bad |= f; break; }
                 const uint32_t made = k.kind == 0u ? 1u : k.length;
                 f |= (uint64_t)P + made > a.cap;
-                f |= k.kind == 1u && (k.dist > P || k.dist > obsize || (int32_t)((p0 + k.used) >> 3) >= isize - 2);     // D8; COPY hold (:1600)
+                f |= k.kind == 1u && (k.dist > P || k.dist > obsize || rules::copy_hold(p0 + k.used, isize));     // D8; COPY hold (:1600)
                 if (!f && nt >= a.tcap) {
                     // the list is full (tokens of two or three bits: long runs): the rest of the item goes on as an item of its own -- the
                     // emit takes items in any order, each with its own position

@@ -13,13 +13,15 @@
 // a 2 KiB LDS history ring and is flushed to HBM as full 64-byte lines.
 // The reference's table layout (10-bit instant table + incremental-mask retry) is FPGA-specific; a
 // canonical count/offset decoder returns the same symbols for every valid code.  Invalid code
-// descriptions are HDLZ_E_BAD_TREE (zlib's acceptance rules: over-subscribed sets rejected, incomplete
-// sets only with exactly one code of length 1 -- or, for the distance code, with none at all).
+// descriptions are HDLZ_E_BAD_TREE (zlib's acceptance rules, hdlz_inflate_rules.h: over-subscribed sets
+// rejected, incomplete sets only with exactly one code of length 1 -- or, for the distance code, with none at all).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
+#include "hdlz_inflate_rules.h"
 
 namespace hdlz {
+using namespace rules;
 
 constexpr uint32_t DRING = 2048;    // history ring bytes (power of two)
 constexpr uint32_t DCHUNK = 64;
@@ -46,32 +48,11 @@ struct __attribute__((aligned(16))) DynLds {
     uint64_t mdesc[64];              // commit: the window's matches whose source lies before the window (position, length, distance)
 };
 
-typedef uint32_t __attribute__((aligned(1))) u32u;
 #ifdef HDLZ_DYN_MARKS                         // tools/phase_count.py --src hdlz_inflate_dyn.hip -DHDLZ_DYN_MARKS --kernel k_inflate_dynILb0E
 #define DYN_MARK(name) asm volatile("; @@PHASE " name ::: "memory")
 #else
 #define DYN_MARK(name) do {} while (0)
 #endif
-
-__device__ __forceinline__ uint32_t dload32(const uint8_t* __restrict__ z, uint32_t ip, uint32_t zn) {
-    if (ip + 4u <= zn) return *reinterpret_cast<const u32u*>(z + ip);
-    uint32_t v = 0;
-    for (uint32_t k = 0; k < 4u; k++)
-        if (ip + k < zn) v |= (uint32_t)z[ip + k] << (8u * k);
-    return v;
-}
-
-// RFC1951 3.2.5 in closed form, branch-free (these run per lane inside the window decode)
-__device__ __forceinline__ void d_length_info(uint32_t token, uint32_t& base, uint32_t& eb) {
-    const uint32_t e = max(token >> 2, 1u) - 1u;                     // 0 for token < 8
-    const uint32_t b = token < 8u ? token : ((4u + (token & 3u)) << e);
-    eb = token == 28u ? 0u : e;
-    base = token == 28u ? 258u : 3u + b;
-}
-__device__ __forceinline__ void d_dist_info(uint32_t dc, uint32_t& base, uint32_t& eb) {
-    eb = max(dc >> 1, 1u) - 1u;                                      // 0 for dc < 4
-    base = 1u + (dc < 4u ? dc : ((2u + (dc & 1u)) << eb));
-}
 
 // canonical code construction, wave-parallel (all 64 lanes call it; n <= 320):
 //   counts by LDS atomics, offsets by a 15-step serial prefix, symbol placement ordered by (length, value)
@@ -209,8 +190,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         const uint32_t cap = STREAM ? (out_limit < cap0 ? out_limit : cap0) : cap0;      // STREAM: reaching it is a stop, not an error
         const uint32_t inbits = 8u * zn;                                                 // (zn < 2^28)
         const uint32_t obsize = a.obsize ? a.obsize : 32768u;
-        const uint32_t len_mask = a.obsize ? ((1u << (31u - (uint32_t)__builtin_clz(a.obsize))) - 1u) : 0xFFFFu;
-        const int32_t isize = (int32_t)zn - 1;
+        const uint32_t len_mask = stored_len_mask(a.obsize);
+        const int32_t isize = isize_of(zn);
 
         uint32_t status = HDLZ_OK;
         uint32_t o = 0;                     // bytes produced
@@ -225,7 +206,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             if (ip - iwbase >= IWIN) {                                                                   \
                 __syncthreads();                                                                         \
                 iwbase = ip;                                                                             \
-                for (uint32_t k = lane; k < IWIN / 4u; k += 64u) L.iwin[k] = dload32(z, iwbase + 4u * k, zn); \
+                for (uint32_t k = lane; k < IWIN / 4u; k += 64u) L.iwin[k] = load32(z, iwbase + 4u * k, zn); \
                 __syncthreads();                                                                         \
             }                                                                                            \
             bb |= (uint64_t)L.iwin[(ip - iwbase) >> 2] << bc; bc += 32u; ip += 4u;                       \
@@ -245,7 +226,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             if ((bitp >> 3) - iwbase >= IWIN - 32u) {               // (also true for the "force a fill" value of iwbase)
                 __syncthreads();
                 iwbase = (bitp >> 3) & ~3u;
-                for (uint32_t k = lane; k < IWIN / 4u; k += 64u) L.iwin[k] = dload32(z, iwbase + 4u * k, zn);
+                for (uint32_t k = lane; k < IWIN / 4u; k += 64u) L.iwin[k] = load32(z, iwbase + 4u * k, zn);
                 __syncthreads();
             }
         };
@@ -294,9 +275,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                 if (STREAM && resumed) {                      // the rest of a stored block the previous call could not finish
                     length = r_srem; p0 = save_bit >> 3;
                 } else {
-                    const uint32_t dio = BITPOS() & 7u;
-                    uint32_t skip = 8u - dio;
-                    if (skip <= 2u) skip = 16u - dio;
+                    const uint32_t skip = stored_len_skip(BITPOS() & 7u);
                     length = (uint32_t)(bb >> skip) & 0xFFFFu & len_mask;
                     TAKE(skip + 16u);
                     REFILL();
@@ -366,26 +345,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             } else {
                 // BL (deflate.py:1090-1114)
                 REFILL();
-                nlen = ((uint32_t)bb & 31u) + 257u;
-                ndist = ((uint32_t)(bb >> 5) & 31u) + 1u;
-                const uint32_t ncode = ((uint32_t)(bb >> 10) & 15u) + 4u;
+                uint32_t ncode;
+                const bool fields_ok = dyn_header_fields((uint32_t)bb, nlen, ndist, ncode);
                 TAKE(14u);
-                if (nlen > 286u || ndist > 30u) FAIL(HDLZ_E_BAD_TREE);
+                if (!fields_ok) FAIL(HDLZ_E_BAD_TREE);
                 for (uint32_t s = lane; s < 320u; s += 64u) L.lengths[s] = 0;
                 __syncthreads();
-                static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
                 uint32_t hbp = BITPOS();                            // from here on the header is read through the window
                 {
                     // the ncode 3-bit lengths of the code-length code: lane i takes its own field (ncode * 3 <= 57 bits)
                     ensure_window(hbp);
                     const uint64_t x = bits64(hbp);
-                    if (lane < ncode) L.lengths[order[lane]] = (uint8_t)((uint32_t)(x >> (3u * lane)) & 7u);
+                    if (lane < ncode) L.lengths[CL_ORDER[lane]] = (uint8_t)((uint32_t)(x >> (3u * lane)) & 7u);
                     hbp += 3u * ncode;
                 }
                 __syncthreads();
                 canon_build(L, 0, L.lengths, L.csym, 19, lane);
                 __syncthreads();
-                if (L.left[0] != 0) FAIL(HDLZ_E_BAD_TREE);
+                if (!cl_code_ok(L.left[0])) FAIL(HDLZ_E_BAD_TREE);
                 XCode XC;
                 build_x(XC, L.cnt[0]);
                 __syncthreads();
@@ -402,9 +379,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                         uint32_t len, symi;
                         xwalk(XC, (uint32_t)x, len, symi);
                         const uint32_t sym = L.csym[min(symi, 18u)];
-                        const uint32_t eb = sym == 16u ? 2u : sym == 17u ? 3u : sym == 18u ? 7u : 0u;
-                        const uint32_t ev = (uint32_t)(x >> min(len, 15u)) & ((1u << eb) - 1u);
-                        const uint32_t rep = sym < 16u ? 1u : sym == 18u ? 11u + ev : 3u + ev;
+                        const uint32_t eb = cl_extra_bits(sym);
+                        const uint32_t rep = cl_repeat(sym, (uint32_t)(x >> min(len, 15u)) & ((1u << eb) - 1u));
                         packed = len <= 15u ? ((len + eb) | (sym << 8) | (rep << 16)) : 0u;
                     }
                     uint32_t cur = 0;
@@ -412,10 +388,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                         const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)packed, (int)cur);
                         if (t == 0u) FAIL(HDLZ_E_BAD_TREE);
                         const uint32_t sym = (t >> 8) & 255u, rep = t >> 16;
-                        uint32_t val = 0;
-                        if (sym < 16u) val = sym;
-                        else if (sym == 16u) { if (idx == 0u) FAIL(HDLZ_E_BAD_TREE); val = prev; }
-                        if (idx + rep > nlen + ndist) FAIL(HDLZ_E_BAD_TREE);
+                        if (!cl_step_ok(sym, idx, rep, nlen + ndist)) FAIL(HDLZ_E_BAD_TREE);
+                        const uint32_t val = cl_value(sym, prev);
                         for (uint32_t k = lane; k < rep; k += 64u) L.lengths[idx + k] = (uint8_t)val;
                         prev = val;
                         idx += rep;
@@ -430,14 +404,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                 canon_build(L, 2, L.lengths + nlen, L.dsym, (int)ndist, lane);
                 __syncthreads();
                 {
-                    const int l1 = L.left[1], l2 = L.left[2];
-                    // an incomplete set only as exactly one code of length 1 (zlib inflate_table: max == 1; puff: count[0] + count[1] == n)
-                    if (l1 < 0 || (l1 > 0 && !((int)nlen - (int)L.cnt[1][0] == 1 && L.cnt[1][1] == 1))) FAIL(HDLZ_E_BAD_TREE);
-                    // an EMPTY distance set (a block of literals only) is legal, RFC1951 3.2.7 -- zlib's inflate_table (max == 0)
-                    // and puff accept it; a distance symbol met later then finds no code (dlen > 15 -> BAD_SYMBOL)
-                    if (l2 < 0 || (l2 > 0 && !((int)ndist == (int)L.cnt[2][0] || ((int)ndist - (int)L.cnt[2][0] == 1 && L.cnt[2][1] == 1)))) FAIL(HDLZ_E_BAD_TREE);
+                    // (the codes of a set: its symbols without the ones of length 0.  An empty distance set is legal -- a distance
+                    // symbol met later then finds no code: dlen > 15 -> BAD_SYMBOL)
+                    if (!code_set_ok(L.left[1], nlen - L.cnt[1][0], L.cnt[1][1], false)) FAIL(HDLZ_E_BAD_TREE);
+                    if (!code_set_ok(L.left[2], ndist - L.cnt[2][0], L.cnt[2][1], true)) FAIL(HDLZ_E_BAD_TREE);
                 }
-                if (sfinal && (int32_t)(BITPOS() >> 3) > isize - 3) FAIL(HDLZ_E_NO_EOF);
+                if (sfinal && no_eof_behind_code(BITPOS(), isize)) FAIL(HDLZ_E_NO_EOF);
                 if (STREAM) {                                        // the block's code lengths travel with the session
                     for (uint32_t k = lane; k < 320u; k += 64u) ist->lengths[k] = L.lengths[k];
                     if (lane == 0) { ist->nlen = nlen; ist->ndist = ndist; }
@@ -495,7 +467,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                         ismatch = valid && sym > 256u;
                         token = sym - 257u;
                         uint32_t lbase, leb, dbase, deb;
-                        d_length_info(min(token, 28u), lbase, leb);
+                        length_info_sel(min(token, 28u), lbase, leb);
                         const uint64_t x1 = x >> len;
                         tlen = lbase + ((uint32_t)x1 & ((1u << leb) - 1u));
                         const uint64_t x2 = x1 >> leb;
@@ -506,7 +478,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                             xwalk(XD, (uint32_t)x2, dlen, dsymi);
                             ds = L.dsym[min(dsymi, 31u)];
                         }
-                        d_dist_info(min(ds, 29u), dbase, deb);
+                        dist_info_sel(min(ds, 29u), dbase, deb);
                         distance = dbase + ((uint32_t)(x2 >> min(dlen, 15u)) & ((1u << deb) - 1u));
                         mvalid = ismatch && token < 29u && dlen - 1u <= 14u && ds < 30u;
                         total = mvalid ? len + leb + dlen + deb : len;
@@ -544,13 +516,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                     {
                         const uint32_t outcode = STREAM ? ST_NEEDOUT : (uint32_t)HDLZ_E_OUT_CAPACITY;
                         uint32_t m = ((uint64_t)pos + tlen > cap) ? outcode : 0u;
-                        m = (sfinal && (int32_t)((bitpos + total) >> 3) >= isize - 2) ? (uint32_t)HDLZ_E_NO_EOF : m;      // COPY hold, :1600
+                        m = (sfinal && copy_hold(bitpos + total, isize)) ? (uint32_t)HDLZ_E_NO_EOF : m;
                         m = (distance > pos || distance > obsize) ? (uint32_t)HDLZ_E_BAD_DISTANCE : m;                    // deflate.py:1506-1508, D8
                         m = ds >= 30u ? (uint32_t)HDLZ_E_BAD_DISTANCE : m;
                         m = (dlen > 15u || token >= 29u) ? (uint32_t)HDLZ_E_BAD_SYMBOL : m;
                         st = lit ? (pos >= cap ? outcode : 0u) : m;
                         st = eobt ? ST_EOB : st;
-                        st = (sfinal && (int32_t)((bitpos + len) >> 3) > isize - 3) ? (uint32_t)HDLZ_E_NO_EOF : st;       // deflate.py:1535-1539
+                        st = (sfinal && no_eof_behind_code(bitpos + len, isize)) ? (uint32_t)HDLZ_E_NO_EOF : st;
                         st = (!valid || zleaf) ? (uint32_t)HDLZ_E_BAD_SYMBOL : st;                    // zero leaf, deflate.py:212,:1437-1439
                         // STREAM, more input to come: a token is only decoded when its 64 bits are here; the end-of-input checks
                         // (deflate.py:1535-1539, :1600) are the final call's business -- and hold for every token decoded earlier
@@ -683,34 +655,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     }
 }
 
-// second pass after k_inflate (streams it flagged with HDLZ_E_DYNAMIC_UNSUPPORTED), or -- `all` -- the only pass
-// the streams whose status is HDLZ_E_DYNAMIC_UNSUPPORTED, whatever the flags (the several-streams form of hdlz_inflate_par.hip flags what
-// it gives up on -- under HDLZ_INFLATE_ASSUME_FIXED too, where the batch kernels' second pass has nothing to do)
-hipError_t launch_inflate_dyn_flagged(const InflateArgs& a, hipStream_t stream) {
+// one wave per stream, at most 65536 workgroups (the kernel strides); list mode (few_n) runs for fewer than lane_min streams: no more
+// blocks than that
+template <bool MEMBERS, class Args>
+static hipError_t launch_dyn(const Args& a, hipStream_t stream, const uint32_t* few_n, uint32_t lane_min) {
     if (a.nstreams == 0) return hipSuccess;
-    const uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
-    hipLaunchKernelGGL(k_inflate_dyn<false>, dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, (const uint32_t*)nullptr, 0u);
+    uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
+    if (few_n && lane_min != 0u && g > lane_min) g = lane_min;
+    hipLaunchKernelGGL((k_inflate_dyn<false, MEMBERS>), dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, few_n, lane_min);
     return hipGetLastError();
 }
 
+// the streams whose status is HDLZ_E_DYNAMIC_UNSUPPORTED, whatever the flags (the several-streams form of hdlz_inflate_par.hip flags what
+// it gives up on -- under HDLZ_INFLATE_ASSUME_FIXED too, where the batch kernels' second pass has nothing to do)
+hipError_t launch_inflate_dyn_flagged(const InflateArgs& a, hipStream_t stream) { return launch_dyn<false>(a, stream, nullptr, 0u); }
+
+// second pass after k_inflate (streams it flagged with HDLZ_E_DYNAMIC_UNSUPPORTED), or -- `all` -- the only pass
 hipError_t launch_inflate_dyn(const InflateArgs& a0, hipStream_t stream, bool all, const uint32_t* few_n, uint32_t lane_min) {
-    if (a0.nstreams == 0 || (!all && (a0.flags & HDLZ_INFLATE_ASSUME_FIXED))) return hipSuccess;
+    if (!all && (a0.flags & HDLZ_INFLATE_ASSUME_FIXED)) return hipSuccess;
     InflateArgs a = a0;
     if (all) a.flags |= DYN_ALL;
-    uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
-    if (few_n && lane_min != 0u && g > lane_min) g = lane_min;       // (list mode runs for fewer than lane_min streams: no more blocks than that)
-    hipLaunchKernelGGL(k_inflate_dyn<false>, dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, few_n, lane_min);
-    return hipGetLastError();
+    return launch_dyn<false>(a, stream, few_n, lane_min);
 }
 
 // the member twin (hdlz_unjoin_ws): every member the index checks passed, one wave each
 hipError_t launch_inflate_dyn_members(const MemberArgs& a0, hipStream_t stream) {
-    if (a0.nstreams == 0) return hipSuccess;
     MemberArgs a = a0;
     a.flags |= DYN_ALL;
-    const uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
-    hipLaunchKernelGGL((k_inflate_dyn<false, true>), dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, (const uint32_t*)nullptr, 0u);
-    return hipGetLastError();
+    return launch_dyn<true>(a, stream, nullptr, 0u);
 }
 
 // one call of a resumable session (hdlz_inflate_chunk): the stream bytes known so far, the session state, the output limit

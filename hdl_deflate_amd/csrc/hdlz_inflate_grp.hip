@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
+#include "hdlz_inflate_rules.h"
 #include "hdlz_inflate_tables.h"
 
 namespace hdlz {
@@ -85,10 +86,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(std::conditional_t<M
     uint32_t* fifo = lds.fifo[wave][g];
     const uint32_t cap = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)a.out_pitch;   // o + 258 never wraps
     const uint32_t obsize = a.obsize ? a.obsize : 32768u;
-    const uint32_t len_mask = a.obsize ? ((1u << (31u - (uint32_t)__builtin_clz(a.obsize))) - 1u) : 0xFFFFu;   // deflate.py:329,:714
+    const uint32_t len_mask = stored_len_mask(a.obsize);
     const bool assume_fixed = (a.flags & HDLZ_INFLATE_ASSUME_FIXED) != 0;
     const uint32_t oneblock = (a.flags & HDLZ_INFLATE_ONEBLOCK) ? 1u : 0u;
-    const int32_t isize = (int32_t)zn - 1;            // deflate.py:605
+    const int32_t isize = isize_of(zn);
 
     uint32_t status = HDLZ_OK, out_len = 0;
     bool active = exists;
@@ -179,8 +180,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(std::conditional_t<M
             const uint32_t y = x >> leb;
             // the distance code in closed form (no second dependent table look-up): five reversed bits, RFC1951 3.2.5
             const uint32_t dc = __builtin_bitreverse32(y) >> 27;
-            const uint32_t deb = max(dc >> 1, 1u) - 1u;
-            const uint32_t dbase = 1u + (dc < 4u ? dc : ((2u + (dc & 1u)) << deb));
+            const uint32_t deb = dist_extra_bits(dc), dbase = dist_base(dc, deb);
             const uint32_t distance = dbase + ((y >> 5) & ((1u << deb) - 1u));
             const uint32_t mbits = nbm + leb + 5u + deb;
             const uint32_t om = o + nl;                               // where the copy will start
@@ -196,94 +196,22 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(std::conditional_t<M
             slow = idle & (nl == 0u) & !len_ok;                        // header, EOB, end of the input, invalid data, any failing check
         }
         GT(1);
-        // ------------------------------------------------------------ 3. slow path (wave-uniform branch, rare): k_inflate_tok's, verbatim in
-        // its checks and their order.  ONE block header or end-of-block per step: the FIFO advances once per step (part 1, one half of
-        // 128 bytes), and a step that walked through any number of empty blocks -- 5 bytes per empty stored block, 10 bits per empty
-        // fixed one -- would read past what is loaded (~26 empty stored blocks in a row did)
+        // ------------------------------------------------------------ 3. slow path (wave-uniform branch, rare): the serial path of
+        // hdlz_inflate_rules.h, the text k_inflate_tok runs.  ONE block header or end-of-block per step: the FIFO advances once per step
+        // (part 1, one half of 128 bytes), and a step that walked through any number of empty blocks -- 5 bytes per empty stored block,
+        // 10 bits per empty fixed one -- would read past what is loaded (~26 empty stored blocks in a row did)
         if (ballot64(slow || (active && srem != 0u)) != 0ull) {
-            while (slow && active && rem == 0u && srem == 0u && litn == 0u) {
-                GRP_REFILL();
-                if (need_header) {
-                    // HEADER (deflate.py:677-732)
-                    final_ = ((uint32_t)bb & 1u) | oneblock;
-                    const uint32_t hm = assume_fixed ? 1u : ((uint32_t)(bb >> 1) & 3u);
-                    if (hm == 3u) { GRP_FAIL(HDLZ_E_BAD_BTYPE); break; }
-                    if (hm == 2u) { GRP_FAIL(HDLZ_E_DYNAMIC_UNSUPPORTED); break; }
-                    need_header = false;
-                    if (hm == 0u) {
-                        // stored (deflate.py:709-717): LEN sits `skip` bits after the header start
-                        const uint32_t dio = GRP_BITPOS() & 7u;
-                        uint32_t skip = 8u - dio;
-                        if (skip <= 2u) skip = 16u - dio;
-                        const uint32_t length = (uint32_t)(bb >> skip) & 0xFFFFu & len_mask;
-                        bb >>= (skip + 16u); bc -= (skip + 16u);          // now at NLEN = the reference's di
-                        GRP_REFILL();
-                        bb >>= 16; bc -= 16u;                             // NLEN unchecked (D2); data follows
-                        srem = length;
-                        if (length == 0u) {
-                            // COPY with nothing to copy (deflate.py:1617-1626)
-                            if ((int32_t)(GRP_BITPOS() >> 3) >= isize) { GRP_FAIL(HDLZ_E_NO_EOF); break; }
-                            if (final_) { out_len = o; active = false; break; }
-                            need_header = true;
-                        }
-                    } else {
-                        bb >>= 3; bc -= 3u;
-                    }
-                    break;                                               // (the block's first token: next step)
-                }
-                // NEXT (deflate.py:1409-1445)
-                const uint32_t e = lds.lit[(uint32_t)bb & 511u];
-                const uint32_t nb = e & 15u, code = (e >> 4) & 0x1FFu;
-                if (nb < 1u) { GRP_FAIL(HDLZ_E_BAD_SYMBOL); break; }
-                bb >>= nb; bc -= nb;
-                // INFLATE (deflate.py:1519-1591)
-                if ((int32_t)(GRP_BITPOS() >> 3) > isize - 3) { GRP_FAIL(HDLZ_E_NO_EOF); break; }   // :1535-1539
-                if (code == 256u) {
-                    if (final_) { out_len = o; active = false; break; }   // D6
-                    need_header = true;
-                    break;                                               // (the next block's header: next step)
-                }
-                if (code < 256u) {
-                    if (o >= cap) { GRP_FAIL(HDLZ_E_OUT_CAPACITY); break; }
-                    litv = code; litn = 1;
-                    break;
-                }
-                const uint32_t token = code - 257u;
-                if (token >= 29u) { GRP_FAIL(HDLZ_E_BAD_SYMBOL); break; }
-                uint32_t lbase, leb;
-                length_info(token, lbase, leb);
-                const uint32_t tlength = lbase + ((uint32_t)bb & ((1u << leb) - 1u));
-                bb >>= leb; bc -= leb;
-                const uint32_t dc = __builtin_bitreverse32((uint32_t)bb) >> 27;
-                if (dc >= 30u) { GRP_FAIL(HDLZ_E_BAD_DISTANCE); break; }
-                bb >>= 5;
-                uint32_t dbase, deb;
-                dist_info(dc, dbase, deb);
-                const uint32_t distance = dbase + ((uint32_t)bb & ((1u << deb) - 1u));
-                bb >>= deb;
-                bc -= 5u + deb;
-                if (distance > o || distance > obsize) { GRP_FAIL(HDLZ_E_BAD_DISTANCE); break; }        // D8
-                if ((int32_t)(GRP_BITPOS() >> 3) >= isize - 2) { GRP_FAIL(HDLZ_E_NO_EOF); break; }      // COPY hold, :1600
-                if ((uint64_t)o + tlength > cap) { GRP_FAIL(HDLZ_E_OUT_CAPACITY); break; }
-                rem = tlength;
-                dist = distance;
-            }
-            // stored COPY (deflate.py:1603-1616): one byte per step (rare: level-0 streams, incompressible blocks)
-            if (active && srem != 0u && litn == 0u && rem == 0u) {
-                GRP_REFILL();
-                if ((int32_t)(GRP_BITPOS() >> 3) >= isize) { GRP_FAIL(HDLZ_E_NO_EOF); }
-                else if (o >= cap) { GRP_FAIL(HDLZ_E_OUT_CAPACITY); }
-                else {
-                    litv = (uint32_t)bb & 0xFFu; litn = 1;
-                    bb >>= 8; bc -= 8u;
-                    srem--;
-                    if (srem == 0u) {                              // the block ends with this byte (deflate.py:1617-1626)
-                        if ((int32_t)(GRP_BITPOS() >> 3) >= isize) { GRP_FAIL(HDLZ_E_NO_EOF); litn = 0; }
-                        else if (final_) { out_len = o + 1u; active = false; }      // (the byte is still emitted below)
-                        else need_header = true;
-                    }
-                }
-            }
+#define GRP_LIT_AT(bits) lds.lit[(bits) & 511u]
+#define GRP_DIST_CODE(bits, nbits, dbase, deb) const uint32_t dc = __builtin_bitreverse32(bits) >> 27;  /* five reversed bits, as on the fast path */ \
+            if (dc >= 30u) { GRP_FAIL(HDLZ_E_BAD_DISTANCE); break; }                                          \
+            (nbits) = 5u; dist_info(dc, (dbase), (deb))
+#define GRP_NO_DYNAMIC true
+#define GRP_BLOCK_TABLES(hm)
+#define GRP_DIST_REFILL()
+#define GRP_MATCH_TAKEN(distance)
+#define GRP_NEXT_BLOCK break                                                /* (the block's first token, the next block's header: next step) */
+            HDLZ_SERIAL_ITEMS(GRP)
+            HDLZ_SERIAL_STORED_BYTE(GRP)
         }
         GT(2);
         // ------------------------------------------------------------ 4. move, up to 16 bytes per step: lanes 0 .. litn - 1 write the literals,
@@ -362,19 +290,19 @@ __global__ __launch_bounds__(64 * WAVES) void k_inflate_grp(std::conditional_t<M
 
 }  // namespace grp
 
-hipError_t launch_inflate_grp(const InflateArgs& a, hipStream_t stream) {
+template <bool MEMBERS, class Args>
+static hipError_t launch_grp(const Args& a, hipStream_t stream) {
     if (a.nstreams == 0) return hipSuccess;
     const uint64_t per_wg = (uint64_t)grp::NS * grp::WAVES;
-    hipLaunchKernelGGL(grp::k_inflate_grp<false>, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);
+    hipLaunchKernelGGL(grp::k_inflate_grp<MEMBERS>, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);
     return hipGetLastError();
 }
 
+hipError_t launch_inflate_grp(const InflateArgs& a, hipStream_t stream) { return launch_grp<false>(a, stream); }
+
 hipError_t launch_inflate_grp_members(const MemberArgs& a, hipStream_t stream) {
     if (a.m_dst) return hipErrorInvalidValue;      // the task view's destinations: k_inflate_dyn<false, true> alone takes them
-    if (a.nstreams == 0) return hipSuccess;
-    const uint64_t per_wg = (uint64_t)grp::NS * grp::WAVES;
-    hipLaunchKernelGGL(grp::k_inflate_grp<true>, dim3((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), dim3(64 * grp::WAVES), 0, stream, a);
-    return hipGetLastError();
+    return launch_grp<true>(a, stream);
 }
 
 }  // namespace hdlz

@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "hdlz_device.h"
+#include "hdlz_inflate_rules.h"
 #include "hdlz_inflate_tables.h"
 #include "hdlz_inflate_par.h"
 
@@ -160,7 +161,7 @@ __device__ __forceinline__ void spec_token(uint32_t x, const uint32_t* lit, cons
     // the distance code's extra bits in closed form (RFC1951: codes 0..3 none, then (code >> 1) - 1; 30 and 31 do not exist) instead of
     // the dst[] look-up: a second DEPENDENT LDS round trip on every token of a chain that is one lane's serial latency
     const uint32_t dc = __builtin_bitreverse32(__builtin_amdgcn_ubfe(y, leb, 5u)) >> 27;
-    const uint32_t deb = max(dc >> 1, 1u) - 1u;
+    const uint32_t deb = rules::dist_extra_bits(dc);
     const bool islit = type == (uint32_t)T_LIT;
     const bool bad = (nb == 0u) | (type == (uint32_t)T_BAD) | ((type == (uint32_t)T_LEN) & (dc >= 30u));
     const bool iseob = type == (uint32_t)T_EOB;
@@ -482,7 +483,7 @@ __global__ __launch_bounds__(64) void k_par_tokens(ParArgs a_) {
     const uint32_t c = c0 + lane;
     const bool have = c < nused;
     const uint32_t emode = eob_mode(a);
-    const int32_t isize = (int32_t)a.zn - 1;              // deflate.py:605
+    const int32_t isize = rules::isize_of(a.zn);
     const uint32_t obsize = a.obsize ? a.obsize : 32768u;
     const uint32_t b_c = FIRST_BIT + c * a.chbits, end = b_c + a.chbits;
     uint32_t pos = have ? b_c + a.entry8[c] : 0u, P = have ? a.opos[c] : 0u;
@@ -527,15 +528,15 @@ __global__ __launch_bounds__(64) void k_par_tokens(ParArgs a_) {
             const uint32_t tl = lbase + __builtin_amdgcn_ubfe(y, 0u, leb);
             // (the distance table in closed form, RFC1951 3.2.5: no second dependent LDS look-up on the lane's serial chain)
             const uint32_t dc = __builtin_bitreverse32(__builtin_amdgcn_ubfe(y, leb, 5u)) >> 27;
-            const uint32_t deb = max(dc >> 1, 1u) - 1u;
-            const uint32_t D = (dc < 4u ? dc + 1u : 1u + ((2u + (dc & 1u)) << deb)) + __builtin_amdgcn_ubfe(y, leb + 5u, deb);
+            const uint32_t deb = rules::dist_extra_bits(dc);
+            const uint32_t D = rules::dist_base(dc, deb) + __builtin_amdgcn_ubfe(y, leb + 5u, deb);
             const bool islit = code < 256u, iseob = code == 256u, islen = code > 256u;
             const uint32_t used = islen ? nb + leb + 5u + deb : nb;
             const uint32_t made = islit ? 1u : tl;
-            bool f = (nb < 1u) | ((int32_t)((pos + nb) >> 3) > isize - 3);                        // zero leaf; NO EOF (deflate.py:1535-1539)
+            bool f = (nb < 1u) | rules::no_eof_behind_code(pos + nb, isize);                      // zero leaf; NO EOF (deflate.py:1535-1539)
             f |= !iseob & ((uint64_t)P + made > a.cap);                                           // capacity
             f |= islen & ((code - 257u >= 29u) | (dc >= 30u) | (D > P) | (D > obsize) |           // BAD_SYMBOL, BAD_DISTANCE, D8
-                          ((int32_t)((pos + used) >> 3) >= isize - 2));                           // COPY hold (deflate.py:1600)
+                          rules::copy_hold(pos + used, isize));                                   // COPY hold (deflate.py:1600)
             const bool go = !(f | iseob);
             bool stop = f;
             // (the token list is written FOUR tokens at a time: a store per token and lane is 64 requests of 4 bytes to 64 different lines

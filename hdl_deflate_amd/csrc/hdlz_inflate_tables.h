@@ -3,11 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hdlz_inflate_rules.h"
 
 namespace hdlz {
 namespace tok {
+using namespace rules;       // (load32, length_info, dist_info: the closed forms the tables below are filled from)
 
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 __attribute__((aligned(1))) u32x4_unaligned;
@@ -15,24 +16,6 @@ struct __attribute__((packed, aligned(1))) u128_unaligned { uint64_t lo, hi; };
 
 __device__ __forceinline__ uint32_t rev(uint32_t v, uint32_t nbits) { return __builtin_bitreverse32(v) >> (32u - nbits); }
 
-__device__ __forceinline__ uint32_t load32(const uint8_t* __restrict__ z, uint32_t ip, uint32_t zn) {
-    if (ip + 4u <= zn) return *reinterpret_cast<const u32_unaligned*>(z + ip);
-    uint32_t v = 0;
-    for (uint32_t k = 0; k < 4u; k++)
-        if (ip + k < zn) v |= (uint32_t)z[ip + k] << (8u * k);
-    return v;
-}
-
-// RFC1951 tables in closed form (deflate.py:100-110)
-__device__ __forceinline__ void length_info(uint32_t token, uint32_t& base, uint32_t& eb) {
-    if (token < 8u) { base = 3u + token; eb = 0; }
-    else if (token == 28u) { base = 258u; eb = 0; }
-    else { eb = (token >> 2) - 1u; base = 3u + ((4u + (token & 3u)) << eb); }
-}
-__device__ __forceinline__ void dist_info(uint32_t dc, uint32_t& base, uint32_t& eb) {
-    if (dc < 4u) { base = 1u + dc; eb = 0; }
-    else { eb = (dc >> 1) - 1u; base = 1u + ((2u + (dc & 1u)) << eb); }
-}
 // the widened stat_leaves (deflate.py:151-216): nbits[3:0] | sym[12:4] | type[14:13] | lbase[24:16] | leb[27:25]
 enum { T_LIT = 0, T_LEN = 1, T_EOB = 2, T_BAD = 3 };
 __device__ __forceinline__ uint32_t lit_entry(uint32_t c, bool zero_leaf) {

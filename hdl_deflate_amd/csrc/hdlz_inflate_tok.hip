@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
+#include "hdlz_inflate_rules.h"
 #include "hdlz_inflate_tables.h"
 
 namespace hdlz {
@@ -241,10 +242,10 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
     const uint32_t lane4 = lane << 2;
     const uint32_t cap = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFE00ull ? 0xFFFFFE00u : (uint32_t)a.out_pitch;   // o + 258 never wraps
     const uint32_t obsize = a.obsize ? a.obsize : 32768u;
-    const uint32_t len_mask = a.obsize ? ((1u << (31u - (uint32_t)__builtin_clz(a.obsize))) - 1u) : 0xFFFFu;   // deflate.py:329,:714
+    const uint32_t len_mask = stored_len_mask(a.obsize);
     const bool assume_fixed = (a.flags & HDLZ_INFLATE_ASSUME_FIXED) != 0;
     const uint32_t oneblock = (a.flags & HDLZ_INFLATE_ONEBLOCK) ? 1u : 0u;
-    const int32_t isize = (int32_t)zn - 1;            // deflate.py:605
+    const int32_t isize = isize_of(zn);
 
     uint32_t status = HDLZ_OK;
     uint32_t out_len = 0;
@@ -417,7 +418,7 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
         bb >>= ((bitp) & 7u); bc -= ((bitp) & 7u);                                                         \
     } while (0)
     // ---- DYN: the tables of a block, fixed (hm = 1: deflate.py:1066-1073) or dynamic (hm = 2: BL/READBL/REPEAT deflate.py:1084-1202,
-    // the canonical codes :1204-1400).  Returns the status; the acceptance rules are k_inflate_dyn's (zlib's).  A block whose
+    // the canonical codes :1204-1400).  Returns the status; the acceptance rules are hdlz_inflate_rules.h's (zlib's).  A block whose
     // literal/length code has more than CAP symbols is HDLZ_E_DYNAMIC_UNSUPPORTED here: the stream stays flagged for the next pass.
     auto build_tables = [&](const uint32_t hm) -> uint32_t {
         if constexpr (!DYN) return HDLZ_E_DYNAMIC_UNSUPPORTED;
@@ -439,19 +440,17 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
                     x_decode<7>(XC, (uint32_t)bb, len, ci, valid);
                     if (!valid) return HDLZ_E_BAD_TREE;
                     const uint32_t sym = CS.get(min(ci, 18u));
-                    const uint32_t eb = sym < 16u ? 0u : sym == 16u ? 2u : sym == 17u ? 3u : 7u;
-                    const uint32_t ev = (uint32_t)(bb >> len) & ((1u << eb) - 1u);
-                    const uint32_t rep = sym < 16u ? 1u : sym == 18u ? 11u + ev : 3u + ev;
+                    const uint32_t eb = cl_extra_bits(sym);
+                    const uint32_t rep = cl_repeat(sym, (uint32_t)(bb >> len) & ((1u << eb) - 1u));
                     bb >>= (len + eb); bc -= len + eb;
-                    if (sym == 16u && idx == 0u) return HDLZ_E_BAD_TREE;
-                    if (idx + rep > total) return HDLZ_E_BAD_TREE;
-                    const uint32_t val = sym < 16u ? sym : sym == 16u ? prev : 0u;
+                    if (!cl_step_ok(sym, idx, rep, total)) return HDLZ_E_BAD_TREE;
+                    const uint32_t val = cl_value(sym, prev);
                     // (a repeat may run from the literal/length lengths into the distance lengths)
                     const uint32_t nl = idx < nlen ? min(rep, nlen - idx) : 0u, nd = rep - nl;
                     if constexpr (!decltype(place)::value) {
                         nL.add(val, nl);
                         nD.add(val, nd);
-                        has256 = has256 || (val != 0u && idx <= 256u && idx + rep > 256u);
+                        has256 = has256 || (val != 0u && cl_run_covers_eob(idx, rep));
                     } else if (val != 0u) {
                         if (nl) {
                             const uint32_t pos = nL.get(val);
@@ -488,25 +487,23 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
             } else {
                 // BL (deflate.py:1090-1114)
                 TOK_REFILL();
-                nlen = ((uint32_t)bb & 31u) + 257u;
-                ndist = ((uint32_t)(bb >> 5) & 31u) + 1u;
-                const uint32_t ncode = ((uint32_t)(bb >> 10) & 15u) + 4u;
+                uint32_t ncode;
+                const bool fields_ok = dyn_header_fields((uint32_t)bb, nlen, ndist, ncode);
                 bb >>= 14; bc -= 14u;
-                if (nlen > 286u || ndist > 30u) return HDLZ_E_BAD_TREE;
+                if (!fields_ok) return HDLZ_E_BAD_TREE;
                 // the code-length code: 3-bit lengths in the order of RFC1951 3.2.7, kept as 3-bit fields by symbol
-                constexpr uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
                 uint64_t cl = 0;
 #pragma unroll
                 for (int i = 0; i < 19; i++) {
                     if ((i & 7) == 0) TOK_REFILL();
-                    if ((uint32_t)i < ncode) { cl |= (uint64_t)((uint32_t)bb & 7u) << (3 * order[i]); bb >>= 3; bc -= 3u; }
+                    if ((uint32_t)i < ncode) { cl |= (uint64_t)((uint32_t)bb & 7u) << (3 * CL_ORDER[i]); bb >>= 3; bc -= 3u; }
                 }
                 uint64_t cw = 0;                       // symbols per length, 5-bit fields
 #pragma unroll
                 for (int s_ = 0; s_ < 19; s_++) cw += 1ull << (5u * ((uint32_t)(cl >> (3 * s_)) & 7u));
                 int32_t left; uint32_t cum;
                 x_build<7>(XC, [&](int l) { return (uint32_t)(cw >> (5 * l)) & 31u; }, left, cum);
-                if (left != 0) return HDLZ_E_BAD_TREE;
+                if (!cl_code_ok(left)) return HDLZ_E_BAD_TREE;
                 uint64_t ow = 0;                       // first slot per length in the sorted list, then the next free one
                 {
                     uint32_t off = 0;
@@ -526,10 +523,7 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
             x_build<15>(XL, [&](int l) { return nL.at(l); }, l1, c1);
             x_build<15>(XD, [&](int l) { return nD.at(l); }, l2, c2);
             if (hm == 2u) {
-                // incomplete sets only with exactly one code of length 1 (zlib inflate_table: max == 1) -- or, for the distance code,
-                // with none at all (RFC1951 3.2.7)
-                if (l1 < 0 || (l1 > 0 && !(c1 == 1u && nL.at(1) == 1u))) return HDLZ_E_BAD_TREE;
-                if (l2 < 0 || (l2 > 0 && !(c2 == 0u || (c2 == 1u && nD.at(1) == 1u)))) return HDLZ_E_BAD_TREE;
+                if (!code_set_ok(l1, c1, nL.at(1), false) || !code_set_ok(l2, c2, nD.at(1), true)) return HDLZ_E_BAD_TREE;
                 if (c1 > CAP) return HDLZ_E_DYNAMIC_UNSUPPORTED;       // (only CAP_SMALL: at most 286 symbols are coded)
                 {                                      // counts -> first slot per length
                     F16 fL, fD;
@@ -541,7 +535,7 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
                 }
                 TOK_RESYNC(p0);
                 lens_pass(std::true_type{});
-                if ((int32_t)(TOK_BITPOS() >> 3) > isize - 3) return HDLZ_E_NO_EOF;
+                if (no_eof_behind_code(TOK_BITPOS(), isize)) return HDLZ_E_NO_EOF;
             }
             return HDLZ_OK;
         }
@@ -779,97 +773,19 @@ __global__ __launch_bounds__(DYN ? 64 : 256) void k_inflate_tok(std::conditional
         TOK_MARK("slow");
         // ------------------------------------------------------------ 1b. slow path (wave-uniform branch, rare)
         if (ballot64(slow || (active && srem != 0u)) != 0ull) {
-            while (slow && active && rem == 0u && srem == 0u && litn == 0u) {
-                TOK_REFILL();
-                if (need_header) {
-                    // HEADER (deflate.py:677-732)
-                    final_ = ((uint32_t)bb & 1u) | oneblock;
-                    const uint32_t hm = assume_fixed ? 1u : ((uint32_t)(bb >> 1) & 3u);
-                    if (hm == 3u) { TOK_FAIL(HDLZ_E_BAD_BTYPE); break; }
-                    if (!DYN && hm == 2u) { TOK_FAIL(HDLZ_E_DYNAMIC_UNSUPPORTED); break; }
-                    need_header = false;
-                    if (hm == 0u) {
-                        // stored (deflate.py:709-717): LEN sits `skip` bits after the header start
-                        const uint32_t dio = TOK_BITPOS() & 7u;
-                        uint32_t skip = 8u - dio;
-                        if (skip <= 2u) skip = 16u - dio;
-                        const uint32_t length = (uint32_t)(bb >> skip) & 0xFFFFu & len_mask;
-                        bb >>= (skip + 16u); bc -= (skip + 16u);          // now at NLEN = the reference's di
-                        TOK_REFILL();
-                        bb >>= 16; bc -= 16u;                             // NLEN unchecked (D2); data follows
-                        srem = length;
-                        if (length == 0u) {
-                            // COPY with nothing to copy (deflate.py:1617-1626)
-                            if ((int32_t)(TOK_BITPOS() >> 3) >= isize) { TOK_FAIL(HDLZ_E_NO_EOF); break; }
-                            if (final_) { out_len = o; active = false; break; }
-                            need_header = true;
-                        }
-                    } else {
-                        bb >>= 3; bc -= 3u;
-                        if constexpr (DYN) {
-                            const uint32_t tst = build_tables(hm);
-                            if (tst != HDLZ_OK) { TOK_FAIL(tst); break; }
-                        }
-                    }
-                    continue;
-                }
-                // NEXT (deflate.py:1409-1445; DYN: D_NEXT :1447-1517 for the distance)
-                const uint32_t e = lit_at((uint32_t)bb);
-                const uint32_t nb = e & 15u, code = (e >> 4) & 0x1FFu;
-                if (nb < 1u) { TOK_FAIL(HDLZ_E_BAD_SYMBOL); break; }
-                bb >>= nb; bc -= nb;
-                // INFLATE (deflate.py:1519-1591)
-                if ((int32_t)(TOK_BITPOS() >> 3) > isize - 3) { TOK_FAIL(HDLZ_E_NO_EOF); break; }   // :1535-1539
-                if (code == 256u) {
-                    if (final_) { out_len = o; active = false; break; }   // D6
-                    need_header = true;
-                    continue;
-                }
-                if (code < 256u) {
-                    if (o >= cap) { TOK_FAIL(HDLZ_E_OUT_CAPACITY); break; }
-                    litv = code; litn = 1;
-                    break;
-                }
-                const uint32_t token = code - 257u;
-                if (token >= 29u) { TOK_FAIL(HDLZ_E_BAD_SYMBOL); break; }
-                uint32_t lbase, leb, dnb;
-                length_info(token, lbase, leb);
-                const uint32_t tlength = lbase + ((uint32_t)bb & ((1u << leb) - 1u));
-                bb >>= leb; bc -= leb;
-                if constexpr (DYN) TOK_REFILL();                   // 15 + 5 bits are gone, 15 + 13 may follow
-                const uint32_t de = dst_at((uint32_t)bb, dnb);
-                if (de == NO_DCODE) { TOK_FAIL(HDLZ_E_BAD_SYMBOL); break; }
-                if (de == BAD_DCODE) { TOK_FAIL(HDLZ_E_BAD_DISTANCE); break; }
-                bb >>= dnb;
-                const uint32_t deb = (de >> 16) & 15u;
-                const uint32_t distance = (de & 0xFFFFu) + ((uint32_t)bb & ((1u << deb) - 1u));
-                bb >>= deb;
-                bc -= dnb + deb;
-                if (distance > o || distance > obsize) { TOK_FAIL(HDLZ_E_BAD_DISTANCE); break; }        // D8
-                if ((int32_t)(TOK_BITPOS() >> 3) >= isize - 2) { TOK_FAIL(HDLZ_E_NO_EOF); break; }      // COPY hold, :1600
-                if ((uint64_t)o + tlength > cap) { TOK_FAIL(HDLZ_E_OUT_CAPACITY); break; }
-                rem = tlength;
-                dist = distance;
-                if (distance > NEAR) {
-                    far4 = *reinterpret_cast<const u32x4_unaligned*>(out + (o - distance));
-                }
-            }
-            // stored COPY (deflate.py:1603-1616): one byte per round (rare: level-0 streams, incompressible blocks)
-            if (active && srem != 0u && litn == 0u && rem == 0u) {
-                TOK_REFILL();
-                if ((int32_t)(TOK_BITPOS() >> 3) >= isize) { TOK_FAIL(HDLZ_E_NO_EOF); }
-                else if (o >= cap) { TOK_FAIL(HDLZ_E_OUT_CAPACITY); }
-                else {
-                    litv = (uint32_t)bb & 0xFFu; litn = 1;
-                    bb >>= 8; bc -= 8u;
-                    srem--;
-                    if (srem == 0u) {                              // the block ends with this byte (deflate.py:1617-1626)
-                        if ((int32_t)(TOK_BITPOS() >> 3) >= isize) { TOK_FAIL(HDLZ_E_NO_EOF); litn = 0; }
-                        else if (final_) { out_len = o + 1u; active = false; }      // (the byte is still emitted below)
-                        else need_header = true;
-                    }
-                }
-            }
+            // (hdlz_inflate_rules.h: the serial path's one text; here any number of headers and end-of-block codes per round)
+#define TOK_LIT_AT(bits) lit_at(bits)
+#define TOK_DIST_CODE(bits, nbits, dbase, deb) const uint32_t de = dst_at((bits), (nbits));                          \
+            if (de == NO_DCODE) { TOK_FAIL(HDLZ_E_BAD_SYMBOL); break; }                                             \
+            if (de == BAD_DCODE) { TOK_FAIL(HDLZ_E_BAD_DISTANCE); break; }                                          \
+            (dbase) = de & 0xFFFFu; (deb) = (de >> 16) & 15u
+#define TOK_NO_DYNAMIC (!DYN)
+#define TOK_BLOCK_TABLES(hm) if constexpr (DYN) { const uint32_t tst = build_tables(hm); if (tst != HDLZ_OK) { TOK_FAIL(tst); break; } }
+#define TOK_DIST_REFILL() if constexpr (DYN) TOK_REFILL()                  /* 15 + 5 bits are gone, 15 + 13 may follow */
+#define TOK_MATCH_TAKEN(distance) if ((distance) > NEAR) far4 = *reinterpret_cast<const u32x4_unaligned*>(out + (o - (distance)))
+#define TOK_NEXT_BLOCK continue
+            HDLZ_SERIAL_ITEMS(TOK)
+            HDLZ_SERIAL_STORED_BYTE(TOK)
         }
         TOK_TIME(3);
         TOK_TIME_ROUND();
@@ -1051,21 +967,23 @@ size_t inflate_tok_work_bytes(uint64_t nstreams, bool ragged) {
     return round256(sizeof(uint32_t) * (l.pass1 > l.pass2 ? l.pass1 : l.pass2));
 }
 
-hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Work& w) {
+// pass 1 for either argument record: `lens` is the offsets array the stream lengths come from (InflateArgs::in_off, null for pitched
+// input, or MemberArgs::m_off)
+template <bool MEMBERS, class Args>
+static hipError_t launch_tok_pass1(const Args& a, const uint64_t* lens, hipStream_t stream, const Work& w) {
     if (a.nstreams == 0) return hipSuccess;
     typedef tok::Lds<false, tok::CAP_FULL> L;
     const uint64_t per_wg = 64u * L::WAVES;
     const dim3 grid((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), block(64 * L::WAVES);
     // ragged input of more than one wave: the lanes take the streams in the order of their length class (see k_bin_*)
-    const size_t nws = tok::lists_of(a.nstreams, a.in_off != nullptr, false).pass1;
+    const size_t nws = tok::lists_of(a.nstreams, lens != nullptr, false).pass1;
     if (nws != 0u) {
         uint32_t* ws = nullptr;                  // ws[0 .. BIN_WORDS): the bins (see tok::BIN_WORDS); the list behind them
-        const uint32_t n = (uint32_t)a.nstreams;
         hipError_t e = w.get(sizeof(uint32_t) * nws, stream, reinterpret_cast<uint8_t**>(&ws));
         if (e == hipSuccess) {
-            e = tok::bin_streams(a.in_off, n, ws, ws + tok::BIN_WORDS, stream);
+            e = tok::bin_streams(lens, (uint32_t)a.nstreams, ws, ws + tok::BIN_WORDS, stream);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL>), grid, block, 0, stream, a,
+                hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL, MEMBERS>), grid, block, 0, stream, a,
                                    (const uint32_t*)(ws + tok::BIN_WORDS), (const uint32_t*)(ws + tok::NBIN), 0u,
                                    (const uint32_t*)(ws + tok::NBIN), (const uint32_t*)nullptr);
                 e = hipGetLastError();
@@ -1075,38 +993,19 @@ hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Wo
         }
         (void)hipGetLastError();                 // no scratch: stream order
     }
-    hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL>), grid, block, 0, stream, a, (const uint32_t*)nullptr,
+    hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL, MEMBERS>), grid, block, 0, stream, a, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
     return hipGetLastError();
 }
 
-// the member twin (hdlz_unjoin_ws): launch_inflate_tok with the lists ordered by the MEMBER lengths (a.m_off as in_off); no second pass
+hipError_t launch_inflate_tok(const InflateArgs& a, hipStream_t stream, const Work& w) {
+    return launch_tok_pass1<false>(a, a.in_off, stream, w);
+}
+
+// the member twin (hdlz_unjoin_ws): the lists ordered by the MEMBER lengths; no second pass
 hipError_t launch_inflate_tok_members(const MemberArgs& a, hipStream_t stream, const Work& w) {
     if (a.m_dst) return hipErrorInvalidValue;      // the task view's destinations: k_inflate_dyn<false, true> alone takes them
-    if (a.nstreams == 0) return hipSuccess;
-    typedef tok::Lds<false, tok::CAP_FULL> L;
-    const uint64_t per_wg = 64u * L::WAVES;
-    const dim3 grid((unsigned)((a.nstreams + per_wg - 1u) / per_wg)), block(64 * L::WAVES);
-    const size_t nws = tok::lists_of(a.nstreams, true, false).pass1;
-    if (nws != 0u) {
-        uint32_t* ws = nullptr;
-        hipError_t e = w.get(sizeof(uint32_t) * nws, stream, reinterpret_cast<uint8_t**>(&ws));
-        if (e == hipSuccess) {
-            e = tok::bin_streams(a.m_off, (uint32_t)a.nstreams, ws, ws + tok::BIN_WORDS, stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL, true>), grid, block, 0, stream, a,
-                                   (const uint32_t*)(ws + tok::BIN_WORDS), (const uint32_t*)(ws + tok::NBIN), 0u,
-                                   (const uint32_t*)(ws + tok::NBIN), (const uint32_t*)nullptr);
-                e = hipGetLastError();
-            }
-            const hipError_t e2 = w.put(reinterpret_cast<uint8_t*>(ws), stream);
-            return e != hipSuccess ? e : e2;
-        }
-        (void)hipGetLastError();                 // no scratch: stream order
-    }
-    hipLaunchKernelGGL((tok::k_inflate_tok<false, tok::CAP_FULL, true>), grid, block, 0, stream, a, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    return hipGetLastError();
+    return launch_tok_pass1<true>(a, a.m_off, stream, w);
 }
 
 // second pass of the lane-per-stream mapping: the streams with dynamic-tree blocks, one lane each again.  `all`: every stream

@@ -191,9 +191,34 @@ def test_inflate_group_decode_has_one_source():
     csrc = os.path.join(REPO, "hdl_deflate_amd", "csrc")
     txt = open(os.path.join(csrc, "hdlz_inflate_tok.hip")).read()
     assert txt.count("#define TOK_FIXED_GROUP(") == 1 and txt.count("TOK_FIXED_GROUP(false,") == 1 and txt.count("TOK_FIXED_GROUP(true,") == 1
-    # the distance look-up behind a length: the group decode, the DYN fast path has its own (x_decode), the slow path
-    assert txt.count("dst_at((uint32_t)") == 2
+    # the distance look-up behind a length: the group decode once (the DYN fast path has its own, x_decode), and the serial path once --
+    # its text is hdlz_inflate_rules.h's, which asks this kernel's TOK_DIST_CODE step for the look-up
+    rules = open(os.path.join(csrc, "hdlz_inflate_rules.h")).read()
+    assert txt.count("dst_at((uint32_t)") == 1 and txt.count("dst_at((bits)") == 1 and txt.count("#define TOK_DIST_CODE(") == 1
+    assert rules.count("K##_DIST_CODE((uint32_t)bb") == 1 and txt.count("HDLZ_SERIAL_ITEMS(TOK)") == 1
     assert sum(1 for ln in txt.splitlines() if ln.startswith("#if")) <= 5
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h")):
             assert '#include "hdlz_inflate_tok.hip"' not in open(os.path.join(csrc, f)).read(), f
+
+
+def test_inflate_rules_have_one_source():
+    """the deflate block rules the five inflate decoders apply -- the order of the code-length code, where a stored LEN sits, the mask on
+    it, the two end-of-input margins, the input load -- are stated ONCE, in hdlz_inflate_rules.h, which all five include; a decoder that
+    pastes one back (the last rule fix had to be made three times) is named here"""
+    csrc = os.path.join(REPO, "hdl_deflate_amd", "csrc")
+    rules = "hdlz_inflate_rules.h"
+    code = {f: re.sub(r"/\*.*?\*/", "", re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read()), flags=re.S)
+            for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+
+    def sites(pattern):
+        return [f for f, t in code.items() for _ in re.findall(pattern, t)]
+
+    for what, pattern, where in (("the order table's initialiser", r"16,\s*17,\s*18,\s*0,\s*8", [rules]),
+                                 ("stored_len_skip", r"skip <= 2u", [rules]),
+                                 ("stored_len_mask", r"__builtin_clz\((?:a\.)?obsize\)", [rules]),
+                                 ("no_eof_behind_code", r"isize - 3", [rules]), ("copy_hold", r"isize - 2", [rules]),
+                                 ("the wave decoder's own load", r"dload32", [])):
+        assert sites(pattern) == where, "%s (%s) stands in %s" % (what, pattern, sites(pattern))
+    for f in ("hdlz_inflate_tok.hip", "hdlz_inflate_grp.hip", "hdlz_inflate_dyn.hip", "hdlz_inflate_par.hip", "hdlz_inflate_any.hip"):
+        assert '#include "%s"' % rules in code[f], f
