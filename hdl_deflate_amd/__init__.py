@@ -13,6 +13,8 @@ from .constants import (IDLE, WRITE, READ, STARTC, STARTD, OK, E_SHORT_INPUT, E_
 from .port import Sig, DeflatePort, deflate                         # noqa: F401
 from . import bgzf                                                  # noqa: F401  (host-only: virtual offsets, .gzi files)
 from .bgzf import virtual_offset, split_virtual, gzi_dumps, gzi_loads   # noqa: F401
+from .zip import ZipIndex                                           # noqa: F401  (what Engine.zip_index returns)
+from .npz import load_npz                                           # noqa: F401  (.npz files into device tensors)
 
 
 def join_bound(nblocks, in_len):

@@ -102,6 +102,17 @@ GUNZIP_SIGNATURES = {
     "hdlz_gunzip_ws": (ci, _BATCH_IN + [vp, u64, vp, vp, vp, vp, vp, sz, vp]),
 }
 GUNZIP_EXPORTS = tuple(GUNZIP_SIGNATURES)
+# ... and of include/hdlz_zip.h: ZIP archives, the directory indexed and the entries read on the device (tests/test_zip_cabi.py)
+ZIP_SIGNATURES = {
+    "hdlz_zip_index_work_bytes": (sz, [u64, u64]),
+    # d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, work_bytes, stream
+    "hdlz_zip_index_ws": (ci, [vp, u64, u64, u32, vp, vp, vp, sz, vp]),
+    "hdlz_zip_inflate_work_bytes": (sz, [u64, u32, u64]),
+    # d_file, file_len, d_entries, first, count, in_len, d_out, out_cap, d_entry_status, d_result, d_work, work_bytes, stream
+    "hdlz_zip_inflate_ws": (ci, [vp, u64, vp, u64, u64, u32, vp, u64, vp, vp, vp, sz, vp]),
+}
+ZIP_EXPORTS = tuple(ZIP_SIGNATURES)
+ZIP_LARGE_MIN = 16384          # HDLZ_ZIP_LARGE_MIN
 _lib = None
 
 
@@ -156,6 +167,23 @@ class BgzfRangesResult(ctypes.Structure):
     _fields_ = [("total_out", u64), ("ntasks", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
 
 
+class ZipEntry(ctypes.Structure):
+    """hdlz_zip_entry: one record of hdlz_zip_index_ws (48 bytes)"""
+    _fields_ = [("cd_off", u64), ("payload_off", u64), ("out_off", u64), ("csize", u32), ("usize", u32), ("crc", u32),
+                ("method", ctypes.c_uint16), ("flags", ctypes.c_uint16), ("name_len", ctypes.c_uint16), ("reserved", ctypes.c_uint16),
+                ("status", u32)]
+
+
+class ZipIndexResult(ctypes.Structure):
+    """hdlz_zip_index_result: the result record of hdlz_zip_index_ws (40 bytes)"""
+    _fields_ = [("nentries", u64), ("total_out", u64), ("cd_off", u64), ("cd_size", u64), ("status", u32), ("reserved", u32)]
+
+
+class ZipInflateResult(ctypes.Structure):
+    """hdlz_zip_inflate_result: the result record of hdlz_zip_inflate_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -176,7 +204,7 @@ def load():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
-            list(GUNZIP_SIGNATURES.items()):
+            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

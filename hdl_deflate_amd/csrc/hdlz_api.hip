@@ -770,4 +770,84 @@ int hdlz_gunzip_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pi
     return launched(hdlz::launch_gunzip_judge(g, st), "launch k_gunzip_judge");
 }
 
+// ---- include/hdlz_zip.h: ZIP archives, the directory indexed and the entries read on the device (hdlz_zip.hip)
+size_t hdlz_zip_index_work_bytes(uint64_t file_len, uint64_t entry_cap) {
+    (void)entry_cap;
+    return file_len > 0xFFFFFFFFull ? 0u : hdlz::zip_index_work_bytes();
+}
+
+int hdlz_zip_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip_entry* d_entries,
+                      hdlz_zip_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || (file_len && !d_file)) return fail_param("null device pointer");
+    if (entry_cap && !d_entries) return fail_param("d_entries is null with entry_cap > 0");
+    if (file_len > 0xFFFFFFFFull) return fail_param("file_len too large (below 2^32: ZIP64 is out of scope)");
+    if (entry_cap > 0xFFFFFFFFull) return fail_param("entry_cap too large (below 2^32)");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (work_too_small(hdlz::zip_index_work_bytes(), d_work, work_bytes, "hdlz_zip_index_work_bytes(file_len, entry_cap)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_entries, d_result, d_work)) return fail_align(8, "d_entries / d_result / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_zip_index(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, static_cast<hipStream_t>(stream)),
+                    "launch k_zip_end");
+}
+
+// The scratch of hdlz_zip_inflate_ws, laid out once for the size query and the call: six words per entry (length, status, end bit, room,
+// CRC-32, the checks' verdict), three 64-bit words per entry (the decoder's view: start, end, destination) and -- one entry -- a CRC word
+// per 32 KiB tile of out_cap and the share of the batch call's path, which takes what is left from `decode` on.
+struct ZipScratch {
+    uint32_t *len, *status, *end_bit, *cap, *crc, *verdict;
+    uint64_t *m_off, *m_end;
+    uint8_t** m_dst;
+    uint32_t* tiles;
+    size_t decode;
+    size_t bytes;
+};
+static ZipScratch zip_scratch(void* base, uint64_t count, uint32_t in_len, uint64_t out_cap) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const size_t per = hdlz::round256(24u * (size_t)count);
+    const size_t tiles = count == 1 ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(out_cap)) : 0u;
+    auto w32 = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * count)); };
+    auto w64 = [&](uint64_t k) { return reinterpret_cast<uint64_t*>(b + per + 8u * (size_t)(k * count)); };
+    return {w32(0), w32(1), w32(2), w32(3), w32(4), w32(5), w64(0), w64(1), reinterpret_cast<uint8_t**>(w64(2)),
+            tiles ? reinterpret_cast<uint32_t*>(b + 2u * per) : nullptr, 2u * per + tiles,
+            2u * per + tiles + (count == 1 ? hdlz::round256(hdlz_inflate_work_bytes(1, in_len, out_cap & ~3ull, 0, 1)) : 0u)};
+}
+size_t hdlz_zip_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) {
+    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_scratch(nullptr, count, in_len, out_cap).bytes;
+}
+
+int hdlz_zip_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip_entry* d_entries, uint64_t first, uint64_t count,
+                        uint32_t in_len, uint8_t* d_out, uint64_t out_cap, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
+                        void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("d_result is required");
+    if (count && any_null(d_file, d_entries)) return fail_param("null device pointer");
+    if (out_cap && !d_out) return fail_param("d_out is null with out_cap > 0");
+    if (first > 0x7FFFFFFFull || count > 0x7FFFFFFFull || first + count > 0x7FFFFFFFull) return fail_param("first + count too large (below 2^31)");
+    if (file_len > 0xFFFFFFFFull) return fail_param("file_len too large (below 2^32: ZIP64 is out of scope)");
+    if (misaligned(8, d_entries, d_result)) return fail_align(8, "d_entries / d_result");
+    if (misaligned(4, d_entry_status)) return fail_align(4, "d_entry_status");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    const ZipScratch s = zip_scratch(d_work, count, in_len, out_cap);
+    if (count && work_too_small(s.bytes, d_work, work_bytes, "hdlz_zip_inflate_work_bytes(count, in_len, out_cap)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // one entry takes the batch call's path, which stores words, when its row is one that path accepts; else the task view
+    const bool single = count == 1 && out_cap >= 4u && !misaligned(4, d_out);
+    const hdlz::ZipArgs z{d_file, file_len, d_entries ? d_entries + first : nullptr, count, in_len, d_out, out_cap, d_entry_status, d_result,
+                          s.len, s.status, s.end_bit, s.cap, s.crc, s.verdict, s.m_off, s.m_end, s.m_dst, single ? s.tiles : nullptr, single};
+    if (const int rc = launched(hdlz::launch_zip_check(z, st), "launch k_zip_check"); rc != HDLZ_OK) return rc;
+    if (single) {
+        // a large entry: the batch call's path over the two-word index the checks left on the device -- the whole-GPU chains for a
+        // large payload, their fallbacks, the wave for a small one; in_len is the bound the call was given
+        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
+        if (const int rc = inflate_batch_impl(d_file, s.m_off, 0, in_len, 1, 0, 0, d_out, out_cap & ~3ull, s.len, s.status, w, stream, s.end_bit); rc != HDLZ_OK) return rc;
+    } else if (count) {
+        hdlz::MemberArgs a = member_args(d_file, count, 0, d_out, s.len, s.status, s.end_bit, s.m_off);   // (BFINAL is honoured)
+        a.m_end = s.m_end; a.m_dst = s.m_dst; a.m_dst_cap = s.cap;                                     // the task view
+        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+    }
+    if (const int rc = launched(hdlz::launch_zip_copy(z, st), "launch k_zip_copy"); rc != HDLZ_OK) return rc;
+    if (const int rc = launched(hdlz::launch_zip_crc(z, st), "launch k_zip_crc_*"); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_zip_judge(z, st), "launch k_zip_judge");
+}
+
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include "../../include/hdlz_bgzf_range.h"   // (includes hdlz_bgzf.h, hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
 #include "../../include/hdlz_bgzf_stored.h"
 #include "../../include/hdlz_gunzip.h"
+#include "../../include/hdlz_zip.h"
 
 namespace hdlz {
 
@@ -339,5 +340,36 @@ size_t gunzip_tile_words(uint64_t nstreams, uint64_t out_pitch);
 hipError_t launch_gunzip_heads(const GunzipArgs& a, hipStream_t stream);
 hipError_t launch_gunzip_crc(const GunzipArgs& a, hipStream_t stream);
 hipError_t launch_gunzip_judge(const GunzipArgs& a, hipStream_t stream);
+
+// hdlz_zip.hip: hdlz_zip_index_ws and what hdlz_zip_inflate_ws runs around the decode (include/hdlz_zip.h)
+size_t zip_index_work_bytes();
+hipError_t launch_zip_index(const uint8_t* file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip_entry* entries,
+                            hdlz_zip_index_result* result, void* work, hipStream_t stream);
+struct ZipArgs {
+    const uint8_t* in;
+    uint64_t in_len;                  // file_len
+    const hdlz_zip_entry* entries;    // the call's d_entries + first
+    uint64_t count;
+    uint32_t bound;                   // the call's in_len
+    uint8_t* out;
+    uint64_t out_cap;
+    uint32_t* entry_status;           // nullable
+    hdlz_zip_inflate_result* result;
+    uint32_t* len;                    // scratch, per entry, as in BgzfArgs: the decoded length / the workgroup's lowest failed entry
+    uint32_t* status;                 // ... the decoder's status word (a stored entry: FFFFFFFF, left alone), then the verdict
+    uint32_t* end_bit;                // ... where the final block ended: a bit (the task view) or, single, a byte
+    uint32_t* cap;                    // ... MemberArgs::m_dst_cap
+    uint32_t* crc;                    // ... the CRC-32 of the slot
+    uint32_t* verdict;                // ... the checks in front of the decode
+    uint64_t* m_off;                  // scratch, per entry: MemberArgs::m_off; single: with m_end[0] the ragged index of one stream
+    uint64_t* m_end;                  // ... MemberArgs::m_end (the word behind m_off[count - 1])
+    uint8_t** m_dst;                  // ... MemberArgs::m_dst
+    uint32_t* tiles;                  // scratch, single: one word per 32 KiB tile of out_cap (else null)
+    bool single;                      // count == 1 on the batch call's path
+};
+hipError_t launch_zip_check(const ZipArgs& a, hipStream_t stream);
+hipError_t launch_zip_copy(const ZipArgs& a, hipStream_t stream);
+hipError_t launch_zip_crc(const ZipArgs& a, hipStream_t stream);
+hipError_t launch_zip_judge(const ZipArgs& a, hipStream_t stream);
 
 }  // namespace hdlz

@@ -525,6 +525,108 @@ class Engine(object):
             return e.status, b""
         return OK, bytes(out.cpu().numpy().tobytes())
 
+    # -- ZIP archives (include/hdlz_zip.h): the directory indexed and the entries read on the device
+    @_on_device
+    def zip_index(self, d_file, entry_cap=None, out_align=1):
+        """d_file: flat uint8 device tensor, a ZIP file (.zip, .npz, .jar, .whl, .docx) -> a ZipIndex (hdl_deflate_amd/zip.py): the device
+        records of hdlz_zip_index_ws, its result record, a host copy of the records and the entries' names.  A status that is not OK --
+        the record's or an entry's -- is returned, not raised: the entries in front of a stop stay valid and indexed.  entry_cap: room
+        for that many records (default: the sizing call first, then the call with the true count); out_align: every entry's slot in the
+        flat output starts at a multiple of it (a power of two up to 256).  One host sync per call for the record, one for the records
+        and one for the names."""
+        from .zip import ZipIndex, ENTRY_DTYPE, decode_name
+        import numpy as np
+        self._is_bytes(d_file, "d_file", flat=True)
+        n, dev = d_file.numel(), d_file.device
+        scratch = self._scratch(self.lib.hdlz_zip_index_work_bytes(n, 0), None, full=True)
+        cap = 0 if entry_cap is None else int(entry_cap)
+        while True:
+            entries = torch.empty((cap, 6), dtype=torch.int64, device=dev)
+            rec = self._record("hdlz_zip_index_ws", _lib.ZipIndexResult, scratch, d_file.data_ptr() if n else None, n, cap, out_align,
+                               entries.data_ptr() if cap else None)
+            if entry_cap is not None or rec.status != E_OUT_CAPACITY or rec.nentries <= cap:
+                break
+            cap = rec.nentries
+        k = min(cap, rec.nentries)
+        entries = entries[:k]
+        host = np.frombuffer(entries.cpu().numpy().tobytes(), dtype=ENTRY_DTYPE)
+        # the names: bytes [cd_off + 46, cd_off + 46 + name_len) of every record, gathered on the device, one copy to the host
+        lens = host["name_len"].astype(np.int64)
+        ends = np.cumsum(lens)
+        raw = b""
+        if k and int(ends[-1]):
+            starts = torch.from_numpy((host["cd_off"].astype(np.int64) + 46) - (ends - lens)).to(dev)
+            at = torch.repeat_interleave(starts, torch.from_numpy(lens).to(dev)) + torch.arange(int(ends[-1]), dtype=torch.int64, device=dev)
+            raw = d_file[at].cpu().numpy().tobytes()
+        names = [decode_name(raw[int(e - l):int(e)], int(f)) for e, l, f in zip(ends, lens, host["flags"])]
+        return ZipIndex(entries, rec, host, names, out_align)
+
+    @_on_device
+    def inflate_zip(self, d_file, index=None, first=0, count=None, out=None, work=None):
+        """d_file: flat uint8 device tensor, a ZIP file; index: its ZipIndex (default: taken here, with slots at multiples of 16)
+        -> (out uint8[n], out_off int64[count], status int32[count]), all on the device: entry first + k of the index stands at
+        out[out_off[k] : out_off[k] + usize] and has status[k] -- HDLZ_OK, or why it was not read; nothing is raised for an entry.  Any
+        range [first, first + count) reads without the rest.  The range is routed here: maximal runs of entries below ZIP_LARGE_MIN
+        compressed bytes go in one hdlz_zip_inflate_ws call each, a wave per entry; every larger entry goes in a call of its own, decoded
+        by the whole GPU (when its slot starts at a multiple of 4: index with out_align >= 4) -- in ascending order, all into the same
+        flat `out`.  out: at least the range's bytes rounded up to 4 (default: allocated here); work: the scratch of the largest call,
+        uint8 at a multiple of 256 (default: allocated here).  No host sync behind the index."""
+        self._is_bytes(d_file, "d_file", flat=True)
+        dev = d_file.device
+        if index is None:
+            index = self.zip_index(d_file, out_align=16)
+        host, E = index.host, len(index.host)
+        count = E - first if count is None else int(count)
+        if not 0 <= first <= first + count <= E:
+            raise ValueError("entries [%d, %d) are not a range of the index's %d entries" % (first, first + count, E))
+        ok = host["status"] == OK
+        rel = (host["out_off"] - (host["out_off"][first] if count else 0)).astype("int64")
+        size = host["usize"].astype("int64") * ok
+        total = int(rel[first + count - 1] + size[first + count - 1]) if count else 0
+        room = (total + 3) & ~3
+        if out is None:
+            out = torch.empty(room, dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out", flat=True, room=room)
+        status = torch.empty(count, dtype=torch.int32, device=dev)
+        out_off = index.entries[first:first + count, 2] - (index.entries[first, 2] if count else 0)
+        # the calls: (first entry, count, in_len, out_cap)
+        calls, e, end = [], first, first + count
+        while e < end:
+            if ok[e] and host["csize"][e] >= _lib.ZIP_LARGE_MIN:
+                calls.append((e, 1, int(host["csize"][e]) + 6, min((int(size[e]) + 3) & ~3, out.numel() - int(rel[e]))))
+                e += 1
+                continue
+            b = e
+            while e < end and not (ok[e] and host["csize"][e] >= _lib.ZIP_LARGE_MIN):
+                e += 1
+            cap = int(rel[e - 1] + size[e - 1] - rel[b])
+            calls.append((b, e - b, 0, cap if e - b > 1 else min((cap + 3) & ~3, out.numel() - int(rel[b]))))      # (one entry: a row of whole words)
+        need = max([self.lib.hdlz_zip_inflate_work_bytes(c, il, cap) for _, c, il, cap in calls] + [0])
+        scratch = self._scratch(need, work, torch.uint8)
+        results = torch.empty((max(len(calls), 1), 3), dtype=torch.int64, device=dev)
+        for k, (b, c, il, cap) in enumerate(calls):
+            self._check(self.lib.hdlz_zip_inflate_ws(d_file.data_ptr(), d_file.numel(), index.entries.data_ptr(), b, c, il,
+                                                     out.data_ptr() + int(rel[b]) if out.numel() else None, cap,
+                                                     status.data_ptr() + 4 * (b - first), results[k].data_ptr(), scratch[1], scratch[2],
+                                                     self._stream()), "hdlz_zip_inflate_ws")
+        return out[:total], out_off, status
+
+    def read_zip_bytes(self, z):
+        """the bytes of a ZIP file -> (status, {name: bytes}): every entry that read OK, as zipfile's read() gives it (of two entries of
+        one name the later one).  status: that of the lowest failed entry; when every indexed entry is sound, that of the index (a
+        directory that stops early, a file that is no ZIP)."""
+        d = self._stage(z)[:len(z)]
+        index = self.zip_index(d, out_align=16)
+        out, out_off, status = self.inflate_zip(d, index)
+        data, off, st = out.cpu().numpy(), out_off.cpu().numpy(), status.cpu().numpy()
+        files, worst = {}, OK
+        for k, name in enumerate(index.names):
+            if st[k] == OK:
+                files[name] = data[off[k]:off[k] + int(index.host["usize"][k])].tobytes()
+            elif worst == OK:
+                worst = int(st[k])
+        return (worst if worst != OK else index.record.status), files
+
     # -- STARTC for ONE large stream, spread over the whole GPU (same bytes as compress_batch with one block)
     STREAM_MIN = 1 << 14          # measured crossover with the single-wave batch path: ~8 KiB
     LARGE_BLOCK, MANY_WAVES = 1 << 16, 1200   # compress_batch: up to this many blocks of at least this size -> stream passes

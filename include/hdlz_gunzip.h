@@ -57,7 +57,8 @@
  *
  * Out of scope: several members of one stream decoded in one call (the caller moves on by d_in_used); the lane and group mappings for
  * batches (the member twins of k_inflate_tok and k_inflate_grp have no dynamic-tree pass) and the whole-GPU path for more than one
- * stream per call; obsize and HDLZ_INFLATE_ASSUME_FIXED semantics; writing header fields of other writers.
+ * stream per call; obsize and HDLZ_INFLATE_ASSUME_FIXED semantics; writing header fields of other writers; ZIP archives (taken up by
+ * hdlz_zip.h).
  */
 #ifndef HDLZ_GUNZIP_H
 #define HDLZ_GUNZIP_H
