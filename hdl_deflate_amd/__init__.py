@@ -14,7 +14,7 @@ from .port import Sig, DeflatePort, deflate                         # noqa: F401
 from . import bgzf                                                  # noqa: F401  (host-only: virtual offsets, .gzi files)
 from .bgzf import virtual_offset, split_virtual, gzi_dumps, gzi_loads   # noqa: F401
 from .zip import ZipIndex                                           # noqa: F401  (what Engine.zip_index returns)
-from .npz import load_npz                                           # noqa: F401  (.npz files into device tensors)
+from .npz import load_npz, save_npz                                 # noqa: F401  (.npz files into device tensors, and back)
 
 
 def join_bound(nblocks, in_len):

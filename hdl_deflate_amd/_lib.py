@@ -113,6 +113,16 @@ ZIP_SIGNATURES = {
 }
 ZIP_EXPORTS = tuple(ZIP_SIGNATURES)
 ZIP_LARGE_MIN = 16384          # HDLZ_ZIP_LARGE_MIN
+# ... and of include/hdlz_zip_write.h: a ZIP archive written from the rows of one compress batch (tests/test_zip_write_cabi.py)
+ZIP_WRITE_SIGNATURES = {
+    "hdlz_zip_write_bound": (sz, [u64, u64, u32, u64, u64]),      # nentries, nblocks, block_len, total_in, names_len
+    "hdlz_zip_write_work_bytes": (sz, [u64, u64]),                # nentries, nblocks
+    # d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks, d_blk_first, d_crc,
+    # flags, dos_datetime, out_align, total_in, d_file, file_cap, d_entries, d_result, d_work, work_bytes, stream
+    "hdlz_zip_write_ws": (ci, [vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u32, u32, u32, u64, vp, u64, vp, vp, vp, sz, vp]),
+}
+ZIP_WRITE_EXPORTS = tuple(ZIP_WRITE_SIGNATURES)
+ZIP_FLAG_UTF8 = 0x800          # HDLZ_ZIP_FLAG_UTF8
 _lib = None
 
 
@@ -184,6 +194,11 @@ class ZipInflateResult(ctypes.Structure):
     _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
 
 
+class ZipWriteResult(ctypes.Structure):
+    """hdlz_zip_write_result: the result record of hdlz_zip_write_ws (40 bytes)"""
+    _fields_ = [("file_len", u64), ("cd_off", u64), ("cd_size", u64), ("nstored", u64), ("status", u32), ("first_bad", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -204,7 +219,7 @@ def load():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
-            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()):
+            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -850,4 +850,37 @@ int hdlz_zip_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip
     return launched(hdlz::launch_zip_judge(z, st), "launch k_zip_judge");
 }
 
+// ---- include/hdlz_zip_write.h: a ZIP archive written from the rows of one compress batch (hdlz_zip_write.hip)
+size_t hdlz_zip_write_bound(uint64_t nentries, uint64_t nblocks, uint32_t block_len, uint64_t total_in, uint64_t names_len) {
+    (void)nblocks; (void)block_len;                          // (a payload is never longer than its entry)
+    return 22u + 76u * (size_t)nentries + 2u * (size_t)names_len + (size_t)total_in;
+}
+
+size_t hdlz_zip_write_work_bytes(uint64_t nentries, uint64_t nblocks) {
+    return nentries > 65535u || nblocks > 0x7FFFFFFFull ? 0u : hdlz::zip_write_work_bytes(nentries, nblocks);
+}
+
+int hdlz_zip_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const uint8_t* d_names, const uint64_t* d_name_off, uint64_t nentries,
+                      const uint64_t* d_in_off, const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                      const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, const uint32_t* d_crc, uint32_t flags,
+                      uint32_t dos_datetime, uint32_t out_align, uint64_t total_in, uint8_t* d_file, uint64_t file_cap,
+                      hdlz_zip_entry* d_entries, hdlz_zip_write_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("d_result is required");
+    if (nentries > 65535u) return fail_param("nentries too large (at most 65535: ZIP64 is out of scope)");
+    if (nblocks > 0x7FFFFFFFull || (nblocks && !nentries)) return fail_param("nblocks too large for one launch (2^31 - 1 rows), or rows without entries");
+    if (nentries && (any_null(d_in, d_names, d_crc) || any_null(d_ent_off, d_name_off, d_blk_first))) return fail_param("null device pointer (the entries)");
+    if (nblocks && (any_null(d_in_off, d_end_bits) || any_null(d_len, d_status) || !d_rows)) return fail_param("null device pointer (the rows)");
+    if (file_cap && !d_file) return fail_param("d_file is null with file_cap > 0");
+    if (flags & ~(uint32_t)HDLZ_ZIP_FLAG_UTF8) return fail_param("flags: only HDLZ_ZIP_FLAG_UTF8 may be set");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (work_too_small(hdlz::zip_write_work_bytes(nentries, nblocks), d_work, work_bytes, "hdlz_zip_write_work_bytes(nentries, nblocks)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_ent_off, d_name_off, d_in_off, d_end_bits, d_blk_first) || misaligned(8, d_entries) || misaligned(8, d_result) || misaligned(8, d_work))
+        return fail_align(8, "d_ent_off / d_name_off / d_in_off / d_end_bits / d_blk_first / d_entries / d_result / d_work");
+    if (misaligned(4, d_len, d_status, d_crc)) return fail_align(4, "d_len / d_status / d_crc");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hdlz::ZipWriteArgs a{d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks,
+                         d_blk_first, d_crc, flags, dos_datetime, out_align, total_in, d_file, file_cap, d_entries, d_result, {}};
+    return launched(hdlz::launch_zip_write(a, d_work, static_cast<hipStream_t>(stream)), "launch k_zipw_*");
+}
+
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "../../include/hdlz_bgzf_stored.h"
 #include "../../include/hdlz_gunzip.h"
 #include "../../include/hdlz_zip.h"
+#include "../../include/hdlz_zip_write.h"
 
 namespace hdlz {
 
@@ -371,5 +372,40 @@ hipError_t launch_zip_check(const ZipArgs& a, hipStream_t stream);
 hipError_t launch_zip_copy(const ZipArgs& a, hipStream_t stream);
 hipError_t launch_zip_crc(const ZipArgs& a, hipStream_t stream);
 hipError_t launch_zip_judge(const ZipArgs& a, hipStream_t stream);
+
+// hdlz_zip_write.hip: hdlz_zip_write_ws (include/hdlz_zip_write.h).  The scratch, carved by the launcher: E = nentries
+struct ZipWriteWork {
+    uint32_t* ticket;                 // the scan's ticket (+ pad), ...
+    unsigned long long *desc, *desc2; // ... its look-back words per tile: the member lengths; the two counts
+    uint64_t *pre, *cnt;              // per row (+ 1): the exclusive prefix of |M_b|; of the failed rows (bits 0 .. 30) and the contradictory ones
+    uint64_t* head;                   // the summary: is the file written, the tiles of the stored copy, did an entry fail
+    uint64_t *pay, *cdrec, *out_off;  // per entry: payload_off, where its central record starts, out_off
+    uint32_t *csize, *form, *tile0;   // per entry: c_e; method | status << 8; (E + 1 words) the first tile of the stored copy
+};
+struct ZipWriteArgs {
+    const uint8_t* in;
+    const uint64_t* ent_off;
+    const uint8_t* names;
+    const uint64_t* name_off;
+    uint64_t nentries;
+    const uint64_t* in_off;
+    const uint8_t* rows;
+    uint64_t pitch;
+    const uint32_t* len;
+    const uint64_t* end_bits;
+    const uint32_t* status;
+    uint64_t nblocks;
+    const uint64_t* blk_first;
+    const uint32_t* crc;
+    uint32_t flags, datetime, out_align;
+    uint64_t total_in;
+    uint8_t* file;
+    uint64_t cap;
+    hdlz_zip_entry* entries;          // nullable
+    hdlz_zip_write_result* result;
+    ZipWriteWork w;
+};
+size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks);
+hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream);
 
 }  // namespace hdlz

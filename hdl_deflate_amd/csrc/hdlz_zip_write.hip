@@ -1,0 +1,430 @@
+// hdlz_zip_write.hip -- the kernels of include/hdlz_zip_write.h: a ZIP archive written from the rows of ONE compress
+// batch.  A ZIP is ragged twice -- entries, and blocks inside entries --, a header with a name of any length stands in front of every
+// payload and a directory behind them, and whether an entry is deflated at all depends on the sum of ALL its members: so, unlike k_join,
+// the scan cannot copy on its way.  Three kernels behind the zeroing of the look-back words:
+//
+// k_zipw_scan    a tile join's first half (hdlz_frame.h: tile_scan, tile_lookback): a workgroup takes a TILE of 256 consecutive rows by a
+//                ticket and leaves, per row, the exclusive prefix of the member lengths |M_b| and of two counts in one word -- rows
+//                whose status is not HDLZ_OK (bits 0 .. 30) and rows whose length, end bit and pitch contradict each other (bits
+//                31 .. 61; a block of negative length counts among them) --, so that an entry's payload length and "does a block of
+//                mine fail" are each two loads.  The two look-backs run side by side, a wave each.
+// k_zipw_plan    ONE workgroup of 1024 threads, 64 entries each at most: the checks of step 1, c_e and the form, the scans of the record
+//                sizes (local offsets, directory offsets, out_off, the tiles of the stored copy) -> the plan in the scratch; thread 0
+//                writes the end record and the result record.  An entry with a failed row walks its rows for the largest status:
+//                the one serial loop, on the failing path only.
+// k_zipw_gather  the hot path, three kinds of workgroup in one grid (a kind per range of blockIdx.x, uniform over a workgroup):
+//                  rows     16 consecutive rows a workgroup (256 from 65536 rows on), a quarter of them a wave.  Every wave finds its
+//                           first row's entry by a 64-way search in d_blk_first (three rounds of dependent loads, not sixteen), its
+//                           other rows' entries among the next 64 (one round), and leaves every row's source, destination and
+//                           lengths in LDS: what depends on the plan is loaded once a wave, all its rows at a time, not row after
+//                           row, and no wave waits for another's loads.  A deflated entry's row: M_b to its place with BFINAL
+//                           cleared and the marker appended -- k_join's loop, four 16-byte loads in flight a lane --, 03 00 behind
+//                           the entry's last member.  A stored entry's row: the block's input bytes (copy_to_aligned16).
+//                  tiles    the stored entries WITHOUT rows, cut into tiles of 64 KiB: a workgroup finds its tile's entry by a search
+//                           in the plan's tile prefix and copies with copy_to_aligned16; the number of these workgroups comes from
+//                           total_in and nentries, and they stride when that understated the bytes.
+//                  entries  a wave per entry: the 30 and the 46 header bytes (a lane a byte, picked from the words of the record), the
+//                           name behind both (copy_to_aligned16), d_entries[e].
+// Plain stores only; all bulk stores are 16 bytes to 16-byte aligned addresses.  Loads: the index arrays; names exactly; of a row only
+// [2, d_len - 4) and only for a deflated entry; of an entry only its bytes and only when it is stored.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "hdlz_device.h"
+#include "hdlz_compress_common.h"                        // the framing constants: HEADER_BITS, block_nbytes
+#include "hdlz_frame.h"                                  // the tile's scan and look-back, the wave reductions, copy_to_aligned16
+
+namespace hdlz {
+namespace zipw {
+
+constexpr uint32_t LOCREC = 30u, CDREC = 46u, EOCD = 22u;
+constexpr uint32_t SIG_LOCAL = 0x04034B50u, SIG_CD = 0x02014B50u, SIG_EOCD = 0x06054B50u;
+constexpr uint32_t VERSION = 20u;                                // needed to extract, and made by (host 0): 2.0
+constexpr uint32_t METHOD_DEFLATED = 8u, NAME_LEN_MAX = 65535u;
+constexpr uint64_t NO_ZIP64 = 0xFFFFFFFFull;                     // a size or offset of FFFFFFFF means "see the ZIP64 field"
+constexpr uint32_t PLAN_THREADS = 1024u, PLAN_WAVES = PLAN_THREADS / 64u;      // 65535 entries: 64 a thread
+constexpr uint32_t STORE_TILE = 65536u;                          // 16 stores of 16 bytes a thread
+constexpr uint32_t ROWS_MAX = 256u, ROWS_FEW = 16u, ROWS_MANY_MIN = 1u << 16;      // rows a workgroup of the gather takes: 16, or 256 from 65536 rows on (not measured: between the profile's two shapes)
+constexpr uint32_t COUNT_BITS = 31u;                             // nblocks < 2^31: two counts fit under the look-back word's state bits
+constexpr uint64_t COUNT_MASK = (1ull << COUNT_BITS) - 1u;
+// the summary at w.head
+enum { H_WRITE = 0, H_TILES = 1, H_FAILED = 2 };
+
+typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+typedef v4 __attribute__((aligned(1))) v4u;
+
+// |M_b| and the bytes of it that come from the row; 0: the row's three words contradict each other (hdlz_join.h)
+__device__ __forceinline__ uint32_t member_len(const ZipWriteArgs& a, uint64_t b, uint32_t& body) {
+    const uint32_t n = a.len[b];
+    const uint64_t E = a.end_bits[b];
+    body = 0u;
+    if (E < HEADER_BITS || block_nbytes(E) + 4u != (uint64_t)n || (uint64_t)n > a.pitch) return 0u;
+    const uint32_t nbytes = n - 4u;
+    const uint32_t p = (uint32_t)(8ull * nbytes - E) - 7u;       // pad bits behind the end-of-block code
+    body = nbytes - 2u;
+    return body + (p >= 3u ? 4u : 5u);
+}
+
+// the first index i of v[0 .. n) with v[i] > x (n: none) -- v ascending
+template <class T>
+__device__ __forceinline__ uint32_t upper_bound(const T* __restrict__ v, uint32_t n, uint64_t x) {
+    uint32_t lo = 0u, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((uint64_t)v[mid] > x) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+
+// ---- (a) the prefixes over the rows
+__global__ __launch_bounds__(JT) void k_zipw_scan(ZipWriteArgs a) {
+    __shared__ uint32_t s_tile;
+    __shared__ uint64_t s_wsum[4], s_wsum2[4], s_base, s_base2;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid == 0u) s_tile = atomicAdd(a.w.ticket, 1u);
+    __syncthreads();
+    const uint32_t tile = s_tile;
+    const uint64_t b = (uint64_t)tile * JT + tid;
+    uint32_t m = 0u, k = 0u;                                      // k: failed in the low half, contradictory in the high half
+    if (b < a.nblocks) {
+        if (a.status[b] != HDLZ_OK) k = 1u;
+        else {
+            uint32_t body;
+            m = member_len(a, b, body);
+            if (a.in_off[b + 1u] < a.in_off[b]) m = 0u;           // (a block of negative length: the copy of a stored entry's rows trusts these)
+            if (m == 0u) k = 1u << 16;
+        }
+    }
+    // (a tile's counts are at most 256: they are scanned as halves of one word and widened to COUNT_BITS for the look-back)
+    auto wide = [](uint64_t v) { return (v & 0xFFFFu) | ((v >> 16) << COUNT_BITS); };
+    uint64_t tsum, tsum2;
+    const uint64_t local = tile_scan(m, lane, wave, s_wsum, tsum);
+    const uint64_t local2 = wide(tile_scan(k, lane, wave, s_wsum2, tsum2));
+    tsum2 = wide(tsum2);
+    // the two look-backs side by side, a wave each: neither chain waits for the other's
+    const bool last_tile = (uint64_t)(tile + 1u) * JT >= a.nblocks;
+    if (wave == 0u) {
+        const uint64_t base = tile_lookback(a.w.desc, tile, tsum, lane);
+        if (lane == 0u) {
+            s_base = base;
+            if (last_tile) a.w.pre[a.nblocks] = base + tsum;
+        }
+    } else if (wave == 1u) {
+        const uint64_t base2 = tile_lookback(a.w.desc2, tile, tsum2, lane);
+        if (lane == 0u) {
+            s_base2 = base2;
+            if (last_tile) a.w.cnt[a.nblocks] = base2 + tsum2;
+        }
+    }
+    __syncthreads();
+    if (b < a.nblocks) { a.w.pre[b] = s_base + local; a.w.cnt[b] = s_base2 + local2; }
+}
+
+// byte i of the record whose little-endian words are w[0 .. N)
+template <int N>
+__device__ __forceinline__ uint8_t record_byte(const uint32_t (&w)[N], uint32_t i) {
+    uint32_t x = 0u;
+    static_for<0, N>([&](auto k) {
+        if ((i >> 2) == (uint32_t)k) x = w[k];
+    });
+    return (uint8_t)(x >> (8u * (i & 3u)));
+}
+
+// ---- (b) the plan: thread t takes the entries [per t, per (t + 1)), per = ceil(E / 1024)
+__global__ __launch_bounds__(PLAN_THREADS) void k_zipw_plan(ZipWriteArgs a) {
+    __shared__ uint64_t s_wave[PLAN_WAVES][4];
+    __shared__ uint32_t s_worst[PLAN_WAVES], s_first[PLAN_WAVES], s_nst[PLAN_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t E = (uint32_t)a.nentries;
+    const uint64_t amask = (uint64_t)a.out_align - 1u;
+    const uint32_t per = (E + PLAN_THREADS - 1u) / PLAN_THREADS;        // at most 64
+    const uint32_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
+    uint64_t mine[4] = {0u, 0u, 0u, 0u};                          // local records, central records, output slots, tiles of the stored copy
+    uint32_t worst = HDLZ_OK, first = NONE, nst = 0u;
+    for (uint32_t e = lo; e < hi; e++) {
+        const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e];
+        const uint64_t F0 = a.blk_first[e], F1 = a.blk_first[e + 1u];
+        uint32_t st = HDLZ_OK, method = 0u;
+        uint64_t c = u;
+        if (F0 > F1 || F1 > a.nblocks) st = HDLZ_E_BAD_PARAM;
+        else if (F1 > F0) {
+            const uint64_t k = a.w.cnt[F1] - a.w.cnt[F0];         // (both counts ascend: the halves subtract without a borrow)
+            if (k & COUNT_MASK) {
+                for (uint64_t b = F0; b < F1; b++) st = max(st, a.status[b]);
+            } else if (k >> COUNT_BITS) st = HDLZ_E_BAD_PARAM;
+            else if (a.in_off[F1] - a.in_off[F0] != u) st = HDLZ_E_BAD_PARAM;
+        }
+        if (st == HDLZ_OK && n > NAME_LEN_MAX) st = HDLZ_E_BAD_PARAM;
+        if (st == HDLZ_OK && u >= NO_ZIP64) st = HDLZ_E_OUT_CAPACITY;
+        if (st == HDLZ_OK && F1 > F0) {
+            const uint64_t cd = a.w.pre[F1] - a.w.pre[F0] + 2u;   // the members and 03 00
+            if (cd < u) { method = METHOD_DEFLATED; c = cd; }
+        }
+        a.w.csize[e] = (uint32_t)c;
+        a.w.form[e] = method | (st << 8);
+        if (st == HDLZ_OK) {
+            mine[0] += LOCREC + n + c; mine[1] += CDREC + n; mine[2] += (u + amask) & ~amask;
+            if (F0 == F1) mine[3] += (u + STORE_TILE - 1u) / STORE_TILE;
+            nst += method == 0u ? 1u : 0u;
+        } else {
+            worst = max(worst, st);
+            first = min(first, e);
+        }
+    }
+    uint64_t v[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        v[q] = mine[q];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t t = __shfl_up(v[q], o, 64);
+            if (lane >= (uint32_t)o) v[q] += t;
+        }
+        if (lane == 63u) s_wave[wave][q] = v[q];
+    }
+    {
+        const uint32_t rw = wave_max(worst), rf = wave_min(first), rn = wave_add(nst);
+        if (lane == 0u) { s_worst[wave] = rw; s_first[wave] = rf; s_nst[wave] = rn; }
+    }
+    __syncthreads();
+    uint64_t base[4], total[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        base[q] = v[q] - mine[q];
+        total[q] = 0u;
+        for (uint32_t k = 0; k < PLAN_WAVES; k++) {
+            if (k < wave) base[q] += s_wave[k][q];
+            total[q] += s_wave[k][q];
+        }
+    }
+    worst = HDLZ_OK; first = NONE; nst = 0u;
+    for (uint32_t k = 0; k < PLAN_WAVES; k++) { worst = max(worst, s_worst[k]); first = min(first, s_first[k]); nst += s_nst[k]; }
+    const bool failed = worst != HDLZ_OK;
+    const uint64_t cd_off = total[0], cd_size = total[1], file_len = cd_off + cd_size + EOCD;
+    const bool limit = cd_off >= NO_ZIP64 || file_len > NO_ZIP64;       // (the local offsets ascend to cd_off)
+    const bool write = !failed && !limit && file_len <= a.cap;
+    for (uint32_t e = lo; e < hi; e++) {
+        const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e];
+        const bool none = a.blk_first[e] == a.blk_first[e + 1u];
+        a.w.pay[e] = base[0] + LOCREC + n; a.w.cdrec[e] = cd_off + base[1]; a.w.out_off[e] = base[2]; a.w.tile0[e] = (uint32_t)base[3];
+        if ((a.w.form[e] >> 8) == HDLZ_OK) {
+            base[0] += LOCREC + n + a.w.csize[e]; base[1] += CDREC + n; base[2] += (u + amask) & ~amask;
+            if (none) base[3] += (u + STORE_TILE - 1u) / STORE_TILE;
+        }
+    }
+    if (tid != 0u) return;
+    a.w.tile0[E] = write ? (uint32_t)total[3] : 0u;
+    a.w.head[H_WRITE] = write ? 1u : 0u; a.w.head[H_TILES] = write ? total[3] : 0u; a.w.head[H_FAILED] = failed ? 1u : 0u;
+    hdlz_zip_write_result res;
+    res.file_len = failed ? 0u : file_len; res.cd_off = failed ? 0u : cd_off; res.cd_size = failed ? 0u : cd_size; res.nstored = failed ? 0u : nst;
+    res.status = failed ? worst : (limit || file_len > a.cap) ? (uint32_t)HDLZ_E_OUT_CAPACITY : (uint32_t)HDLZ_OK;
+    res.first_bad = first;
+    *a.result = res;
+    if (!write) return;
+    uint8_t* t = a.file + cd_off + cd_size;
+    const uint32_t w[6] = {SIG_EOCD, 0u, E | (E << 16), (uint32_t)cd_size, (uint32_t)cd_off, 0u};
+    for (uint32_t i = 0; i < EOCD; i++) t[i] = record_byte(w, i);
+}
+
+// the number of elements of the ascending v[0 .. n) that are <= x (the first index with v[i] > x), by a whole wave: 64 probes a round,
+// so three rounds of dependent loads for the 65536 words of a ZIP's entries where a lane alone takes sixteen
+__device__ __forceinline__ uint32_t wave_upper_bound(const uint64_t* __restrict__ v, uint32_t n, uint64_t x, uint32_t lane) {
+    uint32_t base = 0u, width = n;
+    while (width > 64u) {
+        const uint32_t chunk = (width + 63u) / 64u, p = (lane + 1u) * chunk - 1u;      // lane i probes the last word of chunk i
+        const uint32_t c = (uint32_t)__builtin_popcountll(ballot64(p < width && v[base + p] <= x));
+        base += c * chunk;                                        // (the chunks in front hold only words <= x)
+        width = width - c * chunk < chunk ? width - c * chunk : chunk;
+    }
+    return base + (uint32_t)__builtin_popcountll(ballot64(lane < width && v[base + lane] <= x));
+}
+
+// byte i of M_b followed by 03 00: [0, bl) from the row (src = row + 2; byte 0: BFINAL cleared), zeros, FF FF at [m - 2, m), then 03 00
+__device__ __forceinline__ uint8_t member_byte(const uint8_t* src, uint32_t i, uint32_t bl, uint32_t m) {
+    if (i < bl) return i == 0u ? (uint8_t)(src[0] & 0xFEu) : src[i];
+    if (i < m - 2u) return (uint8_t)0u;
+    return i < m ? (uint8_t)0xFFu : i == m ? (uint8_t)0x03u : (uint8_t)0u;
+}
+
+// ---- (c) the gather.  A row of the rows' part, as a wave leaves it in LDS for its own copy loop
+enum { ROW_SKIP = 0, ROW_STORED = 1, ROW_MEMBER = 2, ROW_LAST_MEMBER = 3 };
+
+__global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t row_groups, uint32_t tile_groups, uint32_t rows_per_group) {
+    __shared__ uint64_t s_dst[ROWS_MAX], s_src[ROWS_MAX];         // where the row's bytes go in the file; where they come from (rows / in)
+    __shared__ uint32_t s_len[ROWS_MAX], s_m[ROWS_MAX], s_kind[ROWS_MAX];      // the bytes taken from there; |M_b|
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t E = (uint32_t)a.nentries;
+    const bool write = a.w.head[H_WRITE] != 0u;                   // (uniform over the grid)
+    if (blockIdx.x < row_groups) {
+        // ---- rows
+        if (!write) return;
+        // every wave looks up and copies its own quarter of the group's rows: no wave waits for another's loads
+        const uint32_t per = rows_per_group / 4u, w0 = wave * per;          // 4 or 64 rows a wave
+        const uint64_t b0 = (uint64_t)blockIdx.x * rows_per_group + w0;      // the wave's first row
+        {
+            // the entry of the wave's first row by the whole wave; the rows behind it lie in that entry or in one of the next 64,
+            // which one round of loads shows (a lane whose row lies further on -- many entries without rows -- searches alone)
+            const uint32_t ub0 = wave_upper_bound(a.blk_first, E + 1u, b0, lane);       // F_{ub0 - 1} <= b0 < F_{ub0}
+            const uint64_t next = ub0 + lane <= E ? a.blk_first[ub0 + lane] : ~0ull;
+            uint32_t ub = ub0;
+            for (uint32_t r = 0; r < per; r++) {
+                const uint32_t c = (uint32_t)__builtin_popcountll(ballot64(next <= b0 + r));
+                if (lane == r) ub = ub0 + c;
+            }
+            const uint64_t b = b0 + lane;
+            uint32_t kind = ROW_SKIP;
+            if (lane < per && b < a.nblocks) {
+                if (ub == ub0 + 64u) ub = upper_bound(a.blk_first, E + 1u, b);
+                if (ub >= 1u && ub <= E) {                        // (else: a row that no entry owns)
+                    const uint32_t e = ub - 1u;
+                    const uint64_t F0 = a.blk_first[e], skip = a.in_off[b] - a.in_off[F0];      // skip: the entry's bytes in front of this block
+                    if ((a.w.form[e] & 0xFFu) != METHOD_DEFLATED) {
+                        kind = ROW_STORED;                        // a stored entry that has rows: the block's input bytes
+                        s_dst[w0 + lane] = a.w.pay[e] + skip; s_src[w0 + lane] = a.ent_off[e] + skip;
+                        s_len[w0 + lane] = (uint32_t)(a.in_off[b + 1u] - a.in_off[b]); s_m[w0 + lane] = 0u;
+                    } else {
+                        uint32_t bl;
+                        const uint32_t m = member_len(a, b, bl);
+                        kind = b + 1u == a.blk_first[ub] ? ROW_LAST_MEMBER : ROW_MEMBER;
+                        s_dst[w0 + lane] = a.w.pay[e] + (a.w.pre[b] - a.w.pre[F0]); s_src[w0 + lane] = b * a.pitch + 2u;
+                        s_len[w0 + lane] = bl; s_m[w0 + lane] = m;
+                    }
+                }
+            }
+            if (lane < per) s_kind[w0 + lane] = kind;
+        }
+        wave_lds_order();                                         // (the wave reads only what it wrote itself)
+        {
+            for (uint32_t r = w0; r < w0 + per; r++) {
+                const uint32_t kind = s_kind[r];
+                if (kind == ROW_SKIP) continue;
+                if (kind == ROW_STORED) {
+                    copy_to_aligned16(a.file + s_dst[r], a.in + s_src[r], s_len[r], lane, 64u);
+                    continue;
+                }
+                const uint32_t bl = s_len[r], m = s_m[r];
+                const uint32_t rn = m + (kind == ROW_LAST_MEMBER ? 2u : 0u);
+                const uint8_t* __restrict__ src = a.rows + s_src[r];
+                uint8_t* __restrict__ dst = a.file + s_dst[r];
+                const uint32_t head = min(rn, (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u));
+                if (lane < head) dst[lane] = member_byte(src, lane, bl, m);
+                const uint32_t body = bl > head ? (bl - head) >> 4 : 0u;      // whole 16-byte chunks of the row's bytes: no load leaves row[2 .. nbytes)
+                const uint8_t* s16 = src + head;
+                uint8_t* d16 = dst + head;
+                uint32_t k = lane;
+                for (; k + 192u < body; k += 256u) {              // four loads in flight a lane
+                    v4 x0 = *reinterpret_cast<const v4u*>(s16 + 16u * k), x1 = *reinterpret_cast<const v4u*>(s16 + 16u * (k + 64u));
+                    v4 x2 = *reinterpret_cast<const v4u*>(s16 + 16u * (k + 128u)), x3 = *reinterpret_cast<const v4u*>(s16 + 16u * (k + 192u));
+                    if (head == 0u && k == 0u) x0.x &= ~1u;       // (the member starts at a 16-byte boundary: BFINAL sits in the body)
+                    *reinterpret_cast<v4*>(d16 + 16u * k) = x0; *reinterpret_cast<v4*>(d16 + 16u * (k + 64u)) = x1;
+                    *reinterpret_cast<v4*>(d16 + 16u * (k + 128u)) = x2; *reinterpret_cast<v4*>(d16 + 16u * (k + 192u)) = x3;
+                }
+                for (; k < body; k += 64u) {
+                    v4 x = *reinterpret_cast<const v4u*>(s16 + 16u * k);
+                    if (head == 0u && k == 0u) x.x &= ~1u;
+                    *reinterpret_cast<v4*>(d16 + 16u * k) = x;
+                }
+                const uint32_t done = head + 16u * body;          // at most 15 bytes of the row, the marker and 03 00 are left
+                if (done + lane < rn) dst[done + lane] = member_byte(src, done + lane, bl, m);
+            }
+        }
+        return;
+    }
+    if (blockIdx.x < row_groups + tile_groups) {
+        // ---- tiles of the stored entries without rows
+        __shared__ uint32_t s_e;
+        const uint64_t ntiles = a.w.head[H_TILES];                // (0 unless the file is written)
+        for (uint64_t t = blockIdx.x - row_groups; t < ntiles; t += tile_groups) {
+            if (tid == 0u) s_e = upper_bound(a.w.tile0, E + 1u, t) - 1u;      // tile0[e] <= t < tile0[e + 1]
+            __syncthreads();
+            const uint32_t e = s_e;
+            const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], at = (t - a.w.tile0[e]) * STORE_TILE;
+            const uint32_t n = u - at < STORE_TILE ? (uint32_t)(u - at) : STORE_TILE;
+            copy_to_aligned16(a.file + a.w.pay[e] + at, a.in + a.ent_off[e] + at, n, tid, 256u);
+            __syncthreads();                                      // (s_e has been read)
+        }
+        return;
+    }
+    // ---- entries: the two headers, the name behind both, the record
+    const uint32_t e = (blockIdx.x - row_groups - tile_groups) * 4u + wave;
+    if (e >= E) return;
+    const uint32_t form = a.w.form[e], method = form & 0xFFu, csize = a.w.csize[e], crc = a.crc[e];
+    const uint32_t usize = (uint32_t)(a.ent_off[e + 1u] - a.ent_off[e]), n = (uint32_t)(a.name_off[e + 1u] - a.name_off[e]);
+    const uint64_t pay = a.w.pay[e], L = pay - LOCREC - n, cd = a.w.cdrec[e];
+    if (a.entries && lane == 0u) {
+        hdlz_zip_entry rec;
+        const bool sound = a.w.head[H_FAILED] == 0u;
+        rec.cd_off = sound ? cd : 0u; rec.payload_off = sound ? pay : 0u; rec.out_off = sound ? a.w.out_off[e] : 0u;
+        rec.csize = sound ? csize : 0u; rec.usize = sound ? usize : 0u; rec.crc = sound ? crc : 0u;
+        rec.method = (uint16_t)(sound ? method : 0u); rec.flags = (uint16_t)(sound ? a.flags : 0u); rec.name_len = (uint16_t)(sound ? n : 0u);
+        rec.reserved = 0u;
+        rec.status = form >> 8;
+        a.entries[e] = rec;
+    }
+    if (!write) return;
+    const uint32_t time = a.datetime & 0xFFFFu, date = a.datetime >> 16;
+    const uint32_t lw[8] = {SIG_LOCAL, VERSION | (a.flags << 16), method | (time << 16), date | (crc << 16), (crc >> 16) | (csize << 16),
+                            (csize >> 16) | (usize << 16), (usize >> 16) | (n << 16), 0u};
+    const uint32_t cw[12] = {SIG_CD, VERSION | (VERSION << 16), a.flags | (method << 16), time | (date << 16), crc, csize, usize, n, 0u, 0u,
+                             (uint32_t)L << 16, (uint32_t)L >> 16};
+    if (lane < LOCREC) a.file[L + lane] = record_byte(lw, lane);
+    if (lane < CDREC) a.file[cd + lane] = record_byte(cw, lane);
+    const uint8_t* name = a.names + a.name_off[e];
+    copy_to_aligned16(a.file + L + LOCREC, name, n, lane, 64u);
+    copy_to_aligned16(a.file + cd + CDREC, name, n, lane, 64u);
+}
+
+}  // namespace zipw
+
+// the scratch, in this order, every piece a multiple of 256 bytes (include/hdlz_zip_write.h states the sum)
+static ZipWriteWork zip_write_work(void* work, uint64_t nentries, uint64_t nblocks, size_t* bytes) {
+    const uintptr_t base = reinterpret_cast<uintptr_t>(work);
+    const uint64_t ntiles = join_tiles(nblocks);
+    size_t at = 0;
+    auto piece = [&](size_t n) { const uintptr_t p = base + at; at += round256(n); return p; };
+    ZipWriteWork w;
+    w.ticket = reinterpret_cast<uint32_t*>(piece(8u + 16u * (size_t)ntiles));
+    w.desc = reinterpret_cast<unsigned long long*>(w.ticket + 2);
+    w.desc2 = w.desc + ntiles;
+    w.pre = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nblocks + 1u)));
+    w.cnt = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nblocks + 1u)));
+    w.head = reinterpret_cast<uint64_t*>(piece(256u));
+    w.pay = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nentries + 1u)));
+    w.cdrec = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nentries + 1u)));
+    w.out_off = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nentries + 1u)));
+    w.csize = reinterpret_cast<uint32_t*>(piece(4u * ((size_t)nentries + 1u)));
+    w.form = reinterpret_cast<uint32_t*>(piece(4u * ((size_t)nentries + 1u)));
+    w.tile0 = reinterpret_cast<uint32_t*>(piece(4u * ((size_t)nentries + 1u)));
+    *bytes = at;
+    return w;
+}
+
+size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks) {
+    size_t bytes;
+    (void)zip_write_work(nullptr, nentries, nblocks, &bytes);
+    return bytes;
+}
+
+hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream) {
+    using namespace zipw;
+    size_t bytes;
+    a.w = zip_write_work(work, a.nentries, a.nblocks, &bytes);
+    const uint64_t ntiles = join_tiles(a.nblocks);
+    hipError_t e = hipSuccess;
+    if (ntiles) {
+        e = zero_words(a.w.ticket, (uint32_t)(2u + 4u * ntiles), stream);      // the ticket and both look-back words of every tile
+        if (e == hipSuccess) e = launch(k_zipw_scan, dim3((unsigned)ntiles), dim3(JT), stream, a);
+    }
+    if (e == hipSuccess) e = launch(k_zipw_plan, dim3(1), dim3(PLAN_THREADS), stream, a);
+    if (e != hipSuccess) return e;
+    // the gather's three kinds of workgroup, every count from what the host knows
+    // rows a workgroup: 16 keep every CU busy with a few thousand large rows; with many small ones 64 spread the search over more rows
+    const uint32_t rows_per_group = a.nblocks >= ROWS_MANY_MIN ? ROWS_MAX : ROWS_FEW;
+    const uint64_t row_groups = (a.nblocks + rows_per_group - 1u) / rows_per_group;
+    uint64_t tile_groups = a.nentries ? a.total_in / STORE_TILE + a.nentries : 0u;      // (an entry ends in at most one partial tile)
+    if (tile_groups > (1u << 17)) tile_groups = 1u << 17;
+    const uint64_t entry_groups = (a.nentries + 3u) / 4u;
+    if (row_groups + tile_groups + entry_groups == 0u) return hipSuccess;
+    return launch(k_zipw_gather, dim3((unsigned)(row_groups + tile_groups + entry_groups)), dim3(256), stream, a, (uint32_t)row_groups, (uint32_t)tile_groups, rows_per_group);
+}
+
+}  // namespace hdlz

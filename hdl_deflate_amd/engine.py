@@ -627,6 +627,128 @@ class Engine(object):
                 worst = int(st[k])
         return (worst if worst != OK else index.record.status), files
 
+    # -- ZIP archives written on the device (include/hdlz_zip_write.h)
+    ZIP_CRC_TILED_MIN = 1 << 17   # an entry of at least this many bytes gets a hdlz_crc32_ws call of its own
+
+    @_on_device
+    def compress_zip(self, d_in, entry_lengths, names, block=1 << 16, cwindow=32, maxmatch=10, store=None, out=None,
+                     date_time=(1980, 1, 1, 0, 0, 0), out_align=1):
+        """d_in: flat uint8 device tensor, the entries' bytes one behind the other; entry_lengths: their lengths, a host sequence;
+        names: their names (str, written as UTF-8 -- flag bit 11 is set when one of them is not ASCII -- or bytes)
+        -> (file uint8[file_len], ZipIndex): a ZIP archive that zipfile, unzip and numpy.load read, and its index as zip_index would
+        return it (out_align: what its slots' starts are multiples of) -- the file is not indexed again.  Every entry of at least 5
+        bytes is cut into blocks of `block` bytes (chain.plan_blocks), ALL blocks of all entries are compressed in one ragged
+        hdlz_compress_batch_bits, and hdlz_zip_write_ws writes every entry deflated or stored, whichever is shorter; an entry under 5
+        bytes, or one with store[e] true, gets no blocks and is stored.  The CRC-32 of the entries is taken on the same stream
+        (crc32_batch; an entry of at least ZIP_CRC_TILED_MIN bytes by crc32, the whole GPU).  date_time: (year, month, day, hour,
+        minute, second) of every entry.  `out`: the file's buffer (default: hdlz_zip_write_bound bytes).  One host sync (the record,
+        with the entries' records behind it); raises HdlzStatusError -- with .first_bad, the lowest failed entry -- on a status that
+        is not OK."""
+        from .zip import ZipIndex, ENTRY_DTYPE, decode_name
+        import numpy as np
+        z = self._zip_batch(d_in, entry_lengths, names, block, cwindow, maxmatch, store)
+        if out is None:
+            out = torch.empty(self.lib.hdlz_zip_write_bound(z.E, z.B, block, z.total, z.names.numel()), dtype=torch.uint8, device=d_in.device)
+        rec, res, back = self._zip_write(z, out, date_time, out_align)
+        _raise_unless_ok(rec, "compress_zip")
+        host = np.frombuffer(back.tobytes(), dtype=ENTRY_DTYPE)
+        total_out = int(host["out_off"][-1]) + int(host["usize"][-1]) if z.E else 0
+        record = _lib.ZipIndexResult(z.E, total_out, rec.cd_off, rec.cd_size, OK, 0)
+        index = ZipIndex(res.view(z.E, 6), record, host, [n if isinstance(n, str) else decode_name(n, z.flags) for n in names], out_align)
+        index.write_record = rec
+        return out[:rec.file_len], index
+
+    def _zip_batch(self, d_in, entry_lengths, names, block, cwindow, maxmatch, store):
+        """what hdlz_zip_write_ws is given, on the device: the index arrays and the names (one staged copy), the CRC-32 of every entry,
+        the rows of ONE hdlz_compress_batch_bits over all blocks of all entries -> a namespace of them (E entries, B blocks)"""
+        from types import SimpleNamespace
+        from .chain import plan_blocks
+        from .zip import FLAG_UTF8
+        import numpy as np
+        self._is_bytes(d_in, "d_in", flat=True)
+        lens = [int(x) for x in entry_lengths]
+        E, total, dev = len(lens), d_in.numel(), d_in.device
+        names = list(names)
+        if len(names) != E or (store is not None and len(store) != E):
+            raise ValueError("%d entries, %d names%s" % (E, len(names), "" if store is None else ", %d store flags" % len(store)))
+        if min(lens, default=0) < 0 or sum(lens) != total:
+            raise ValueError("the entries' lengths add up to %d bytes, d_in holds %d" % (sum(lens), total))
+        if E > 65535:
+            raise ValueError("%d entries: a ZIP without ZIP64 holds at most 65535" % E)
+        if not 32 <= block < (1 << 31):
+            raise ValueError("block must be in [32, 2^31)")
+        raw = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
+        flags = FLAG_UTF8 if any(not r.isascii() for r in raw) else 0
+        # the block plan: per entry chain.plan_blocks, none for an entry under 5 bytes or one that is to be stored
+        ent_off, name_off, blk_first, in_off, blocked = [0], [0], [0], [0], []
+        for e, u in enumerate(lens):
+            ent_off.append(ent_off[-1] + u)
+            name_off.append(name_off[-1] + len(raw[e]))
+            if u >= 5 and not (store is not None and store[e]):
+                blocked.append(e)
+                for _, ln in plan_blocks(u, block):
+                    in_off.append(in_off[-1] + ln)
+            blk_first.append(len(in_off) - 1)
+        B = len(in_off) - 1
+        # every index array and the names in ONE staged copy: four arrays of 64-bit words, the names' bytes behind them
+        words = np.array(ent_off + name_off + blk_first + in_off, dtype=np.int64)
+        staged = torch.from_numpy(np.concatenate([words.view(np.uint8), np.frombuffer(b"".join(raw), np.uint8)])).to(dev)
+        idx = staged[:8 * words.size].view(torch.int64)
+        d_ent_off, d_name_off, d_blk_first, d_in_off = idx[:E + 1], idx[E + 1:2 * E + 2], idx[2 * E + 2:3 * E + 3], idx[3 * E + 3:]
+        # the CRC-32: runs of small entries in one crc32_batch each, a large entry by the tiled kernels into its own word
+        crc = torch.zeros(max(E, 1), dtype=torch.int32, device=dev).view(torch.uint32)      # (a run without bytes is not summed: its words stay 0)
+        e = 0
+        while e < E:
+            if lens[e] >= self.ZIP_CRC_TILED_MIN:
+                self.crc32(d_in[ent_off[e]:ent_off[e + 1]], out=crc[e:e + 1])
+                e += 1
+                continue
+            b = e
+            while e < E and lens[e] < self.ZIP_CRC_TILED_MIN:
+                e += 1
+            if ent_off[e] > ent_off[b]:
+                self.crc32_batch(d_in[ent_off[b]:ent_off[e]], offsets=d_ent_off[b:e + 1], out=crc[b:e])
+        # ONE ragged compress over all blocks of all entries; the blocked entries in a buffer of their own when others lie between them
+        pitch = pitch_for(block)
+        rows, out_len, status = self._results(None, (B, pitch), B, dev)
+        end_bits = torch.empty(B, dtype=torch.int64, device=dev)
+        if B:
+            cin = d_in if in_off[-1] == total else torch.cat([d_in[ent_off[k]:ent_off[k + 1]] for k in blocked])
+            cin = self._aligned_input(cin, in_off[-1])
+            rc = self.lib.hdlz_compress_batch_bits(cin.data_ptr(), d_in_off.data_ptr(), 0, block, B, cwindow, maxmatch, rows.data_ptr(), pitch,
+                                                   out_len.data_ptr(), status.data_ptr(), end_bits.data_ptr(), self._stream())
+            self._check(rc, "hdlz_compress_batch_bits")
+        return SimpleNamespace(E=E, B=B, total=total, flags=flags, d_in=d_in, ent_off=d_ent_off, names=staged[8 * words.size:], name_off=d_name_off,
+                               in_off=d_in_off, rows=rows, pitch=pitch, len=out_len, end_bits=end_bits, status=status, blk_first=d_blk_first, crc=crc,
+                               staged=staged)
+
+    def _zip_write(self, z, out, date_time, out_align):
+        """hdlz_zip_write_ws over a _zip_batch into `out` -> (the record, the entries' records int64[6 E] on the device, the same on the
+        host): the record and the entries' records stand in one tensor and come back in one copy, the call's one host sync"""
+        from .zip import dos_datetime
+        self._is_bytes(out, "out", flat=True)
+        nres = ctypes.sizeof(_lib.ZipWriteResult) // 8
+        res = torch.empty(nres + 6 * z.E, dtype=torch.int64, device=self.device)
+        scratch = self._scratch(self.lib.hdlz_zip_write_work_bytes(z.E, z.B), None)
+        ptr = lambda t: t.data_ptr() if z.B else None                    # (no blocks: the per-block arrays are null)
+        some = lambda t: t.data_ptr() if t.numel() else z.staged.data_ptr()   # (no byte of an empty buffer is read: any address will do)
+        rc = self.lib.hdlz_zip_write_ws(some(z.d_in), z.ent_off.data_ptr(), some(z.names), z.name_off.data_ptr(), z.E, ptr(z.in_off), ptr(z.rows),
+                                        z.pitch, ptr(z.len), ptr(z.end_bits), ptr(z.status), z.B, z.blk_first.data_ptr(), z.crc.data_ptr(), z.flags,
+                                        dos_datetime(date_time), out_align, z.total, out.data_ptr() if out.numel() else None, out.numel(),
+                                        res[nres:].data_ptr() if z.E else None, res.data_ptr(), scratch[1], scratch[2], self._stream())
+        self._check(rc, "hdlz_zip_write_ws")
+        back = res.cpu().numpy()
+        return _lib.ZipWriteResult.from_buffer_copy(back[:nres].tobytes()), res[nres:], back[nres:]
+
+    def write_zip_bytes(self, files, **kw):
+        """{name: bytes} -> the bytes of a ZIP archive holding them in that order, the counterpart of read_zip_bytes; the keywords of
+        compress_zip (block, cwindow, maxmatch, store, date_time) pass through"""
+        names = list(files)
+        data = [bytes(files[n]) for n in names]
+        d = self._stage(b"".join(data))[:sum(len(x) for x in data)]
+        out, _ = self.compress_zip(d, [len(x) for x in data], names, **kw)
+        return bytes(out.cpu().numpy().tobytes())
+
     # -- STARTC for ONE large stream, spread over the whole GPU (same bytes as compress_batch with one block)
     STREAM_MIN = 1 << 14          # measured crossover with the single-wave batch path: ~8 KiB
     LARGE_BLOCK, MANY_WAVES = 1 << 16, 1200   # compress_batch: up to this many blocks of at least this size -> stream passes

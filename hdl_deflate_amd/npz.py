@@ -1,5 +1,6 @@
-""".npz files (numpy.savez, numpy.savez_compressed) read into device tensors: the ZIP directory is indexed and every entry decoded and
-judged on the device (include/hdlz_zip.h); only the few header bytes of each .npy entry come to the host, no array byte does."""
+""".npz files (numpy.savez, numpy.savez_compressed) read into device tensors and written from them: the ZIP directory is indexed and
+every entry decoded and judged on the device (include/hdlz_zip.h), the file is written there (include/hdlz_zip_write.h); only the few
+header bytes of each .npy entry pass through the host, no array byte does."""
 import ast
 
 import numpy as np
@@ -101,3 +102,42 @@ def load_npz(engine, data):
             piece = piece.clone()                     # (a writer that does not align the data: a device copy, still no host byte)
         arrays[index.names[k][:-4]] = piece.view(dtype).reshape(shape)
     return arrays
+
+
+def _npy_descr(dtype):
+    """a torch dtype -> its .npy descr: the reverse of _torch_dtype's table; raises for a dtype that is not in it (bfloat16 is one)"""
+    import torch
+    table = {torch.bool: "|b1", torch.uint8: "|u1", torch.int8: "|i1", torch.int16: "<i2", torch.int32: "<i4", torch.int64: "<i8",
+             torch.float16: "<f2", torch.float32: "<f4", torch.float64: "<f8", torch.complex64: "<c8", torch.complex128: "<c16"}
+    if dtype not in table:
+        raise Error("save_npz: dtype %r has no .npy counterpart" % (dtype,))
+    return table[dtype]
+
+
+def save_npz(engine, arrays, compressed=True, **kw):
+    """{name: device tensor} -> a flat uint8 device tensor, the .npz file numpy.load and load_npz read (numpy.savez_compressed; with
+    compressed=False every entry is stored, as numpy.savez does).  Per tensor a .npy version 1.0 header is made on the host by numpy's
+    own writer -- a few bytes; all headers are staged in one copy --, the entry is that header and the tensor's bytes in C order, its
+    name `name + ".npy"`; the file is written by Engine.compress_zip, whose keywords (block, cwindow, maxmatch, date_time) pass
+    through.  No array byte crosses to the host."""
+    import io
+    import torch
+    names, tensors, heads = [], [], []
+    for name, t in arrays.items():
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == engine.device):
+            raise Error("save_npz: %r is not a tensor on %s" % (name, engine.device))
+        h = io.BytesIO()
+        np.lib.format.write_array_header_1_0(h, {"descr": _npy_descr(t.dtype), "fortran_order": False, "shape": tuple(t.shape)})
+        names.append(name + ".npy")
+        heads.append(h.getvalue())
+        flat = t.reshape(-1).contiguous()
+        tensors.append((torch.view_as_real(flat).reshape(-1) if flat.is_complex() else flat).view(torch.uint8))
+    staged = engine._stage(b"".join(heads))
+    pieces, lens, at = [], [], 0
+    for h, t in zip(heads, tensors):
+        pieces += [staged[at:at + len(h)], t]
+        lens.append(len(h) + t.numel())
+        at += len(h)
+    d_in = torch.cat(pieces) if pieces else torch.empty(0, dtype=torch.uint8, device=engine.device)
+    out, _ = engine.compress_zip(d_in, lens, names, store=None if compressed else [True] * len(names), **kw)
+    return out

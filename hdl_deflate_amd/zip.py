@@ -1,5 +1,6 @@
-"""Host side of include/hdlz_zip.h: the index of a ZIP file as Engine.zip_index returns it, the numpy view of its records and the
-decoding of entry names.  Nothing here computes on file data: the directory is indexed and the entries are read on the device."""
+"""Host side of include/hdlz_zip.h and hdlz_zip_write.h: the index of a ZIP file as Engine.zip_index and Engine.compress_zip return
+it, the numpy view of its records, the decoding of entry names and the date words of a header.  Nothing here computes on file data:
+the directory is indexed, the entries are read and the file is written on the device."""
 import numpy as np
 
 # hdlz_zip_entry, 48 bytes (little-endian, as the device writes it)
@@ -14,6 +15,14 @@ def decode_name(raw, flags):
     return raw.decode("utf-8") if flags & FLAG_UTF8 else raw.decode("cp437")
 
 
+def dos_datetime(date_time):
+    """(year, month, day, hour, minute, second) -> date << 16 | time, the MS-DOS words of a ZIP header (what hdlz_zip_write_ws takes)"""
+    y, mo, d, h, mi, s = (int(x) for x in date_time)
+    if not (1980 <= y <= 2107 and 1 <= mo <= 12 and 1 <= d <= 31 and 0 <= h < 24 and 0 <= mi < 60 and 0 <= s < 60):
+        raise ValueError("date_time %r is outside what a ZIP header holds (1980 .. 2107)" % (date_time,))
+    return ((y - 1980) << 9 | mo << 5 | d) << 16 | (h << 11 | mi << 5 | s >> 1)
+
+
 class ZipIndex(object):
     """The index of a ZIP file (Engine.zip_index).
     entries    int64[k, 6] on the device: the k records of hdlz_zip_index_ws (48 bytes each), what Engine.inflate_zip passes on
@@ -21,7 +30,10 @@ class ZipIndex(object):
     host       the records on the host, a numpy array of ENTRY_DTYPE (cd_off, payload_off, out_off, csize, usize, crc, method, flags,
                name_len, status)
     names      the entries' names, in the directory's order
-    out_align  what the slots' starts are multiples of"""
+    out_align  what the slots' starts are multiples of
+    write_record   an index that Engine.compress_zip hands back with the file it wrote: the writer's record (_lib.ZipWriteResult:
+               file_len, cd_off, cd_size, nstored, status, first_bad); None for an index that was read"""
+    write_record = None
 
     def __init__(self, entries, record, host, names, out_align):
         self.entries, self.record, self.host, self.names, self.out_align = entries, record, host, names, out_align

@@ -45,10 +45,10 @@
  * The record's status is that of step 1, else HDLZ_E_OUT_CAPACITY (step 5), else that of step 2; the statuses of step 3 stand in the
  * entries only.
  *
- * Out of scope: writing ZIP files; ZIP64 (the locator is refused, FFFFFFFF sizes and offsets fail the entry); encryption; methods other
- * than 0 and 8; self-extracting prefixes (offsets count from the file's first byte) and multi-disk archives; the lane and group mappings
- * of the batch decoders; several large entries on the whole-GPU path in one call (the caller makes one call per large entry:
- * Engine.inflate_zip does).
+ * Out of scope: writing ZIP files (hdlz_zip_write.h, the extension of this header, does); ZIP64 (the locator is refused, FFFFFFFF sizes
+ * and offsets fail the entry); encryption; methods other than 0 and 8; self-extracting prefixes (offsets count from the file's first
+ * byte) and multi-disk archives; the lane and group mappings of the batch decoders; several large entries on the whole-GPU path in one
+ * call (the caller makes one call per large entry: Engine.inflate_zip does).
  */
 #ifndef HDLZ_ZIP_H
 #define HDLZ_ZIP_H
