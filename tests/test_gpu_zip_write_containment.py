@@ -61,9 +61,11 @@ def write_call(engine, label, case, cap_delta=0, out_align=1, mis=(0, 0, 0, 0), 
         a.fill("len", np.array([len(r[0]) for r in rows], np.uint32).tobytes())
         a.fill("status", bytes(4 * B))
         a.fill("crc", np.array([en["crc"] for en in w.entries], np.uint32).tobytes())
+        image = a.view("rows").cpu().numpy().copy()              # the pattern, put back in ONE copy with the rows' bytes in it
         for b, (z, _, deflated) in enumerate(rows):
             if deflated:
-                a.fill("rows", z[2:len(z) - 4], b * pitch + 2)    # (78 9C, the Adler-32 and a stored entry's rows stay the pattern)
+                image[b * pitch + 2:b * pitch + len(z) - 4] = np.frombuffer(z[2:len(z) - 4], np.uint8)      # (78 9C, the Adler-32 and a stored entry's rows stay the pattern)
+        a.fill("rows", image)
 
     def call(a):
         rc = L.hdlz_zip_write_ws(a.ptr("in"), a.ptr("ent_off"), a.ptr("names"), a.ptr("name_off"), E, a.ptr("in_off") if B else None,
@@ -132,6 +134,14 @@ def test_tiles_of_rows_and_entry_counts(engine):
     big = dict(label="stored tiles", items=[("a", Z.noise(200000, 1)), ("b", b""), ("c", Z.noise(65536, 2)), ("d", Z.noise(65537, 3)), ("e", W.soft(5000, 4))],
                block=2048, store=[True, False, True, True, False])
     write_call(engine, "stored entries of several tiles", big, mis=(13, 2, 6, 11))
+
+
+def test_many_tiles_and_rowless_runs(engine):
+    """zip_write_ref.shape_cases(): 65536 rows -- 256 tiles of the scan, so pre[0 .. B], cnt[0 .. B] and the look-back words of more
+    than one window, and the gather with 256 rows a workgroup -- and the runs of entries without rows, where a lane searches alone;
+    a write outside the scratch passed, which the file's bytes cannot show, is a violation here"""
+    write_call(engine, "65536 rows", W.shape_case("65536 rows across the seams"), mis=(3, 5, 7, 9))
+    write_call(engine, "rowless runs", W.shape_case("rowless runs of 62 to 200 entries"), mis=(1, 7, 5, 3))
 
 
 def test_a_file_that_does_not_fit_is_not_begun(engine):

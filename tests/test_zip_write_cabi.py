@@ -134,9 +134,9 @@ def test_parameter_errors_come_before_the_device_in_their_order():
 LABELS = [c["label"] for c in W.all_cases()]
 
 
-@pytest.mark.parametrize("label", LABELS)
+@pytest.mark.parametrize("label", LABELS + list(W.SHAPE_LABELS))
 def test_the_reference_file_reads_as_the_rule_says(label):
-    case = {c["label"]: c for c in W.all_cases()}[label]
+    case = {c["label"]: c for c in W.all_cases()}.get(label) or W.shape_case(label)
     w = W.written(label)
     z, items = w.file, case["items"]
     zf = zipfile.ZipFile(io.BytesIO(z))
@@ -198,6 +198,129 @@ def test_the_cases_cover_what_they_are_meant_to():
     assert all(1 <= en["name_len"] <= 16 for en in w.entries) and len({en["name_len"] for en in w.entries}) > 8
     assert [en["name_len"] for en in W.written("names of 300 and 65535 bytes").entries] == [5, 300, 65535, 4]
     assert len(W.written("no entry").file) == 22 and W.written("65535 empty entries").record["nstored"] == 65535
+
+
+# ---- the shape cases: each one proved, from its arrays alone, to reach the branch of hdlz_zip_write.hip it is for.  The model of the
+# lookup (zip_write_ref.gather_lookup) judges the CASES; what the device must write is zip_write_ref.expected alone.
+def _lookup(label):
+    case = W.shape_case(label)
+    first, B = W.batch_arrays(case)
+    F = np.asarray(first, np.int64)
+    g = W.gather_lookup(F, B)
+    assert np.array_equal(g.entry, np.searchsorted(F, np.arange(B), side="right") - 1), label      # the lookup as modelled finds every row's entry
+    return case, F, B, g
+
+
+def test_the_model_of_the_wave_search_is_an_upper_bound():
+    import bisect
+    for n in list(range(1, 300)) + list(range(4095, 4162)) + [5000, 65535, 65536]:
+        v = np.sort(np.random.default_rng(n).integers(0, 3 * n, n)).astype(np.int64)
+        seen = set()
+        for x in (-1, 0, int(v[0]), int(v[n // 3]) - 1, int(v[n // 2]), int(v[-1]) - 1, int(v[-1]), int(v[-1]) + 1):
+            got, rounds = W.wave_upper_bound(v, x)
+            assert got == bisect.bisect_right(v.tolist(), x), (n, x)
+            seen.add(rounds)
+        assert seen <= ({1} if n <= 64 else {2} if n <= 4096 and n % 64 == 0 else {2, 3}) and max(seen) == (1 if n <= 64 else 2 if n <= 4096 else 3), (n, seen)
+
+
+def test_the_shape_cases_reach_the_branches_they_are_for():
+    k = W.kernel_constants()
+    assert k.ROWS_MAX == 4 * 64 and k.ROWS_FEW == 4 * 4 and k.JT == 256 and k.PLAN_THREADS == 16 * 64
+    assert len(W.SHAPE_LABELS) == len(set(W.SHAPE_LABELS)) == 14 and not set(W.SHAPE_LABELS) & {c["label"] for c in W.all_cases()}
+    soft, noise = W.alphabet()
+    assert len(soft) == 32 and len(noise) == 16 and {len(b) for b in soft + noise} == {32}
+
+    # -- search widths: E + 1 words in one round, in two, and in three where the second round is itself wider than 64
+    rounds = {}
+    for E in W.MANY:
+        case, F, B, g = _lookup("%d entries of 1 to 3 rows" % E)
+        w = W.written(case["label"])
+        assert len(case["items"]) == E and g.per == 4 and not g.fallback.any()
+        rows = np.diff(F)
+        assert set(rows.tolist()) == {0, 1, 2, 3} and 0 < np.count_nonzero(rows == 0) < E // 8
+        assert 0 in w.methods and 8 in w.methods and any(m == 0 and n for m, n in zip(w.methods, rows))      # stored without and with rows
+        rounds[E] = set(g.rounds.tolist())
+    assert rounds[63] == {1} and rounds[64] == {2} and rounds[4095] == {2} and rounds[1023] == rounds[1024] == rounds[1025] == rounds[2049] == {2}
+    assert rounds[4096] == {2, 3} and rounds[4097] == {2, 3}      # (two rounds: the waves whose first row lies in the partial last chunk)
+
+    # -- the ragged plan: per entries a thread, the threads that take all of them, the entries of the one thread that takes fewer
+    claimed = {63: (1, 63, 0), 64: (1, 64, 0), 1023: (1, 1023, 0), 1024: (1, 1024, 0), 1025: (2, 512, 1), 2049: (3, 683, 0), 4095: (4, 1023, 3),
+               4096: (4, 1024, 0), 4097: (5, 819, 2), 65535: (64, 1023, 63)}
+    for E, claim in claimed.items():
+        assert W.plan_share(E) == claim, E
+    for E in (1023, 1024, 1025, 2049, 4095, 4096, 4097):
+        w = W.written("%d entries of 1 to 3 rows" % E)
+        per = claimed[E][0]
+        size = np.array([30 + en["name_len"] + en["csize"] for en in w.entries] + [0] * (k.PLAN_THREADS * per - E), np.int64)
+        threads = size.reshape(k.PLAN_THREADS, per).sum(axis=1)
+        waves = threads.reshape(16, 64).sum(axis=1)
+        busy = -(-E // per)                                      # the threads that take an entry; neighbours leave different partial sums
+        assert np.count_nonzero(np.diff(threads[:busy])) > 0.8 * busy and busy > 64 and np.diff(waves[:-(-busy // 64)]).all(), E
+    # the entries the failure tests fail: with rows, in three waves of the plan, the last one in the ragged last thread
+    case, F, B, g = _lookup("4097 entries of 1 to 3 rows")
+    assert all(F[e + 1] > F[e] for e in W.FAIL_ENTRIES)
+    assert [e // 5 // 64 for e in W.FAIL_ENTRIES] == [1, 2, 12, 12] and W.FAIL_ENTRIES[3] // 5 == claimed[4097][1] and W.FAIL_ENTRIES[3] == 4097 - 1
+
+    # -- rowless runs: the lone search exactly from 63 entries between two rows of a wave on
+    case, F, B, g = _lookup("rowless runs of 62 to 200 entries")
+    assert g.per == 4
+    e, positions = 0, set()
+    for R in W.RUNS:
+        for n in W.RUN_ROWS:
+            front, behind = int(F[e]) + n - 1, int(F[e]) + n      # the rows in front of and behind the run
+            assert F[e] % 4 == 0 and F[e + 1] - F[e] == n and (np.diff(F[e + 1:e + R + 2]) == 0).all() and F[e + R + 2] > F[e + R + 1] == behind
+            assert {len(d) for _, d in case["items"][e + 1:e + R + 1]} == {0, 3, 40} and set(case["store"][e + 1:e + 4]) == {False, True}
+            positions.add(front % 4)
+            same_wave = front // 4 == behind // 4
+            assert same_wave == (n < 4)
+            assert bool(g.fallback[behind]) == (same_wave and R >= 63), (R, n)
+            assert g.fallback[behind:int(F[e + R + 2])].all() == bool(g.fallback[behind]) and g.entry[behind] == e + R + 1
+            e += R + 2
+    assert positions == {0, 1, 2, 3} and e == len(case["items"]) and int(g.fallback.sum()) == 4 * (3 + 2 + 1)
+    assert 8 in W.written(case["label"]).methods
+
+    # -- the dispatch seam: the same entries at 65535 rows (16 a workgroup) and at 65536 (256 a workgroup, 64 a wave)
+    for n, group in ((65535, k.ROWS_FEW), (65536, k.ROWS_MAX)):
+        case, F, B, g = _lookup("%d rows across the seams" % n)
+        w = W.written(case["label"])
+        assert B == n and g.rows_per_group == group and g.per == group // 4
+        assert (n >= k.ROWS_MANY_MIN) == (n == 65536) and B % group == (0 if n == 65536 else 15)      # (65535: a partial last group)
+        assert -(-B // k.JT) > 128                               # tiles: the look-backs go on past their first window of 64, twice
+        assert [d[:32 * 100] for _, d in case["items"][:12]] == [d[:32 * 100] for _, d in W.shape_case("65535 rows across the seams")["items"][:12]]
+        assert set((F % 64).tolist()) >= {0, 1} and set((F % 256).tolist()) >= {0, 1} and any(f // k.JT > 64 for f in F[:-1])
+        spans = lambda e, step: (F[e] // step + 1) * step < F[e + 1]
+        stored = [e for e in range(len(F) - 1) if w.methods[e] == 0 and F[e + 1] > F[e]]
+        assert len(stored) >= 2 and [W.SEAM_FORMS[e] for e in stored] == ["n"] * len(stored)
+        assert any(spans(e, k.JT) and spans(e, group) and F[e + 1] - F[e] > 32 * k.JT for e in stored)      # stored with rows, over many tiles and groups
+        assert any(W.SEAM_FORMS[e] == "m" and w.methods[e] == 8 and F[e + 1] - F[e] > 64 * k.JT for e in range(len(F) - 1))
+        assert {p >= 3 for p in w.pads} == {False, True}         # both marker lengths among the members of deflated entries
+    # the rows the failure tests tamper with: in entries of many tiles, away from their ends, behind tile 64 and behind tile 128
+    (e1, b1), (e2, b2) = W.SEAM_STATUS, W.SEAM_CONTRADICTION
+    assert e1 < e2 and F[e1] + 1024 < b1 < F[e1 + 1] - 1024 and F[e2] + 1024 < b2 < F[e2 + 1] - 1024
+    assert b1 // k.JT > 64 and b2 // k.JT > 128 and F[e1] // k.JT < 64 < 128 < F[e2] // k.JT      # cnt[F1] - cnt[F0] across look-back windows
+    assert all(F[e + 1] > F[e] for e in (e1 - 1, e1 + 1, e2 - 1, e2 + 1))
+    assert w.methods[e1] == 0 and w.methods[e2] == 8
+
+    # -- many entries and many rows at once: three rounds and the lone search with 64 rows a wave, per = 64 in the plan
+    case, F, B, g = _lookup("65535 entries and more rows")
+    w = W.written(case["label"])
+    rows = np.diff(F)
+    assert len(case["items"]) == 65535 and B >= k.ROWS_MANY_MIN and g.per == 64 and 3 in set(g.rounds.tolist())
+    assert set(rows.tolist()) == {0, 1, 2, 3}
+    with_rows = sum(1 for m, n in zip(w.methods, rows) if m == 0 and n)
+    assert 65535 // 12 < with_rows < 65535 // 5 and w.methods.count(8) > 30000
+    lo, hi = W.MANY_ROWS_RUN[0], sum(W.MANY_ROWS_RUN)
+    assert not rows[lo:hi].any() and rows[lo - 1] and rows[hi]
+    assert (F[lo] - 1) // 64 == F[hi] // 64 and g.fallback[F[hi]] and g.entry[F[hi]] == hi      # the rows on either side of the run in one wave
+    assert {p >= 3 for p in w.pads} == {False, True}
+
+    # -- stored tiles among many entries: the tiles' search runs over a prefix in which most entries have one tile or none
+    case, F, B, g = _lookup("stored tiles among 300 entries")
+    w = W.written(case["label"])
+    tiles = [-(-len(d) // k.STORE_TILE) if F[e + 1] == F[e] else 0 for e, (_, d) in enumerate(case["items"])]
+    assert len(tiles) == 300 and tiles.count(0) > 30 and tiles.count(1) > 150 and sorted(t for t in tiles if t > 1) == [2, 4]
+    assert sorted(len(d) for (_, d), s in zip(case["items"], case["store"]) if s) == list(W.BIG_STORED)
+    assert w.methods.count(8) == 3 and B > 3 and case["block"] == 2048
 
 
 def test_numpy_loads_the_reference_npz():

@@ -1,6 +1,8 @@
 """What hdlz_zip_write_ws and Engine.compress_zip must answer (a helper module like zip_ref.py, not a conftest): THE FILE RULE of
 include/hdlz_zip_write.h as a serial text in plain Python, built from joined_ref.member_of (the CPU oracle's rows, the end bit and the
-marker) and zlib.crc32 -- never from device output --, and the case lists the CPU and the GPU tests share.
+marker) and zlib.crc32 -- never from device output --, and the case lists the CPU and the GPU tests share: all_cases(), thorough
+about the format and small, and shape_cases(), large in what the kernels branch on, with a model of the gather's row lookup that
+proves which branch a case reaches.
 tests/test_zip_write_cabi.py holds this rule against zipfile, numpy.load and the index rule of zip_ref.py on every case."""
 import functools
 import io
@@ -184,8 +186,211 @@ def all_cases():
 
 @functools.lru_cache(maxsize=None)
 def written(label, out_align=1):
-    c = {c["label"]: c for c in all_cases()}[label]
+    c = {c["label"]: c for c in all_cases()}.get(label) or shape_case(label)
     return expected(c["items"], block=c["block"], store=c["store"], out_align=out_align)
+
+
+# ---- the shapes: cases that are large in what the kernels of hdlz_zip_write.hip BRANCH on -- entries, rows, rowless runs, tiles --,
+# kept out of all_cases().  Their entries are concatenations of a few dozen blocks of 32 bytes, so member_of, which caches by content,
+# meets every row of every case after the first few dozen calls; an entry's length is a multiple of 32, so plan_blocks cuts it at
+# the alphabet's blocks.
+@functools.lru_cache(maxsize=None)
+def alphabet():
+    """(32 soft blocks, 16 noise blocks) of 32 bytes: members of 20 to 23 and of 39 to 41 bytes, pad bits 1 to 7 among them -- an
+    entry of soft blocks alone is deflated, one of noise blocks alone is stored with its rows"""
+    return tuple(soft(32, 9000 + k) for k in range(32)), tuple(Z.noise(32, 9100 + k) for k in range(16))
+
+
+def of_blocks(r, k, form):
+    """an entry of k alphabet blocks drawn with the generator r; form "s": soft, "n": noise, "m": mixed, a noise block in five"""
+    s, n = alphabet()
+    noisy = {"s": np.zeros(k, bool), "n": np.ones(k, bool), "m": r.integers(0, 5, k) == 0}[form]
+    pick = r.integers(0, 1 << 16, k)
+    return b"".join(n[p % len(n)] if q else s[p % len(s)] for p, q in zip(pick.tolist(), noisy.tolist()))
+
+
+def _name(e):
+    return "abcde"[:e % 6] + "%d" % e                            # (unique, 1 to 10 bytes: the records' sizes vary from entry to entry)
+
+
+ROWLESS = (b"", b"abc", soft(40, 77))                            # entries without rows: empty, under 5 bytes, store=True
+
+
+def _rowless(items, store, k):
+    items.append((_name(len(items)), ROWLESS[k % 3]))
+    store.append(k % 3 == 2)
+
+
+def many_entries(E, seed, rows=(1, 2, 3), weights=None, run=None):
+    """E entries of 1 to 3 rows (or of `rows`, drawn with `weights`), about one in 8 of them noise and one in 8 mixed, and about one
+    in 16 without rows; run = (entry, length): from that entry on `length` entries without rows, one with rows on either side"""
+    r = np.random.default_rng(seed)
+    nrows = r.choice(rows, E, p=weights).tolist()
+    kind = r.integers(0, 16, E).tolist()
+    lo, hi = (run[0], run[0] + run[1]) if run else (E, E)
+    items, store = [], []
+    for e in range(E):
+        beside = e in (lo - 1, hi)
+        k = max(nrows[e], 1) if beside else nrows[e]
+        if lo <= e < hi or k == 0 or (kind[e] == 0 and not beside and e not in FAIL_ENTRIES):
+            _rowless(items, store, e)
+        else:
+            items.append((_name(e), of_blocks(r, k, "n" if kind[e] in (1, 2) else "m" if kind[e] in (3, 4) else "s")))
+            store.append(False)
+    return items, store
+
+
+MANY = (63, 64, 4095, 4096, 4097, 1023, 1024, 1025, 2049)       # E + 1 around 64 and 4096 for the search, E around 1024 k for the plan
+FAIL_ENTRIES = (330, 700, 4000, 4096)                            # the entries the failure tests at E = 4097 tamper with: they have rows
+RUNS, RUN_ROWS = (62, 63, 64, 65, 200), (1, 2, 3, 4)
+SEAM_ROWS = (1, 255, 256, 257, 63, 64, 65, 4096, 16383, 16385, 20000, 3000, 5000, 2, 2)
+SEAM_FORMS = "ssmnsnsmnsmnsss"
+SEAM_STATUS, SEAM_CONTRADICTION = (8, 20000), (10, 50000)       # (entry, row) the failure tests at 65536 rows tamper with
+MANY_ROWS_RUN = (30000, 100)                                     # the run of rowless entries in the 65535-entry case
+BIG_STORED = (65535, 65536, 65537, 3 * 65536 + 1)
+SHAPE_LABELS = tuple("%d entries of 1 to 3 rows" % E for E in MANY) + ("rowless runs of 62 to 200 entries", "65535 rows across the seams",
+                                                                       "65536 rows across the seams", "65535 entries and more rows",
+                                                                       "stored tiles among 300 entries")
+LARGE_SHAPES = SHAPE_LABELS[-3:-1]                               # the two cases that take 256 rows a workgroup
+
+
+@functools.lru_cache(maxsize=None)
+def shape_case(label):
+    """one case of SHAPE_LABELS, built when it is asked for (the labels alone cost nothing at collection)"""
+    at = SHAPE_LABELS.index(label)
+    if at < len(MANY):
+        # search widths: E + 1 = 64 words are one round of wave_upper_bound, 65 two (chunk = 2), 4096 two, 4097 and 4098 three
+        # (chunk = 65: the second round is wider than 64 again).  ragged plan: per = ceil(E / 1024) entries a thread of k_zipw_plan,
+        # a last thread with fewer at 1025, 4095 and 4097, none ragged at 1023, 1024, 2049 and 4096
+        items, store = many_entries(MANY[at], 9200 + at)
+        return _case(label, items, store=store)
+    if label.startswith("rowless"):
+        # the lone binary search of the gather: a row whose entry lies 64 or more entries behind the wave's first row's.  Every triple
+        # -- an entry of k rows, R entries without rows, an entry of rows -- starts at a wave's first row (4 rows a wave), so the row
+        # in front of the run stands at position k - 1 and, for k < 4, the row behind the run in the same wave: 63 or more entries
+        # lie between them from R = 63 on
+        r = np.random.default_rng(9300)
+        items, store = [], []
+        for R in RUNS:
+            for k in RUN_ROWS:
+                items.append((_name(len(items)), of_blocks(r, k, "sn"[k % 2])))
+                store.append(False)
+                for j in range(R):
+                    _rowless(items, store, j)
+                items.append((_name(len(items)), of_blocks(r, (4 - k) or 4, "sm"[R % 2])))
+                store.append(False)
+        return _case(label, items, store=store)
+    if label.endswith("rows across the seams"):
+        # the dispatch seam ROWS_MANY_MIN: the same entries cut to 65535 rows (16 rows a workgroup) and to 65536 (256 rows, 64 a wave);
+        # entries begin on and beside wave, group and tile seams, three are noise (stored with rows over many tiles and groups)
+        n = int(label.split()[0])
+        r = np.random.default_rng(9400)
+        data = [of_blocks(r, k, f) for k, f in zip(SEAM_ROWS, SEAM_FORMS)]
+        items, left = [], n
+        for e, d in enumerate(data):
+            if left:
+                items.append((_name(e), d[:32 * min(left, SEAM_ROWS[e])]))
+                left -= min(left, SEAM_ROWS[e])
+        return _case(label, items)
+    if label.startswith("65535 entries"):
+        # many entries and many rows at once: three rounds of the search with 64 rows a wave, per = 64 in the plan, and one run of 100
+        # rowless entries so that the lone search is reached with 64 rows a wave, too
+        items, store = many_entries(65535, 9500, rows=(0, 1, 2, 3), weights=(0.15, 0.5, 0.25, 0.1), run=MANY_ROWS_RUN)
+        return _case(label, items, store=store)
+    # stored tiles among many entries: the `tiles` workgroups search tile0[0 .. E] of about 300 entries, most of them of one tile or of
+    # none.  (Their strided path needs more than 2^17 tiles, 8 GiB of stored entries: out of reach at test size, and not tested.)
+    r = np.random.default_rng(9600)
+    kind = r.integers(0, 8, 300).tolist()
+    items, store = [], []
+    for e in range(300):
+        big = {40: 0, 41: 1, 150: 2, 299: 3}.get(e)
+        if big is not None:
+            items.append((_name(e), Z.noise(BIG_STORED[big], 9600 + e)))
+        elif e in (3, 100, 298):
+            items.append((_name(e), soft(3000 + 1111 * (e % 7), 9600 + e)))       # deflated, with rows
+        else:
+            items.append((_name(e), b"wxyz"[:kind[e] % 4 + 1] if kind[e] < 6 else b""))
+        store.append(big is not None)
+    return _case(label, items, block=2048, store=store)
+
+
+def shape_cases():
+    return [shape_case(label) for label in SHAPE_LABELS]
+
+
+# ---- a model of the gather's row lookup, for the CPU test that proves from a case's arrays which branch the case reaches.  It
+# asserts the CASES, never the device: what the file must be comes from expected() alone.
+@functools.lru_cache(maxsize=None)
+def kernel_constants():
+    """the constants of hdlz_zip_write.hip and hdlz_frame.h the regimes hang on, read out of the source text"""
+    import os
+    import re
+    from types import SimpleNamespace
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hdl_deflate_amd", "csrc")
+    found = {}
+    for name, path in (("ROWS_FEW", "hdlz_zip_write.hip"), ("ROWS_MAX", "hdlz_zip_write.hip"), ("ROWS_MANY_MIN", "hdlz_zip_write.hip"),
+                       ("PLAN_THREADS", "hdlz_zip_write.hip"), ("STORE_TILE", "hdlz_zip_write.hip"), ("JT", "hdlz_frame.h")):
+        m = re.findall(r"\b%s\s*=\s*([0-9u< ]+?)\s*[,;]" % name, open(os.path.join(csrc, path)).read())
+        assert len(m) == 1, (name, m)
+        expr = m[0].replace("u", "")
+        assert re.fullmatch(r"[0-9]+( << [0-9]+)?", expr), (name, m[0])
+        found[name] = eval(expr, {"__builtins__": {}})
+    return SimpleNamespace(**found)
+
+
+def wave_upper_bound(v, x):
+    """wave_upper_bound of hdlz_zip_write.hip over the ascending numpy array v -> (how many words are <= x, rounds of loads)"""
+    base, width, rounds = 0, len(v), 1
+    lanes = np.arange(64)
+    while width > 64:
+        chunk = (width + 63) // 64
+        p = (lanes + 1) * chunk - 1                              # lane i probes the last word of chunk i
+        c = int(np.count_nonzero(v[base + p[p < width]] <= x))
+        base += c * chunk
+        width = min(width - c * chunk, chunk)
+        rounds += 1
+    return base + int(np.count_nonzero(v[base:base + width] <= x)), rounds
+
+
+def gather_lookup(blk_first, nblocks):
+    """the row lookup of k_zipw_gather -> a namespace: rows_per_group, per (rows a wave), rounds[wave] (the loads of the wave's own
+    search), fallback[row] (the lane searches alone) and entry[row] (what the lookup finds: -1 for a row that no entry owns)"""
+    from types import SimpleNamespace
+    k = kernel_constants()
+    F = np.asarray(blk_first, np.int64)
+    E = len(F) - 1
+    group = k.ROWS_MAX if nblocks >= k.ROWS_MANY_MIN else k.ROWS_FEW
+    per = group // 4
+    nwaves = -(-nblocks // group) * 4
+    rounds, fallback, entry = np.zeros(nwaves, np.int64), np.zeros(nblocks, bool), np.full(nblocks, -1, np.int64)
+    far = np.iinfo(np.int64).max
+    for w in range(nwaves):
+        b0 = w * per
+        ub0, rounds[w] = wave_upper_bound(F, b0)
+        nxt = np.full(64, far, np.int64)                         # lane l holds F[ub0 + l], or "none" behind F[E]
+        nxt[:max(0, min(64, E + 1 - ub0))] = F[ub0:ub0 + 64]
+        b = np.arange(b0, min(b0 + per, nblocks))
+        c = np.searchsorted(nxt, b, side="right")                # the ballot: how many of the 64 words are <= b
+        ub = ub0 + c
+        alone = c == 64
+        ub[alone] = np.searchsorted(F, b[alone], side="right")
+        fallback[b] = alone
+        entry[b] = np.where((ub >= 1) & (ub <= E), ub - 1, -1)
+    return SimpleNamespace(rows_per_group=group, per=per, rounds=rounds, fallback=fallback, entry=entry)
+
+
+def plan_share(E):
+    """k_zipw_plan's split of E entries -> (per, threads that take `per` entries, entries of the one thread behind them that takes fewer)"""
+    per = -(-E // kernel_constants().PLAN_THREADS)
+    return per, (E // per if per else 0), (E % per if per else 0)
+
+
+def batch_arrays(case):
+    """(blk_first, nblocks) of a case as Engine.compress_zip plans it"""
+    first = [0]
+    for e, (_, d) in enumerate(case["items"]):
+        first.append(first[-1] + len(plan(len(d), case["block"], bool(case["store"] and case["store"][e]))))
+    return first, first[-1]
 
 
 # ---- .npz: the entries save_npz hands to compress_zip, from the same headers
