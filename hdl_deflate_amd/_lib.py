@@ -123,6 +123,18 @@ ZIP_WRITE_SIGNATURES = {
 }
 ZIP_WRITE_EXPORTS = tuple(ZIP_WRITE_SIGNATURES)
 ZIP_FLAG_UTF8 = 0x800          # HDLZ_ZIP_FLAG_UTF8
+# ... and of include/hdlz_zip64.h: ZIP64 archives indexed, read and written (tests/test_zip64_cabi.py)
+ZIP64_SIGNATURES = {
+    "hdlz_zip64_index_work_bytes": (sz, [u64, u64]),
+    "hdlz_zip64_index_ws": (ci, [vp, u64, u64, u32, vp, vp, vp, sz, vp]),                              # as hdlz_zip_index_ws
+    "hdlz_zip64_inflate_work_bytes": (sz, [u64, u32, u64]),
+    "hdlz_zip64_inflate_ws": (ci, [vp, u64, vp, u64, u64, u32, vp, u64, vp, vp, vp, sz, vp]),          # as hdlz_zip_inflate_ws
+    "hdlz_zip64_write_bound": (sz, [u64, u64, u32, u64, u64]),
+    "hdlz_zip64_write_work_bytes": (sz, [u64, u64]),
+    # as hdlz_zip_write_ws, zip64_from behind out_align
+    "hdlz_zip64_write_ws": (ci, [vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u32, u32, u32, u64, u64, vp, u64, vp, vp, vp, sz, vp]),
+}
+ZIP64_EXPORTS = tuple(ZIP64_SIGNATURES)
 _lib = None
 
 
@@ -184,6 +196,13 @@ class ZipEntry(ctypes.Structure):
                 ("status", u32)]
 
 
+class Zip64Entry(ctypes.Structure):
+    """hdlz_zip64_entry: one record of hdlz_zip64_index_ws (64 bytes)"""
+    _fields_ = [("cd_off", u64), ("payload_off", u64), ("out_off", u64), ("csize", u64), ("usize", u64), ("crc", u32), ("status", u32),
+                ("method", ctypes.c_uint16), ("flags", ctypes.c_uint16), ("name_len", ctypes.c_uint16), ("reserved", ctypes.c_uint16),
+                ("reserved2", u64)]
+
+
 class ZipIndexResult(ctypes.Structure):
     """hdlz_zip_index_result: the result record of hdlz_zip_index_ws (40 bytes)"""
     _fields_ = [("nentries", u64), ("total_out", u64), ("cd_off", u64), ("cd_size", u64), ("status", u32), ("reserved", u32)]
@@ -219,7 +238,7 @@ def load():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
-            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()):
+            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

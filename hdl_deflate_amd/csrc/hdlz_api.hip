@@ -801,7 +801,8 @@ struct ZipScratch {
     size_t decode;
     size_t bytes;
 };
-static ZipScratch zip_scratch(void* base, uint64_t count, uint32_t in_len, uint64_t out_cap) {
+// `row`: what the one-stream path is given of out_cap (hdlz_zip_inflate_ws: all of it, in whole words)
+static ZipScratch zip_scratch(void* base, uint64_t count, uint32_t in_len, uint64_t out_cap, uint64_t row) {
     const uintptr_t b = reinterpret_cast<uintptr_t>(base);
     const size_t per = hdlz::round256(24u * (size_t)count);
     const size_t tiles = count == 1 ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(out_cap)) : 0u;
@@ -809,37 +810,40 @@ static ZipScratch zip_scratch(void* base, uint64_t count, uint32_t in_len, uint6
     auto w64 = [&](uint64_t k) { return reinterpret_cast<uint64_t*>(b + per + 8u * (size_t)(k * count)); };
     return {w32(0), w32(1), w32(2), w32(3), w32(4), w32(5), w64(0), w64(1), reinterpret_cast<uint8_t**>(w64(2)),
             tiles ? reinterpret_cast<uint32_t*>(b + 2u * per) : nullptr, 2u * per + tiles,
-            2u * per + tiles + (count == 1 ? hdlz::round256(hdlz_inflate_work_bytes(1, in_len, out_cap & ~3ull, 0, 1)) : 0u)};
+            2u * per + tiles + (count == 1 ? hdlz::round256(hdlz_inflate_work_bytes(1, in_len, row, 0, 1)) : 0u)};
 }
 size_t hdlz_zip_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) {
-    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_scratch(nullptr, count, in_len, out_cap).bytes;
+    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_scratch(nullptr, count, in_len, out_cap, out_cap & ~3ull).bytes;
 }
 
-int hdlz_zip_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip_entry* d_entries, uint64_t first, uint64_t count,
-                        uint32_t in_len, uint8_t* d_out, uint64_t out_cap, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
-                        void* d_work, size_t work_bytes, void* stream) {
+}  // extern "C"
+// hdlz_zip_inflate_ws and hdlz_zip64_inflate_ws (include/hdlz_zip64.h): `row` is what the one-stream path is given of out_cap
+template <class Rec>
+static int zip_inflate_impl(const uint8_t* d_file, uint64_t file_len, const Rec* d_entries, uint64_t first, uint64_t count, uint32_t in_len,
+                            uint8_t* d_out, uint64_t out_cap, uint64_t row, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
+                            void* d_work, size_t work_bytes, void* stream, const char* query) {
     if (!d_result) return fail_param("d_result is required");
     if (count && any_null(d_file, d_entries)) return fail_param("null device pointer");
     if (out_cap && !d_out) return fail_param("d_out is null with out_cap > 0");
     if (first > 0x7FFFFFFFull || count > 0x7FFFFFFFull || first + count > 0x7FFFFFFFull) return fail_param("first + count too large (below 2^31)");
-    if (file_len > 0xFFFFFFFFull) return fail_param("file_len too large (below 2^32: ZIP64 is out of scope)");
+    if (sizeof(Rec) == sizeof(hdlz_zip_entry) && file_len > 0xFFFFFFFFull) return fail_param("file_len too large (below 2^32: ZIP64 is out of scope)");
     if (misaligned(8, d_entries, d_result)) return fail_align(8, "d_entries / d_result");
     if (misaligned(4, d_entry_status)) return fail_align(4, "d_entry_status");
     if (misaligned(256, d_work)) return fail_align(256, "d_work");
-    const ZipScratch s = zip_scratch(d_work, count, in_len, out_cap);
-    if (count && work_too_small(s.bytes, d_work, work_bytes, "hdlz_zip_inflate_work_bytes(count, in_len, out_cap)")) return HDLZ_E_BAD_PARAM;
+    const ZipScratch s = zip_scratch(d_work, count, in_len, out_cap, row);
+    if (count && work_too_small(s.bytes, d_work, work_bytes, query)) return HDLZ_E_BAD_PARAM;
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // one entry takes the batch call's path, which stores words, when its row is one that path accepts; else the task view
     const bool single = count == 1 && out_cap >= 4u && !misaligned(4, d_out);
-    const hdlz::ZipArgs z{d_file, file_len, d_entries ? d_entries + first : nullptr, count, in_len, d_out, out_cap, d_entry_status, d_result,
+    const hdlz::ZipArgsT<Rec> z{d_file, file_len, d_entries ? d_entries + first : nullptr, count, in_len, d_out, out_cap, d_entry_status, d_result,
                           s.len, s.status, s.end_bit, s.cap, s.crc, s.verdict, s.m_off, s.m_end, s.m_dst, single ? s.tiles : nullptr, single};
     if (const int rc = launched(hdlz::launch_zip_check(z, st), "launch k_zip_check"); rc != HDLZ_OK) return rc;
     if (single) {
         // a large entry: the batch call's path over the two-word index the checks left on the device -- the whole-GPU chains for a
         // large payload, their fallbacks, the wave for a small one; in_len is the bound the call was given
         const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
-        if (const int rc = inflate_batch_impl(d_file, s.m_off, 0, in_len, 1, 0, 0, d_out, out_cap & ~3ull, s.len, s.status, w, stream, s.end_bit); rc != HDLZ_OK) return rc;
+        if (const int rc = inflate_batch_impl(d_file, s.m_off, 0, in_len, 1, 0, 0, d_out, row, s.len, s.status, w, stream, s.end_bit); rc != HDLZ_OK) return rc;
     } else if (count) {
         hdlz::MemberArgs a = member_args(d_file, count, 0, d_out, s.len, s.status, s.end_bit, s.m_off);   // (BFINAL is honoured)
         a.m_end = s.m_end; a.m_dst = s.m_dst; a.m_dst_cap = s.cap;                                     // the task view
@@ -848,6 +852,48 @@ int hdlz_zip_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip
     if (const int rc = launched(hdlz::launch_zip_copy(z, st), "launch k_zip_copy"); rc != HDLZ_OK) return rc;
     if (const int rc = launched(hdlz::launch_zip_crc(z, st), "launch k_zip_crc_*"); rc != HDLZ_OK) return rc;
     return launched(hdlz::launch_zip_judge(z, st), "launch k_zip_judge");
+}
+
+extern "C" {
+
+int hdlz_zip_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip_entry* d_entries, uint64_t first, uint64_t count,
+                        uint32_t in_len, uint8_t* d_out, uint64_t out_cap, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
+                        void* d_work, size_t work_bytes, void* stream) {
+    return zip_inflate_impl(d_file, file_len, d_entries, first, count, in_len, d_out, out_cap, out_cap & ~3ull, d_entry_status, d_result, d_work,
+                            work_bytes, stream, "hdlz_zip_inflate_work_bytes(count, in_len, out_cap)");
+}
+
+// ---- include/hdlz_zip64.h: ZIP64 indexed and read; written: further down (the generalised index kernels of hdlz_zip.hip, and its read kernels over the 64-byte record)
+size_t hdlz_zip64_index_work_bytes(uint64_t file_len, uint64_t entry_cap) {
+    (void)file_len;
+    return entry_cap > 0x7FFFFFFFull ? 0u : hdlz::zip64_index_work_bytes(entry_cap);
+}
+
+int hdlz_zip64_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip64_entry* d_entries,
+                        hdlz_zip_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || (file_len && !d_file)) return fail_param("null device pointer");
+    if (entry_cap && !d_entries) return fail_param("d_entries is null with entry_cap > 0");
+    if (entry_cap > 0x7FFFFFFFull) return fail_param("entry_cap too large (below 2^31)");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (work_too_small(hdlz::zip64_index_work_bytes(entry_cap), d_work, work_bytes, "hdlz_zip64_index_work_bytes(file_len, entry_cap)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_entries, d_result, d_work)) return fail_align(8, "d_entries / d_result / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_zip64_index(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, static_cast<hipStream_t>(stream)),
+                    "launch k_zip64_end");
+}
+
+// the row the one-stream path is given: the decoders' room ends at 2^32 - 512 (a stored entry needs none of it)
+static uint64_t zip64_row(uint64_t out_cap) { return (out_cap & ~3ull) < 0xFFFFFE00ull ? out_cap & ~3ull : 0xFFFFFE00ull; }
+
+size_t hdlz_zip64_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) {
+    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_scratch(nullptr, count, in_len, out_cap, zip64_row(out_cap)).bytes;
+}
+
+int hdlz_zip64_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip64_entry* d_entries, uint64_t first, uint64_t count,
+                          uint32_t in_len, uint8_t* d_out, uint64_t out_cap, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
+                          void* d_work, size_t work_bytes, void* stream) {
+    return zip_inflate_impl(d_file, file_len, d_entries, first, count, in_len, d_out, out_cap, zip64_row(out_cap), d_entry_status, d_result, d_work,
+                            work_bytes, stream, "hdlz_zip64_inflate_work_bytes(count, in_len, out_cap)");
 }
 
 // ---- include/hdlz_zip_write.h: a ZIP archive written from the rows of one compress batch (hdlz_zip_write.hip)
@@ -881,6 +927,40 @@ int hdlz_zip_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const uint
     hdlz::ZipWriteArgs a{d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks,
                          d_blk_first, d_crc, flags, dos_datetime, out_align, total_in, d_file, file_cap, d_entries, d_result, {}};
     return launched(hdlz::launch_zip_write(a, d_work, static_cast<hipStream_t>(stream)), "launch k_zipw_*");
+}
+
+// ---- include/hdlz_zip64.h: ZIP64 written (the scan and the gather of hdlz_zip_write.hip, a plan for any number of entries)
+size_t hdlz_zip64_write_bound(uint64_t nentries, uint64_t nblocks, uint32_t block_len, uint64_t total_in, uint64_t names_len) {
+    (void)nblocks; (void)block_len;
+    return 98u + 124u * (size_t)nentries + 2u * (size_t)names_len + (size_t)total_in;
+}
+
+size_t hdlz_zip64_write_work_bytes(uint64_t nentries, uint64_t nblocks) {
+    return nentries > 0x7FFFFFFFull || nblocks > 0x7FFFFFFFull ? 0u : hdlz::zip_write_work_bytes(nentries, nblocks, true);
+}
+
+int hdlz_zip64_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const uint8_t* d_names, const uint64_t* d_name_off, uint64_t nentries,
+                        const uint64_t* d_in_off, const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                        const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, const uint32_t* d_crc, uint32_t flags,
+                        uint32_t dos_datetime, uint32_t out_align, uint64_t zip64_from, uint64_t total_in, uint8_t* d_file, uint64_t file_cap,
+                        hdlz_zip64_entry* d_entries, hdlz_zip_write_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("d_result is required");
+    if (nentries > 0x7FFFFFFFull) return fail_param("nentries too large (2^31 - 1 entries)");
+    if (nblocks > 0x7FFFFFFFull || (nblocks && !nentries)) return fail_param("nblocks too large for one launch (2^31 - 1 rows), or rows without entries");
+    if (nentries && (any_null(d_in, d_names, d_crc) || any_null(d_ent_off, d_name_off, d_blk_first))) return fail_param("null device pointer (the entries)");
+    if (nblocks && (any_null(d_in_off, d_end_bits) || any_null(d_len, d_status) || !d_rows)) return fail_param("null device pointer (the rows)");
+    if (file_cap && !d_file) return fail_param("d_file is null with file_cap > 0");
+    if (flags & ~(uint32_t)HDLZ_ZIP_FLAG_UTF8) return fail_param("flags: only HDLZ_ZIP_FLAG_UTF8 may be set");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (zip64_from > 0xFFFFFFFFull) return fail_param("zip64_from must be at most FFFFFFFF");
+    if (work_too_small(hdlz::zip_write_work_bytes(nentries, nblocks, true), d_work, work_bytes, "hdlz_zip64_write_work_bytes(nentries, nblocks)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_ent_off, d_name_off, d_in_off, d_end_bits, d_blk_first) || misaligned(8, d_entries) || misaligned(8, d_result) || misaligned(8, d_work))
+        return fail_align(8, "d_ent_off / d_name_off / d_in_off / d_end_bits / d_blk_first / d_entries / d_result / d_work");
+    if (misaligned(4, d_len, d_status, d_crc)) return fail_align(4, "d_len / d_status / d_crc");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hdlz::ZipWriteArgs a{d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks,
+                         d_blk_first, d_crc, flags, dos_datetime, out_align, total_in, d_file, file_cap, nullptr, d_result, {}, d_entries, zip64_from};
+    return launched(hdlz::launch_zip_write(a, d_work, static_cast<hipStream_t>(stream), true), "launch k_zipw64_*");
 }
 
 }  // extern "C"

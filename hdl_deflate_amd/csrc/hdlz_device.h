@@ -9,6 +9,7 @@
 #include "../../include/hdlz_gunzip.h"
 #include "../../include/hdlz_zip.h"
 #include "../../include/hdlz_zip_write.h"
+#include "../../include/hdlz_zip64.h"
 
 namespace hdlz {
 
@@ -346,10 +347,11 @@ hipError_t launch_gunzip_judge(const GunzipArgs& a, hipStream_t stream);
 size_t zip_index_work_bytes();
 hipError_t launch_zip_index(const uint8_t* file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip_entry* entries,
                             hdlz_zip_index_result* result, void* work, hipStream_t stream);
-struct ZipArgs {
+// (Rec: hdlz_zip_entry, or hdlz_zip64_entry for hdlz_zip64_inflate_ws -- the same kernels, instantiated for either record)
+template <class Rec> struct ZipArgsT {
     const uint8_t* in;
     uint64_t in_len;                  // file_len
-    const hdlz_zip_entry* entries;    // the call's d_entries + first
+    const Rec* entries;               // the call's d_entries + first
     uint64_t count;
     uint32_t bound;                   // the call's in_len
     uint8_t* out;
@@ -368,10 +370,21 @@ struct ZipArgs {
     uint32_t* tiles;                  // scratch, single: one word per 32 KiB tile of out_cap (else null)
     bool single;                      // count == 1 on the batch call's path
 };
+using ZipArgs = ZipArgsT<hdlz_zip_entry>;
+using ZipArgs64 = ZipArgsT<hdlz_zip64_entry>;
 hipError_t launch_zip_check(const ZipArgs& a, hipStream_t stream);
 hipError_t launch_zip_copy(const ZipArgs& a, hipStream_t stream);
 hipError_t launch_zip_crc(const ZipArgs& a, hipStream_t stream);
 hipError_t launch_zip_judge(const ZipArgs& a, hipStream_t stream);
+hipError_t launch_zip_check(const ZipArgs64& a, hipStream_t stream);
+hipError_t launch_zip_copy(const ZipArgs64& a, hipStream_t stream);
+hipError_t launch_zip_crc(const ZipArgs64& a, hipStream_t stream);
+hipError_t launch_zip_judge(const ZipArgs64& a, hipStream_t stream);
+
+// hdlz_zip.hip again: hdlz_zip64_index_ws (include/hdlz_zip64.h)
+size_t zip64_index_work_bytes(uint64_t entry_cap);
+hipError_t launch_zip64_index(const uint8_t* file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip64_entry* entries,
+                              hdlz_zip_index_result* result, void* work, hipStream_t stream);
 
 // hdlz_zip_write.hip: hdlz_zip_write_ws (include/hdlz_zip_write.h).  The scratch, carved by the launcher: E = nentries
 struct ZipWriteWork {
@@ -381,6 +394,7 @@ struct ZipWriteWork {
     uint64_t* head;                   // the summary: is the file written, the tiles of the stored copy, did an entry fail
     uint64_t *pay, *cdrec, *out_off;  // per entry: payload_off, where its central record starts, out_off
     uint32_t *csize, *form, *tile0;   // per entry: c_e; method | status << 8; (E + 1 words) the first tile of the stored copy
+    uint64_t* csize64;                // hdlz_zip64_write_ws: c_e in 64 bits, in the piece of csize (then twice as large)
 };
 struct ZipWriteArgs {
     const uint8_t* in;
@@ -404,8 +418,10 @@ struct ZipWriteArgs {
     hdlz_zip_entry* entries;          // nullable
     hdlz_zip_write_result* result;
     ZipWriteWork w;
+    hdlz_zip64_entry* entries64 = nullptr;      // hdlz_zip64_write_ws (wide): its records, nullable, and its zip64_from
+    uint64_t zip64_from = 0xFFFFFFFFull;
 };
-size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks);
-hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream);
+size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks, bool wide = false);
+hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream, bool wide = false);
 
 }  // namespace hdlz

@@ -225,6 +225,188 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_zipw_plan(ZipWriteArgs a) {
     for (uint32_t i = 0; i < EOCD; i++) t[i] = record_byte(w, i);
 }
 
+// ---- hdlz_zip64_write_ws (include/hdlz_zip64.h): the plan for any E and the entries' headers with their ZIP64 fields
+constexpr uint32_t SIG_EOCD64 = 0x06064B50u, SIG_LOCATOR = 0x07064B50u, EOCD64 = 56u, LOCATOR = 20u;
+constexpr uint32_t VERSION64 = 45u, LOCAL_EXTRA64 = 20u;
+
+// the bytes of an entry's local ZIP64 extra, and how many values its central one holds (from = zip64_from)
+__device__ __forceinline__ uint32_t local_extra(uint64_t u, uint64_t c, uint64_t from) { return u >= from || c >= from ? LOCAL_EXTRA64 : 0u; }
+__device__ __forceinline__ uint32_t central_extra(uint64_t u, uint64_t c, uint64_t L, uint64_t from) {
+    const uint32_t k = (u >= from ? 1u : 0u) + (c >= from ? 1u : 0u) + (L >= from ? 1u : 0u);
+    return k ? 4u + 8u * k : 0u;
+}
+
+// the exclusive prefix of every thread's v[0 .. Q) over the workgroup of the plan -> base; total: the sums.  (s: PLAN_WAVES x Q words)
+template <int Q>
+__device__ __forceinline__ void plan_scan(const uint64_t (&mine)[Q], uint64_t (&base)[Q], uint64_t (&total)[Q], uint64_t (*s)[4], uint32_t lane, uint32_t wave) {
+    uint64_t v[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        v[q] = mine[q];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t t = __shfl_up(v[q], o, 64);
+            if (lane >= (uint32_t)o) v[q] += t;
+        }
+    }
+    __syncthreads();                                              // (the scan in front of this one has been read)
+    if (lane == 63u) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) s[wave][q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        base[q] = v[q] - mine[q];
+        total[q] = 0u;
+        for (uint32_t k = 0; k < PLAN_WAVES; k++) {
+            if (k < wave) base[q] += s[k][q];
+            total[q] += s[k][q];
+        }
+    }
+}
+
+// ONE workgroup, thread t the entries [per t, per (t + 1)), per = ceil(E / 1024) without a limit.  A local record's size hangs on u_e and
+// c_e alone, a central record's on the local offset L_e too: so two scans one behind the other -- the local records (with the slots and
+// the tiles), then, L_e known, the central records -- and a coalesced sweep that makes the central offsets, run-relative until then, absolute.
+__global__ __launch_bounds__(PLAN_THREADS) void k_zipw64_plan(ZipWriteArgs a) {
+    __shared__ uint64_t s_wave[PLAN_WAVES][4];
+    __shared__ uint32_t s_worst[PLAN_WAVES], s_first[PLAN_WAVES];
+    __shared__ uint64_t s_cbase[PLAN_THREADS];                    // where each thread's run of central records starts
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t E = a.nentries, from = a.zip64_from;
+    const uint64_t amask = (uint64_t)a.out_align - 1u;
+    const uint64_t per = (E + PLAN_THREADS - 1u) / PLAN_THREADS;
+    const uint64_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
+    uint64_t mine[4] = {0u, 0u, 0u, 0u};                          // local records, entries stored, output slots, tiles of the stored copy
+    uint32_t worst = HDLZ_OK, first = NONE;
+    for (uint64_t e = lo; e < hi; e++) {
+        const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e];
+        const uint64_t F0 = a.blk_first[e], F1 = a.blk_first[e + 1u];
+        uint32_t st = HDLZ_OK, method = 0u;
+        uint64_t c = u;
+        if (F0 > F1 || F1 > a.nblocks) st = HDLZ_E_BAD_PARAM;
+        else if (F1 > F0) {
+            const uint64_t k = a.w.cnt[F1] - a.w.cnt[F0];
+            if (k & COUNT_MASK) {
+                for (uint64_t b = F0; b < F1; b++) st = max(st, a.status[b]);
+            } else if (k >> COUNT_BITS) st = HDLZ_E_BAD_PARAM;
+            else if (a.in_off[F1] - a.in_off[F0] != u) st = HDLZ_E_BAD_PARAM;
+        }
+        if (st == HDLZ_OK && n > NAME_LEN_MAX) st = HDLZ_E_BAD_PARAM;
+        if (st == HDLZ_OK && F1 > F0) {
+            const uint64_t cd = a.w.pre[F1] - a.w.pre[F0] + 2u;   // the members and 03 00
+            if (cd < u) { method = METHOD_DEFLATED; c = cd; }
+        }
+        a.w.csize64[e] = c;
+        a.w.form[e] = method | (st << 8);
+        if (st == HDLZ_OK) {
+            mine[0] += LOCREC + n + local_extra(u, c, from) + c; mine[1] += method == 0u ? 1u : 0u; mine[2] += (u + amask) & ~amask;
+            if (F0 == F1) mine[3] += (u + STORE_TILE - 1u) / STORE_TILE;
+        } else {
+            worst = max(worst, st);
+            first = min(first, (uint32_t)e);
+        }
+    }
+    {
+        const uint32_t rw = wave_max(worst), rf = wave_min(first);
+        if (lane == 0u) { s_worst[wave] = rw; s_first[wave] = rf; }
+    }
+    uint64_t base[4], total[4];
+    plan_scan(mine, base, total, s_wave, lane, wave);             // (its barriers stand behind the stores of s_worst and s_first, too)
+    worst = HDLZ_OK; first = NONE;
+    for (uint32_t k = 0; k < PLAN_WAVES; k++) { worst = max(worst, s_worst[k]); first = min(first, s_first[k]); }
+    const bool failed = worst != HDLZ_OK;
+    const uint64_t cd_off = total[0];
+    // the second scan: the central records, every local offset known
+    uint64_t cmine[1] = {0u}, cbase[1], ctotal[1];
+    for (uint64_t e = lo; e < hi; e++) {
+        const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e], c = a.w.csize64[e];
+        const bool none = a.blk_first[e] == a.blk_first[e + 1u];
+        const uint64_t L = base[0];
+        a.w.pay[e] = L + LOCREC + n + local_extra(u, c, from); a.w.out_off[e] = base[2]; a.w.tile0[e] = (uint32_t)base[3];
+        a.w.cdrec[e] = cmine[0];                                  // relative to the run's first central record, until the sweep below
+        if ((a.w.form[e] >> 8) == HDLZ_OK) {
+            cmine[0] += CDREC + n + central_extra(u, c, L, from);
+            base[0] += LOCREC + n + local_extra(u, c, from) + c; base[2] += (u + amask) & ~amask;
+            if (none) base[3] += (u + STORE_TILE - 1u) / STORE_TILE;
+        }
+    }
+    plan_scan(cmine, cbase, ctotal, s_wave, lane, wave);
+    const uint64_t cd_size = ctotal[0];
+    // pass 2 left every central offset relative to its thread's run: the runs' starts go through LDS and the third pass is one
+    // coalesced sweep -- a load, an add and a store an entry, independent of each other, where a third walk of the runs would cost
+    // as much as the second (a run is latency-bound: profiles/zip64.txt section 5)
+    s_cbase[tid] = cd_off + cbase[0];
+    __syncthreads();
+    for (uint64_t e = tid; e < E; e += PLAN_THREADS) a.w.cdrec[e] += s_cbase[(uint32_t)e / (uint32_t)per];
+    if (tid != 0u) return;
+    const bool big = E > 65535u || cd_off >= from || cd_size >= from;      // the ZIP64 end record and its locator
+    const uint64_t r = cd_off + cd_size, file_len = r + (big ? EOCD64 + LOCATOR : 0u) + EOCD;
+    const bool write = !failed && file_len <= a.cap;
+    a.w.tile0[E] = write ? (uint32_t)total[3] : 0u;
+    a.w.head[H_WRITE] = write ? 1u : 0u; a.w.head[H_TILES] = write ? total[3] : 0u; a.w.head[H_FAILED] = failed ? 1u : 0u;
+    hdlz_zip_write_result res;
+    res.file_len = failed ? 0u : file_len; res.cd_off = failed ? 0u : cd_off; res.cd_size = failed ? 0u : cd_size; res.nstored = failed ? 0u : total[1];
+    res.status = failed ? worst : file_len > a.cap ? (uint32_t)HDLZ_E_OUT_CAPACITY : (uint32_t)HDLZ_OK;
+    res.first_bad = first;
+    *a.result = res;
+    if (!write) return;
+    uint8_t* t = a.file + r;
+    if (big) {
+        const uint32_t w64[19] = {SIG_EOCD64, 44u, 0u, VERSION64 | (VERSION64 << 16), 0u, 0u, (uint32_t)E, (uint32_t)(E >> 32), (uint32_t)E, (uint32_t)(E >> 32),
+                                  (uint32_t)cd_size, (uint32_t)(cd_size >> 32), (uint32_t)cd_off, (uint32_t)(cd_off >> 32),
+                                  SIG_LOCATOR, 0u, (uint32_t)r, (uint32_t)(r >> 32), 1u};
+        for (uint32_t i = 0; i < EOCD64 + LOCATOR; i++) t[i] = record_byte(w64, i);
+        t += EOCD64 + LOCATOR;
+    }
+    const uint32_t n16 = E > 0xFFFFu ? 0xFFFFu : (uint32_t)E;
+    const uint32_t w[6] = {SIG_EOCD, 0u, n16 | (n16 << 16), cd_size >= from ? 0xFFFFFFFFu : (uint32_t)cd_size, cd_off >= from ? 0xFFFFFFFFu : (uint32_t)cd_off, 0u};
+    for (uint32_t i = 0; i < EOCD; i++) t[i] = record_byte(w, i);
+}
+
+// the entries' part of the gather for hdlz_zip64_write_ws, a wave per entry: both headers, the name and the ZIP64 extra behind each, the record
+__device__ __forceinline__ void entry_headers64(const ZipWriteArgs& a, uint32_t e, uint32_t lane, bool write) {
+    const uint64_t from = a.zip64_from;
+    const uint32_t form = a.w.form[e], method = form & 0xFFu, crc = a.crc[e];
+    const uint64_t c = a.w.csize64[e], u = a.ent_off[e + 1u] - a.ent_off[e];
+    const uint32_t n = (uint32_t)(a.name_off[e + 1u] - a.name_off[e]);
+    const uint32_t lx = local_extra(u, c, from);
+    const uint64_t pay = a.w.pay[e], L = pay - LOCREC - n - lx, cd = a.w.cdrec[e];
+    const bool zu = u >= from, zc = c >= from, zl = L >= from;
+    const uint32_t cx = central_extra(u, c, L, from);
+    if (a.entries64 && lane == 0u) {
+        hdlz_zip64_entry rec;
+        const bool sound = a.w.head[H_FAILED] == 0u;
+        rec.cd_off = sound ? cd : 0u; rec.payload_off = sound ? pay : 0u; rec.out_off = sound ? a.w.out_off[e] : 0u;
+        rec.csize = sound ? c : 0u; rec.usize = sound ? u : 0u; rec.crc = sound ? crc : 0u;
+        rec.method = (uint16_t)(sound ? method : 0u); rec.flags = (uint16_t)(sound ? a.flags : 0u); rec.name_len = (uint16_t)(sound ? n : 0u);
+        rec.reserved = 0u; rec.reserved2 = 0u;
+        rec.status = form >> 8;
+        a.entries64[e] = rec;
+    }
+    if (!write) return;
+    const uint32_t time = a.datetime & 0xFFFFu, date = a.datetime >> 16;
+    const uint32_t ver = cx ? VERSION64 : VERSION;                // (a local extra never stands without a central one)
+    const uint32_t lc = lx ? 0xFFFFFFFFu : (uint32_t)c, lu = lx ? 0xFFFFFFFFu : (uint32_t)u;
+    const uint32_t cc = zc ? 0xFFFFFFFFu : (uint32_t)c, cu = zu ? 0xFFFFFFFFu : (uint32_t)u, cl = zl ? 0xFFFFFFFFu : (uint32_t)L;
+    const uint32_t lw[8] = {SIG_LOCAL, ver | (a.flags << 16), method | (time << 16), date | (crc << 16), (crc >> 16) | (lc << 16),
+                            (lc >> 16) | (lu << 16), (lu >> 16) | (n << 16), lx};
+    const uint32_t cw[12] = {SIG_CD, ver | (ver << 16), a.flags | (method << 16), time | (date << 16), crc, cc, cu, n | (cx << 16), 0u, 0u,
+                             cl << 16, cl >> 16};
+    if (lane < LOCREC) a.file[L + lane] = record_byte(lw, lane);
+    if (lane < CDREC) a.file[cd + lane] = record_byte(cw, lane);
+    const uint8_t* name = a.names + a.name_off[e];
+    copy_to_aligned16(a.file + L + LOCREC, name, n, lane, 64u);
+    copy_to_aligned16(a.file + cd + CDREC, name, n, lane, 64u);
+    // the extras: 01 00 10 00 | u | c behind the local name; 01 00 | 8k | the k values that moved, in the order u, c, L, behind the central one
+    const uint32_t xl[5] = {0x00100001u, (uint32_t)u, (uint32_t)(u >> 32), (uint32_t)c, (uint32_t)(c >> 32)};
+    if (lane < lx) a.file[L + LOCREC + n + lane] = record_byte(xl, lane);
+    const uint64_t v0 = zu ? u : zc ? c : L, v1 = zu && zc ? c : L;
+    const uint32_t xc[7] = {1u | ((cx - 4u) << 16), (uint32_t)v0, (uint32_t)(v0 >> 32), (uint32_t)v1, (uint32_t)(v1 >> 32), (uint32_t)L, (uint32_t)(L >> 32)};
+    if (lane < cx) a.file[cd + CDREC + n + lane] = record_byte(xc, lane);
+}
+
 // the number of elements of the ascending v[0 .. n) that are <= x (the first index with v[i] > x), by a whole wave: 64 probes a round,
 // so three rounds of dependent loads for the 65536 words of a ZIP's entries where a lane alone takes sixteen
 __device__ __forceinline__ uint32_t wave_upper_bound(const uint64_t* __restrict__ v, uint32_t n, uint64_t x, uint32_t lane) {
@@ -248,6 +430,8 @@ __device__ __forceinline__ uint8_t member_byte(const uint8_t* src, uint32_t i, u
 // ---- (c) the gather.  A row of the rows' part, as a wave leaves it in LDS for its own copy loop
 enum { ROW_SKIP = 0, ROW_STORED = 1, ROW_MEMBER = 2, ROW_LAST_MEMBER = 3 };
 
+// (W: the call is hdlz_zip64_write_ws -- the rows and the tiles are the same code; the entries' part writes the ZIP64 forms)
+template <bool W>
 __global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t row_groups, uint32_t tile_groups, uint32_t rows_per_group) {
     __shared__ uint64_t s_dst[ROWS_MAX], s_src[ROWS_MAX];         // where the row's bytes go in the file; where they come from (rows / in)
     __shared__ uint32_t s_len[ROWS_MAX], s_m[ROWS_MAX], s_kind[ROWS_MAX];      // the bytes taken from there; |M_b|
@@ -347,6 +531,10 @@ __global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t ro
     // ---- entries: the two headers, the name behind both, the record
     const uint32_t e = (blockIdx.x - row_groups - tile_groups) * 4u + wave;
     if (e >= E) return;
+    if constexpr (W) {
+        entry_headers64(a, e, lane, write);
+        return;
+    }
     const uint32_t form = a.w.form[e], method = form & 0xFFu, csize = a.w.csize[e], crc = a.crc[e];
     const uint32_t usize = (uint32_t)(a.ent_off[e + 1u] - a.ent_off[e]), n = (uint32_t)(a.name_off[e + 1u] - a.name_off[e]);
     const uint64_t pay = a.w.pay[e], L = pay - LOCREC - n, cd = a.w.cdrec[e];
@@ -376,7 +564,8 @@ __global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t ro
 }  // namespace zipw
 
 // the scratch, in this order, every piece a multiple of 256 bytes (include/hdlz_zip_write.h states the sum)
-static ZipWriteWork zip_write_work(void* work, uint64_t nentries, uint64_t nblocks, size_t* bytes) {
+// (wide: hdlz_zip64_write_ws -- c_e is a 64-bit word; include/hdlz_zip64.h states that sum)
+static ZipWriteWork zip_write_work(void* work, uint64_t nentries, uint64_t nblocks, bool wide, size_t* bytes) {
     const uintptr_t base = reinterpret_cast<uintptr_t>(work);
     const uint64_t ntiles = join_tiles(nblocks);
     size_t at = 0;
@@ -391,30 +580,31 @@ static ZipWriteWork zip_write_work(void* work, uint64_t nentries, uint64_t nbloc
     w.pay = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nentries + 1u)));
     w.cdrec = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nentries + 1u)));
     w.out_off = reinterpret_cast<uint64_t*>(piece(8u * ((size_t)nentries + 1u)));
-    w.csize = reinterpret_cast<uint32_t*>(piece(4u * ((size_t)nentries + 1u)));
+    w.csize = reinterpret_cast<uint32_t*>(piece((wide ? 8u : 4u) * ((size_t)nentries + 1u)));
+    w.csize64 = reinterpret_cast<uint64_t*>(w.csize);
     w.form = reinterpret_cast<uint32_t*>(piece(4u * ((size_t)nentries + 1u)));
     w.tile0 = reinterpret_cast<uint32_t*>(piece(4u * ((size_t)nentries + 1u)));
     *bytes = at;
     return w;
 }
 
-size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks) {
+size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks, bool wide) {
     size_t bytes;
-    (void)zip_write_work(nullptr, nentries, nblocks, &bytes);
+    (void)zip_write_work(nullptr, nentries, nblocks, wide, &bytes);
     return bytes;
 }
 
-hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream) {
+hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream, bool wide) {
     using namespace zipw;
     size_t bytes;
-    a.w = zip_write_work(work, a.nentries, a.nblocks, &bytes);
+    a.w = zip_write_work(work, a.nentries, a.nblocks, wide, &bytes);
     const uint64_t ntiles = join_tiles(a.nblocks);
     hipError_t e = hipSuccess;
     if (ntiles) {
         e = zero_words(a.w.ticket, (uint32_t)(2u + 4u * ntiles), stream);      // the ticket and both look-back words of every tile
         if (e == hipSuccess) e = launch(k_zipw_scan, dim3((unsigned)ntiles), dim3(JT), stream, a);
     }
-    if (e == hipSuccess) e = launch(k_zipw_plan, dim3(1), dim3(PLAN_THREADS), stream, a);
+    if (e == hipSuccess) e = launch(wide ? k_zipw64_plan : k_zipw_plan, dim3(1), dim3(PLAN_THREADS), stream, a);
     if (e != hipSuccess) return e;
     // the gather's three kinds of workgroup, every count from what the host knows
     // rows a workgroup: 16 keep every CU busy with a few thousand large rows; with many small ones 64 spread the search over more rows
@@ -424,7 +614,7 @@ hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream) {
     if (tile_groups > (1u << 17)) tile_groups = 1u << 17;
     const uint64_t entry_groups = (a.nentries + 3u) / 4u;
     if (row_groups + tile_groups + entry_groups == 0u) return hipSuccess;
-    return launch(k_zipw_gather, dim3((unsigned)(row_groups + tile_groups + entry_groups)), dim3(256), stream, a, (uint32_t)row_groups, (uint32_t)tile_groups, rows_per_group);
+    return launch(wide ? k_zipw_gather<true> : k_zipw_gather<false>, dim3((unsigned)(row_groups + tile_groups + entry_groups)), dim3(256), stream, a, (uint32_t)row_groups, (uint32_t)tile_groups, rows_per_group);
 }
 
 }  // namespace hdlz

@@ -527,29 +527,45 @@ class Engine(object):
 
     # -- ZIP archives (include/hdlz_zip.h): the directory indexed and the entries read on the device
     @_on_device
-    def zip_index(self, d_file, entry_cap=None, out_align=1):
+    def zip_index(self, d_file, entry_cap=None, out_align=1, zip64="auto"):
         """d_file: flat uint8 device tensor, a ZIP file (.zip, .npz, .jar, .whl, .docx) -> a ZipIndex (hdl_deflate_amd/zip.py): the device
         records of hdlz_zip_index_ws, its result record, a host copy of the records and the entries' names.  A status that is not OK --
         the record's or an entry's -- is returned, not raised: the entries in front of a stop stay valid and indexed.  entry_cap: room
         for that many records (default: the sizing call first, then the call with the true count); out_align: every entry's slot in the
         flat output starts at a multiple of it (a power of two up to 256).  One host sync per call for the record, one for the records
-        and one for the names."""
-        from .zip import ZipIndex, ENTRY_DTYPE, decode_name
+        and one for the names.
+        zip64: "auto" -- a file of 2^32 bytes or more goes to hdlz_zip64_index_ws (include/hdlz_zip64.h); a smaller one to the classic
+        call first and to the new one only when that failed in its step 1 (status != OK and nentries == 0: a locator, say), so a file
+        without a locator returns what it always did.  True / False force one call.  The index says which it was (.zip64): the records
+        of the new call are 64 bytes each (ENTRY64_DTYPE on the host, the same names)."""
+        from .zip import ZipIndex, ENTRY_DTYPE, ENTRY64_DTYPE, decode_name
         import numpy as np
         self._is_bytes(d_file, "d_file", flat=True)
+        if zip64 not in ("auto", True, False):
+            raise ValueError("zip64 must be \"auto\", True or False, not %r" % (zip64,))
         n, dev = d_file.numel(), d_file.device
-        scratch = self._scratch(self.lib.hdlz_zip_index_work_bytes(n, 0), None, full=True)
-        cap = 0 if entry_cap is None else int(entry_cap)
-        while True:
-            entries = torch.empty((cap, 6), dtype=torch.int64, device=dev)
-            rec = self._record("hdlz_zip_index_ws", _lib.ZipIndexResult, scratch, d_file.data_ptr() if n else None, n, cap, out_align,
-                               entries.data_ptr() if cap else None)
-            if entry_cap is not None or rec.status != E_OUT_CAPACITY or rec.nentries <= cap:
-                break
-            cap = rec.nentries
+
+        def run(wide):
+            call, work_bytes, words = ("hdlz_zip64_index_ws", self.lib.hdlz_zip64_index_work_bytes, 8) if wide else \
+                ("hdlz_zip_index_ws", self.lib.hdlz_zip_index_work_bytes, 6)
+            cap = 0 if entry_cap is None else int(entry_cap)
+            while True:
+                entries = torch.empty((cap, words), dtype=torch.int64, device=dev)
+                rec = self._record(call, _lib.ZipIndexResult, self._scratch(work_bytes(n, cap), None, full=True), d_file.data_ptr() if n else None,
+                                   n, cap, out_align, entries.data_ptr() if cap else None)
+                if entry_cap is not None or rec.status != E_OUT_CAPACITY or rec.nentries <= cap:
+                    return entries, rec, cap
+                cap = rec.nentries
+
+        wide = zip64 is True or (zip64 == "auto" and n >= 1 << 32)
+        entries, rec, cap = run(wide)
+        if zip64 == "auto" and not wide and rec.status != OK and rec.nentries == 0:
+            again = run(True)
+            if again[1].status == OK or again[1].nentries:      # (else: no ZIP of either form -- the classic answer stands)
+                wide, (entries, rec, cap) = True, again
         k = min(cap, rec.nentries)
         entries = entries[:k]
-        host = np.frombuffer(entries.cpu().numpy().tobytes(), dtype=ENTRY_DTYPE)
+        host = np.frombuffer(entries.cpu().numpy().tobytes(), dtype=ENTRY64_DTYPE if wide else ENTRY_DTYPE)
         # the names: bytes [cd_off + 46, cd_off + 46 + name_len) of every record, gathered on the device, one copy to the host
         lens = host["name_len"].astype(np.int64)
         ends = np.cumsum(lens)
@@ -559,7 +575,7 @@ class Engine(object):
             at = torch.repeat_interleave(starts, torch.from_numpy(lens).to(dev)) + torch.arange(int(ends[-1]), dtype=torch.int64, device=dev)
             raw = d_file[at].cpu().numpy().tobytes()
         names = [decode_name(raw[int(e - l):int(e)], int(f)) for e, l, f in zip(ends, lens, host["flags"])]
-        return ZipIndex(entries, rec, host, names, out_align)
+        return ZipIndex(entries, rec, host, names, out_align, wide)
 
     @_on_device
     def inflate_zip(self, d_file, index=None, first=0, count=None, out=None, work=None):
@@ -569,8 +585,9 @@ class Engine(object):
         range [first, first + count) reads without the rest.  The range is routed here: maximal runs of entries below ZIP_LARGE_MIN
         compressed bytes go in one hdlz_zip_inflate_ws call each, a wave per entry; every larger entry goes in a call of its own, decoded
         by the whole GPU (when its slot starts at a multiple of 4: index with out_align >= 4) -- in ascending order, all into the same
-        flat `out`.  out: at least the range's bytes rounded up to 4 (default: allocated here); work: the scratch of the largest call,
-        uint8 at a multiple of 256 (default: allocated here).  No host sync behind the index."""
+        flat `out`.  An index of hdlz_zip64_index_ws (index.zip64) is read by hdlz_zip64_inflate_ws, routed the same way.  out: at least
+        the range's bytes rounded up to 4 (default: allocated here); work: the scratch of the largest call, uint8 at a multiple of 256
+        (default: allocated here).  No host sync behind the index."""
         self._is_bytes(d_file, "d_file", flat=True)
         dev = d_file.device
         if index is None:
@@ -593,7 +610,9 @@ class Engine(object):
         calls, e, end = [], first, first + count
         while e < end:
             if ok[e] and host["csize"][e] >= _lib.ZIP_LARGE_MIN:
-                calls.append((e, 1, int(host["csize"][e]) + 6, min((int(size[e]) + 3) & ~3, out.numel() - int(rel[e]))))
+                # (in_len sizes the decoder's scratch: a stored entry of a ZIP64 index, which may hold 4 GiB and more, is only copied)
+                il = 0 if index.zip64 and host["method"][e] == 0 else min(int(host["csize"][e]) + 6, 0xFFFFFFFF)
+                calls.append((e, 1, il, min((int(size[e]) + 3) & ~3, out.numel() - int(rel[e]))))
                 e += 1
                 continue
             b = e
@@ -601,14 +620,15 @@ class Engine(object):
                 e += 1
             cap = int(rel[e - 1] + size[e - 1] - rel[b])
             calls.append((b, e - b, 0, cap if e - b > 1 else min((cap + 3) & ~3, out.numel() - int(rel[b]))))      # (one entry: a row of whole words)
-        need = max([self.lib.hdlz_zip_inflate_work_bytes(c, il, cap) for _, c, il, cap in calls] + [0])
+        work_bytes, inflate, name = (self.lib.hdlz_zip64_inflate_work_bytes, self.lib.hdlz_zip64_inflate_ws, "hdlz_zip64_inflate_ws") if index.zip64 else \
+            (self.lib.hdlz_zip_inflate_work_bytes, self.lib.hdlz_zip_inflate_ws, "hdlz_zip_inflate_ws")
+        need = max([work_bytes(c, il, cap) for _, c, il, cap in calls] + [0])
         scratch = self._scratch(need, work, torch.uint8)
         results = torch.empty((max(len(calls), 1), 3), dtype=torch.int64, device=dev)
         for k, (b, c, il, cap) in enumerate(calls):
-            self._check(self.lib.hdlz_zip_inflate_ws(d_file.data_ptr(), d_file.numel(), index.entries.data_ptr(), b, c, il,
-                                                     out.data_ptr() + int(rel[b]) if out.numel() else None, cap,
-                                                     status.data_ptr() + 4 * (b - first), results[k].data_ptr(), scratch[1], scratch[2],
-                                                     self._stream()), "hdlz_zip_inflate_ws")
+            self._check(inflate(d_file.data_ptr(), d_file.numel(), index.entries.data_ptr(), b, c, il,
+                                out.data_ptr() + int(rel[b]) if out.numel() else None, cap,
+                                status.data_ptr() + 4 * (b - first), results[k].data_ptr(), scratch[1], scratch[2], self._stream()), name)
         return out[:total], out_off, status
 
     def read_zip_bytes(self, z):
@@ -632,7 +652,7 @@ class Engine(object):
 
     @_on_device
     def compress_zip(self, d_in, entry_lengths, names, block=1 << 16, cwindow=32, maxmatch=10, store=None, out=None,
-                     date_time=(1980, 1, 1, 0, 0, 0), out_align=1):
+                     date_time=(1980, 1, 1, 0, 0, 0), out_align=1, zip64="auto"):
         """d_in: flat uint8 device tensor, the entries' bytes one behind the other; entry_lengths: their lengths, a host sequence;
         names: their names (str, written as UTF-8 -- flag bit 11 is set when one of them is not ASCII -- or bytes)
         -> (file uint8[file_len], ZipIndex): a ZIP archive that zipfile, unzip and numpy.load read, and its index as zip_index would
@@ -643,18 +663,28 @@ class Engine(object):
         (crc32_batch; an entry of at least ZIP_CRC_TILED_MIN bytes by crc32, the whole GPU).  date_time: (year, month, day, hour,
         minute, second) of every entry.  `out`: the file's buffer (default: hdlz_zip_write_bound bytes).  One host sync (the record,
         with the entries' records behind it); raises HdlzStatusError -- with .first_bad, the lowest failed entry -- on a status that
-        is not OK."""
-        from .zip import ZipIndex, ENTRY_DTYPE, decode_name
+        is not OK.
+        zip64: "auto" -- hdlz_zip_write_ws, and so the bytes it always wrote, when there are at most 65535 entries and
+        hdlz_zip_write_bound(...) < 2^32 - 1; otherwise hdlz_zip64_write_ws (include/hdlz_zip64.h) with zip64_from = FFFFFFFF: ZIP64
+        fields only where the format needs them.  "always": zip64_from = 0; an integer up to FFFFFFFF is passed through as
+        zip64_from.  The index of the new call has .zip64 set and 64-byte records."""
+        from .zip import ZipIndex, ENTRY_DTYPE, ENTRY64_DTYPE, decode_name
         import numpy as np
+        if zip64 not in ("auto", "always") and not (isinstance(zip64, int) and not isinstance(zip64, bool) and 0 <= zip64 <= 0xFFFFFFFF):
+            raise ValueError("zip64 must be \"auto\", \"always\" or a zip64_from in [0, 0xFFFFFFFF], not %r" % (zip64,))
         z = self._zip_batch(d_in, entry_lengths, names, block, cwindow, maxmatch, store)
+        classic = self.lib.hdlz_zip_write_bound(z.E, z.B, block, z.total, z.names.numel())
+        z.zip64_from = None if zip64 == "auto" and z.E <= 65535 and classic < 0xFFFFFFFF else 0xFFFFFFFF if zip64 == "auto" else 0 if zip64 == "always" else zip64
+        wide = z.zip64_from is not None
         if out is None:
-            out = torch.empty(self.lib.hdlz_zip_write_bound(z.E, z.B, block, z.total, z.names.numel()), dtype=torch.uint8, device=d_in.device)
+            bound = self.lib.hdlz_zip64_write_bound(z.E, z.B, block, z.total, z.names.numel()) if wide else classic
+            out = torch.empty(bound, dtype=torch.uint8, device=d_in.device)
         rec, res, back = self._zip_write(z, out, date_time, out_align)
         _raise_unless_ok(rec, "compress_zip")
-        host = np.frombuffer(back.tobytes(), dtype=ENTRY_DTYPE)
+        host = np.frombuffer(back.tobytes(), dtype=ENTRY64_DTYPE if wide else ENTRY_DTYPE)
         total_out = int(host["out_off"][-1]) + int(host["usize"][-1]) if z.E else 0
         record = _lib.ZipIndexResult(z.E, total_out, rec.cd_off, rec.cd_size, OK, 0)
-        index = ZipIndex(res.view(z.E, 6), record, host, [n if isinstance(n, str) else decode_name(n, z.flags) for n in names], out_align)
+        index = ZipIndex(res.view(z.E, 8 if wide else 6), record, host, [n if isinstance(n, str) else decode_name(n, z.flags) for n in names], out_align, wide)
         index.write_record = rec
         return out[:rec.file_len], index
 
@@ -673,8 +703,6 @@ class Engine(object):
             raise ValueError("%d entries, %d names%s" % (E, len(names), "" if store is None else ", %d store flags" % len(store)))
         if min(lens, default=0) < 0 or sum(lens) != total:
             raise ValueError("the entries' lengths add up to %d bytes, d_in holds %d" % (sum(lens), total))
-        if E > 65535:
-            raise ValueError("%d entries: a ZIP without ZIP64 holds at most 65535" % E)
         if not 32 <= block < (1 << 31):
             raise ValueError("block must be in [32, 2^31)")
         raw = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
@@ -723,26 +751,32 @@ class Engine(object):
                                staged=staged)
 
     def _zip_write(self, z, out, date_time, out_align):
-        """hdlz_zip_write_ws over a _zip_batch into `out` -> (the record, the entries' records int64[6 E] on the device, the same on the
-        host): the record and the entries' records stand in one tensor and come back in one copy, the call's one host sync"""
+        """hdlz_zip_write_ws -- or, with z.zip64_from set, hdlz_zip64_write_ws -- over a _zip_batch into `out` -> (the record, the
+        entries' records int64[6 E] (int64[8 E]) on the device, the same on the host): the record and the entries' records stand in
+        one tensor and come back in one copy, the call's one host sync"""
         from .zip import dos_datetime
         self._is_bytes(out, "out", flat=True)
+        wide = getattr(z, "zip64_from", None) is not None
         nres = ctypes.sizeof(_lib.ZipWriteResult) // 8
-        res = torch.empty(nres + 6 * z.E, dtype=torch.int64, device=self.device)
-        scratch = self._scratch(self.lib.hdlz_zip_write_work_bytes(z.E, z.B), None)
+        res = torch.empty(nres + (8 if wide else 6) * z.E, dtype=torch.int64, device=self.device)
+        scratch = self._scratch((self.lib.hdlz_zip64_write_work_bytes if wide else self.lib.hdlz_zip_write_work_bytes)(z.E, z.B), None)
         ptr = lambda t: t.data_ptr() if z.B else None                    # (no blocks: the per-block arrays are null)
         some = lambda t: t.data_ptr() if t.numel() else z.staged.data_ptr()   # (no byte of an empty buffer is read: any address will do)
-        rc = self.lib.hdlz_zip_write_ws(some(z.d_in), z.ent_off.data_ptr(), some(z.names), z.name_off.data_ptr(), z.E, ptr(z.in_off), ptr(z.rows),
-                                        z.pitch, ptr(z.len), ptr(z.end_bits), ptr(z.status), z.B, z.blk_first.data_ptr(), z.crc.data_ptr(), z.flags,
-                                        dos_datetime(date_time), out_align, z.total, out.data_ptr() if out.numel() else None, out.numel(),
-                                        res[nres:].data_ptr() if z.E else None, res.data_ptr(), scratch[1], scratch[2], self._stream())
-        self._check(rc, "hdlz_zip_write_ws")
+        front = (some(z.d_in), z.ent_off.data_ptr(), some(z.names), z.name_off.data_ptr(), z.E, ptr(z.in_off), ptr(z.rows),
+                 z.pitch, ptr(z.len), ptr(z.end_bits), ptr(z.status), z.B, z.blk_first.data_ptr(), z.crc.data_ptr(), z.flags,
+                 dos_datetime(date_time), out_align)
+        back_ = (z.total, out.data_ptr() if out.numel() else None, out.numel(),
+                 res[nres:].data_ptr() if z.E else None, res.data_ptr(), scratch[1], scratch[2], self._stream())
+        if wide:
+            self._check(self.lib.hdlz_zip64_write_ws(*front, z.zip64_from, *back_), "hdlz_zip64_write_ws")
+        else:
+            self._check(self.lib.hdlz_zip_write_ws(*front, *back_), "hdlz_zip_write_ws")
         back = res.cpu().numpy()
         return _lib.ZipWriteResult.from_buffer_copy(back[:nres].tobytes()), res[nres:], back[nres:]
 
     def write_zip_bytes(self, files, **kw):
         """{name: bytes} -> the bytes of a ZIP archive holding them in that order, the counterpart of read_zip_bytes; the keywords of
-        compress_zip (block, cwindow, maxmatch, store, date_time) pass through"""
+        compress_zip (block, cwindow, maxmatch, store, date_time, zip64) pass through"""
         names = list(files)
         data = [bytes(files[n]) for n in names]
         d = self._stage(b"".join(data))[:sum(len(x) for x in data)]

@@ -118,8 +118,8 @@ def save_npz(engine, arrays, compressed=True, **kw):
     """{name: device tensor} -> a flat uint8 device tensor, the .npz file numpy.load and load_npz read (numpy.savez_compressed; with
     compressed=False every entry is stored, as numpy.savez does).  Per tensor a .npy version 1.0 header is made on the host by numpy's
     own writer -- a few bytes; all headers are staged in one copy --, the entry is that header and the tensor's bytes in C order, its
-    name `name + ".npy"`; the file is written by Engine.compress_zip, whose keywords (block, cwindow, maxmatch, date_time) pass
-    through.  No array byte crosses to the host."""
+    name `name + ".npy"`; the file is written by Engine.compress_zip, whose keywords (block, cwindow, maxmatch, date_time, zip64) pass
+    through: past 65535 arrays or 4 GiB the file is ZIP64, as numpy's own is.  No array byte crosses to the host."""
     import io
     import torch
     names, tensors, heads = [], [], []

@@ -7,6 +7,10 @@ import numpy as np
 ENTRY_DTYPE = np.dtype([("cd_off", "<u8"), ("payload_off", "<u8"), ("out_off", "<u8"), ("csize", "<u4"), ("usize", "<u4"), ("crc", "<u4"),
                         ("method", "<u2"), ("flags", "<u2"), ("name_len", "<u2"), ("reserved", "<u2"), ("status", "<u4")])
 assert ENTRY_DTYPE.itemsize == 48
+# hdlz_zip64_entry, 64 bytes (include/hdlz_zip64.h): the same names, so code that reads index.host[...] works on both
+ENTRY64_DTYPE = np.dtype([("cd_off", "<u8"), ("payload_off", "<u8"), ("out_off", "<u8"), ("csize", "<u8"), ("usize", "<u8"), ("crc", "<u4"),
+                          ("status", "<u4"), ("method", "<u2"), ("flags", "<u2"), ("name_len", "<u2"), ("reserved", "<u2"), ("reserved2", "<u8")])
+assert ENTRY64_DTYPE.itemsize == 64
 FLAG_UTF8 = 0x800
 
 
@@ -25,7 +29,9 @@ def dos_datetime(date_time):
 
 class ZipIndex(object):
     """The index of a ZIP file (Engine.zip_index).
-    entries    int64[k, 6] on the device: the k records of hdlz_zip_index_ws (48 bytes each), what Engine.inflate_zip passes on
+    entries    int64[k, 6] on the device: the k records of hdlz_zip_index_ws (48 bytes each), what Engine.inflate_zip passes on;
+               int64[k, 8] when zip64 is set: the records of hdlz_zip64_index_ws (64 bytes each, host: ENTRY64_DTYPE, the same names)
+    zip64      which of the two calls wrote the records
     record     the call's result record (_lib.ZipIndexResult: nentries, total_out, cd_off, cd_size, status)
     host       the records on the host, a numpy array of ENTRY_DTYPE (cd_off, payload_off, out_off, csize, usize, crc, method, flags,
                name_len, status)
@@ -35,8 +41,8 @@ class ZipIndex(object):
                file_len, cd_off, cd_size, nstored, status, first_bad); None for an index that was read"""
     write_record = None
 
-    def __init__(self, entries, record, host, names, out_align):
-        self.entries, self.record, self.host, self.names, self.out_align = entries, record, host, names, out_align
+    def __init__(self, entries, record, host, names, out_align, zip64=False):
+        self.entries, self.record, self.host, self.names, self.out_align, self.zip64 = entries, record, host, names, out_align, bool(zip64)
 
     def __len__(self):
         return len(self.host)

@@ -46,9 +46,10 @@
  * entries only.
  *
  * Out of scope: writing ZIP files (hdlz_zip_write.h, the extension of this header, does); ZIP64 (the locator is refused, FFFFFFFF sizes
- * and offsets fail the entry); encryption; methods other than 0 and 8; self-extracting prefixes (offsets count from the file's first
- * byte) and multi-disk archives; the lane and group mappings of the batch decoders; several large entries on the whole-GPU path in one
- * call (the caller makes one call per large entry: Engine.inflate_zip does).
+ * and offsets fail the entry: hdlz_zip64.h, the extension behind hdlz_zip_write.h, reads such files); encryption; methods other than
+ * 0 and 8; self-extracting prefixes (offsets count from the file's first byte) and multi-disk archives; the lane and group mappings
+ * of the batch decoders; several large entries on the whole-GPU path in one call (the caller makes one call per large entry:
+ * Engine.inflate_zip does).
  */
 #ifndef HDLZ_ZIP_H
 #define HDLZ_ZIP_H

@@ -49,9 +49,10 @@
  *      ready index --, also when the file did not fit.  When an entry failed: every record is zero but its status, which is the
  *      entry's own (HDLZ_OK for a sound one).
  *
- * Out of scope: ZIP64; data descriptors; extra fields and payload alignment (zipalign); comments; per-entry times or attributes;
- * encryption; appending to an existing archive; dynamic-tree blocks; a member-parallel read of this writer's own entries (the ZIP
- * carries no block index: hdlz_zip_inflate_ws reads an entry as any inflater does).
+ * Out of scope: ZIP64 (hdlz_zip64.h, the extension of this header, reads and writes it: hdlz_zip64_write_ws); data descriptors; extra fields
+ * and payload alignment (zipalign); comments; per-entry times or attributes; encryption; appending to an existing archive;
+ * dynamic-tree blocks; a member-parallel read of this writer's own entries (the ZIP carries no block index: hdlz_zip_inflate_ws
+ * reads an entry as any inflater does).
  */
 #ifndef HDLZ_ZIP_WRITE_H
 #define HDLZ_ZIP_WRITE_H
