@@ -27,8 +27,9 @@
 //   4. greedy parse ("di += m / di += 1", deflate.py:960,1008): every lane folds its run into a
 //      transfer function "entry skip (0..9) -> exit skip", 10 nibbles packed in 40 bits, by a
 //      backward pass; a 64-step scalar readlane chain composes them across the wave.
-//   5. token bits (R6/R7) from per-wave LDS look-up tables (literal: [byte] -> code|nbits, match:
-//      [len][dist] -> code|nbits), in-lane prefix sums + wave scan -> bit offsets, then every
+//   5. token bits (R6/R7) from per-wave LDS look-up tables (literal: [byte] -> code << 9 | nbits, match:
+//      [len][dist] -> code << 9 | nbits; the count in the LOW bits: a lane's bit count is the sum of its
+//      entries, masked once), wave scan -> bit offsets, then every
 //      token is OR-ed into an LDS bit buffer at its own bit offset (ds_or_b32), coalesced dword
 //      flush to HBM; the partial word is carried to the next tile.
 //   6. Adler-32 (R8) by per-lane byte sums / index-weighted sums (v_sad_u8 / v_dot4_u32_u8).

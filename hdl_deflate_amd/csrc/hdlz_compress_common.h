@@ -32,8 +32,17 @@ constexpr int LUT_MATCH = 256;      // [len-3][dist-1] (CWINDOW <= 32) or [dist-
 constexpr uint32_t LUT_MATCH_BYTE = 4u * LUT_LIT;
 constexpr int LUT_LEN = 16;         // [len-1] -> the length code (wide windows: the match LUT is [dist-1] only)   at LUT word 512
 constexpr uint32_t LUT_LEN_BYTE = 4u * (LUT_LIT + LUT_MATCH);
-constexpr uint32_t NB_SHIFT = 27;   // LUT entry = code (27 bits) | nbits << 27
-constexpr uint32_t CODE_MASK = (1u << NB_SHIFT) - 1u;
+// LUT entry = code << CODE_SHIFT | nbits << NB_SHIFT: the bit count in the LOW bits (0..4; 5..8 are zero), the code from bit 9 up.  A sum of
+// entries then carries the sum of their counts in its low 9 bits -- carries of the code field go upward only -- so token_codes adds
+// whole entries and masks once per lane instead of shifting and adding per position.  A lane's counts sum to at most 32 * 9 = 288 bits
+// (32 nine-bit literals; a match's 18 bits -- the widest, CWINDOW 256 -- cover at least three positions, 6 bits per position).
+// One entry's code is at most 18 bits: 9 + 18 = 27 bits of the word.
+constexpr uint32_t NB_SHIFT = 0;
+constexpr uint32_t CODE_SHIFT = 9;
+constexpr uint32_t NB_MASK = 31u << NB_SHIFT;                   // a count is at most 18
+constexpr uint32_t NB_SUM_MASK = ((1u << CODE_SHIFT) - 1u) << NB_SHIFT;      // the field a lane's sum of counts lives in
+static_assert(NB_SHIFT == 0 && 32u * 9u <= NB_SUM_MASK && 18u <= NB_MASK, "a lane's 288 bits at most fit below the code field; carries of the codes leave them alone");
+static_assert(CODE_SHIFT + 18u <= 32u, "the widest code (7 + 5 + 6 bits) inside the entry");
 
 struct __attribute__((aligned(16))) WaveLds {
     uint32_t in[IN_BYTES / 4];      // byte index = position - tile_start + HALO
@@ -131,7 +140,7 @@ __host__ __device__ constexpr uint32_t literal_entry(uint32_t b) {
     const bool big = b >= 144u;
     const uint32_t v = big ? (0x100u + b) : (0x30u + b);
     const uint32_t nb = big ? 9u : 8u;
-    return (__builtin_bitreverse32(v) >> (32u - nb)) | (nb << NB_SHIFT);
+    return ((__builtin_bitreverse32(v) >> (32u - nb)) << CODE_SHIFT) | (nb << NB_SHIFT);
 }
 // distance part of a match token (R6, deflate.py:836-882): rev5(dist code) | extra<<5 in 5+eb bits,
 // placed behind the 7-bit length code; nbits = 12 + eb
@@ -145,19 +154,20 @@ __host__ __device__ constexpr uint32_t dist_entry(uint32_t d) {
         extra = dd & ((1u << eb) - 1u);
     }
     const uint32_t dcode = __builtin_bitreverse32(c) >> 27;
-    return ((dcode | (extra << 5)) << 7) | ((12u + eb) << NB_SHIFT);
+    return (((dcode | (extra << 5)) << 7) << CODE_SHIFT) | ((12u + eb) << NB_SHIFT);
 }
-// 7-bit code of length symbol 254+m (no extra bits for m <= 10)
-__host__ __device__ constexpr uint32_t length_code(uint32_t m) { return __builtin_bitreverse32(m - 2u) >> 25; }
+// 7-bit code of length symbol 254+m (no extra bits for m <= 10), in the code field; it carries no count (dist_entry's covers it)
+__host__ __device__ constexpr uint32_t length_code(uint32_t m) { return (__builtin_bitreverse32(m - 2u) >> 25) << CODE_SHIFT; }
 // pinned against RFC 1951 3.2.5 / 3.2.6 (codes go out LSB first, so a Huffman code is stored bit-reversed; extra bits are not):
-static_assert(literal_entry(0) == (0x0Cu | 8u << NB_SHIFT), "literal 0: 8 bits, 00110000 reversed");
-static_assert(literal_entry(143) == (0xFDu | 8u << NB_SHIFT), "literal 143: 8 bits, 10111111 reversed");
-static_assert(literal_entry(144) == (0x13u | 9u << NB_SHIFT), "literal 144: 9 bits, 110010000 reversed");
-static_assert(literal_entry(255) == (0x1FFu | 9u << NB_SHIFT), "literal 255: 9 bits, all ones");
-static_assert(length_code(3) == 0x40u && length_code(10) == 0x08u, "lengths 3 / 10: symbols 257 / 264 = 7-bit codes 0000001 / 0001000 reversed");
+static_assert(literal_entry(0) == (0x0Cu << CODE_SHIFT | 8u << NB_SHIFT), "literal 0: 8 bits, 00110000 reversed");
+static_assert(literal_entry(143) == (0xFDu << CODE_SHIFT | 8u << NB_SHIFT), "literal 143: 8 bits, 10111111 reversed");
+static_assert(literal_entry(144) == (0x13u << CODE_SHIFT | 9u << NB_SHIFT), "literal 144: 9 bits, 110010000 reversed");
+static_assert(literal_entry(255) == (0x1FFu << CODE_SHIFT | 9u << NB_SHIFT), "literal 255: 9 bits, all ones");
+static_assert(length_code(3) == 0x40u << CODE_SHIFT && length_code(10) == 0x08u << CODE_SHIFT, "lengths 3 / 10: symbols 257 / 264 = 7-bit codes 0000001 / 0001000 reversed");
 static_assert(dist_entry(1) == (12u << NB_SHIFT), "distance 1: code 0, no extra bits: 7 + 5 bits");
-static_assert(dist_entry(5) == ((0x04u << 7) | 13u << NB_SHIFT), "distance 5: code 4 (00100), one extra bit 0");
-static_assert(dist_entry(32) == (((0x12u | 7u << 5) << 7) | 15u << NB_SHIFT), "distance 32: code 9 (01001 reversed), three extra bits 111");
+static_assert(dist_entry(5) == ((0x04u << 7) << CODE_SHIFT | 13u << NB_SHIFT), "distance 5: code 4 (00100), one extra bit 0");
+static_assert(dist_entry(32) == (((0x12u | 7u << 5) << 7) << CODE_SHIFT | 15u << NB_SHIFT), "distance 32: code 9 (01001 reversed), three extra bits 111");
+static_assert(dist_entry(256) == (((0x1Eu | 63u << 5) << 7) << CODE_SHIFT | 18u << NB_SHIFT), "distance 256: code 15 (01111 reversed), six extra bits 111111: the widest entry");
 
 // the LUT of the CWINDOW <= 32 kernels -- literal [byte] at word 0, match [len-3][dist-1] at word 256 -- depends on nothing: ONE constant
 // table.  The one-tile kernels with the bit search fetch it into LDS per tile (their LDS is the mismatch words until the extension is
@@ -346,6 +356,8 @@ __device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uin
 // (x0 .. x7: the lane's own 32 bytes as dwords, in registers)
 // KEEP: neq_d of every distance goes to neq_col[(d & 31) * 64] (neq_col = NEQ + lane: one ds_write_b32 at a fixed address register +
 // immediate offset, where neq is complete and before the DPP for nx) -- what make_tokens_bits reads instead of comparing bytes again
+// (Measured and dropped, profiles/tile_diet.txt: nx read back from that row -- ds_read_b32 at NEQ + min(lane + 1, 63), the reads of four
+// distances issued a group ahead -- instead of the DPP move: 32 slow instructions fewer, -0.01 .. -0.02 ms, inside the run-to-run spread.)
 // WORK THE DATA DOES NOT NEED is skipped by wave-uniform branches (the result is the same bit for bit):
 //   a DEAD PLANE  O_b is the same word s = 0 or 0xFFFFFFFF in all 64 lanes (bit 7 of ASCII text; three planes of decimal digits; seven of
 //           '0' / '1' text): then P_b = s and every candidate word C_b = s, so the plane adds nothing to any neq.  The planes are the
@@ -817,6 +829,8 @@ __device__ __forceinline__ void make_tokens(const uint32_t* in, uint32_t lds_run
 //          words themselves (end_cap_word: bit N - 2 - p_run of the lane that holds it, so ffbl(x) <= N - 5 - p wherever p is eligible;
 //          a lane whose word has no such bit has N - 2 - p_run >= 32 and N - 5 - p >= 7 >= Kmax - 3 for its i <= 22, and its i >= 23
 //          read on into the next lane's word, which carries the bit or leaves at least 7 again)
+//          (Measured and dropped, profiles/tile_diet.txt: the cap as a sentinel bit, ffbl(x | 1 << (Kmax - 3)), a v_or_b32 in place of the
+//          v_min_u32: 30 slow instructions fewer per tile and no difference in time)
 // Lane 0's bits j < d compare against lane 63's bytes (the search's rotate): a position i of lane 0 is eligible only for d <= i, and its
 // bits j >= i + 3 > d look at the block's own bytes.  11 VALU instructions per position (12 for i >= 23) against 22, one or two
 // conflict-free ds_read_b32 (bank = column, whatever the row) against three gathered dwords.
@@ -1051,13 +1065,18 @@ __device__ __forceinline__ uint32_t chain_skips_serial(uint64_t P, uint32_t lane
 }
 
 // ---- phase 5a, token bits (R6/R7; DISTANCE deflate.py:836-882, literal emit :1005-1016) from the per-wave LDS LUTs:
-// code[i] = LUT entry (code | nbits << 27) of every token START, 0 elsewhere; returns the lane's bit count.
+// code[i] = LUT entry (code << CODE_SHIFT | nbits) of every token START, 0 elsewhere; returns the lane's bit count.
 //   c0      this lane's entry skip (a value >= 32 = the lane starts no token at all)
 //   LIMIT   only positions i < nlimit may start a token (padding positions of a packed small block)
+// The bit count is the sum of the ENTRIES, masked once: the counts sit in the entries' low bits (NB_SUM_MASK), one v_add per position
+// (half a v_add3) where a count in the top bits cost a shift as well.
+// (Measured and dropped, profiles/tile_diet.txt: the start flag as a mask in a register -- (c - 4) >> 31, v_bitop3 select, v_and: 5.5
+// instructions per position, all of the 1.96-cycle class, where hipcc turns the selects below into a v_cmp and an exec-masked region
+// with five scalar instructions per position -- was 0.03 ms SLOWER on the headline, three runs against three.)
 template <int NCH, bool LIMIT>
 __device__ __forceinline__ uint32_t token_codes(const uint8_t* lut8, uint32_t (&tok)[RUN], uint32_t c0, uint32_t nlimit,
                                                 uint32_t (&code)[RUN]) {
-    uint32_t lane_bits = 0;
+    uint32_t acc = 0;                                         // sum of the entries: its NB_SUM_MASK field is the lane's bit count
     uint32_t c = 4u * c0;                                     // positions still covered by the last token, times four (the token word's unit)
     static_for<0, RUN>([&](auto I) {
         constexpr int i = decltype(I)::value;
@@ -1070,11 +1089,11 @@ __device__ __forceinline__ uint32_t token_codes(const uint8_t* lut8, uint32_t (&
         if constexpr (NCH != 1)                               // wide windows: [dist] LUT + the length code from its own small LUT
             ee |= *reinterpret_cast<const uint32_t*>(lut8 + LUT_LEN_BYTE + lenm1x4);        // (computed: six VALU instructions per position)
         code[i] = start ? ee : 0u;
-        lane_bits += code[i] >> NB_SHIFT;
+        acc += code[i];
         constexpr int CG = HDLZ_CODE_GROUP;
-        if constexpr ((i & (CG - 1)) == CG - 1) { pin_range<(i & ~(CG - 1)), (i & ~(CG - 1)) + CG>(code); asm volatile("" : "+v"(c), "+v"(lane_bits)); PHASE_FENCE(); }
+        if constexpr ((i & (CG - 1)) == CG - 1) { pin_range<(i & ~(CG - 1)), (i & ~(CG - 1)) + CG>(code); asm volatile("" : "+v"(c), "+v"(acc)); PHASE_FENCE(); }
     });
-    return lane_bits;
+    return (acc & NB_SUM_MASK) >> NB_SHIFT;
 }
 
 // inclusive wave scan (all 64 lanes must call it): Hillis-Steele inside the rows of 16 (row_shr 1, 2, 4, 8; a lane without a source adds 0),
@@ -1099,13 +1118,13 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
 __device__ __forceinline__ void scatter_codes(uint8_t* out8, const uint32_t (&code)[RUN], uint32_t bp) {
 #pragma unroll
     for (int i = 0; i < RUN; i += 2) {
-        const uint32_t n0 = code[i] >> NB_SHIFT;
-        const uint32_t c = ((code[i + 1] & CODE_MASK) << n0) | (code[i] & CODE_MASK);
+        const uint32_t n0 = (code[i] & NB_MASK) >> NB_SHIFT;
+        const uint32_t c = ((code[i + 1] >> CODE_SHIFT) << n0) | (code[i] >> CODE_SHIFT);
         const uint64_t v = (uint64_t)c << (bp & 31u);
         uint32_t* w = reinterpret_cast<uint32_t*>(out8 + ((bp >> 3) & ~3u));
         __hip_atomic_fetch_or(w, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_or(w + 1, (uint32_t)(v >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        bp += n0 + (code[i + 1] >> NB_SHIFT);
+        bp += n0 + ((code[i + 1] & NB_MASK) >> NB_SHIFT);
         if ((i & 6) == 6) { asm volatile("" : "+v"(bp)); PHASE_FENCE(); }
     }
 }
