@@ -34,6 +34,18 @@ def gunzip_work_bytes(nstreams, in_len, out_pitch, ragged=False):
     return _lib.load().hdlz_gunzip_work_bytes(nstreams, in_len, out_pitch, 1 if ragged else 0)
 
 
+def gzip_members_index_work_bytes(file_len):
+    """the scratch hdlz_gzip_members_index_ws asks for (hdlz_gzip_members_index_work_bytes: host arithmetic of the library)"""
+    from . import _lib
+    return _lib.load().hdlz_gzip_members_index_work_bytes(file_len)
+
+
+def gzip_members_inflate_work_bytes(nmembers):
+    """the scratch hdlz_gzip_members_inflate_ws asks for (hdlz_gzip_members_inflate_work_bytes) -- Engine.inflate_gzip_members's `work`"""
+    from . import _lib
+    return _lib.load().hdlz_gzip_members_inflate_work_bytes(nmembers)
+
+
 def Engine(*a, **kw):
     """The HIP batch engine (imports torch lazily)."""
     from .engine import Engine as _E

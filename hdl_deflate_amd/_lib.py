@@ -135,6 +135,16 @@ ZIP64_SIGNATURES = {
     "hdlz_zip64_write_ws": (ci, [vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u32, u32, u32, u64, u64, vp, u64, vp, vp, vp, sz, vp]),
 }
 ZIP64_EXPORTS = tuple(ZIP64_SIGNATURES)
+# ... and of include/hdlz_gzip_members.h: a gzip file of many members, indexed by a guess and read verified (tests/test_gzip_members_cabi.py)
+GZIP_MEMBERS_SIGNATURES = {
+    "hdlz_gzip_members_index_work_bytes": (sz, [u64]),
+    # d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, work_bytes, stream
+    "hdlz_gzip_members_index_ws": (ci, [vp, u64, u64, vp, vp, vp, vp, sz, vp]),
+    "hdlz_gzip_members_inflate_work_bytes": (sz, [u64]),
+    # d_file, file_len, d_off, d_out_off, nmembers, d_out, out_cap, d_member_status, d_result, d_work, work_bytes, stream
+    "hdlz_gzip_members_inflate_ws": (ci, [vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, sz, vp]),
+}
+GZIP_MEMBERS_EXPORTS = tuple(GZIP_MEMBERS_SIGNATURES)
 _lib = None
 
 
@@ -189,6 +199,16 @@ class BgzfRangesResult(ctypes.Structure):
     _fields_ = [("total_out", u64), ("ntasks", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
 
 
+class GzipMembersIndexResult(ctypes.Structure):
+    """hdlz_gzip_members_index_result: the result record of hdlz_gzip_members_index_ws (24 bytes)"""
+    _fields_ = [("nmembers", u64), ("total_out", u64), ("status", u32), ("reserved", u32)]
+
+
+class GzipMembersInflateResult(ctypes.Structure):
+    """hdlz_gzip_members_inflate_result: the result record of hdlz_gzip_members_inflate_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class ZipEntry(ctypes.Structure):
     """hdlz_zip_entry: one record of hdlz_zip_index_ws (48 bytes)"""
     _fields_ = [("cd_off", u64), ("payload_off", u64), ("out_off", u64), ("csize", u32), ("usize", u32), ("crc", u32),
@@ -238,7 +258,8 @@ def load():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
-            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()):
+            list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()) + \
+            list(GZIP_MEMBERS_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -770,6 +770,62 @@ int hdlz_gunzip_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pi
     return launched(hdlz::launch_gunzip_judge(g, st), "launch k_gunzip_judge");
 }
 
+// ---- include/hdlz_gzip_members.h: a gzip file of many members, indexed by a guess and read verified (hdlz_gzip_members.hip)
+size_t hdlz_gzip_members_index_work_bytes(uint64_t file_len) { return hdlz::gzip_members_index_work_bytes(file_len); }
+
+int hdlz_gzip_members_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off,
+                               hdlz_gzip_members_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (any_null(d_off, d_out_off, d_result) || (file_len && !d_file)) return fail_param("null device pointer");
+    if (member_cap >= (1ull << 40)) return fail_param("member_cap too large (below 2^40)");
+    if (work_too_small(hdlz::gzip_members_index_work_bytes(file_len), d_work, work_bytes, "hdlz_gzip_members_index_work_bytes(file_len)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_off, d_out_off, d_result, d_work)) return fail_align(8, "d_off / d_out_off / d_result / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_gzip_members_index(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream)),
+                    "launch k_gzm_scan");
+}
+
+// The scratch of hdlz_gzip_members_inflate_ws, laid out once for the size query and the call: five words per member (length, status,
+// end bit, p, the CRC-32), then the decoder's view: m_off and m_end of nmembers words, m_out_off of nmembers + 1.  No members: no scratch.
+struct GzipMembersScratch {
+    uint32_t *len, *status, *end_bit, *p, *crc;
+    uint64_t *m_off, *m_end, *m_out_off;
+    size_t bytes;
+};
+static GzipMembersScratch gzip_members_scratch(void* base, uint64_t nmembers) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const size_t n = (size_t)nmembers, per = hdlz::round256(20u * n), idx = hdlz::round256(24u * n + 8u);
+    auto words = [&](size_t k) { return reinterpret_cast<uint32_t*>(b + 4u * k * n); };
+    uint64_t* const v = reinterpret_cast<uint64_t*>(b + per);
+    return {words(0), words(1), words(2), words(3), words(4), v, v + n, v + 2u * n, n ? per + idx : 0u};
+}
+size_t hdlz_gzip_members_inflate_work_bytes(uint64_t nmembers) {
+    return nmembers > 0x7FFFFFFFull ? 0u : gzip_members_scratch(nullptr, nmembers).bytes;
+}
+
+int hdlz_gzip_members_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_off, const uint64_t* d_out_off, uint64_t nmembers,
+                                 uint8_t* d_out, uint64_t out_cap, uint32_t* d_member_status, hdlz_gzip_members_inflate_result* d_result,
+                                 void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || (nmembers && any_null(d_file, d_off, d_out_off)) || (out_cap && !d_out)) return fail_param("null device pointer");
+    if (nmembers > 0x7FFFFFFFull) return fail_param("nmembers too large for one call (2^31 - 1 members)");
+    if (misaligned(8, d_off, d_out_off, d_result)) return fail_align(8, "d_off / d_out_off / d_result");
+    if (misaligned(4, d_member_status)) return fail_align(4, "d_member_status");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    const GzipMembersScratch s = gzip_members_scratch(d_work, nmembers);
+    if (work_too_small(s.bytes, d_work, work_bytes, "hdlz_gzip_members_inflate_work_bytes(nmembers)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const hdlz::GzipMembersArgs u{d_file, file_len, d_off, d_out_off, nmembers, out_cap, d_member_status, d_result, s.len, s.status, s.end_bit,
+                                  s.p, s.crc, s.m_off, s.m_end, s.m_out_off};
+    if (nmembers) {
+        if (const int rc = launched(hdlz::launch_gzip_members_heads(u, st), "launch k_gzm_heads"); rc != HDLZ_OK) return rc;
+        hdlz::MemberArgs a = member_args(d_file, nmembers, 0, d_out, u.len, u.status, u.end_bit, u.m_off);   // (BFINAL is honoured)
+        a.m_end = u.m_end; a.m_out_off = u.m_out_off; a.m_out_cap = out_cap;
+        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+        if (const int rc = launched(hdlz::launch_crc32_batch(d_out, u.m_out_off, 0, 0, nmembers, u.crc, u.status, st), "launch k_crc32_batch"); rc != HDLZ_OK) return rc;
+    }
+    return launched(hdlz::launch_gzip_members_judge(u, st), "launch k_gzm_judge");
+}
+
 // ---- include/hdlz_zip.h: ZIP archives, the directory indexed and the entries read on the device (hdlz_zip.hip)
 size_t hdlz_zip_index_work_bytes(uint64_t file_len, uint64_t entry_cap) {
     (void)entry_cap;

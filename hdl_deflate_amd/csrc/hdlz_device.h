@@ -7,6 +7,7 @@
 #include "../../include/hdlz_bgzf_range.h"   // (includes hdlz_bgzf.h, hdlz_gzip.h, hdlz_unjoin.h, hdlz_join.h and hdlz.h)
 #include "../../include/hdlz_bgzf_stored.h"
 #include "../../include/hdlz_gunzip.h"
+#include "../../include/hdlz_gzip_members.h"
 #include "../../include/hdlz_zip.h"
 #include "../../include/hdlz_zip_write.h"
 #include "../../include/hdlz_zip64.h"
@@ -342,6 +343,32 @@ size_t gunzip_tile_words(uint64_t nstreams, uint64_t out_pitch);
 hipError_t launch_gunzip_heads(const GunzipArgs& a, hipStream_t stream);
 hipError_t launch_gunzip_crc(const GunzipArgs& a, hipStream_t stream);
 hipError_t launch_gunzip_judge(const GunzipArgs& a, hipStream_t stream);
+
+// hdlz_gzip_members.hip: the member index of a plain gzip file and what hdlz_gzip_members_inflate_ws runs around the member decode
+// (include/hdlz_gzip_members.h)
+size_t gzip_members_index_work_bytes(uint64_t file_len);
+hipError_t launch_gzip_members_index(const uint8_t* file, uint64_t file_len, uint64_t member_cap, uint64_t* off, uint64_t* out_off,
+                                     hdlz_gzip_members_index_result* result, void* work, hipStream_t stream);
+struct GzipMembersArgs {
+    const uint8_t* in;
+    uint64_t in_len;             // file_len
+    const uint64_t* off;
+    const uint64_t* out_off;
+    uint64_t nmembers;
+    uint64_t out_cap;
+    uint32_t* member_status;     // nullable
+    hdlz_gzip_members_inflate_result* result;
+    uint32_t* len;               // scratch, per member, as in BgzfArgs: the decoded length / the workgroup's lowest failed member
+    uint32_t* status;            // ... the index checks and the header's verdict, then the decoder's status, then the verdict
+    uint32_t* end_bit;
+    uint32_t* p;                 // ... the offset of the first payload byte
+    uint32_t* crc;               // ... the CRC-32 of the slot
+    uint64_t* m_off;             // scratch, per member: MemberArgs::m_off (off[b] + p)
+    uint64_t* m_end;             // ... MemberArgs::m_end (off[b + 1])
+    uint64_t* m_out_off;         // scratch, nmembers + 1 words: out_off[b] - out_off[0]
+};
+hipError_t launch_gzip_members_heads(const GzipMembersArgs& a, hipStream_t stream);
+hipError_t launch_gzip_members_judge(const GzipMembersArgs& a, hipStream_t stream);
 
 // hdlz_zip.hip: hdlz_zip_index_ws and what hdlz_zip_inflate_ws runs around the decode (include/hdlz_zip.h)
 size_t zip_index_work_bytes();

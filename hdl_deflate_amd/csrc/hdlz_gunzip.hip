@@ -2,7 +2,8 @@
 // stream's gzip member in front of it, the CRC-32 of every decoded row and the verdict behind it.  The decode itself is an existing
 // kernel either way (hdlz_api.hip): the member view of the wave-per-stream decoder, or -- one stream -- the batch call's own path.
 //
-// k_gunzip_heads      a wave per stream: the RFC 1952 header in the order of the member rule.  The zero bytes that end FNAME and
+// k_gunzip_heads      a wave per stream: the RFC 1952 header in the order of the member rule (walk and wave_crc32 of hdlz_gzip_walk.h,
+//                     which hdlz_gzip_members.hip shares).  The zero bytes that end FNAME and
 //                     FCOMMENT are found 64 bytes a step (bounds-checked byte loads, one ballot); FHCRC, when its flag is set, is the
 //                     CRC-32 of the header bytes in front of it, a strip per lane and a tree over the wave (crc_byte, crc_mul and
 //                     crc_xpow of hdlz_crc32.h: no table).  Writes p, the header's verdict and the decoder's view of the stream.
@@ -15,11 +16,11 @@
 #include <stdint.h>
 #include "hdlz_device.h"
 #include "hdlz_crc32.h"
+#include "hdlz_gzip_walk.h"
 
 namespace hdlz {
 namespace gunzip {
 
-constexpr uint32_t FHCRC = 2u, FEXTRA = 4u, FNAME = 8u, FCOMMENT = 16u, FRESERVED = 0xE0u;      // (FTEXT, bit 0, is ignored)
 constexpr uint32_t ROWS_MAX = 65536u;          // rows of at least this capacity take the tiles mapping (two tiles and more)
 
 __device__ __forceinline__ void stream_of(const GunzipArgs& a, uint64_t b, uint64_t& start, uint64_t& len) {
@@ -29,58 +30,6 @@ __device__ __forceinline__ void stream_of(const GunzipArgs& a, uint64_t b, uint6
 __device__ __forceinline__ uint32_t row_len(const GunzipArgs& a, uint64_t b) {
     const uint32_t cap = a.out_pitch > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)a.out_pitch, n = a.out_len[b];
     return n < cap ? n : cap;
-}
-
-// the crc32 of z[0 .. H) by one wave -> every lane's return value.  Lane l runs the strip [l S, (l + 1) S) of the bytes RIGHT-aligned
-// in 64 S (the zero bytes in front are free), a bit a step; the tree multiplies the earlier neighbour by x^(8 S 2^k), as crc_tile_word does
-__device__ __forceinline__ uint32_t wave_crc32(const uint8_t* __restrict__ z, uint32_t H) {
-    const uint32_t lane = threadIdx.x & 63u, S = (H + 63u) >> 6, pad = 64u * S - H;
-    uint32_t c = 0;
-    for (uint32_t v = lane * S; v < (lane + 1u) * S; v++)
-        if (v >= pad) c = crc_byte(c, z[v - pad]);
-    uint32_t m = crc_xpow(8ull * S);
-#pragma unroll
-    for (uint32_t k = 0; k < 6u; k++) {
-        c = crc_mul(c, m) ^ (uint32_t)__shfl_down((int)c, 1u << k, 64);
-        m = crc_mul(m, m);
-    }
-    c = (uint32_t)__shfl((int)c, 0, 64);
-    return c ^ crc_mul(CRC_INIT, crc_xpow(8ull * H)) ^ CRC_INIT;
-}
-
-// the header walk of one member: z[0 .. len) -> the verdict; p = the offset of the first payload byte when it is HDLZ_OK
-__device__ __forceinline__ uint32_t walk(const uint8_t* __restrict__ z, uint64_t len, uint64_t& p) {
-    const uint32_t lane = threadIdx.x & 63u;
-    if (len < 10u) return HDLZ_E_NO_EOF;
-    const uint32_t flg = z[3];
-    if (z[0] != 0x1Fu || z[1] != 0x8Bu || z[2] != 8u || (flg & FRESERVED)) return HDLZ_E_BAD_HEADER;
-    uint64_t pos = 10u;                                   // (MTIME, XFL, OS: skipped)
-    if (flg & FEXTRA) {
-        if (pos + 2u > len) return HDLZ_E_NO_EOF;
-        const uint32_t xlen = (uint32_t)z[pos] | ((uint32_t)z[pos + 1u] << 8);
-        pos += 2u;
-        if (pos + xlen > len) return HDLZ_E_NO_EOF;
-        pos += xlen;
-    }
-#pragma unroll 1
-    for (uint32_t field = FNAME; field <= FCOMMENT; field <<= 1) {
-        if (!(flg & field)) continue;
-        for (;;) {                                        // 64 bytes a step; nothing at or behind len is loaded
-            if (pos >= len) return HDLZ_E_NO_EOF;         // unterminated
-            const uint64_t q = pos + lane;
-            const uint64_t zero = ballot64(q < len && z[q] == 0u);
-            if (zero) { pos += (uint32_t)__builtin_ctzll(zero) + 1u; break; }
-            pos += 64u;
-        }
-    }
-    if (flg & FHCRC) {
-        if (pos + 2u > len) return HDLZ_E_NO_EOF;
-        const uint32_t want = (uint32_t)z[pos] | ((uint32_t)z[pos + 1u] << 8);
-        if ((wave_crc32(z, (uint32_t)pos) & 0xFFFFu) != want) return HDLZ_E_BAD_HEADER;
-        pos += 2u;
-    }
-    p = pos;
-    return HDLZ_OK;
 }
 
 __global__ __launch_bounds__(64) void k_gunzip_heads(GunzipArgs a) {

@@ -887,6 +887,171 @@ class Engine(object):
             pos += int(used.item())
         return OK, b"".join(pieces)
 
+    # -- gzip files of many members: found, decoded and verified in one pass (include/hdlz_gzip_members.h)
+    # read_gzip: spans from here on take the one-stream route.  ONE member costs its wave about 0.18 us a compressed byte and the
+    # one-stream route 0.6 to 0.8 ms up to 512 KiB (profiles/gzip_members.txt, section 4): alone, a member is faster there from
+    # between 4 and 7.5 KiB on.  But the waves of a file run side by side and the one-stream calls one behind the other, three
+    # host syncs each, so M members of S bytes are faster by waves while S is below M times that span.  The default is the
+    # smallest power of two above BGZF's largest member (64 KiB), so that blocked files never leave the wave route: there a
+    # wave (23 ms) costs some 33 one-stream calls.
+    GZIP_BIG_MEMBER = 1 << 17
+
+    @_on_device
+    def gzip_index(self, d_file, member_cap=None):
+        """d_file: flat uint8 device tensor, a gzip file of any number of members -> (member_offsets int64[M + 1], out_offsets
+        int64[M + 1], record): the GUESS of hdlz_gzip_members_index_ws -- every position that looks like a member header (and position
+        0) starts a member, and the word in front of the next one is taken for its ISIZE.  The read verifies it (inflate_gzip_members).
+        The record is a _lib.GzipMembersIndexResult (nmembers, total_out, status).  One host sync for the record.  member_cap: room for
+        that many members (default: a guess, file_len // 4096 + 16); when the file holds more, the call is made once more with the
+        true count."""
+        self._is_bytes(d_file, "d_file", flat=True)
+        n, dev = d_file.numel(), d_file.device
+        cap = n // 4096 + 16 if member_cap is None else int(member_cap)
+        scratch = self._scratch(self.lib.hdlz_gzip_members_index_work_bytes(n), None)
+        while True:
+            off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            rec = self._record("hdlz_gzip_members_index_ws", _lib.GzipMembersIndexResult, scratch, d_file.data_ptr() if n else None, n, cap,
+                               off.data_ptr(), out_off.data_ptr())
+            if rec.status != E_OUT_CAPACITY or rec.nmembers <= cap:
+                return off[:rec.nmembers + 1], out_off[:rec.nmembers + 1], rec
+            cap = rec.nmembers
+
+    def _gzip_members_call(self, d_file, off, out_off, B, out, out_cap, status, work=None):
+        """one hdlz_gzip_members_inflate_ws, enqueued: no host read -> the record's device tensor"""
+        result = torch.empty(ctypes.sizeof(_lib.GzipMembersInflateResult) // 8, dtype=torch.int64, device=self.device)
+        work, wptr, wbytes = self._scratch(self.lib.hdlz_gzip_members_inflate_work_bytes(B), work, torch.uint8)
+        self._check(self.lib.hdlz_gzip_members_inflate_ws(d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B,
+                                                          out.data_ptr() if out_cap else None, out_cap, status.data_ptr() if B else None,
+                                                          result.data_ptr(), wptr, wbytes, self._stream()), "hdlz_gzip_members_inflate_ws")
+        return result
+
+    @_on_device
+    def inflate_gzip_members(self, d_file, index=None, members=None, out=None, work=None):
+        """the raw verified read of hdlz_gzip_members_inflate_ws: d_file as in gzip_index, index: its (member_offsets, out_offsets)
+        (default: taken here), members=(b0, b1): only those -> (out uint8[total], member_status int32[B], record): member b's bytes
+        are out[out_offsets[b] - out_offsets[b0] : out_offsets[b + 1] - out_offsets[b0]] where member_status[b] is OK; every other
+        member is one the guess got wrong or the file has damaged -- no repair here, and nothing is raised on a member's status
+        (read_gzip repairs).  The record is a _lib.GzipMembersInflateResult (out_len, first_bad, status).  `work`: the call's scratch,
+        a uint8 device tensor of at least hdlz_gzip_members_inflate_work_bytes(b1 - b0) bytes at a multiple of 256."""
+        self._is_bytes(d_file, "d_file", flat=True)
+        dev = d_file.device
+        off, out_off = (self.gzip_index(d_file)[:2]) if index is None else (index[0], index[1])
+        _is_index(off)
+        _is_index(out_off, off.numel())
+        M = off.numel() - 1
+        b0, b1 = (0, M) if members is None else (int(members[0]), int(members[1]))
+        if not 0 <= b0 <= b1 <= M:
+            raise ValueError("members=(%d, %d) is not a range of the file's %d members" % (b0, b1, M))
+        off, out_off, B = off[b0:b1 + 1], out_off[b0:b1 + 1], b1 - b0
+        total = int((out_off[B] - out_off[0]).item()) if B else 0
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out", room=total)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        result = self._gzip_members_call(d_file, off, out_off, B, out, total, status, work)
+        return out[:total], status, _lib.GzipMembersInflateResult.from_buffer_copy(result.cpu().numpy().tobytes())
+
+    def _gzip_one(self, d_file, pos, tail_isize):
+        """one iteration of inflate_gzip_bytes's loop at `pos`: the one-stream call (a large member: the whole GPU), with that loop's
+        capacities -> (status, the member's bytes on the device, bytes consumed)"""
+        rest = d_file.numel() - pos
+        bound = inflate_cap(rest)
+        isize = tail_isize if rest >= 4 else bound
+        for cap in ([isize, bound] if isize < bound else [bound]):
+            out, ol, st, used, _ = self.inflate_gzip(d_file[pos:pos + rest], in_len=rest, nblocks=1, out_pitch=max(16, (cap + 15) // 16 * 16))
+            st = int(st.item())
+            if st != E_OUT_CAPACITY:
+                break
+        return (st, None, 0) if st != OK else (st, out[0, :int(ol.item())], int(used.item()))
+
+    @_on_device
+    def read_gzip(self, d_file, big_member=None):
+        """d_file: flat uint8 device tensor, a .gz file of any number of members of any writer -> (out uint8[n] on the device, report),
+        with inflate_gzip_bytes's acceptance (gzip.decompress's: members back to back, zero bytes behind a member ignored, anything
+        else E_BAD_HEADER) but the members found and decoded in parallel: one gzip_index call, the verified read of every run of
+        spans below `big_member` compressed bytes (default GZIP_BIG_MEMBER) enqueued without a sync in between, one D2H of the
+        statuses (and one of the index's two arrays, which the walk below bisects).  Verified members are taken from where they lie.  Where the walk meets a member that did not verify -- a look-alike
+        header split it, padding stands behind it, it is damaged -- or a span of big_member bytes and more, ONE iteration of
+        inflate_gzip_bytes's loop runs there (the one-stream inflate_gzip call, then the skip of zero bytes) and the walk resumes at
+        the candidate that stands where it ended; where none stands there the same call is made anyway and its answer is the file's.
+        report: .status (OK: out is the data; else out is empty), .members (delivered), .candidates (of the index), .repairs and .big
+        (one-stream calls of either kind), .member_status (numpy int32[candidates]; -1: not sent to the verified read)."""
+        import bisect
+        import types
+        import numpy as np
+        self._is_bytes(d_file, "d_file", flat=True)
+        n, dev = d_file.numel(), d_file.device
+        big_member = self.GZIP_BIG_MEMBER if big_member is None else int(big_member)
+        off, out_off, rec = self.gzip_index(d_file)
+        M = int(rec.nmembers)
+        h_off, h_out = off.cpu().tolist(), out_off.cpu().tolist()
+        is_big = [h_off[b + 1] - h_off[b] >= big_member for b in range(M)]
+        status = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        runs, b = {}, 0                                   # first member of a run -> (its last + 1, its output)
+        while b < M:
+            if is_big[b]:
+                b += 1
+                continue
+            e = b
+            while e < M and not is_big[e]:
+                e += 1
+            total = h_out[e] - h_out[b]
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+            self._gzip_members_call(d_file, off[b:e + 1], out_off[b:e + 1], e - b, out, total, status[b:e])
+            for k in range(b, e):
+                runs[k] = (b, out)
+            b = e
+        h_status = status.cpu().numpy()                   # the one D2H of the statuses
+        report = types.SimpleNamespace(status=OK, members=0, candidates=M, repairs=0, big=0, member_status=h_status)
+        tail_isize = int.from_bytes(bytes(d_file[n - 4:].cpu().numpy().tobytes()), "little") if n >= 4 else 0
+        pieces, pos = [], 0
+        while pos < n:
+            if report.members:                            # zero bytes behind a member are padding
+                while pos < n:
+                    nz = torch.nonzero(d_file[pos:pos + (1 << 20)])
+                    if nz.numel():
+                        pos += int(nz[0].item())
+                        break
+                    pos = min(n, pos + (1 << 20))
+                if pos == n:
+                    break
+            b = bisect.bisect_left(h_off, pos, 0, M)
+            b = b if b < M and h_off[b] == pos else None
+            if b is not None and h_status[b] == OK:
+                e = b
+                while e < M and h_status[e] == OK:
+                    e += 1
+                b0, out = runs[b]
+                pieces.append(out[h_out[b] - h_out[b0]:h_out[e] - h_out[b0]])
+                report.members += e - b
+                pos = h_off[e]
+                continue
+            st, out, used = self._gzip_one(d_file, pos, tail_isize)
+            if b is not None and is_big[b]:
+                report.big += 1
+            else:
+                report.repairs += 1
+            if st != OK:
+                rest = n - pos
+                if report.members and rest < 10 and not b"\x1f\x8b\x08".startswith(bytes(d_file[pos:pos + 3].cpu().numpy().tobytes())):
+                    st = E_BAD_HEADER                     # (as inflate_gzip_bytes: too short for the device to look at the magic)
+                report.status = st
+                return torch.empty(0, dtype=torch.uint8, device=dev), report
+            pieces.append(out)
+            report.members += 1
+            pos += used
+        if len(pieces) == 1:
+            return pieces[0], report
+        return (torch.cat(pieces) if pieces else torch.empty(0, dtype=torch.uint8, device=dev)), report
+
+    def read_gzip_bytes(self, z, big_member=None):
+        """the bytes of a .gz file -> (status, bytes): what inflate_gzip_bytes answers wherever that is not E_OUT_CAPACITY, through
+        read_gzip -- a launch chain for the whole file, not one per member"""
+        d = self._stage(z)[:len(z)]
+        out, report = self.read_gzip(d, big_member=big_member)
+        return report.status, bytes(out.cpu().numpy().tobytes()) if report.status == OK else b""
+
     # -- archive compaction (SURVEY 8(f) rank 2)
     @_on_device
     def compact(self, rows, lens, offsets=None, archive=None):

@@ -55,7 +55,8 @@
  * reads:  only bytes of the streams themselves, at any alignment; of row b only bytes below d_out_len[b] (whole 16-byte pieces where
  *         they lie inside them, single bytes else): nothing behind the decoded length reaches a result.
  *
- * Out of scope: several members of one stream decoded in one call (the caller moves on by d_in_used); the lane and group mappings for
+ * Out of scope: several members of one stream decoded in one call (the caller moves on by d_in_used; a file of many members is taken
+ * up by hdlz_gzip_members.h, which finds and verifies them in parallel); the lane and group mappings for
  * batches (the member twins of k_inflate_tok and k_inflate_grp have no dynamic-tree pass) and the whole-GPU path for more than one
  * stream per call; obsize and HDLZ_INFLATE_ASSUME_FIXED semantics; writing header fields of other writers; ZIP archives (taken up by
  * hdlz_zip.h).
