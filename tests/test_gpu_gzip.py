@@ -65,8 +65,9 @@ def device_crcs(L, d_buf, cases):
 
 @pytest.mark.parametrize("kind", ["random", "zeros", "ff"])
 def test_crc32_against_zlib(engine, kind):
-    """every length 0 .. 80, the lengths around a strip, a wave's share and a tile, whole tiles, and 257 / 513 / 1000 tiles plus 7 bytes
-    (a second Horner step in the finishing workgroup from 1024 words on); base pointers 0, 1, 4 and 15 bytes off a 16-byte boundary.
+    """every length 0 .. 80, the lengths around a strip, a wave's share and a tile, whole tiles, and 257 / 513 / 1000 tiles plus 7 bytes:
+    one tile a workgroup and one word a thread of the finishing workgroup (the second tile of a workgroup, from 1025 tiles on, and the
+    second Horner step, from 1024 tiles on: tests/test_gpu_second_trips.py); base pointers 0, 1, 4 and 15 bytes off a 16-byte boundary.
     The slices lie inside one larger buffer: a load in front of the data or behind it would change the random case."""
     h = host_data(kind)
     d = dev(h)
