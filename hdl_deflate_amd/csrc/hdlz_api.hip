@@ -53,7 +53,12 @@ int check_device() {
 }
 
 // ---- The vocabulary of the parameter checks.  Every entry point states its OWN sequence of checks, one `if (...) return ...;` line
-// each, in front of check_device(); what a check tests and how its refusal reads is written here once.
+// each, in front of check_device(); what a check tests and how its refusal reads is written here once.  Twins -- two entry points
+// whose sequences are the same line for line -- share one body (join_checks, member_index_impl, zip_index_impl, zip_inflate_impl,
+// zip_write_impl); nothing else is shared, and no table drives a check.
+// Behind the checks, what the container readers share is written once as well: Carver lays out a call's scratch (the size query and
+// the call go through the same function), decode_members is the wave-per-member decode of a call's MemberView (with the CRC-32 of
+// what decoded, where asked), inflate_one the batch call's path for a call of one stream.
 template <class... P>
 bool any_null(const P*... p) { return (... || !p); }
 // is one of the pointers off a multiple of k (a power of two)?  A null pointer is aligned.
@@ -91,18 +96,57 @@ int join_checks(bool null_pointer, uint64_t nblocks, const void* d_off, const vo
     if (misaligned(4, d_crc)) return fail_align(4, "d_crc");
     return HDLZ_OK;
 }
+// hdlz_bgzf_index_ws and hdlz_gzip_members_index_ws (include/hdlz_gzip_members.h): the member index of a file, by either scan
+template <class Result>
+int member_index_impl(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off, Result* d_result,
+                      void* d_work, size_t work_bytes, void* stream, size_t need, const char* query,
+                      hipError_t (*launch)(const uint8_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, Result*, void*, hipStream_t), const char* kernel) {
+    if (any_null(d_off, d_out_off, d_result) || (file_len && !d_file)) return fail_param("null device pointer");
+    if (member_cap >= (1ull << 40)) return fail_param("member_cap too large (below 2^40)");
+    if (work_too_small(need, d_work, work_bytes, query)) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_off, d_out_off, d_result, d_work)) return fail_align(8, "d_off / d_out_off / d_result / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(launch(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream)), kernel);
+}
 // the scratch of a call: the caller's buffer (the _ws entry points), or the library's stream-ordered pool
 hdlz::Work caller_work(void* d_work, size_t work_bytes) { return hdlz::Work{static_cast<uint8_t*>(d_work), d_work ? work_bytes : 0u, true}; }
 hdlz::Work pooled_work() { return hdlz::Work{nullptr, 0u, false}; }
-// The member view of one flat input (hdlz::MemberArgs): n members at m_off, decoded into `out`, the three result arrays in scratch.
-// What the three callers differ in stays with them: m_out_off / m_out_len / m_out_cap, m_gap, the task view.
-hdlz::MemberArgs member_args(const uint8_t* in, uint64_t n, uint32_t flags, uint8_t* out, uint32_t* len, uint32_t* status, uint32_t* end_bit,
-                             const uint64_t* m_off) {
-    hdlz::MemberArgs a;
-    a.in = in; a.in_off = nullptr; a.in_pitch = 0; a.in_len = 0; a.nstreams = n; a.flags = flags; a.obsize = 0;
-    a.out = out; a.out_pitch = 0; a.out_len = len; a.status = status; a.in_used = end_bit;
-    a.m_off = m_off; a.m_out_off = nullptr; a.m_out_len = 0; a.m_out_cap = 0;
+// A call's scratch, carved front to back.  The base is an integer: the size query carves from 0 through the same function as the
+// call, and bytes() is its answer.  Pieces are packed; align256() starts the next one on a multiple of 256 bytes.
+struct Carver {
+    uintptr_t base;
+    size_t at = 0;
+    template <class T> T* take(size_t count) { const size_t o = at; at += sizeof(T) * count; return reinterpret_cast<T*>(base + o); }
+    void align256() { at = hdlz::round256(at); }
+    size_t bytes() const { return at; }
+};
+uintptr_t address(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+// what a layout that ends in a decoder's share answers: the bytes of it all, and the offset from which that share takes what is left
+struct Laid { size_t bytes, decode; };
+// What a caller's view of the member decoders differs in: the fields of hdlz::MemberArgs of the same names, and the decoder's flags
+// (0: BFINAL is honoured, a member may hold any number of blocks of any type).  m_dst and m_dst_cap: the task view.
+struct MemberView {
+    const uint64_t *m_off, *m_end = nullptr, *m_out_off = nullptr;
+    uint64_t m_out_cap = 0;
+    uint32_t m_out_len = 0, m_gap = 0;
+    uint8_t* const* m_dst = nullptr;
+    const uint32_t* m_dst_cap = nullptr;
+    uint32_t flags = 0;
+};
+// The member view of one flat input (hdlz::MemberArgs): n members seen through v, decoded into `out`, the three result arrays in scratch.
+hdlz::MemberArgs member_args(const uint8_t* in, uint64_t n, uint8_t* out, uint32_t* len, uint32_t* status, uint32_t* end_bit, const MemberView& v) {
+    hdlz::MemberArgs a{};
+    a.in = in; a.nstreams = n; a.flags = v.flags; a.out = out; a.out_len = len; a.status = status; a.in_used = end_bit;
+    a.m_off = v.m_off; a.m_end = v.m_end; a.m_out_off = v.m_out_off; a.m_out_len = v.m_out_len; a.m_out_cap = v.m_out_cap; a.m_gap = v.m_gap;
+    a.m_dst = v.m_dst; a.m_dst_cap = v.m_dst_cap;
     return a;
+}
+// One decode step: a wave per member (k_inflate_dyn's member twin) over the n members of `in` seen through v.  crc: then the CRC-32 of
+// what every member decoded, out + m_out_off[b] on, into crc[b] -- a member whose status is not HDLZ_OK is skipped.
+int decode_members(const uint8_t* in, uint64_t n, uint8_t* out, uint32_t* len, uint32_t* status, uint32_t* end_bit, const MemberView& v, hipStream_t st,
+                   uint32_t* crc = nullptr) {
+    if (const int rc = launched(hdlz::launch_inflate_dyn_members(member_args(in, n, out, len, status, end_bit, v), st), "launch the member decode"); rc != HDLZ_OK) return rc;
+    return crc ? launched(hdlz::launch_crc32_batch(out, v.m_out_off, 0, 0, n, crc, status, st), "launch k_crc32_batch") : HDLZ_OK;
 }
 }  // namespace
 
@@ -330,6 +374,14 @@ int inflate_batch_impl(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t i
     return launched(nstreams > 0xFFFFFFFFull ? hdlz::launch_inflate_dyn(a, st, false) : hdlz::launch_inflate_tok_dyn(a, st, false, w),
                     "launch the dynamic-tree pass");
 }
+// One stream (the .gz file of hdlz_gunzip_ws, the large entry of hdlz_zip_inflate_ws): the batch call's path over the two-word ragged
+// index `idx` that the call's checks left on the device -- the whole-GPU chains for a large stream, their fallbacks, the wave for a
+// small one.  in_len is the bound the call was given; the path takes what is left of the caller's scratch from `decode` on.
+int inflate_one(const uint8_t* d_in, const uint64_t* idx, uint32_t in_len, uint8_t* d_out, uint64_t row, uint32_t* d_out_len, uint32_t* d_status,
+                uint32_t* d_in_used, void* d_work, size_t work_bytes, size_t decode, void* stream) {
+    return inflate_batch_impl(d_in, idx, 0, in_len, 1, 0, 0, d_out, row, d_out_len, d_status,
+                              caller_work(static_cast<uint8_t*>(d_work) + decode, work_bytes - decode), stream, d_in_used);
+}
 }  // namespace
 
 extern "C" {
@@ -481,23 +533,19 @@ int hdlz_inflate_chunk(const uint8_t* d_in, uint32_t in_len, int final, uint32_t
 // ---- include/hdlz_unjoin.h: a joined stream read back member by member (the member view of the batch decoders; hdlz_unjoin.hip)
 // (and include/hdlz_gzip.h: the gzip form differs in the checksum's share of the scratch and in what runs behind the decode)
 // The scratch of hdlz_unjoin_ws / hdlz_unjoin_gzip_ws, laid out ONCE for the size query and the call: three words per member (length,
-// status, end bit), the checksum's words per 32 KiB tile of the output (gzip: one CRC word; zlib: an (A, C) pair), the decoder's share.
-struct UnjoinScratch {
-    uint32_t *len, *status, *end_bit;
-    uint2* tiles;
-    size_t decode;               // the offset of the decoder's share: it takes what is left from there
-    size_t bytes;
-};
-static UnjoinScratch unjoin_scratch(void* base, uint64_t nmembers, uint64_t total_out, uint32_t flags, bool gzip) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);       // (integer arithmetic: the size query lays out from a null base)
-    const size_t per = hdlz::round256(12u * (size_t)nmembers);
-    const size_t tiles = gzip ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(total_out)) : hdlz::round256(sizeof(uint2) * hdlz::unjoin_tiles(total_out));
-    auto words = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * nmembers)); };
-    return {words(0), words(1), words(2), reinterpret_cast<uint2*>(b + per), per + tiles,
-            per + tiles + hdlz::round256(hdlz_inflate_work_bytes(nmembers, 0, 0, flags, 1))};
+// status, end bit), the checksum's words per 32 KiB tile of the output (gzip: one CRC word; zlib: an (A, C) pair), the decoder's share,
+// which takes what is left from `decode` on.
+static Laid unjoin_layout(hdlz::UnjoinArgs& u, uintptr_t base, uint32_t flags, bool gzip) {
+    Carver c{base};
+    u.len = c.take<uint32_t>(u.nmembers); u.status = c.take<uint32_t>(u.nmembers); u.end_bit = c.take<uint32_t>(u.nmembers); c.align256();
+    u.tiles = gzip ? reinterpret_cast<uint2*>(c.take<uint32_t>(hdlz::crc32_tiles(u.out_cap))) : c.take<uint2>(hdlz::unjoin_tiles(u.out_cap)); c.align256();
+    const size_t decode = c.bytes();
+    c.take<uint8_t>(hdlz::round256(hdlz_inflate_work_bytes(u.nmembers, 0, 0, flags, 1)));
+    return {c.bytes(), decode};
 }
 static size_t unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags, bool gzip) {
-    return nmembers > 0x7FFFFFFFull ? 0u : unjoin_scratch(nullptr, nmembers, total_out, flags, gzip).bytes;
+    hdlz::UnjoinArgs u{nullptr, 0, nullptr, nullptr, 0, nmembers, nullptr, total_out};
+    return nmembers > 0x7FFFFFFFull ? 0u : unjoin_layout(u, 0, flags, gzip).bytes;
 }
 size_t hdlz_unjoin_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) { return unjoin_work_bytes(nmembers, total_out, flags, false); }
 size_t hdlz_unjoin_gzip_work_bytes(uint64_t nmembers, uint64_t total_out, uint32_t flags) { return unjoin_work_bytes(nmembers, total_out, flags, true); }
@@ -512,20 +560,19 @@ static int unjoin_impl(const uint8_t* d_stream, uint64_t stream_len, const uint6
     if (misaligned(4, d_out)) return fail_align(4, "d_out");
     if (misaligned(8, d_off, d_out_off, d_result)) return fail_align(8, "d_off / d_out_off / d_result");
     if (misaligned(256, d_work)) return fail_align(256, "d_work");
-    const UnjoinScratch s = unjoin_scratch(d_work, nmembers, out_cap, flags, gzip);
-    if (work_too_small(s.bytes, d_work, work_bytes, gzip ? "hdlz_unjoin_gzip_work_bytes(nmembers, out_cap, flags)" : "hdlz_unjoin_work_bytes(nmembers, out_cap, flags)"))
-        return HDLZ_E_BAD_PARAM;
+    hdlz::UnjoinArgs u{d_stream, stream_len, d_off, d_out_off, out_len, nmembers, d_out, out_cap, d_member_status, d_result};
+    const Laid l = unjoin_layout(u, address(d_work), flags, gzip);
+    if (work_too_small(l.bytes, d_work, work_bytes,
+                       gzip ? "hdlz_unjoin_gzip_work_bytes(nmembers, out_cap, flags)" : "hdlz_unjoin_work_bytes(nmembers, out_cap, flags)")) return HDLZ_E_BAD_PARAM;
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const hdlz::UnjoinArgs u{d_stream, stream_len, d_off, d_out_off, out_len, nmembers, d_out, out_cap, d_member_status, d_result,
-                             s.len, s.status, s.end_bit, s.tiles};
     if (const int rc = launched(hdlz::launch_unjoin_index(u, st), "launch k_unjoin_index"); rc != HDLZ_OK) return rc;
     if (nmembers) {
-        hdlz::MemberArgs a = member_args(d_stream, nmembers, HDLZ_INFLATE_ONEBLOCK, d_out, u.len, u.status, u.end_bit, d_off);   // (BFINAL is not read: a member is one block)
-        a.m_out_off = d_out_off; a.m_out_len = out_len; a.m_out_cap = out_cap;
+        const MemberView v{d_off, nullptr, d_out_off, out_cap, out_len, 0, nullptr, nullptr, HDLZ_INFLATE_ONEBLOCK};   // (BFINAL is not read: a member is one block)
+        const hdlz::MemberArgs a = member_args(d_stream, nmembers, d_out, u.len, u.status, u.end_bit, v);
         // the mapping: the thresholds of hdlz_inflate_batch_ws, or the hint; never the whole-GPU chains
         const Mapping map = mapping_of(nmembers, flags);
-        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
+        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + l.decode, work_bytes - l.decode);
         if (const int rc = launched(map == Mapping::wave ? hdlz::launch_inflate_dyn_members(a, st) : map == Mapping::group ? hdlz::launch_inflate_grp_members(a, st)
                                                                                                             : hdlz::launch_inflate_tok_members(a, st, w),
                       "launch the member decode"); rc != HDLZ_OK) return rc;
@@ -623,33 +670,22 @@ size_t hdlz_bgzf_index_work_bytes(uint64_t file_len) { return hdlz::bgzf_index_w
 
 int hdlz_bgzf_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off,
                        hdlz_bgzf_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
-    if (any_null(d_off, d_out_off, d_result) || (file_len && !d_file)) return fail_param("null device pointer");
-    if (member_cap >= (1ull << 40)) return fail_param("member_cap too large (below 2^40)");
-    const size_t need = hdlz::bgzf_index_work_bytes(file_len);
-    if (work_too_small(need, d_work, work_bytes, "hdlz_bgzf_index_work_bytes(file_len)")) return HDLZ_E_BAD_PARAM;
-    if (misaligned(8, d_off, d_out_off, d_result, d_work)) return fail_align(8, "d_off / d_out_off / d_result / d_work");
-    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
-    return launched(hdlz::launch_bgzf_index(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream)),
-                    "launch k_bgzf_scan");
+    return member_index_impl(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, work_bytes, stream, hdlz::bgzf_index_work_bytes(file_len),
+                             "hdlz_bgzf_index_work_bytes(file_len)", hdlz::launch_bgzf_index, "launch k_bgzf_scan");
 }
 
 // The scratch of hdlz_bgzf_inflate_ws, laid out once for the size query and the call: three words per member (length, status, end bit),
 // the two shifted offset arrays of nmembers + 1 words (BgzfArgs::m_off, m_out_off), one CRC word per member.  No members: no scratch.
-struct BgzfScratch {
-    uint32_t *len, *status, *end_bit;
-    uint64_t *m_off, *m_out_off;
-    uint32_t* crc;
-    size_t bytes;
-};
-static BgzfScratch bgzf_inflate_scratch(void* base, uint64_t nmembers) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
-    const size_t per = hdlz::round256(12u * (size_t)nmembers), idx = hdlz::round256(16u * ((size_t)nmembers + 1u));
-    auto words = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * nmembers)); };
-    return {words(0), words(1), words(2), reinterpret_cast<uint64_t*>(b + per), reinterpret_cast<uint64_t*>(b + per + 8u * ((size_t)nmembers + 1u)),
-            reinterpret_cast<uint32_t*>(b + per + idx), nmembers ? per + idx + hdlz::round256(4u * (size_t)nmembers) : 0u};
+static size_t bgzf_inflate_layout(hdlz::BgzfArgs& u, uintptr_t base) {
+    Carver c{base};
+    u.len = c.take<uint32_t>(u.nmembers); u.status = c.take<uint32_t>(u.nmembers); u.end_bit = c.take<uint32_t>(u.nmembers); c.align256();
+    u.m_off = c.take<uint64_t>(u.nmembers + 1u); u.m_out_off = c.take<uint64_t>(u.nmembers + 1u); c.align256();
+    u.crc = c.take<uint32_t>(u.nmembers); c.align256();
+    return u.nmembers ? c.bytes() : 0u;
 }
 size_t hdlz_bgzf_inflate_work_bytes(uint64_t nmembers, uint32_t flags) {
-    return nmembers > 0x7FFFFFFFull || flags != 0u ? 0u : bgzf_inflate_scratch(nullptr, nmembers).bytes;
+    hdlz::BgzfArgs u{nullptr, 0, nullptr, nullptr, nmembers};
+    return nmembers > 0x7FFFFFFFull || flags != 0u ? 0u : bgzf_inflate_layout(u, 0);
 }
 
 int hdlz_bgzf_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_off, const uint64_t* d_out_off, uint64_t nmembers,
@@ -660,18 +696,14 @@ int hdlz_bgzf_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_
     if (flags != 0u) return fail_param("flags must be 0 (hdlz_bgzf_inflate_ws decodes a wave per member: the mapping hints do not apply)");
     if (misaligned(8, d_off, d_out_off, d_result)) return fail_align(8, "d_off / d_out_off / d_result");
     if (misaligned(256, d_work)) return fail_align(256, "d_work");
-    const BgzfScratch s = bgzf_inflate_scratch(d_work, nmembers);
-    if (work_too_small(s.bytes, d_work, work_bytes, "hdlz_bgzf_inflate_work_bytes(nmembers, flags)")) return HDLZ_E_BAD_PARAM;
+    hdlz::BgzfArgs u{d_file, file_len, d_off, d_out_off, nmembers, d_out, out_cap, d_member_status, d_result};
+    if (work_too_small(bgzf_inflate_layout(u, address(d_work)), d_work, work_bytes, "hdlz_bgzf_inflate_work_bytes(nmembers, flags)")) return HDLZ_E_BAD_PARAM;
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const hdlz::BgzfArgs u{d_file, file_len, d_off, d_out_off, nmembers, d_out, out_cap, d_member_status, d_result, s.len, s.status, s.end_bit,
-                           s.m_off, s.m_out_off, s.crc};
     if (const int rc = launched(hdlz::launch_bgzf_check(u, st), "launch k_bgzf_check"); rc != HDLZ_OK) return rc;
     if (nmembers) {
-        hdlz::MemberArgs a = member_args(d_file, nmembers, 0, d_out, u.len, u.status, u.end_bit, u.m_off);   // (BFINAL is honoured: a member may hold any number of blocks of any type)
-        a.m_out_off = u.m_out_off; a.m_out_cap = out_cap; a.m_gap = 18u;
-        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
-        if (const int rc = launched(hdlz::launch_crc32_batch(d_out, u.m_out_off, 0, 0, nmembers, u.crc, u.status, st), "launch k_crc32_batch"); rc != HDLZ_OK) return rc;
+        const MemberView v{u.m_off, nullptr, u.m_out_off, out_cap, 0, 18u};                      // (m_gap: the next member's header)
+        if (const int rc = decode_members(d_file, nmembers, d_out, u.len, u.status, u.end_bit, v, st, u.crc); rc != HDLZ_OK) return rc;
     }
     return launched(hdlz::launch_bgzf_judge(u, st), "launch k_bgzf_judge");
 }
@@ -702,9 +734,8 @@ int hdlz_bgzf_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uin
     u.range_off = d_range_off; u.range_status = d_range_status; u.task_cap = task_cap; u.result = d_result;
     if (const int rc = launched(hdlz::launch_bgzf_ranges_plan(u, st), "launch the plan kernels (k_ranges_resolve, k_ranges_scan, k_ranges_expand)"); rc != HDLZ_OK) return rc;
     if (nranges && task_cap) {
-        hdlz::MemberArgs a = member_args(d_file, task_cap, 0, d_out, u.t_len, u.t_status, u.t_end_bit, u.t_off);   // (slots behind ntasks are marked as refused)
-        a.m_end = u.t_end; a.m_dst = u.t_dst; a.m_dst_cap = u.t_cap;                               // the task view
-        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+        const MemberView v{u.t_off, u.t_end, nullptr, 0, 0, 0, u.t_dst, u.t_cap};                 // the task view (slots behind ntasks are marked as refused)
+        if (const int rc = decode_members(d_file, task_cap, d_out, u.t_len, u.t_status, u.t_end_bit, v, st); rc != HDLZ_OK) return rc;
     }
     return launched(hdlz::launch_bgzf_ranges_finish(u, st),
                     "launch the finish kernels (k_ranges_crc, k_ranges_judge, k_ranges_slice, k_ranges_finish, k_ranges_record)");
@@ -714,24 +745,20 @@ int hdlz_bgzf_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uin
 // The scratch of hdlz_gunzip_ws, laid out once for the size query and the call: three words per stream (p, the header's verdict, the
 // CRC-32), the decoder's view of 2 nstreams offsets, one CRC word per 32 KiB tile of row capacity where the rows are tiled, and -- one
 // stream -- the share of the batch call's path, which takes what is left from `decode` on.
-struct GunzipScratch {
-    uint32_t *p, *verdict, *crcw;
-    uint64_t* idx;
-    uint32_t* tiles;
-    size_t decode;
-    size_t bytes;
-};
-static GunzipScratch gunzip_scratch(void* base, uint64_t nstreams, uint32_t in_len, uint64_t out_pitch) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
-    const size_t per = hdlz::round256(12u * (size_t)nstreams), idx = hdlz::round256(16u * (size_t)nstreams);
-    const size_t words = hdlz::gunzip_tile_words(nstreams, out_pitch), tiles = hdlz::round256(sizeof(uint32_t) * words);
-    auto words_at = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * nstreams)); };
-    return {words_at(0), words_at(1), words_at(2), reinterpret_cast<uint64_t*>(b + per), words ? reinterpret_cast<uint32_t*>(b + per + idx) : nullptr,
-            per + idx + tiles, per + idx + tiles + (nstreams == 1 ? hdlz::round256(hdlz_inflate_work_bytes(1, in_len, out_pitch, 0, 1)) : 0u)};
+static Laid gunzip_layout(hdlz::GunzipArgs& g, uintptr_t base) {
+    Carver c{base};
+    g.p = c.take<uint32_t>(g.nstreams); g.verdict = c.take<uint32_t>(g.nstreams); g.crcw = c.take<uint32_t>(g.nstreams); c.align256();
+    g.idx = c.take<uint64_t>(2u * g.nstreams); c.align256();
+    const size_t words = hdlz::gunzip_tile_words(g.nstreams, g.out_pitch);
+    g.tiles = words ? c.take<uint32_t>(words) : nullptr; c.align256();
+    const size_t decode = c.bytes();
+    if (g.nstreams == 1) c.take<uint8_t>(hdlz::round256(hdlz_inflate_work_bytes(1, g.in_len, g.out_pitch, 0, 1)));
+    return {c.bytes(), decode};
 }
 size_t hdlz_gunzip_work_bytes(uint64_t nstreams, uint32_t in_len, uint64_t out_pitch, int ragged) {
     if (nstreams == 0 || nstreams > 0x7FFFFFFFull || (!ragged && in_len >= 0x10000000u) || (nstreams > 1 && out_pitch > 0xFFFFFFFFull)) return 0;
-    return gunzip_scratch(nullptr, nstreams, in_len, out_pitch).bytes;
+    hdlz::GunzipArgs g{nullptr, nullptr, 0, in_len, nstreams, nullptr, out_pitch};
+    return gunzip_layout(g, 0).bytes;
 }
 
 int hdlz_gunzip_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pitch, uint32_t in_len, uint64_t nstreams, uint8_t* d_out,
@@ -747,24 +774,19 @@ int hdlz_gunzip_ws(const uint8_t* d_in, const uint64_t* d_in_off, uint64_t in_pi
     if (misaligned(8, d_in_off)) return fail_align(8, "d_in_off");
     if (misaligned(4, d_out_len, d_status, d_in_used, d_crc)) return fail_align(4, "d_out_len / d_status / d_in_used / d_crc");
     if (misaligned(256, d_work)) return fail_align(256, "d_work");
-    const GunzipScratch s = gunzip_scratch(d_work, nstreams, in_len, out_pitch);
-    if (nstreams && work_too_small(s.bytes, d_work, work_bytes, "hdlz_gunzip_work_bytes(nstreams, in_len, out_pitch, ragged)")) return HDLZ_E_BAD_PARAM;
+    hdlz::GunzipArgs g{d_in, d_in_off, in_pitch, in_len, nstreams, d_out, out_pitch, d_out_len, d_status, d_in_used, d_crc};
+    const Laid l = gunzip_layout(g, address(d_work));
+    if (nstreams && work_too_small(l.bytes, d_work, work_bytes, "hdlz_gunzip_work_bytes(nstreams, in_len, out_pitch, ragged)")) return HDLZ_E_BAD_PARAM;
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     if (nstreams == 0) return HDLZ_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool single = nstreams == 1;
-    const hdlz::GunzipArgs g{d_in, d_in_off, in_pitch, in_len, nstreams, d_out, out_pitch, d_out_len, d_status, d_in_used, d_crc,
-                             s.p, s.verdict, s.crcw, s.idx, s.tiles, single};
+    const bool single = g.single = nstreams == 1;
     if (const int rc = launched(hdlz::launch_gunzip_heads(g, st), "launch k_gunzip_heads"); rc != HDLZ_OK) return rc;
-    if (single) {
-        // the .gz file: the batch call's path over the two-word index the header walk left on the device -- the whole-GPU chains for
-        // a large stream, their fallbacks, the wave for a small one; in_len is the bound the call was given
-        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
-        if (const int rc = inflate_batch_impl(d_in, s.idx, 0, in_len, 1, 0, 0, d_out, out_pitch, d_out_len, d_status, w, stream, d_in_used); rc != HDLZ_OK) return rc;
+    if (single) {                                                                                 // the .gz file
+        if (const int rc = inflate_one(d_in, g.idx, in_len, d_out, out_pitch, d_out_len, d_status, d_in_used, d_work, work_bytes, l.decode, stream); rc != HDLZ_OK) return rc;
     } else {
-        hdlz::MemberArgs a = member_args(d_in, nstreams, 0, d_out, d_out_len, d_status, d_in_used, s.idx);   // (BFINAL is honoured)
-        a.m_end = s.idx + nstreams; a.m_out_len = (uint32_t)out_pitch; a.m_out_cap = nstreams * out_pitch;
-        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+        const MemberView v{g.idx, g.idx + nstreams, nullptr, nstreams * out_pitch, (uint32_t)out_pitch};   // (rows: member b decodes to d_out + b * out_pitch)
+        if (const int rc = decode_members(d_in, nstreams, d_out, d_out_len, d_status, d_in_used, v, st); rc != HDLZ_OK) return rc;
     }
     if (const int rc = launched(hdlz::launch_gunzip_crc(g, st), "launch k_gunzip_crc_*"); rc != HDLZ_OK) return rc;
     return launched(hdlz::launch_gunzip_judge(g, st), "launch k_gunzip_judge");
@@ -775,31 +797,22 @@ size_t hdlz_gzip_members_index_work_bytes(uint64_t file_len) { return hdlz::gzip
 
 int hdlz_gzip_members_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t member_cap, uint64_t* d_off, uint64_t* d_out_off,
                                hdlz_gzip_members_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
-    if (any_null(d_off, d_out_off, d_result) || (file_len && !d_file)) return fail_param("null device pointer");
-    if (member_cap >= (1ull << 40)) return fail_param("member_cap too large (below 2^40)");
-    if (work_too_small(hdlz::gzip_members_index_work_bytes(file_len), d_work, work_bytes, "hdlz_gzip_members_index_work_bytes(file_len)")) return HDLZ_E_BAD_PARAM;
-    if (misaligned(8, d_off, d_out_off, d_result, d_work)) return fail_align(8, "d_off / d_out_off / d_result / d_work");
-    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
-    return launched(hdlz::launch_gzip_members_index(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, static_cast<hipStream_t>(stream)),
-                    "launch k_gzm_scan");
+    return member_index_impl(d_file, file_len, member_cap, d_off, d_out_off, d_result, d_work, work_bytes, stream, hdlz::gzip_members_index_work_bytes(file_len),
+                             "hdlz_gzip_members_index_work_bytes(file_len)", hdlz::launch_gzip_members_index, "launch k_gzm_scan");
 }
 
 // The scratch of hdlz_gzip_members_inflate_ws, laid out once for the size query and the call: five words per member (length, status,
 // end bit, p, the CRC-32), then the decoder's view: m_off and m_end of nmembers words, m_out_off of nmembers + 1.  No members: no scratch.
-struct GzipMembersScratch {
-    uint32_t *len, *status, *end_bit, *p, *crc;
-    uint64_t *m_off, *m_end, *m_out_off;
-    size_t bytes;
-};
-static GzipMembersScratch gzip_members_scratch(void* base, uint64_t nmembers) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
-    const size_t n = (size_t)nmembers, per = hdlz::round256(20u * n), idx = hdlz::round256(24u * n + 8u);
-    auto words = [&](size_t k) { return reinterpret_cast<uint32_t*>(b + 4u * k * n); };
-    uint64_t* const v = reinterpret_cast<uint64_t*>(b + per);
-    return {words(0), words(1), words(2), words(3), words(4), v, v + n, v + 2u * n, n ? per + idx : 0u};
+static size_t gzip_members_layout(hdlz::GzipMembersArgs& u, uintptr_t base) {
+    Carver c{base};
+    u.len = c.take<uint32_t>(u.nmembers); u.status = c.take<uint32_t>(u.nmembers); u.end_bit = c.take<uint32_t>(u.nmembers);
+    u.p = c.take<uint32_t>(u.nmembers); u.crc = c.take<uint32_t>(u.nmembers); c.align256();
+    u.m_off = c.take<uint64_t>(u.nmembers); u.m_end = c.take<uint64_t>(u.nmembers); u.m_out_off = c.take<uint64_t>(u.nmembers + 1u); c.align256();
+    return u.nmembers ? c.bytes() : 0u;
 }
 size_t hdlz_gzip_members_inflate_work_bytes(uint64_t nmembers) {
-    return nmembers > 0x7FFFFFFFull ? 0u : gzip_members_scratch(nullptr, nmembers).bytes;
+    hdlz::GzipMembersArgs u{nullptr, 0, nullptr, nullptr, nmembers};
+    return nmembers > 0x7FFFFFFFull ? 0u : gzip_members_layout(u, 0);
 }
 
 int hdlz_gzip_members_inflate_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_off, const uint64_t* d_out_off, uint64_t nmembers,
@@ -810,69 +823,58 @@ int hdlz_gzip_members_inflate_ws(const uint8_t* d_file, uint64_t file_len, const
     if (misaligned(8, d_off, d_out_off, d_result)) return fail_align(8, "d_off / d_out_off / d_result");
     if (misaligned(4, d_member_status)) return fail_align(4, "d_member_status");
     if (misaligned(256, d_work)) return fail_align(256, "d_work");
-    const GzipMembersScratch s = gzip_members_scratch(d_work, nmembers);
-    if (work_too_small(s.bytes, d_work, work_bytes, "hdlz_gzip_members_inflate_work_bytes(nmembers)")) return HDLZ_E_BAD_PARAM;
+    hdlz::GzipMembersArgs u{d_file, file_len, d_off, d_out_off, nmembers, out_cap, d_member_status, d_result};
+    if (work_too_small(gzip_members_layout(u, address(d_work)), d_work, work_bytes, "hdlz_gzip_members_inflate_work_bytes(nmembers)")) return HDLZ_E_BAD_PARAM;
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const hdlz::GzipMembersArgs u{d_file, file_len, d_off, d_out_off, nmembers, out_cap, d_member_status, d_result, s.len, s.status, s.end_bit,
-                                  s.p, s.crc, s.m_off, s.m_end, s.m_out_off};
     if (nmembers) {
         if (const int rc = launched(hdlz::launch_gzip_members_heads(u, st), "launch k_gzm_heads"); rc != HDLZ_OK) return rc;
-        hdlz::MemberArgs a = member_args(d_file, nmembers, 0, d_out, u.len, u.status, u.end_bit, u.m_off);   // (BFINAL is honoured)
-        a.m_end = u.m_end; a.m_out_off = u.m_out_off; a.m_out_cap = out_cap;
-        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
-        if (const int rc = launched(hdlz::launch_crc32_batch(d_out, u.m_out_off, 0, 0, nmembers, u.crc, u.status, st), "launch k_crc32_batch"); rc != HDLZ_OK) return rc;
+        const MemberView v{u.m_off, u.m_end, u.m_out_off, out_cap};
+        if (const int rc = decode_members(d_file, nmembers, d_out, u.len, u.status, u.end_bit, v, st, u.crc); rc != HDLZ_OK) return rc;
     }
     return launched(hdlz::launch_gzip_members_judge(u, st), "launch k_gzm_judge");
 }
 
-// ---- include/hdlz_zip.h: ZIP archives, the directory indexed and the entries read on the device (hdlz_zip.hip; DESIGN.md 4.6i)
-size_t hdlz_zip_index_work_bytes(uint64_t file_len, uint64_t entry_cap) {
-    (void)entry_cap;
-    return file_len > 0xFFFFFFFFull ? 0u : hdlz::zip_index_work_bytes();
-}
-
-int hdlz_zip_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip_entry* d_entries,
-                      hdlz_zip_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+}  // extern "C"
+// hdlz_zip_index_ws and hdlz_zip64_index_ws (include/hdlz_zip64.h; Rec: hdlz_zip_entry or hdlz_zip64_entry): the classic form ends at
+// 2^32 bytes and records, the wide one at 2^31 records
+template <class Rec>
+static int zip_index_impl(const uint8_t* d_file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, Rec* d_entries, hdlz_zip_index_result* d_result,
+                          void* d_work, size_t work_bytes, void* stream, size_t need, const char* query,
+                          hipError_t (*launch)(const uint8_t*, uint64_t, uint64_t, uint32_t, Rec*, hdlz_zip_index_result*, void*, hipStream_t), const char* kernel) {
+    constexpr bool wide = sizeof(Rec) != sizeof(hdlz_zip_entry);
     if (!d_result || (file_len && !d_file)) return fail_param("null device pointer");
     if (entry_cap && !d_entries) return fail_param("d_entries is null with entry_cap > 0");
-    if (file_len > 0xFFFFFFFFull) return fail_param("file_len too large (below 2^32: ZIP64 is out of scope)");
-    if (entry_cap > 0xFFFFFFFFull) return fail_param("entry_cap too large (below 2^32)");
+    if (!wide && file_len > 0xFFFFFFFFull) return fail_param("file_len too large (below 2^32: ZIP64 is out of scope)");
+    if (entry_cap > (wide ? 0x7FFFFFFFull : 0xFFFFFFFFull)) return fail_param(wide ? "entry_cap too large (below 2^31)" : "entry_cap too large (below 2^32)");
     if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
-    if (work_too_small(hdlz::zip_index_work_bytes(), d_work, work_bytes, "hdlz_zip_index_work_bytes(file_len, entry_cap)")) return HDLZ_E_BAD_PARAM;
+    if (work_too_small(need, d_work, work_bytes, query)) return HDLZ_E_BAD_PARAM;
     if (misaligned(8, d_entries, d_result, d_work)) return fail_align(8, "d_entries / d_result / d_work");
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
-    return launched(hdlz::launch_zip_index(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, static_cast<hipStream_t>(stream)),
-                    "launch k_zip_end");
+    return launched(launch(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, static_cast<hipStream_t>(stream)), kernel);
 }
-
-// The scratch of hdlz_zip_inflate_ws, laid out once for the size query and the call: six words per entry (length, status, end bit, room,
-// CRC-32, the checks' verdict), three 64-bit words per entry (the decoder's view: start, end, destination) and -- one entry -- a CRC word
-// per 32 KiB tile of out_cap and the share of the batch call's path, which takes what is left from `decode` on.
-struct ZipScratch {
-    uint32_t *len, *status, *end_bit, *cap, *crc, *verdict;
-    uint64_t *m_off, *m_end;
-    uint8_t** m_dst;
-    uint32_t* tiles;
-    size_t decode;
-    size_t bytes;
-};
-// `row`: what the one-stream path is given of out_cap (hdlz_zip_inflate_ws: all of it, in whole words)
-static ZipScratch zip_scratch(void* base, uint64_t count, uint32_t in_len, uint64_t out_cap, uint64_t row) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
-    const size_t per = hdlz::round256(24u * (size_t)count);
-    const size_t tiles = count == 1 ? hdlz::round256(sizeof(uint32_t) * hdlz::crc32_tiles(out_cap)) : 0u;
-    auto w32 = [&](uint64_t k) { return reinterpret_cast<uint32_t*>(b + 4u * (size_t)(k * count)); };
-    auto w64 = [&](uint64_t k) { return reinterpret_cast<uint64_t*>(b + per + 8u * (size_t)(k * count)); };
-    return {w32(0), w32(1), w32(2), w32(3), w32(4), w32(5), w64(0), w64(1), reinterpret_cast<uint8_t**>(w64(2)),
-            tiles ? reinterpret_cast<uint32_t*>(b + 2u * per) : nullptr, 2u * per + tiles,
-            2u * per + tiles + (count == 1 ? hdlz::round256(hdlz_inflate_work_bytes(1, in_len, row, 0, 1)) : 0u)};
+// The scratch of hdlz_zip_inflate_ws and hdlz_zip64_inflate_ws, laid out once for the size query and the call: six words per entry
+// (length, status, end bit, room, CRC-32, the checks' verdict), three 64-bit words per entry (the decoder's view: start, end,
+// destination) and -- one entry -- a CRC word per 32 KiB tile of out_cap and the share of the batch call's path, which takes what is
+// left from `decode` on.  `row`: what the one-stream path is given of out_cap (hdlz_zip_inflate_ws: all of it, in whole words)
+template <class Rec>
+static Laid zip_layout(hdlz::ZipArgsT<Rec>& z, uintptr_t base, uint64_t row) {
+    Carver c{base};
+    z.len = c.take<uint32_t>(z.count); z.status = c.take<uint32_t>(z.count); z.end_bit = c.take<uint32_t>(z.count);
+    z.cap = c.take<uint32_t>(z.count); z.crc = c.take<uint32_t>(z.count); z.verdict = c.take<uint32_t>(z.count); c.align256();
+    z.m_off = c.take<uint64_t>(z.count); z.m_end = c.take<uint64_t>(z.count); z.m_dst = c.take<uint8_t*>(z.count); c.align256();
+    const size_t words = z.count == 1 ? hdlz::crc32_tiles(z.out_cap) : 0u;
+    z.tiles = words ? c.take<uint32_t>(words) : nullptr; c.align256();
+    const size_t decode = c.bytes();
+    if (z.count == 1) c.take<uint8_t>(hdlz::round256(hdlz_inflate_work_bytes(1, z.bound, row, 0, 1)));
+    return {c.bytes(), decode};
 }
-size_t hdlz_zip_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) {
-    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_scratch(nullptr, count, in_len, out_cap, out_cap & ~3ull).bytes;
+static size_t zip_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap, uint64_t row) {
+    hdlz::ZipArgs z{nullptr, 0, nullptr, count, in_len, nullptr, out_cap};
+    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_layout(z, 0, row).bytes;
 }
-
-}  // extern "C"
+// the row the one-stream path is given: the decoders' room ends at 2^32 - 512 (a stored entry needs none of it)
+static uint64_t zip64_row(uint64_t out_cap) { return (out_cap & ~3ull) < 0xFFFFFE00ull ? out_cap & ~3ull : 0xFFFFFE00ull; }
 // hdlz_zip_inflate_ws and hdlz_zip64_inflate_ws (include/hdlz_zip64.h): `row` is what the one-stream path is given of out_cap
 template <class Rec>
 static int zip_inflate_impl(const uint8_t* d_file, uint64_t file_len, const Rec* d_entries, uint64_t first, uint64_t count, uint32_t in_len,
@@ -886,24 +888,20 @@ static int zip_inflate_impl(const uint8_t* d_file, uint64_t file_len, const Rec*
     if (misaligned(8, d_entries, d_result)) return fail_align(8, "d_entries / d_result");
     if (misaligned(4, d_entry_status)) return fail_align(4, "d_entry_status");
     if (misaligned(256, d_work)) return fail_align(256, "d_work");
-    const ZipScratch s = zip_scratch(d_work, count, in_len, out_cap, row);
-    if (count && work_too_small(s.bytes, d_work, work_bytes, query)) return HDLZ_E_BAD_PARAM;
+    hdlz::ZipArgsT<Rec> z{d_file, file_len, d_entries ? d_entries + first : nullptr, count, in_len, d_out, out_cap, d_entry_status, d_result};
+    const Laid l = zip_layout(z, address(d_work), row);
+    if (count && work_too_small(l.bytes, d_work, work_bytes, query)) return HDLZ_E_BAD_PARAM;
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // one entry takes the batch call's path, which stores words, when its row is one that path accepts; else the task view
-    const bool single = count == 1 && out_cap >= 4u && !misaligned(4, d_out);
-    const hdlz::ZipArgsT<Rec> z{d_file, file_len, d_entries ? d_entries + first : nullptr, count, in_len, d_out, out_cap, d_entry_status, d_result,
-                          s.len, s.status, s.end_bit, s.cap, s.crc, s.verdict, s.m_off, s.m_end, s.m_dst, single ? s.tiles : nullptr, single};
+    const bool single = z.single = count == 1 && out_cap >= 4u && !misaligned(4, d_out);
+    if (!single) z.tiles = nullptr;
     if (const int rc = launched(hdlz::launch_zip_check(z, st), "launch k_zip_check"); rc != HDLZ_OK) return rc;
-    if (single) {
-        // a large entry: the batch call's path over the two-word index the checks left on the device -- the whole-GPU chains for a
-        // large payload, their fallbacks, the wave for a small one; in_len is the bound the call was given
-        const hdlz::Work w = caller_work(static_cast<uint8_t*>(d_work) + s.decode, work_bytes - s.decode);
-        if (const int rc = inflate_batch_impl(d_file, s.m_off, 0, in_len, 1, 0, 0, d_out, row, s.len, s.status, w, stream, s.end_bit); rc != HDLZ_OK) return rc;
+    if (single) {                                                                                 // a large entry (m_off[0], m_end[0]: its ragged index)
+        if (const int rc = inflate_one(d_file, z.m_off, in_len, d_out, row, z.len, z.status, z.end_bit, d_work, work_bytes, l.decode, stream); rc != HDLZ_OK) return rc;
     } else if (count) {
-        hdlz::MemberArgs a = member_args(d_file, count, 0, d_out, s.len, s.status, s.end_bit, s.m_off);   // (BFINAL is honoured)
-        a.m_end = s.m_end; a.m_dst = s.m_dst; a.m_dst_cap = s.cap;                                     // the task view
-        if (const int rc = launched(hdlz::launch_inflate_dyn_members(a, st), "launch the member decode"); rc != HDLZ_OK) return rc;
+        const MemberView v{z.m_off, z.m_end, nullptr, 0, 0, 0, z.m_dst, z.cap};                        // the task view
+        if (const int rc = decode_members(d_file, count, d_out, z.len, z.status, z.end_bit, v, st); rc != HDLZ_OK) return rc;
     }
     if (const int rc = launched(hdlz::launch_zip_copy(z, st), "launch k_zip_copy"); rc != HDLZ_OK) return rc;
     if (const int rc = launched(hdlz::launch_zip_crc(z, st), "launch k_zip_crc_*"); rc != HDLZ_OK) return rc;
@@ -911,6 +909,20 @@ static int zip_inflate_impl(const uint8_t* d_file, uint64_t file_len, const Rec*
 }
 
 extern "C" {
+
+// ---- include/hdlz_zip.h: ZIP archives, the directory indexed and the entries read on the device (hdlz_zip.hip; DESIGN.md 4.6i)
+size_t hdlz_zip_index_work_bytes(uint64_t file_len, uint64_t entry_cap) {
+    (void)entry_cap;
+    return file_len > 0xFFFFFFFFull ? 0u : hdlz::zip_index_work_bytes();
+}
+
+int hdlz_zip_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip_entry* d_entries,
+                      hdlz_zip_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    return zip_index_impl(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, work_bytes, stream, hdlz::zip_index_work_bytes(),
+                          "hdlz_zip_index_work_bytes(file_len, entry_cap)", hdlz::launch_zip_index, "launch k_zip_end");
+}
+
+size_t hdlz_zip_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) { return zip_inflate_work_bytes(count, in_len, out_cap, out_cap & ~3ull); }
 
 int hdlz_zip_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip_entry* d_entries, uint64_t first, uint64_t count,
                         uint32_t in_len, uint8_t* d_out, uint64_t out_cap, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
@@ -927,23 +939,11 @@ size_t hdlz_zip64_index_work_bytes(uint64_t file_len, uint64_t entry_cap) {
 
 int hdlz_zip64_index_ws(const uint8_t* d_file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip64_entry* d_entries,
                         hdlz_zip_index_result* d_result, void* d_work, size_t work_bytes, void* stream) {
-    if (!d_result || (file_len && !d_file)) return fail_param("null device pointer");
-    if (entry_cap && !d_entries) return fail_param("d_entries is null with entry_cap > 0");
-    if (entry_cap > 0x7FFFFFFFull) return fail_param("entry_cap too large (below 2^31)");
-    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
-    if (work_too_small(hdlz::zip64_index_work_bytes(entry_cap), d_work, work_bytes, "hdlz_zip64_index_work_bytes(file_len, entry_cap)")) return HDLZ_E_BAD_PARAM;
-    if (misaligned(8, d_entries, d_result, d_work)) return fail_align(8, "d_entries / d_result / d_work");
-    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
-    return launched(hdlz::launch_zip64_index(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, static_cast<hipStream_t>(stream)),
-                    "launch k_zip64_end");
+    return zip_index_impl(d_file, file_len, entry_cap, out_align, d_entries, d_result, d_work, work_bytes, stream, hdlz::zip64_index_work_bytes(entry_cap),
+                          "hdlz_zip64_index_work_bytes(file_len, entry_cap)", hdlz::launch_zip64_index, "launch k_zip64_end");
 }
 
-// the row the one-stream path is given: the decoders' room ends at 2^32 - 512 (a stored entry needs none of it)
-static uint64_t zip64_row(uint64_t out_cap) { return (out_cap & ~3ull) < 0xFFFFFE00ull ? out_cap & ~3ull : 0xFFFFFE00ull; }
-
-size_t hdlz_zip64_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) {
-    return count == 0 || count > 0x7FFFFFFFull ? 0u : zip_scratch(nullptr, count, in_len, out_cap, zip64_row(out_cap)).bytes;
-}
+size_t hdlz_zip64_inflate_work_bytes(uint64_t count, uint32_t in_len, uint64_t out_cap) { return zip_inflate_work_bytes(count, in_len, out_cap, zip64_row(out_cap)); }
 
 int hdlz_zip64_inflate_ws(const uint8_t* d_file, uint64_t file_len, const hdlz_zip64_entry* d_entries, uint64_t first, uint64_t count,
                           uint32_t in_len, uint8_t* d_out, uint64_t out_cap, uint32_t* d_entry_status, hdlz_zip_inflate_result* d_result,
@@ -962,27 +962,41 @@ size_t hdlz_zip_write_work_bytes(uint64_t nentries, uint64_t nblocks) {
     return nentries > 65535u || nblocks > 0x7FFFFFFFull ? 0u : hdlz::zip_write_work_bytes(nentries, nblocks);
 }
 
-int hdlz_zip_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const uint8_t* d_names, const uint64_t* d_name_off, uint64_t nentries,
-                      const uint64_t* d_in_off, const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
-                      const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, const uint32_t* d_crc, uint32_t flags,
-                      uint32_t dos_datetime, uint32_t out_align, uint64_t total_in, uint8_t* d_file, uint64_t file_cap,
-                      hdlz_zip_entry* d_entries, hdlz_zip_write_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+// hdlz_zip_write_ws and hdlz_zip64_write_ws (include/hdlz_zip64.h: wide, with its records in d_entries64 and its zip64_from)
+static int zip_write_impl(const uint8_t* d_in, const uint64_t* d_ent_off, const uint8_t* d_names, const uint64_t* d_name_off, uint64_t nentries,
+                          const uint64_t* d_in_off, const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                          const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, const uint32_t* d_crc, uint32_t flags,
+                          uint32_t dos_datetime, uint32_t out_align, uint64_t total_in, uint8_t* d_file, uint64_t file_cap, hdlz_zip_entry* d_entries,
+                          hdlz_zip64_entry* d_entries64, hdlz_zip_write_result* d_result, void* d_work, size_t work_bytes, void* stream, bool wide,
+                          uint64_t zip64_from) {
     if (!d_result) return fail_param("d_result is required");
-    if (nentries > 65535u) return fail_param("nentries too large (at most 65535: ZIP64 is out of scope)");
+    if (nentries > (wide ? 0x7FFFFFFFull : 65535u)) return fail_param(wide ? "nentries too large (2^31 - 1 entries)" : "nentries too large (at most 65535: ZIP64 is out of scope)");
     if (nblocks > 0x7FFFFFFFull || (nblocks && !nentries)) return fail_param("nblocks too large for one launch (2^31 - 1 rows), or rows without entries");
     if (nentries && (any_null(d_in, d_names, d_crc) || any_null(d_ent_off, d_name_off, d_blk_first))) return fail_param("null device pointer (the entries)");
     if (nblocks && (any_null(d_in_off, d_end_bits) || any_null(d_len, d_status) || !d_rows)) return fail_param("null device pointer (the rows)");
     if (file_cap && !d_file) return fail_param("d_file is null with file_cap > 0");
     if (flags & ~(uint32_t)HDLZ_ZIP_FLAG_UTF8) return fail_param("flags: only HDLZ_ZIP_FLAG_UTF8 may be set");
     if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
-    if (work_too_small(hdlz::zip_write_work_bytes(nentries, nblocks), d_work, work_bytes, "hdlz_zip_write_work_bytes(nentries, nblocks)")) return HDLZ_E_BAD_PARAM;
-    if (misaligned(8, d_ent_off, d_name_off, d_in_off, d_end_bits, d_blk_first) || misaligned(8, d_entries) || misaligned(8, d_result) || misaligned(8, d_work))
+    if (zip64_from > 0xFFFFFFFFull) return fail_param("zip64_from must be at most FFFFFFFF");
+    if (work_too_small(hdlz::zip_write_work_bytes(nentries, nblocks, wide), d_work, work_bytes,
+                       wide ? "hdlz_zip64_write_work_bytes(nentries, nblocks)" : "hdlz_zip_write_work_bytes(nentries, nblocks)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_ent_off, d_name_off, d_in_off, d_end_bits, d_blk_first) || misaligned(8, d_entries, d_entries64) || misaligned(8, d_result) || misaligned(8, d_work))
         return fail_align(8, "d_ent_off / d_name_off / d_in_off / d_end_bits / d_blk_first / d_entries / d_result / d_work");
     if (misaligned(4, d_len, d_status, d_crc)) return fail_align(4, "d_len / d_status / d_crc");
     if (const int rc = check_device(); rc != HDLZ_OK) return rc;
     hdlz::ZipWriteArgs a{d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks,
-                         d_blk_first, d_crc, flags, dos_datetime, out_align, total_in, d_file, file_cap, d_entries, d_result, {}};
-    return launched(hdlz::launch_zip_write(a, d_work, static_cast<hipStream_t>(stream)), "launch k_zipw_*");
+                         d_blk_first, d_crc, flags, dos_datetime, out_align, total_in, d_file, file_cap, d_entries, d_result, {}, d_entries64, zip64_from};
+    return launched(hdlz::launch_zip_write(a, d_work, static_cast<hipStream_t>(stream), wide), wide ? "launch k_zipw64_*" : "launch k_zipw_*");
+}
+
+int hdlz_zip_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const uint8_t* d_names, const uint64_t* d_name_off, uint64_t nentries,
+                      const uint64_t* d_in_off, const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                      const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, const uint32_t* d_crc, uint32_t flags,
+                      uint32_t dos_datetime, uint32_t out_align, uint64_t total_in, uint8_t* d_file, uint64_t file_cap,
+                      hdlz_zip_entry* d_entries, hdlz_zip_write_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    return zip_write_impl(d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks, d_blk_first, d_crc,
+                          flags, dos_datetime, out_align, total_in, d_file, file_cap, d_entries, nullptr, d_result, d_work, work_bytes, stream, false,
+                          0xFFFFFFFFull);                    // (the args record's default: the classic form has no zip64_from)
 }
 
 // ---- include/hdlz_zip64.h: ZIP64 written (the scan and the gather of hdlz_zip_write.hip, a plan for any number of entries)
@@ -1000,23 +1014,8 @@ int hdlz_zip64_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const ui
                         const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, const uint32_t* d_crc, uint32_t flags,
                         uint32_t dos_datetime, uint32_t out_align, uint64_t zip64_from, uint64_t total_in, uint8_t* d_file, uint64_t file_cap,
                         hdlz_zip64_entry* d_entries, hdlz_zip_write_result* d_result, void* d_work, size_t work_bytes, void* stream) {
-    if (!d_result) return fail_param("d_result is required");
-    if (nentries > 0x7FFFFFFFull) return fail_param("nentries too large (2^31 - 1 entries)");
-    if (nblocks > 0x7FFFFFFFull || (nblocks && !nentries)) return fail_param("nblocks too large for one launch (2^31 - 1 rows), or rows without entries");
-    if (nentries && (any_null(d_in, d_names, d_crc) || any_null(d_ent_off, d_name_off, d_blk_first))) return fail_param("null device pointer (the entries)");
-    if (nblocks && (any_null(d_in_off, d_end_bits) || any_null(d_len, d_status) || !d_rows)) return fail_param("null device pointer (the rows)");
-    if (file_cap && !d_file) return fail_param("d_file is null with file_cap > 0");
-    if (flags & ~(uint32_t)HDLZ_ZIP_FLAG_UTF8) return fail_param("flags: only HDLZ_ZIP_FLAG_UTF8 may be set");
-    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
-    if (zip64_from > 0xFFFFFFFFull) return fail_param("zip64_from must be at most FFFFFFFF");
-    if (work_too_small(hdlz::zip_write_work_bytes(nentries, nblocks, true), d_work, work_bytes, "hdlz_zip64_write_work_bytes(nentries, nblocks)")) return HDLZ_E_BAD_PARAM;
-    if (misaligned(8, d_ent_off, d_name_off, d_in_off, d_end_bits, d_blk_first) || misaligned(8, d_entries) || misaligned(8, d_result) || misaligned(8, d_work))
-        return fail_align(8, "d_ent_off / d_name_off / d_in_off / d_end_bits / d_blk_first / d_entries / d_result / d_work");
-    if (misaligned(4, d_len, d_status, d_crc)) return fail_align(4, "d_len / d_status / d_crc");
-    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
-    hdlz::ZipWriteArgs a{d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks,
-                         d_blk_first, d_crc, flags, dos_datetime, out_align, total_in, d_file, file_cap, nullptr, d_result, {}, d_entries, zip64_from};
-    return launched(hdlz::launch_zip_write(a, d_work, static_cast<hipStream_t>(stream), true), "launch k_zipw64_*");
+    return zip_write_impl(d_in, d_ent_off, d_names, d_name_off, nentries, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks, d_blk_first, d_crc,
+                          flags, dos_datetime, out_align, total_in, d_file, file_cap, nullptr, d_entries, d_result, d_work, work_bytes, stream, true, zip64_from);
 }
 
 }  // extern "C"

@@ -24,6 +24,13 @@ def _raise_unless_ok(rec, what, base=0):
         raise HdlzStatusError(rec.status, what, first_bad=base + rec.first_bad if hasattr(rec, "first_bad") else None)
 
 
+def _gzip_tail_status(st, behind_member, rest, head):
+    """the status of a gzip walk whose one-stream call failed with `st`, `rest` bytes in front of the file's end: behind a member, fewer
+    than 10 bytes that do not begin like the magic (head(): the first three of them) are no member -- too short for the device to
+    look at the magic -- so E_BAD_HEADER, as gzip.decompress answers"""
+    return E_BAD_HEADER if behind_member and rest < 10 and not b"\x1f\x8b\x08".startswith(head()) else st
+
+
 def _is_index(t, count=None):
     """an index array as the library reads it: int64, contiguous, on the device (and of `count` words)"""
     assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and (count is None or t.numel() == count), \
@@ -87,12 +94,47 @@ class Engine(object):
         assert nbytes >= need or not full, "the scratch holds %d bytes, the call needs %d" % (nbytes, need)
         return work, (work.data_ptr() if nbytes else None), nbytes
 
-    def _record(self, fn, Struct, scratch, *args):
-        """a library call that ends (..., d_result, d_work, work_bytes, stream) -> its result record: the record's tensor sized by the
-        struct, the call with `scratch` (what _scratch returned) and its check, the record read back -- the one host sync"""
+    def _enqueue(self, fn, Struct, scratch, *args):
+        """a library call that ends (..., d_result, d_work, work_bytes, stream), enqueued: the record's tensor sized by the struct, the
+        call with `scratch` (what _scratch returned) and its check -> the record's device tensor; no host sync"""
         result = torch.empty(ctypes.sizeof(Struct) // 8, dtype=torch.int64, device=self.device)
         self._check(getattr(self.lib, fn)(*args, result.data_ptr(), scratch[1], scratch[2], self._stream()), fn)
-        return Struct.from_buffer_copy(result.cpu().numpy().tobytes())
+        return result
+
+    def _record(self, fn, Struct, scratch, *args):
+        """_enqueue, and the record read back -- the one host sync -> the result record"""
+        return Struct.from_buffer_copy(self._enqueue(fn, Struct, scratch, *args).cpu().numpy().tobytes())
+
+    def _member_index(self, call, Struct, work_bytes, d_file, member_cap):
+        """bgzf_index and gzip_index: the index call with room for member_cap members (default: a guess, file_len // 4096 + 16), made once
+        more with the true count when the file holds more -> (member_offsets int64[M + 1], out_offsets int64[M + 1], record)"""
+        self._is_bytes(d_file, "d_file", flat=True)
+        n, dev = d_file.numel(), d_file.device
+        cap = n // 4096 + 16 if member_cap is None else int(member_cap)
+        scratch = self._scratch(work_bytes(n), None)
+        while True:
+            off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            rec = self._record(call, Struct, scratch, d_file.data_ptr() if n else None, n, cap, off.data_ptr(), out_off.data_ptr())
+            if rec.status != E_OUT_CAPACITY or rec.nmembers <= cap:
+                return off[:rec.nmembers + 1], out_off[:rec.nmembers + 1], rec
+            cap = rec.nmembers
+
+    def _member_range(self, off, out_off, members, out):
+        """members=(b0, b1) of a file's index (None: all of them) and where they decode to -> (off, out_off, B, total, out): the two
+        index slices of B + 1 words, the range's bytes -- one host sync -- and `out` (default: allocated here) with room for them"""
+        _is_index(off)
+        _is_index(out_off, off.numel())
+        M = off.numel() - 1
+        b0, b1 = (0, M) if members is None else (int(members[0]), int(members[1]))
+        if not 0 <= b0 <= b1 <= M:
+            raise ValueError("members=(%d, %d) is not a range of the file's %d members" % (b0, b1, M))
+        off, out_off, B = off[b0:b1 + 1], out_off[b0:b1 + 1], b1 - b0
+        total = int((out_off[B] - out_off[0]).item()) if B else 0
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=off.device)
+        self._is_bytes(out, "out", room=total)
+        return off, out_off, B, total, out
 
     def _aligned_input(self, d_in, n):
         """the compress kernels load whole 16-byte pieces: an input that does not start at a multiple of 16 or has fewer than 16 bytes
@@ -381,17 +423,7 @@ class Engine(object):
         not OK is returned, not raised: the M members in front of the failure stay valid and indexed.  The members are found on the
         device; one host sync for the record.  member_cap: room for that many members (default: a guess, file_len // 4096 + 16); when
         the file holds more, the call is made once more with the true count."""
-        self._is_bytes(d_file, "d_file", flat=True)
-        n, dev = d_file.numel(), d_file.device
-        cap = n // 4096 + 16 if member_cap is None else int(member_cap)
-        scratch = self._scratch(self.lib.hdlz_bgzf_index_work_bytes(n), None)
-        while True:
-            off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
-            out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
-            rec = self._record("hdlz_bgzf_index_ws", _lib.BgzfIndexResult, scratch, d_file.data_ptr() if n else None, n, cap, off.data_ptr(), out_off.data_ptr())
-            if rec.status != E_OUT_CAPACITY or rec.nmembers <= cap:
-                return off[:rec.nmembers + 1], out_off[:rec.nmembers + 1], rec
-            cap = rec.nmembers
+        return self._member_index("hdlz_bgzf_index_ws", _lib.BgzfIndexResult, self.lib.hdlz_bgzf_index_work_bytes, d_file, member_cap)
 
     @_on_device
     def inflate_bgzf(self, d_file, index=None, members=None, out=None, work=None):
@@ -403,17 +435,7 @@ class Engine(object):
         with .first_bad, counted from b0 -- on a status that is not OK.  `work`: the call's scratch, a uint8 device tensor of at
         least hdlz_bgzf_inflate_work_bytes(b1 - b0, 0) bytes at a multiple of 256 (default: allocated here)."""
         self._is_bytes(d_file, "d_file", flat=True)
-        dev = d_file.device
-        off, out_off = self._file_index(d_file, index, "inflate_bgzf")
-        M = off.numel() - 1
-        b0, b1 = (0, M) if members is None else (int(members[0]), int(members[1]))
-        if not 0 <= b0 <= b1 <= M:
-            raise ValueError("members=(%d, %d) is not a range of the file's %d members" % (b0, b1, M))
-        off, out_off, B = off[b0:b1 + 1], out_off[b0:b1 + 1], b1 - b0
-        total = int((out_off[B] - out_off[0]).item()) if B else 0
-        if out is None:
-            out = torch.empty(total, dtype=torch.uint8, device=dev)
-        self._is_bytes(out, "out", room=total)
+        off, out_off, B, total, out = self._member_range(*self._file_index(d_file, index, "inflate_bgzf"), members, out)
         rec = self._record("hdlz_bgzf_inflate_ws", _lib.BgzfInflateResult, self._scratch(self.lib.hdlz_bgzf_inflate_work_bytes(B, 0), work, torch.uint8),
                            d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B, 0,
                            out.data_ptr() if total else None, total, None)
@@ -620,15 +642,12 @@ class Engine(object):
                 e += 1
             cap = int(rel[e - 1] + size[e - 1] - rel[b])
             calls.append((b, e - b, 0, cap if e - b > 1 else min((cap + 3) & ~3, out.numel() - int(rel[b]))))      # (one entry: a row of whole words)
-        work_bytes, inflate, name = (self.lib.hdlz_zip64_inflate_work_bytes, self.lib.hdlz_zip64_inflate_ws, "hdlz_zip64_inflate_ws") if index.zip64 else \
-            (self.lib.hdlz_zip_inflate_work_bytes, self.lib.hdlz_zip_inflate_ws, "hdlz_zip_inflate_ws")
-        need = max([work_bytes(c, il, cap) for _, c, il, cap in calls] + [0])
-        scratch = self._scratch(need, work, torch.uint8)
-        results = torch.empty((max(len(calls), 1), 3), dtype=torch.int64, device=dev)
-        for k, (b, c, il, cap) in enumerate(calls):
-            self._check(inflate(d_file.data_ptr(), d_file.numel(), index.entries.data_ptr(), b, c, il,
-                                out.data_ptr() + int(rel[b]) if out.numel() else None, cap,
-                                status.data_ptr() + 4 * (b - first), results[k].data_ptr(), scratch[1], scratch[2], self._stream()), name)
+        work_bytes, inflate = (self.lib.hdlz_zip64_inflate_work_bytes, "hdlz_zip64_inflate_ws") if index.zip64 else \
+            (self.lib.hdlz_zip_inflate_work_bytes, "hdlz_zip_inflate_ws")
+        scratch = self._scratch(max([work_bytes(c, il, cap) for _, c, il, cap in calls] + [0]), work, torch.uint8)
+        for b, c, il, cap in calls:                           # (the records are not read: every entry's verdict is in `status`)
+            self._enqueue(inflate, _lib.ZipInflateResult, scratch, d_file.data_ptr(), d_file.numel(), index.entries.data_ptr(), b, c, il,
+                          out.data_ptr() + int(rel[b]) if out.numel() else None, cap, status.data_ptr() + 4 * (b - first))
         return out[:total], out_off, status
 
     def read_zip_bytes(self, z):
@@ -864,27 +883,18 @@ class Engine(object):
         call: out_cap when given; else the ISIZE word at the end of the remaining bytes when it does not exceed inflate_cap(remaining),
         and once more with inflate_cap(remaining) after E_OUT_CAPACITY."""
         n, pos, pieces = len(z), 0, []
-        d = self._stage(z)
+        d = self._stage(z)[:n]
+        tail_isize = int.from_bytes(bytes(z[n - 4:n]), "little") if n >= 4 else 0
         while pos < n:
             if pieces:                               # zero bytes behind a member are padding
                 pos = n - len(bytes(z[pos:]).lstrip(b"\0"))
                 if pos == n:
                     break
-            rest = n - pos
-            bound = inflate_cap(rest)
-            isize = int.from_bytes(bytes(z[n - 4:n]), "little") if rest >= 4 else bound
-            caps = [out_cap] if out_cap is not None else [isize, bound] if isize < bound else [bound]
-            for cap in caps:
-                out, ol, st, used, _ = self.inflate_gzip(d[pos:pos + rest], in_len=rest, nblocks=1, out_pitch=max(16, (cap + 15) // 16 * 16))
-                st = int(st.item())
-                if st != E_OUT_CAPACITY:
-                    break
+            st, out, used = self._gzip_one(d, pos, tail_isize, out_cap)
             if st != OK:
-                if pieces and rest < 10 and not b"\x1f\x8b\x08".startswith(bytes(z[pos:pos + 3])):
-                    st = E_BAD_HEADER                # (too short for the device to look at the magic: what stands there is no member)
-                return st, b""
-            pieces.append(bytes(out[0, :int(ol.item())].cpu().numpy().tobytes()))
-            pos += int(used.item())
+                return _gzip_tail_status(st, bool(pieces), n - pos, lambda: bytes(z[pos:pos + 3])), b""
+            pieces.append(bytes(out.cpu().numpy().tobytes()))
+            pos += used
         return OK, b"".join(pieces)
 
     # -- gzip files of many members: found, decoded and verified in one pass (include/hdlz_gzip_members.h)
@@ -904,27 +914,14 @@ class Engine(object):
         The record is a _lib.GzipMembersIndexResult (nmembers, total_out, status).  One host sync for the record.  member_cap: room for
         that many members (default: a guess, file_len // 4096 + 16); when the file holds more, the call is made once more with the
         true count."""
-        self._is_bytes(d_file, "d_file", flat=True)
-        n, dev = d_file.numel(), d_file.device
-        cap = n // 4096 + 16 if member_cap is None else int(member_cap)
-        scratch = self._scratch(self.lib.hdlz_gzip_members_index_work_bytes(n), None)
-        while True:
-            off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
-            out_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
-            rec = self._record("hdlz_gzip_members_index_ws", _lib.GzipMembersIndexResult, scratch, d_file.data_ptr() if n else None, n, cap,
-                               off.data_ptr(), out_off.data_ptr())
-            if rec.status != E_OUT_CAPACITY or rec.nmembers <= cap:
-                return off[:rec.nmembers + 1], out_off[:rec.nmembers + 1], rec
-            cap = rec.nmembers
+        return self._member_index("hdlz_gzip_members_index_ws", _lib.GzipMembersIndexResult, self.lib.hdlz_gzip_members_index_work_bytes, d_file, member_cap)
 
     def _gzip_members_call(self, d_file, off, out_off, B, out, out_cap, status, work=None):
         """one hdlz_gzip_members_inflate_ws, enqueued: no host read -> the record's device tensor"""
-        result = torch.empty(ctypes.sizeof(_lib.GzipMembersInflateResult) // 8, dtype=torch.int64, device=self.device)
-        work, wptr, wbytes = self._scratch(self.lib.hdlz_gzip_members_inflate_work_bytes(B), work, torch.uint8)
-        self._check(self.lib.hdlz_gzip_members_inflate_ws(d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B,
-                                                          out.data_ptr() if out_cap else None, out_cap, status.data_ptr() if B else None,
-                                                          result.data_ptr(), wptr, wbytes, self._stream()), "hdlz_gzip_members_inflate_ws")
-        return result
+        return self._enqueue("hdlz_gzip_members_inflate_ws", _lib.GzipMembersInflateResult,
+                             self._scratch(self.lib.hdlz_gzip_members_inflate_work_bytes(B), work, torch.uint8),
+                             d_file.data_ptr() if d_file.numel() else None, d_file.numel(), off.data_ptr(), out_off.data_ptr(), B,
+                             out.data_ptr() if out_cap else None, out_cap, status.data_ptr() if B else None)
 
     @_on_device
     def inflate_gzip_members(self, d_file, index=None, members=None, out=None, work=None):
@@ -935,30 +932,20 @@ class Engine(object):
         (read_gzip repairs).  The record is a _lib.GzipMembersInflateResult (out_len, first_bad, status).  `work`: the call's scratch,
         a uint8 device tensor of at least hdlz_gzip_members_inflate_work_bytes(b1 - b0) bytes at a multiple of 256."""
         self._is_bytes(d_file, "d_file", flat=True)
-        dev = d_file.device
-        off, out_off = (self.gzip_index(d_file)[:2]) if index is None else (index[0], index[1])
-        _is_index(off)
-        _is_index(out_off, off.numel())
-        M = off.numel() - 1
-        b0, b1 = (0, M) if members is None else (int(members[0]), int(members[1]))
-        if not 0 <= b0 <= b1 <= M:
-            raise ValueError("members=(%d, %d) is not a range of the file's %d members" % (b0, b1, M))
-        off, out_off, B = off[b0:b1 + 1], out_off[b0:b1 + 1], b1 - b0
-        total = int((out_off[B] - out_off[0]).item()) if B else 0
-        if out is None:
-            out = torch.empty(total, dtype=torch.uint8, device=dev)
-        self._is_bytes(out, "out", room=total)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
+        off, out_off, B, total, out = self._member_range(*(self.gzip_index(d_file)[:2] if index is None else (index[0], index[1])), members, out)
+        status = torch.empty(B, dtype=torch.int32, device=d_file.device)
         result = self._gzip_members_call(d_file, off, out_off, B, out, total, status, work)
         return out[:total], status, _lib.GzipMembersInflateResult.from_buffer_copy(result.cpu().numpy().tobytes())
 
-    def _gzip_one(self, d_file, pos, tail_isize):
-        """one iteration of inflate_gzip_bytes's loop at `pos`: the one-stream call (a large member: the whole GPU), with that loop's
-        capacities -> (status, the member's bytes on the device, bytes consumed)"""
+    def _gzip_one(self, d_file, pos, tail_isize, out_cap=None):
+        """gzip's acceptance of ONE member at `pos`, for both walkers (inflate_gzip_bytes, read_gzip): the one-stream call (a large member:
+        the whole GPU).  Capacity: out_cap when given; else the ISIZE word at the file's end (tail_isize) when it does not exceed
+        inflate_cap(remaining), and once more with inflate_cap(remaining) after E_OUT_CAPACITY
+        -> (status, the member's bytes on the device, bytes consumed)"""
         rest = d_file.numel() - pos
         bound = inflate_cap(rest)
         isize = tail_isize if rest >= 4 else bound
-        for cap in ([isize, bound] if isize < bound else [bound]):
+        for cap in ([out_cap] if out_cap is not None else [isize, bound] if isize < bound else [bound]):
             out, ol, st, used, _ = self.inflate_gzip(d_file[pos:pos + rest], in_len=rest, nblocks=1, out_pitch=max(16, (cap + 15) // 16 * 16))
             st = int(st.item())
             if st != E_OUT_CAPACITY:
@@ -1033,10 +1020,7 @@ class Engine(object):
             else:
                 report.repairs += 1
             if st != OK:
-                rest = n - pos
-                if report.members and rest < 10 and not b"\x1f\x8b\x08".startswith(bytes(d_file[pos:pos + 3].cpu().numpy().tobytes())):
-                    st = E_BAD_HEADER                     # (as inflate_gzip_bytes: too short for the device to look at the magic)
-                report.status = st
+                report.status = _gzip_tail_status(st, report.members > 0, n - pos, lambda: bytes(d_file[pos:pos + 3].cpu().numpy().tobytes()))
                 return torch.empty(0, dtype=torch.uint8, device=dev), report
             pieces.append(out)
             report.members += 1
