@@ -14,6 +14,8 @@ from .port import Sig, DeflatePort, deflate                         # noqa: F401
 from . import bgzf                                                  # noqa: F401  (host-only: virtual offsets, .gzi files)
 from .bgzf import virtual_offset, split_virtual, gzi_dumps, gzi_loads   # noqa: F401
 from .zip import ZipIndex                                           # noqa: F401  (what Engine.zip_index returns)
+from .seek import SeekIndex                                         # noqa: F401  (what Engine.seek_index returns; seek.loads reads its file)
+from . import seek                                                  # noqa: F401
 from .npz import load_npz, save_npz                                 # noqa: F401  (.npz files into device tensors, and back)
 
 

@@ -145,6 +145,20 @@ GZIP_MEMBERS_SIGNATURES = {
     "hdlz_gzip_members_inflate_ws": (ci, [vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, sz, vp]),
 }
 GZIP_MEMBERS_EXPORTS = tuple(GZIP_MEMBERS_SIGNATURES)
+# ... and of include/hdlz_seek.h: the seek index of a gzip or zlib stream and batched ranges through it (tests/test_seek_cabi.py, which
+# also holds its refusals: the recorded fixtures of tests/test_api_refusals.py cover the twelve *_SIGNATURES tables above and predate
+# this header, hence the other name)
+SEEK_CALLS = {
+    "hdlz_seek_index_work_bytes": (sz, [u64, u32, u64, u64]),        # file_len, flags, out_cap, point_cap
+    # d_file, file_len, flags, span, d_out, out_cap, d_bit, d_pos, d_crc, d_win, point_cap, d_result, d_work, work_bytes, stream
+    "hdlz_seek_index_ws": (ci, [vp, u64, u32, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, sz, vp]),
+    "hdlz_seek_ranges_work_bytes": (sz, [u64, u64, u64, u32]),       # nranges, task_cap, seg_cap, flags
+    # d_file, file_len, d_bit, d_pos, d_crc, d_win, npoints, d_ranges, nranges, flags, seg_cap, d_out, out_cap, d_range_off, d_range_status,
+    # task_cap, d_result, d_work, work_bytes, stream
+    "hdlz_seek_read_ranges_ws": (ci, [vp, u64, vp, vp, vp, vp, u64, vp, u64, u32, u64, vp, u64, vp, vp, u64, vp, vp, sz, vp]),
+}
+SEEK_EXPORTS = tuple(SEEK_CALLS)
+SEEK_ZLIB, SEEK_GZIP, SEEK_WINDOW = 1, 2, 32768      # HDLZ_SEEK_ZLIB, HDLZ_SEEK_GZIP, HDLZ_SEEK_WINDOW
 _lib = None
 
 
@@ -197,6 +211,14 @@ class BgzfInflateResult(ctypes.Structure):
 class BgzfRangesResult(ctypes.Structure):
     """hdlz_bgzf_ranges_result: the result record of hdlz_bgzf_read_ranges_ws (32 bytes)"""
     _fields_ = [("total_out", u64), ("ntasks", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
+class SeekResult(ctypes.Structure):
+    """hdlz_seek_result: the result record of hdlz_seek_index_ws (40 bytes)"""
+    _fields_ = [("npoints", u64), ("total_out", u64), ("end_bit", u64), ("max_seg", u64), ("status", u32), ("route", u32)]
+
+
+SeekRangesResult = BgzfRangesResult      # hdlz_seek_ranges_result: a typedef of hdlz_bgzf_ranges_result
 
 
 class GzipMembersIndexResult(ctypes.Structure):
@@ -259,7 +281,7 @@ def load():
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
             list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()) + \
-            list(GZIP_MEMBERS_SIGNATURES.items()):
+            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -741,6 +741,144 @@ int hdlz_bgzf_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uin
                     "launch the finish kernels (k_ranges_crc, k_ranges_judge, k_ranges_slice, k_ranges_finish, k_ranges_record)");
 }
 
+// ---- include/hdlz_seek.h: the seek index of a gzip or zlib stream and batched ranges through it (hdlz_seek.hip)
+// The scratch of hdlz_seek_index_ws, laid out once for the size query and the call: a head (the count of written points; behind it the
+// decoder's two sink words), the one stream's words (length, status, end, and the header walk's three), the walk's two-word index, the
+// recorded points, the checksum's tile words.
+struct SeekIndexWork {
+    uint64_t *head, *sink_head, *idx, *pt_bit, *pt_pos;
+    uint32_t* words;             // out_len, status, in_used, p, verdict, crcw
+    uint8_t* tiles;
+    size_t decode;               // from here on: what the decode path takes
+};
+static uint64_t seek_row(uint64_t out_cap) { return (out_cap & ~3ull) < 0xFFFFFE00ull ? out_cap & ~3ull : 0xFFFFFE00ull; }
+static size_t seek_index_layout(SeekIndexWork& w, uintptr_t base, uint64_t file_len, bool gzip, uint64_t row, uint64_t point_cap) {
+    Carver c{base};
+    w.head = c.take<uint64_t>(16); w.sink_head = c.take<uint64_t>(16); c.align256();
+    w.words = c.take<uint32_t>(64); c.align256();
+    w.idx = c.take<uint64_t>(32); c.align256();
+    w.pt_bit = c.take<uint64_t>(point_cap); c.align256();
+    w.pt_pos = c.take<uint64_t>(point_cap); c.align256();
+    w.tiles = c.take<uint8_t>(8u * (size_t)((row + 32767u) / 32768u)); c.align256();
+    w.decode = c.bytes();
+    c.take<uint8_t>(hdlz::round256(hdlz_inflate_work_bytes(1, (uint32_t)file_len, row, 0, gzip ? 1 : 0)));      // the share of the batch call's path
+    return c.bytes();
+}
+static bool seek_index_shape_ok(uint64_t file_len, uint32_t flags, uint32_t span, uint64_t point_cap) {
+    return (flags == HDLZ_SEEK_ZLIB || flags == HDLZ_SEEK_GZIP) && span != 0u && file_len < 0x10000000ull && point_cap <= 0x7FFFFFFFull;
+}
+static bool seek_ranges_shape_ok(uint64_t nranges, uint64_t task_cap, uint64_t seg_cap, uint32_t flags) {
+    return nranges <= 0x7FFFFFFFull && task_cap <= 0x7FFFFFFFull && seg_cap <= 0xFFFFFE00ull && flags == 0u;
+}
+static size_t seek_ranges_bytes(uint64_t nranges, uint64_t task_cap, uint64_t seg_cap) {
+    if (nranges == 0) return 0;
+    return hdlz::bgzf_ranges_work_bytes(nranges, task_cap, hdlz::round256(seg_cap)) + 3u * hdlz::round256(4u * (size_t)task_cap);
+}
+
+size_t hdlz_seek_index_work_bytes(uint64_t file_len, uint32_t flags, uint64_t out_cap, uint64_t point_cap) {
+    if (!seek_index_shape_ok(file_len, flags, 1u, point_cap)) return 0;
+    SeekIndexWork w;
+    return seek_index_layout(w, 0, file_len, flags == HDLZ_SEEK_GZIP, seek_row(out_cap), point_cap);
+}
+
+int hdlz_seek_index_ws(const uint8_t* d_file, uint64_t file_len, uint32_t flags, uint32_t span, uint8_t* d_out, uint64_t out_cap,
+                       uint64_t* d_bit, uint64_t* d_pos, uint32_t* d_crc, uint8_t* d_win, uint64_t point_cap, hdlz_seek_result* d_result,
+                       void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("null device pointer");
+    if (flags != HDLZ_SEEK_ZLIB && flags != HDLZ_SEEK_GZIP) return fail_param("flags: exactly one of HDLZ_SEEK_ZLIB and HDLZ_SEEK_GZIP");
+    if (span == 0u) return fail_param("span must be at least 1");
+    if (file_len >= 0x10000000ull) return fail_param("file_len too large (streams are limited to 256 MiB - 1)");
+    if (point_cap > 0x7FFFFFFFull) return fail_param("point_cap must be below 2^31");
+    if ((file_len && !d_file) || (out_cap && !d_out) || (point_cap && any_null(d_bit, d_pos, d_crc, d_win))) return fail_param("null device pointer");
+    if (misaligned(8, d_bit, d_pos, d_result)) return fail_align(8, "d_bit / d_pos / d_result");
+    if (misaligned(4, d_crc, d_out)) return fail_align(4, "d_crc / d_out");
+    if (misaligned(16, d_win)) return fail_align(16, "d_win");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    const uint64_t row = seek_row(out_cap);
+    SeekIndexWork w;
+    const bool gzip = flags == HDLZ_SEEK_GZIP;
+    if (work_too_small(seek_index_layout(w, address(d_work), file_len, gzip, row, point_cap), d_work, work_bytes, "hdlz_seek_index_work_bytes(file_len, flags, out_cap, point_cap)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint32_t *out_len = w.words, *status = w.words + 1, *in_used = w.words + 2;
+    const hdlz::PointSink sink{w.sink_head, w.pt_bit, w.pt_pos, (uint32_t)point_cap, span};
+    if (const int rc = launched(hdlz::zero_words(reinterpret_cast<uint32_t*>(w.sink_head), 8u, st), "launch k_zero_words"); rc != HDLZ_OK) return rc;
+    hdlz::GunzipArgs g{d_file, nullptr, 0, (uint32_t)file_len, 1, d_out, row, out_len, status, in_used, nullptr};
+    if (gzip) {
+        g.p = w.words + 3; g.verdict = w.words + 4; g.crcw = w.words + 5; g.idx = w.idx;
+        g.tiles = hdlz::gunzip_tile_words(1, row) ? reinterpret_cast<uint32_t*>(w.tiles) : nullptr;
+        g.single = true;
+        if (const int rc = launched(hdlz::launch_gunzip_heads(g, st), "launch k_gunzip_heads"); rc != HDLZ_OK) return rc;
+    }
+    // the decode of the one stream -- the file (zlib), or the walk's ragged index (gzip) -- on the path of the one-stream calls: the
+    // whole-GPU chains where they apply, which fill the sink themselves or hand on to the recording view of the wave decoder; else that view
+    const hdlz::InflateArgs a{d_file, gzip ? w.idx : nullptr, 0, (uint32_t)file_len, 1, 0, 0, d_out, row, out_len, status, in_used, sink};
+    bool used = false;
+    if (par_applies(1, (uint32_t)file_len, 0)) {
+        const hdlz::Work share = caller_work(static_cast<uint8_t*>(d_work) + w.decode, work_bytes - w.decode);
+        if (const int rc = launched(hdlz::launch_inflate_par(a, st, &used, share), "launch the whole-GPU inflate (k_par_*)"); rc != HDLZ_OK) return rc;
+    }
+    if (!used)
+        if (const int rc = launched(hdlz::launch_inflate_dyn_record(a, st), "launch k_inflate_dyn (the recording view)"); rc != HDLZ_OK) return rc;
+    if (gzip) {
+        if (const int rc = launched(hdlz::launch_gunzip_crc(g, st), "launch k_gunzip_crc_*"); rc != HDLZ_OK) return rc;
+        if (const int rc = launched(hdlz::launch_gunzip_judge(g, st), "launch k_gunzip_judge"); rc != HDLZ_OK) return rc;
+    } else {
+        const hdlz::JudgeArgs j{d_file, nullptr, 0, (uint32_t)file_len, 1, d_out, row, out_len, status, in_used, nullptr,
+                                hdlz::judge_work_bytes(1, row) ? reinterpret_cast<uint2*>(w.tiles) : nullptr};
+        if (const int rc = launched(hdlz::launch_judge(j, st), "launch the judging pass (k_adler_*)"); rc != HDLZ_OK) return rc;
+    }
+    const hdlz::SeekIndexArgs s{d_out, out_len, status, sink, d_bit, d_pos, d_crc, d_win, point_cap, d_result, w.head};
+    return launched(hdlz::launch_seek_index_finish(s, st), "launch the index kernels (k_seek_points, k_seek_windows, k_seek_crc)");
+}
+
+size_t hdlz_seek_ranges_work_bytes(uint64_t nranges, uint64_t task_cap, uint64_t seg_cap, uint32_t flags) {
+    return seek_ranges_shape_ok(nranges, task_cap, seg_cap, flags) ? seek_ranges_bytes(nranges, task_cap, seg_cap) : 0;
+}
+
+int hdlz_seek_read_ranges_ws(const uint8_t* d_file, uint64_t file_len, const uint64_t* d_bit, const uint64_t* d_pos, const uint32_t* d_crc,
+                             const uint8_t* d_win, uint64_t npoints, const uint64_t* d_ranges, uint64_t nranges, uint32_t flags, uint64_t seg_cap,
+                             uint8_t* d_out, uint64_t out_cap, uint64_t* d_range_off, uint32_t* d_range_status, uint64_t task_cap,
+                             hdlz_seek_ranges_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (any_null(d_result, d_range_off) || (nranges && any_null(d_ranges, d_file, d_bit, d_pos, d_crc, d_win)) || (out_cap && !d_out)) return fail_param("null device pointer");
+    if (nranges > 0x7FFFFFFFull || npoints > 0x7FFFFFFFull || task_cap > 0x7FFFFFFFull) return fail_param("nranges, npoints and task_cap must be below 2^31");
+    if (nranges && npoints == 0) return fail_param("npoints: an index has at least one point");
+    if (file_len >= 0x10000000ull) return fail_param("file_len too large (streams are limited to 256 MiB - 1)");
+    if (seg_cap > 0xFFFFFE00ull) return fail_param("seg_cap too large (at most 2^32 - 512)");
+    if (flags) return fail_param("flags: none is defined");
+    if (misaligned(8, d_bit, d_pos, d_ranges, d_range_off, d_result)) return fail_align(8, "d_bit / d_pos / d_ranges / d_range_off / d_result");
+    if (misaligned(4, d_crc, d_range_status)) return fail_align(4, "d_crc / d_range_status");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    if (work_too_small(seek_ranges_bytes(nranges, task_cap, seg_cap), d_work, work_bytes, "hdlz_seek_ranges_work_bytes(nranges, task_cap, seg_cap, flags)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t slot = hdlz::round256(seg_cap);
+    hdlz::SeekRangeArgs s{};
+    hdlz::RangeArgs& u = s.r;
+    u = hdlz::bgzf_ranges_args(d_work, nranges, task_cap, slot);
+    u.in = d_file; u.in_len = file_len; u.off = nullptr; u.out_off = d_pos; u.nmembers = npoints;
+    u.ranges = d_ranges; u.nranges = nranges; u.flags = 0; u.out = d_out; u.out_cap = out_cap;
+    u.range_off = d_range_off; u.range_status = d_range_status; u.task_cap = task_cap; u.result = d_result;
+    s.bit = d_bit; s.crc = d_crc; s.win = d_win; s.seg_cap = seg_cap;
+    {
+        Carver c{address(u.slots) + (size_t)(2u * slot) * (size_t)nranges};      // behind the slots: the three words per task of this call
+        s.t_sbit = c.take<uint32_t>(task_cap); c.align256();
+        s.t_hist = c.take<uint32_t>(task_cap); c.align256();
+        s.t_k = c.take<uint32_t>(task_cap);
+    }
+    if (const int rc = launched(hdlz::launch_ranges_resolve_scan(u, st), "launch the plan kernels (k_ranges_resolve, k_ranges_scan)"); rc != HDLZ_OK) return rc;
+    if (nranges && task_cap) {
+        if (const int rc = launched(hdlz::launch_seek_expand(s, st), "launch k_seek_expand"); rc != HDLZ_OK) return rc;
+        hdlz::SegArgs a{};
+        a.in = d_file; a.nstreams = task_cap; a.out = d_out; a.out_len = u.t_len; a.status = u.t_status; a.in_used = u.t_end_bit;
+        a.t_off = u.t_off; a.t_end = u.t_end; a.t_dst = u.t_dst; a.t_cap = u.t_cap; a.t_sbit = s.t_sbit; a.t_hist = s.t_hist; a.t_k = s.t_k; a.win = d_win; a.bit = d_bit;
+        if (const int rc = launched(hdlz::launch_inflate_dyn_segments(a, st), "launch k_inflate_dyn (the segment view)"); rc != HDLZ_OK) return rc;
+        if (const int rc = launched(hdlz::launch_ranges_crc(u, st), "launch k_ranges_crc"); rc != HDLZ_OK) return rc;
+        if (const int rc = launched(hdlz::launch_seek_judge(s, st), "launch k_seek_judge"); rc != HDLZ_OK) return rc;
+    }
+    return launched(hdlz::launch_ranges_deliver(u, st), "launch the finish kernels (k_ranges_slice, k_ranges_finish, k_ranges_record)");
+}
+
 // ---- include/hdlz_gunzip.h: gzip members of any writer, one per stream (hdlz_gunzip.hip)
 // The scratch of hdlz_gunzip_ws, laid out once for the size query and the call: three words per stream (p, the header's verdict, the
 // CRC-32), the decoder's view of 2 nstreams offsets, one CRC word per 32 KiB tile of row capacity where the rows are tiled, and -- one

@@ -17,31 +17,10 @@
 #include "hdlz_device.h"
 #include "hdlz_crc32.h"
 #include "hdlz_frame.h"
+#include "hdlz_ranges.h"
 
 namespace hdlz {
 namespace bgzf {
-
-constexpr uint32_t RT = 256u;                      // threads of the per-range and per-task kernels, and of the scan
-constexpr uint64_t SLOT = 65536u;
-constexpr uint32_t H_TOTAL = 0u, H_NTASKS = 1u, H_CAPACITY = 2u, H_FIRST = 3u;      // the head's words
-
-// the first i in [0, n) with a[i] > v (upper) or a[i] >= v (lower); n when there is none
-__device__ __forceinline__ uint64_t upper(const uint64_t* __restrict__ a, uint64_t n, uint64_t v) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ uint64_t lower(const uint64_t* __restrict__ a, uint64_t n, uint64_t v) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
 
 // a virtual offset -> its position in the data; false when it names none (step 1)
 __device__ __forceinline__ bool resolve_virtual(const RangeArgs& a, uint64_t v, uint64_t& p) {
@@ -153,7 +132,7 @@ __global__ __launch_bounds__(RT) void k_ranges_expand(RangeArgs a) {
             if (!first && !last) st = HDLZ_E_BAD_PARAM;                           // (only with an index that is not ascending)
             else {
                 const uint64_t slot = 2u * r + (first ? 0u : 1u);
-                dst = a.slots + slot * SLOT;
+                dst = a.slots + slot * a.slot_bytes;
                 a.r_edge[slot] = (uint32_t)t;
             }
         }
@@ -200,7 +179,7 @@ __global__ __launch_bounds__(RT) void k_ranges_slice(RangeArgs a) {
         const uint64_t p0 = a.r_p0[r], p1 = a.r_p1[r];
         const uint64_t s0 = o > p0 ? o : p0, s1 = e < p1 ? e : p1;
         if (s1 <= s0) continue;
-        const uint8_t* __restrict__ src = a.slots + slot * SLOT + (s0 - o);
+        const uint8_t* __restrict__ src = a.slots + slot * a.slot_bytes + (s0 - o);
         uint8_t* __restrict__ dst = a.out + (a.range_off[r] + (s0 - p0));
         copy_to_aligned16(dst, src, (uint32_t)(s1 - s0), tid, RT);
     }
@@ -244,13 +223,13 @@ __global__ void k_ranges_empty(uint64_t* range_off, hdlz_bgzf_ranges_result* res
 
 }  // namespace bgzf
 
-size_t bgzf_ranges_work_bytes(uint64_t R, uint64_t T) {
+size_t bgzf_ranges_work_bytes(uint64_t R, uint64_t T, uint64_t slot_bytes) {
     if (R == 0) return 0;
     return 256u + 4u * round256(8u * ((size_t)R + 1u)) + 3u * round256(4u * (size_t)R) + 3u * round256(8u * (size_t)T) +
-           6u * round256(4u * (size_t)T) + (size_t)(2u * bgzf::SLOT) * (size_t)R;
+           6u * round256(4u * (size_t)T) + (size_t)(2u * slot_bytes) * (size_t)R;
 }
 
-RangeArgs bgzf_ranges_args(void* work, uint64_t R, uint64_t T) {
+RangeArgs bgzf_ranges_args(void* work, uint64_t R, uint64_t T, uint64_t slot_bytes) {
     RangeArgs a{};
     uint8_t* p = static_cast<uint8_t*>(work);
     const size_t r8 = round256(8u * ((size_t)R + 1u)), r4 = round256(4u * (size_t)R), t8 = round256(8u * (size_t)T), t4 = round256(4u * (size_t)T);
@@ -263,32 +242,51 @@ RangeArgs bgzf_ranges_args(void* work, uint64_t R, uint64_t T) {
     a.t_cap = reinterpret_cast<uint32_t*>(take(t4)); a.t_len = reinterpret_cast<uint32_t*>(take(t4)); a.t_status = reinterpret_cast<uint32_t*>(take(t4));
     a.t_end_bit = reinterpret_cast<uint32_t*>(take(t4)); a.t_crc = reinterpret_cast<uint32_t*>(take(t4)); a.t_range = reinterpret_cast<uint32_t*>(take(t4));
     a.slots = p;
+    a.slot_bytes = slot_bytes;
     return a;
 }
 
 static inline dim3 capped(uint64_t n) { return dim3((unsigned)(n < (1u << 20) ? n : (1u << 20))); }
 static inline dim3 groups_of(uint64_t n) { return dim3((unsigned)((n + bgzf::RT - 1u) / bgzf::RT)); }
 
-hipError_t launch_bgzf_ranges_plan(const RangeArgs& a, hipStream_t stream) {
+// (an empty batch: the record at once, and launch_ranges_deliver has nothing left to do)
+hipError_t launch_ranges_resolve_scan(const RangeArgs& a, hipStream_t stream) {
     using namespace bgzf;
     if (a.nranges == 0) return launch(k_ranges_empty, dim3(1), dim3(1), stream, a.range_off, a.result);
     hipError_t e = launch(k_ranges_resolve, groups_of(a.nranges), dim3(RT), stream, a);
     if (e == hipSuccess) e = launch(k_ranges_scan, dim3(1), dim3(RT), stream, a);
-    if (e == hipSuccess && a.task_cap) e = launch(k_ranges_expand, groups_of(a.task_cap), dim3(RT), stream, a);
+    return e;
+}
+
+hipError_t launch_bgzf_ranges_plan(const RangeArgs& a, hipStream_t stream) {
+    using namespace bgzf;
+    hipError_t e = launch_ranges_resolve_scan(a, stream);
+    if (e == hipSuccess && a.nranges && a.task_cap) e = launch(k_ranges_expand, groups_of(a.task_cap), dim3(RT), stream, a);
+    return e;
+}
+
+hipError_t launch_ranges_crc(const RangeArgs& a, hipStream_t stream) {
+    using namespace bgzf;
+    if (a.nranges == 0 || a.task_cap == 0) return hipSuccess;
+    return launch(k_ranges_crc, capped(a.task_cap), dim3(CRC_THREADS), stream, a);
+}
+
+hipError_t launch_ranges_deliver(const RangeArgs& a, hipStream_t stream) {
+    using namespace bgzf;
+    if (a.nranges == 0) return hipSuccess;
+    hipError_t e = hipSuccess;
+    if (a.task_cap) e = launch(k_ranges_slice, capped(2u * a.nranges), dim3(RT), stream, a);
+    if (e == hipSuccess) e = launch(k_ranges_finish, groups_of(a.nranges), dim3(RT), stream, a);
+    if (e == hipSuccess) e = launch(k_ranges_record, dim3(1), dim3(1), stream, a);
     return e;
 }
 
 hipError_t launch_bgzf_ranges_finish(const RangeArgs& a, hipStream_t stream) {
     using namespace bgzf;
     if (a.nranges == 0) return hipSuccess;
-    hipError_t e = hipSuccess;
-    if (a.task_cap) {
-        e = launch(k_ranges_crc, capped(a.task_cap), dim3(CRC_THREADS), stream, a);
-        if (e == hipSuccess) e = launch(k_ranges_judge, groups_of(a.task_cap), dim3(RT), stream, a);
-        if (e == hipSuccess) e = launch(k_ranges_slice, capped(2u * a.nranges), dim3(RT), stream, a);
-    }
-    if (e == hipSuccess) e = launch(k_ranges_finish, groups_of(a.nranges), dim3(RT), stream, a);
-    if (e == hipSuccess) e = launch(k_ranges_record, dim3(1), dim3(1), stream, a);
+    hipError_t e = launch_ranges_crc(a, stream);
+    if (e == hipSuccess && a.task_cap) e = launch(k_ranges_judge, groups_of(a.task_cap), dim3(RT), stream, a);
+    if (e == hipSuccess) e = launch_ranges_deliver(a, stream);
     return e;
 }
 

@@ -11,6 +11,7 @@
 #include "../../include/hdlz_zip.h"
 #include "../../include/hdlz_zip_write.h"
 #include "../../include/hdlz_zip64.h"
+#include "../../include/hdlz_seek.h"
 
 namespace hdlz {
 
@@ -31,6 +32,17 @@ struct CompressArgs {
                                    // for it never takes k_compress_small.
 };
 
+// The POINT SINK of hdlz_seek_index_ws (include/hdlz_seek.h): where the recording view of k_inflate_dyn leaves the seek
+// points of the ONE stream it decodes.  bit == nullptr: no sink, which is what every other caller passes.
+struct PointSink {
+    uint64_t* head = nullptr;    // [0] the count of points, true also past cap; [1] the absolute bit behind the final block's last bit;
+                                 // [2] zeroed by the entry point; 1: the chain route filled the sink (k_any_points), the wave has nothing to do
+    uint64_t* bit = nullptr;     // cap words: the absolute bit of the header in front of point k (8 * the stream's first byte + its own bit)
+    uint64_t* pos = nullptr;     // cap words: the output offset there
+    uint32_t cap = 0;
+    uint32_t span = 1;
+};
+
 struct InflateArgs {
     const uint8_t* in;
     const uint64_t* in_off;
@@ -45,6 +57,7 @@ struct InflateArgs {
     uint32_t* status;
     uint32_t* in_used = nullptr;   // nullable (hdlz_inflate_checked): per stream, the index of the first byte behind the last bit of the final
                                    // block, counted from the stream's first byte; 0 for a stream whose decode fails.  Moves with out_len / status.
+    PointSink sink{};              // hdlz_seek_index_ws only (k_inflate_dyn's recording view); no other kernel looks at it
 };
 
 // The MEMBER VIEW of the batch decoders (hdlz_unjoin_ws): stream b is member b of a joined stream, its output slot a
@@ -65,6 +78,23 @@ struct MemberArgs : InflateArgs {
     uint8_t* const* m_dst = nullptr;      // nullable, k_inflate_dyn<false, true> only: member b decodes to m_dst[b], m_dst_cap[b] bytes of room;
     const uint32_t* m_dst_cap = nullptr;  //   out, m_out_off, m_out_len and m_out_cap are not used then.  The launchers of the other two
                                           //   twins refuse a record with m_dst set (hipErrorInvalidValue): they would decode to out + 0
+};
+// The SEGMENT VIEW of k_inflate_dyn (hdlz_seek_read_ranges_ws): task t is one segment of a seek index -- the blocks
+// between two seek points.  It starts at bit (t_sbit[t] & 7) of byte t_off[t], its input ends in front of byte t_end[t], it decodes to
+// t_dst[t] with exactly t_cap[t] bytes of room, and the t_hist[t] bytes of history in front of it are the last ones of the 32 KiB
+// window win + 32768 * t_k[t].  Bit 31 of t_sbit: the stream's last segment, which ends at BFINAL; every other one stops at the first
+// block header at or behind bit[t_k[t] + 1], the next point's.  Of the base: in, nstreams (the task slots), out_len, status (READ first, as in the member view)
+// and in_used, which receives the absolute bit in the file where the task stopped.
+struct SegArgs : InflateArgs {
+    const uint64_t* t_off;
+    const uint64_t* t_end;
+    uint8_t* const* t_dst;
+    const uint32_t* t_cap;
+    const uint32_t* t_sbit;
+    const uint32_t* t_hist;
+    const uint32_t* t_k;
+    const uint8_t* win;
+    const uint64_t* bit;         // the index's d_bit
 };
 // the stream a decoder sees is in[m_off[b] - 2 .. m_off[b + 1]): it skips two bytes unvalidated (never loaded: the FF FF of the marker in
 // front, or 78 9C; BGZF: the BSIZE field), and the member's own marker (BGZF: its 8-byte trailer) supplies the bytes the end-of-input
@@ -134,6 +164,8 @@ hipError_t launch_inflate_tok_dyn(const InflateArgs& a, hipStream_t stream, bool
 hipError_t launch_inflate_par(const InflateArgs& a, hipStream_t stream, bool* used, const Work& w);
 hipError_t launch_inflate_dyn(const InflateArgs& a, hipStream_t stream, bool all, const uint32_t* few_n = nullptr, uint32_t lane_min = 0);
 hipError_t launch_inflate_dyn_flagged(const InflateArgs& a, hipStream_t stream);
+hipError_t launch_inflate_dyn_record(const InflateArgs& a, hipStream_t stream, const uint32_t* done = nullptr);   // ONE stream, a.sink set: the recording view
+hipError_t launch_inflate_dyn_segments(const SegArgs& a, hipStream_t stream);        // the segment view, a wave per task
 // the judging pass of hdlz_inflate_checked (hdlz_checksum.hip): behind a decode that stored in_used, on the same stream
 struct JudgeArgs {
     const uint8_t* in;
@@ -308,11 +340,42 @@ struct RangeArgs {
     uint8_t** t_dst;
     uint32_t *t_cap, *t_len, *t_status, *t_end_bit, *t_crc, *t_range;
     uint8_t* slots;
+    uint64_t slot_bytes;         // the size of a slot: 65536 for BGZF; hdlz_seek_read_ranges_ws: its seg_cap, rounded up to 256
 };
-size_t bgzf_ranges_work_bytes(uint64_t nranges, uint64_t task_cap);
-RangeArgs bgzf_ranges_args(void* work, uint64_t nranges, uint64_t task_cap);       // the pieces of the scratch; the caller fills in the rest
+size_t bgzf_ranges_work_bytes(uint64_t nranges, uint64_t task_cap, uint64_t slot_bytes = 65536u);
+RangeArgs bgzf_ranges_args(void* work, uint64_t nranges, uint64_t task_cap, uint64_t slot_bytes = 65536u);   // the pieces of the scratch; the caller fills in the rest
 hipError_t launch_bgzf_ranges_plan(const RangeArgs& a, hipStream_t stream);        // resolve, scan, expand and check: in front of the decode
 hipError_t launch_bgzf_ranges_finish(const RangeArgs& a, hipStream_t stream);      // CRC words, judgement, edge slices, statuses, the record
+// ... and the steps of the two that know nothing of a BGZF member, for hdlz_seek_read_ranges_ws (hdlz_seek.hip has its own expand and judge)
+hipError_t launch_ranges_resolve_scan(const RangeArgs& a, hipStream_t stream);     // k_ranges_resolve (plain mode), k_ranges_scan
+hipError_t launch_ranges_crc(const RangeArgs& a, hipStream_t stream);              // k_ranges_crc
+hipError_t launch_ranges_deliver(const RangeArgs& a, hipStream_t stream);          // k_ranges_slice, k_ranges_finish, k_ranges_record
+
+// hdlz_seek.hip: hdlz_seek_index_ws and hdlz_seek_read_ranges_ws (include/hdlz_seek.h)
+struct SeekIndexArgs {
+    const uint8_t* out;          // the decoded stream
+    const uint32_t* out_len;     // the judged call's words for the ONE stream
+    const uint32_t* status;
+    PointSink sink;              // as the decoder filled it
+    uint64_t* bit;               // the caller's four arrays
+    uint64_t* pos;
+    uint32_t* crc;
+    uint8_t* win;
+    uint64_t point_cap;
+    hdlz_seek_result* result;
+    uint64_t* head;              // scratch, 256 bytes: [0] the points the arrays hold (0 when they are not written)
+};
+hipError_t launch_seek_index_finish(const SeekIndexArgs& a, hipStream_t stream);    // k_seek_points, k_seek_windows, k_seek_crc
+struct SeekRangeArgs {
+    RangeArgs r;                 // r.out_off: d_pos; r.nmembers: npoints; r.off is not used
+    const uint64_t* bit;
+    const uint32_t* crc;
+    const uint8_t* win;
+    uint64_t seg_cap;
+    uint32_t *t_sbit, *t_hist, *t_k;      // scratch, task_cap words each: SegArgs
+};
+hipError_t launch_seek_expand(const SeekRangeArgs& a, hipStream_t stream);
+hipError_t launch_seek_judge(const SeekRangeArgs& a, hipStream_t stream);
 
 // hdlz_crc32.hip: CRC-32 of data[0 .. n) -> crc[0].  `words`: one word per 32 KiB tile (crc32_tiles(n) of them; null when n is 0).
 size_t crc32_tiles(uint64_t n);

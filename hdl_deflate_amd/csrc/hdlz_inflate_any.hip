@@ -74,6 +74,8 @@ constexpr uint32_t FIRST_FIX_BITS = 4096;     // a FIRST block that is fixed: th
 constexpr uint32_t NO_OWNER = 0xFFFFu;
 constexpr uint32_t N_END = 0xFFFFFFFEu, N_BAD = 0xFFFFFFFFu;      // successor of a node: the stream ends / no valid successor
 enum { A_NCAND = par::C_ANY0, A_NBLK, A_NX, A_NS, A_OVER, A_WHY, A_NREQ, A_NREQP, A_OPEN };       // this chain's counters in its control words; A_WHY: bits of W_* (diagnostics)
+constexpr uint32_t ENDBIT_WORD = A_OPEN + 1u;                          // one more control word, k_any_rank -> k_any_points: the bit behind the final block
+static_assert(ENDBIT_WORD < par::C_WORDS, "inside the control words");
 enum { W_OVER = 1, W_NODE = 2, W_NEXT = 4, W_CAP = 8, W_CYCLE = 16, W_ITEMS = 32, W_TOKEN = 64, W_TCAP = 128, W_WALK_OWNER = 256, W_WALK_MAP = 512,
        W_WALK_HDR = 1024, W_WALK_STORED = 2048, W_WALK_FIX = 4096, W_WALK_TOK = 8192, W_VERIFY = 16384 };
 
@@ -1013,6 +1015,7 @@ __global__ __launch_bounds__(RANK_T) void k_any_rank(Args a) {
     if (!good) { give_up(v); return; }
     v.ctl[C_TOTAL] = (uint32_t)total;
     v.ctl[par::C_END] = (endbit + 7u) >> 3;
+    v.ctl[ENDBIT_WORD] = endbit;
     v.ctl[C_NUSED] = a.nchunks + nx_items;
     v.ctl[C_FNUSED] = a.nchunks + nx_items;
     v.ctl[C_OK] = 1u;
@@ -1180,6 +1183,45 @@ __global__ __launch_bounds__(64) void k_any_zero(Args a) {
     if (threadIdx.x < par::C_WORDS) ctl[threadIdx.x] = threadIdx.x == (uint32_t)A_OPEN ? open : 0u;
 }
 
+// ================================================================================================ 5. the seek points (hdlz_seek_index_ws)
+// Behind k_par_finish, ONE workgroup, one stream: where this chain delivered the stream, the point rule of include/hdlz_seek.h over
+// S = the stream's first header (the pseudo-node) and every node on the true chain (ok == 2) -- the dynamic headers --, as (header
+// bit, obase).  A thread per node: a node knows its successor's position as obase + nbytes, so it decides whether its successor is a
+// point; the selected ones are gathered in any order (in the candidate list, dead by now), then every one finds its place by counting
+// the selected positions below its own -- they are distinct, a point's cell lies behind its predecessor's -- and is written there.
+// sink.head[2] = 1 tells the recording view of the wave decoder, launched behind this kernel, that the points are in: it returns at once.
+constexpr uint32_t PT_T = 1024;
+__global__ __launch_bounds__(PT_T) void k_any_points(Args a, PointSink sink, const uint32_t* pctl) {
+    const View v = view(a);
+    __shared__ uint32_t s_cnt;
+    const uint32_t tid = threadIdx.x;
+    // (pctl: the other chain's control words, where k_par_finish left the verdict over both)
+    if (pctl[C_OK] == 0u || v.ctl[C_OK] == 0u || v.ctl[par::C_FALLBACK] != 0u) return;      // not this chain's stream: head[2] stays 0
+    const uint32_t n = min(v.ctl[A_NBLK], a.maxb), span = sink.span;
+    uint32_t* selpos = v.cand;                                      // (candcap >= 1024 + 64 * maxb words: room for 2 * (maxb + 1))
+    uint32_t* selbit = v.cand + (a.maxb + 1u);
+    if (tid == 0u) s_cnt = 0u;
+    __syncthreads();
+    for (uint32_t i = tid; i <= n; i += PT_T) {
+        const Node nd = v.node[i < n ? i : a.maxb];
+        if (nd.ok != 2u) continue;
+        if (i == n) { const uint32_t k = atomicAdd(&s_cnt, 1u); selpos[k] = 0u; selbit[k] = 16u; }      // point 0: the first header
+        if (nd.next >= n) continue;                                 // the stream ends behind this node
+        const uint32_t pb = nd.obase + nd.nbytes;
+        if (pb / span > nd.obase / span) { const uint32_t k = atomicAdd(&s_cnt, 1u); selpos[k] = pb; selbit[k] = v.shdr[nd.next]; }
+    }
+    __syncthreads();
+    const uint32_t m = s_cnt;                                       // at most n + 1: one per node on the chain
+    const uint64_t base = 8ull * (uint64_t)(v.z - a.z);
+    for (uint32_t i = tid; i < m; i += PT_T) {
+        const uint32_t p = selpos[i];
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < m; j++) r += selpos[j] < p ? 1u : 0u;
+        if (r < sink.cap) { sink.pos[r] = p; sink.bit[r] = base + selbit[i]; }
+    }
+    if (tid == 0u) { sink.head[0] = m; sink.head[1] = base + v.ctl[ENDBIT_WORD]; sink.head[2] = 1u; }
+}
+
 // streams below ANY_MIN bytes stay with the serial decoder: the chain of launches takes 0.55 ms whatever the stream, one wave 0.2 ms per
 // KB of compressed bytes (0.96 ms at 4.7 KB, 1.64 at 8.9 KB).  Streams per call (any_work_bytes): the more streams, the longer each
 // must be for the chain to beat a wave per stream (profiles/r06_any_batches.txt)
@@ -1275,6 +1317,17 @@ hipError_t launch_inflate_any(const par::ParArgs& p, uint8_t* ws, uint32_t nstr,
     const uint32_t passes = par::passes_for(nitems);
     *passes_out = passes;
     return par::par_launch_emit_jump(q, nitems, passes, nstr, stream);
+}
+
+// hdlz_seek_index_ws, one stream, behind k_par_finish: the points of the stream this chain delivered (k_any_points)
+hipError_t launch_inflate_any_points(const par::ParArgs& p, uint8_t* ws, const PointSink& sink, hipStream_t stream) {
+    using namespace any;
+    Args g;
+    memset(&g, 0, sizeof(g));
+    static_cast<Call&>(g) = Call{p.z, p.zn, p.flags, p.obsize, p.out, p.cap, p.srcn, p.in_pitch, p.out_pitch, p.in_off, ws, p.ws_stride, p.srcA};
+    static_cast<Lay&>(g) = lay_of(p.zn);
+    hipLaunchKernelGGL(k_any_points, dim3(1, 1), dim3(PT_T), 0, stream, g, sink, (const uint32_t*)p.ctl);
+    return hipGetLastError();
 }
 
 }  // namespace hdlz

@@ -143,8 +143,19 @@ __device__ __forceinline__ void xwalk(const XCode& X, uint32_t bits15, uint32_t&
 // far runs out (the reference's `di >= isize - 4 and not i_mode == IDLE` stall, deflate.py:1529-1530) or the output limit
 // is reached (its `do >= i_raddr + OBSIZE` hold, deflate.py:1531-1534, :1597-1599), always stopping BETWEEN two tokens.
 // MEMBERS = true (with STREAM = false): the member view (hdlz_device.h: MemberArgs), as in k_inflate_tok.
-template <bool STREAM, bool MEMBERS = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_inflate_dyn(std::conditional_t<MEMBERS, MemberArgs, InflateArgs> a, hdlz_istate* ist, uint32_t out_limit, const uint32_t* few_n, uint32_t lane_min) {
+// VIEW (with STREAM = false, MEMBERS = false; include/hdlz_seek.h) -- every line of it stands under `if constexpr`, so
+// the instantiations with VIEW = 0 are the kernels they were:
+//   VIEW_RECORD   the recording view: at every block header, where its bit and the output offset are known, the point rule is applied
+//                 against the previous header and a selected one is appended to a.sink (hdlz_device.h: PointSink)
+//   VIEW_SEGMENT  the segment view (hdlz_device.h: SegArgs): a task starts at any bit of its first byte with o = 0 in its own
+//                 destination; the history in front of it is the window's -- the ring is primed from it, and a far source in front of
+//                 the segment is loaded from it --; a task that is not the stream's last stops at the first block header at or behind
+//                 the next point's bit
+constexpr int VIEW_RECORD = 1, VIEW_SEGMENT = 2;
+template <bool MEMBERS, int VIEW>
+using DynArgs = std::conditional_t<VIEW == VIEW_SEGMENT, SegArgs, std::conditional_t<MEMBERS, MemberArgs, InflateArgs>>;
+template <bool STREAM, bool MEMBERS = false, int VIEW = 0>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_inflate_dyn(DynArgs<MEMBERS, VIEW> a, hdlz_istate* ist, uint32_t out_limit, const uint32_t* few_n, uint32_t lane_min) {
     __shared__ DynLds L;
     const uint32_t lane = threadIdx.x;
     // second pass of the lane mapping: this kernel takes the flagged streams only when they are few (*few_n of them, counted by
@@ -158,7 +169,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         uint32_t zn;
         [[maybe_unused]] uint64_t m_o = 0;
         [[maybe_unused]] uint32_t m_cap = 0;
-        if constexpr (MEMBERS) {
+        [[maybe_unused]] uint32_t seg_h = 0, seg_sbit = 0, seg_stop = 0;    // VIEW_SEGMENT: history bytes in the window; the start bit; the next point's bit
+        [[maybe_unused]] bool seg_last = false;
+        [[maybe_unused]] const uint8_t* seg_win = nullptr;
+        [[maybe_unused]] uint32_t pt_n = 0, pt_cell = 0;                // VIEW_RECORD: points so far; the previous header's cell
+        if constexpr (VIEW == VIEW_SEGMENT) {
+            if (a.status[sid] != HDLZ_OK) continue;                     // refused by k_seek_expand, or an idle slot: left alone
+            off = a.t_off[sid];
+            zn = (uint32_t)(a.t_end[sid] - off);                        // (checked: inside the file, below 2^28)
+            seg_h = a.t_hist[sid]; seg_sbit = a.t_sbit[sid] & 7u; seg_last = (a.t_sbit[sid] >> 31) != 0u;
+            seg_win = a.win + 32768ull * a.t_k[sid];
+            seg_stop = (uint32_t)a.bit[a.t_k[sid] + 1u];                // (checked: at most 8 * file_len, below 2^31)
+        } else if constexpr (MEMBERS) {
             if (a.status[sid] != HDLZ_OK) continue;                     // refused by the index checks: left alone
             member_view(a, sid, off, zn, m_o, m_cap);
         } else if (a.in_off) {
@@ -185,8 +207,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         const uint8_t* __restrict__ z = a.in + off;
         uint8_t* out_base = a.out + (MEMBERS ? m_o : sid * a.out_pitch);
         if constexpr (MEMBERS) { if (a.m_dst) out_base = a.m_dst[sid]; }    // the task view: a destination per member
+        if constexpr (VIEW == VIEW_SEGMENT) out_base = a.t_dst[sid];
         uint8_t* __restrict__ out = out_base;
-        const uint32_t cap0 = MEMBERS ? m_cap : a.out_pitch > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)a.out_pitch;
+        [[maybe_unused]] uint32_t seg_cap = 0;
+        if constexpr (VIEW == VIEW_SEGMENT) seg_cap = a.t_cap[sid];
+        const uint32_t cap0 = VIEW == VIEW_SEGMENT ? seg_cap : MEMBERS ? m_cap : a.out_pitch > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)a.out_pitch;
         const uint32_t cap = STREAM ? (out_limit < cap0 ? out_limit : cap0) : cap0;      // STREAM: reaching it is a stop, not an error
         const uint32_t inbits = 8u * zn;                                                 // (zn < 2^28)
         const uint32_t obsize = a.obsize ? a.obsize : 32768u;
@@ -254,6 +279,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             __syncthreads();
             RESYNC(save_bit);
         }
+        if constexpr (VIEW == VIEW_SEGMENT) {
+            // the ring holds what lies in front of o = 0: the window's last min(h, DRING) bytes, at the slots of the "negative" positions
+            const uint32_t hp = seg_h < DRING ? seg_h : DRING;
+            for (uint32_t j = 1u + lane; j <= hp; j += 64u) L.ring[(0u - j) & (DRING - 1u)] = seg_win[32768u - j];
+            __syncthreads();
+            RESYNC(seg_sbit);                                           // no zlib header to skip: the task's first header bit
+        }
         for (;;) {
             uint32_t final_, hm;
             uint32_t blk_bit = 0;
@@ -264,6 +296,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             REFILL();
             blk_bit = BITPOS();
             if (STREAM && !sfinal && blk_bit + 64u > inbits) { save_bit = blk_bit; save_phase = 0; need = 1; goto done; }
+            if constexpr (VIEW == VIEW_RECORD) {
+                // the point rule (include/hdlz_seek.h), S = every header: the first one, and each whose cell lies behind its predecessor's
+                const uint32_t cell = o / a.sink.span;
+                if (pt_n == 0u || cell > pt_cell) {
+                    if (lane == 0 && pt_n < a.sink.cap) { a.sink.bit[pt_n] = 8ull * off + blk_bit; a.sink.pos[pt_n] = o; }
+                    pt_n++;
+                }
+                pt_cell = cell;
+            }
+            if constexpr (VIEW == VIEW_SEGMENT) {
+                // the next point's header (or one behind it): nothing of it is taken (BITPOS() = blk_bit).  Headers in front of it are
+                // decoded whatever o is -- empty blocks in front of a point that a route did not know as boundaries --, and a token
+                // behind the expected length fails as output beyond the room
+                if (!seg_last && (uint32_t)(8ull * off) + blk_bit >= seg_stop) goto done;
+            }
             // HEADER (deflate.py:677-732)
             final_ = ((uint32_t)bb & 1u) | ((a.flags & HDLZ_INFLATE_ONEBLOCK) ? 1u : 0u);   // ONEBLOCK: deflate.py:678,:1542,:1617
             hm = (a.flags & HDLZ_INFLATE_ASSUME_FIXED) ? 1u : ((uint32_t)(bb >> 1) & 3u);   // DYNAMIC=False build: deflate.py:724-732
@@ -517,7 +564,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                         const uint32_t outcode = STREAM ? ST_NEEDOUT : (uint32_t)HDLZ_E_OUT_CAPACITY;
                         uint32_t m = ((uint64_t)pos + tlen > cap) ? outcode : 0u;
                         m = (sfinal && copy_hold(bitpos + total, isize)) ? (uint32_t)HDLZ_E_NO_EOF : m;
-                        m = (distance > pos || distance > obsize) ? (uint32_t)HDLZ_E_BAD_DISTANCE : m;                    // deflate.py:1506-1508, D8
+                        bool too_far = distance > pos || distance > obsize;                                               // deflate.py:1506-1508, D8
+                        if constexpr (VIEW == VIEW_SEGMENT) too_far = distance > obsize || (distance > pos && distance - pos > seg_h);   // distance > pos + h
+                        m = too_far ? (uint32_t)HDLZ_E_BAD_DISTANCE : m;
                         m = ds >= 30u ? (uint32_t)HDLZ_E_BAD_DISTANCE : m;
                         m = (dlen > 15u || token >= 29u) ? (uint32_t)HDLZ_E_BAD_SYMBOL : m;
                         st = lit ? (pos >= cap ? outcode : 0u) : m;
@@ -604,6 +653,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                             const uint32_t src = P - D + (D >= tlength ? i : i % D);
                             uint32_t byte;
                             if ((P + i) - src <= DRING - 512u) byte = L.ring[src & (DRING - 1u)];   // still in the ring for sure
+                            else if constexpr (VIEW == VIEW_SEGMENT) byte = src > P + i ? seg_win[32768u + src] : out[src];   // src wrapped below 0: in front of the segment
                             else byte = out[src];                               // far history: flushed long ago
                             L.ring[(P + i) & (DRING - 1u)] = (uint8_t)byte;
                         }
@@ -625,6 +675,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         // STREAM: a stop for output room that no larger out_limit can ever give (the limit is not below the capacity) is the
         // batch call's HDLZ_E_OUT_CAPACITY, not need = 2 forever
         if (STREAM && status == HDLZ_OK && need == 2u && cap0 <= out_limit) status = HDLZ_E_OUT_CAPACITY;
+        if constexpr (VIEW == VIEW_SEGMENT) {
+            // whatever fails with the expected length out, in front of the next point's bit: the segment does not end where the index says
+            if (status != HDLZ_OK && !seg_last && o >= cap) status = HDLZ_E_NO_EOF;
+        }
         if (status == HDLZ_OK) {
             const uint32_t c0 = o & ~(DCHUNK - 1u);
             if (c0 + lane < o) out[c0 + lane] = L.ring[(c0 + lane) & (DRING - 1u)];
@@ -644,7 +698,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             a.status[sid] = status;
             // where the stream ended (hdlz_inflate_checked): the bit reader stands behind the final block's last bit
             // (MEMBERS: the end bit itself)
-            if (a.in_used) a.in_used[sid] = status != HDLZ_OK ? 0u : MEMBERS ? BITPOS() : (BITPOS() + 7u) >> 3;
+            if (a.in_used) a.in_used[sid] = status != HDLZ_OK ? 0u : VIEW == VIEW_SEGMENT ? (uint32_t)(8ull * off) + BITPOS() : MEMBERS ? BITPOS() : (BITPOS() + 7u) >> 3;
+            if constexpr (VIEW == VIEW_RECORD) { a.sink.head[0] = pt_n; a.sink.head[1] = 8ull * off + BITPOS(); }
         }
         __syncthreads();
 #undef REFILL
@@ -676,6 +731,26 @@ hipError_t launch_inflate_dyn(const InflateArgs& a0, hipStream_t stream, bool al
     InflateArgs a = a0;
     if (all) a.flags |= DYN_ALL;
     return launch_dyn<false>(a, stream, few_n, lane_min);
+}
+
+// hdlz_seek_index_ws: the ONE stream of the call, decoded by the recording view
+// (`done`: nullable, a device word -- not 0: the points are in already, the kernel returns at once)
+hipError_t launch_inflate_dyn_record(const InflateArgs& a0, hipStream_t stream, const uint32_t* done) {
+    if (a0.nstreams != 1 || !a0.sink.bit || !a0.sink.pos || !a0.sink.head || a0.sink.span == 0u) return hipErrorInvalidValue;
+    InflateArgs a = a0;
+    a.flags |= DYN_ALL;
+    hipLaunchKernelGGL((k_inflate_dyn<false, false, VIEW_RECORD>), dim3(1), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, done, 1u);
+    return hipGetLastError();
+}
+
+// hdlz_seek_read_ranges_ws: a wave per task slot (the kernel strides past 65536 workgroups)
+hipError_t launch_inflate_dyn_segments(const SegArgs& a0, hipStream_t stream) {
+    if (a0.nstreams == 0) return hipSuccess;
+    SegArgs a = a0;
+    a.flags |= DYN_ALL;
+    const uint64_t g = a.nstreams < 65536u ? a.nstreams : 65536u;
+    hipLaunchKernelGGL((k_inflate_dyn<false, false, VIEW_SEGMENT>), dim3((unsigned)g), dim3(64), 0, stream, a, (hdlz_istate*)nullptr, 0u, (const uint32_t*)nullptr, 0u);
+    return hipGetLastError();
 }
 
 // the member twin (hdlz_unjoin_ws): every member the index checks passed, one wave each

@@ -105,4 +105,6 @@ size_t any_work_bytes(uint32_t in_len, uint64_t out_pitch, uint32_t flags, uint3
 //  writes them), the stride between the streams' scratch; ws: this chain's part of stream 0's scratch, whose first par::C_WORDS words
 //  are its control words -- read by k_par_finish)
 hipError_t launch_inflate_any(const par::ParArgs& p, uint8_t* ws, uint32_t nstr, hipStream_t stream, uint32_t* passes_out);
+// ... and, one stream, behind k_par_finish: the seek points of the stream that chain delivered (hdlz_seek_index_ws; p.ctl holds the verdict)
+hipError_t launch_inflate_any_points(const par::ParArgs& p, uint8_t* ws, const PointSink& sink, hipStream_t stream);
 }  // namespace hdlz

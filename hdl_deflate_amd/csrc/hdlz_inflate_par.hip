@@ -1067,6 +1067,14 @@ static hipError_t launch_chains(const par::Layout& L, const InflateArgs& a, hipS
         e = hipGetLastError();
     }
     // ONE stream: the serial decoder returns at once when ctl[C_OK] >= 1; several: it redoes the streams k_par_finish flagged
+    if (a.sink.bit) {
+        // hdlz_seek_index_ws (one stream): the chain for any block types leaves its points behind (the chain route); whatever else
+        // happened -- the chains gave up, or the fixed-block chain delivered -- the recording view of the serial decoder runs, which
+        // for a give-up is the run that would decode the stream anyway.  It returns at once when sink.head[2] says the points are in.
+        if (e == hipSuccess && L.any_bytes != 0u) e = launch_inflate_any_points(p, L.any, a.sink, stream);
+        if (e == hipSuccess) e = launch_inflate_dyn_record(a, stream, reinterpret_cast<const uint32_t*>(a.sink.head + 2));
+        return e;
+    }
     if (e == hipSuccess) e = nstr == 1u ? launch_inflate_dyn(a, stream, true, p.ctl + C_OK, 1u) : launch_inflate_dyn_flagged(a, stream);
     return e;
 }

@@ -487,25 +487,29 @@ class Engine(object):
         self._is_bytes(d_file, "d_file", flat=True)
         dev = d_file.device
         off, out_off = self._file_index(d_file, index, "read_bgzf")
-        if not torch.is_tensor(ranges):
-            pairs = [[int(v) - (1 << 64) if int(v) >= 1 << 63 else int(v) for v in pair] for pair in ranges]      # the words are unsigned
-            ranges = torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
-        assert ranges.is_cuda and ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2 and ranges.is_contiguous()
-        R, flags = ranges.shape[0], _lib.BGZF_RANGE_VIRTUAL if virtual else 0
-        query = self.lib.hdlz_bgzf_ranges_work_bytes
+        ranges = self._range_pairs(ranges, dev)
+        flags = _lib.BGZF_RANGE_VIRTUAL if virtual else 0
+        return self._ranged_read("read_bgzf", lambda n, ntasks: self.lib.hdlz_bgzf_ranges_work_bytes(n, ntasks, flags),
+                                 lambda rg, dst, ntasks, scratch: self._read_ranges(d_file, off, out_off, rg, flags, dst, dst.numel(), ntasks, scratch),
+                                 131072, 48, ranges, dev, out, work, max_work_bytes)
+
+    def _ranged_read(self, what, query, call, slot_bytes, task_bytes, ranges, dev, out, work, max_work_bytes):
+        """the groups of read_bgzf and read_seek.  query(n, ntasks): the scratch of a call of n ranges and ntasks tasks, of which
+        slot_bytes are a range's slots and task_bytes a task's words; call(ranges, dst, ntasks, scratch) -> (record, range_off)"""
+        R = ranges.shape[0]
         if work is not None:
             self._is_bytes(work, "work")
             max_work_bytes = work.numel()
         if out is not None:
             self._is_bytes(out, "out")
-        group = max(1, (max_work_bytes - 8192) // (131072 + 256))                  # ranges of two members each
-        while group > 1 and query(group, 2 * group, flags) > max_work_bytes:
+        group = max(1, (max_work_bytes - 8192) // (slot_bytes + 256))               # ranges of two tasks each
+        while group > 1 and query(group, 2 * group) > max_work_bytes:
             group -= 1
         todo = [(g, min(R, g + group)) for g in range(0, R, group)][::-1]          # a stack: the lowest group on top
         pieces, offsets, pos = [], [], 0
 
         def scratch(n, ntasks):
-            need = query(n, ntasks, flags)
+            need = query(n, ntasks)
             return work if work is not None and work.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
         while todo:
             g0, g1 = todo.pop()
@@ -514,22 +518,22 @@ class Engine(object):
                 dst, ntasks = torch.empty(0, dtype=torch.uint8, device=dev), 0     # the sizing call
             else:
                 dst = out[pos:]
-                fit = max(0, max_work_bytes - query(n, 0, flags) - 9 * 256) // 48  # task words that fit behind the group's slots
+                fit = max(0, max_work_bytes - query(n, 0) - 9 * 256) // task_bytes  # task words that fit behind the group's slots
                 ntasks = min(fit, 2 * n + dst.numel() // 256)                      # the guess
-            rec, range_off = self._read_ranges(d_file, off, out_off, rg, flags, dst, dst.numel(), ntasks, scratch(n, ntasks))
+            rec, range_off = call(rg, dst, ntasks, scratch(n, ntasks))
             if rec.status == E_OUT_CAPACITY:                                       # the sizing call, or a guess that did not hold
                 if rec.total_out == (1 << 64) - 1:
-                    raise ValueError("read_bgzf: the lengths of the ranges exceed 64 bits: the index is not ascending")
+                    raise ValueError("%s: the lengths of the ranges exceed 64 bits: the index is not ascending" % what)
                 if out is not None and rec.total_out > dst.numel():
-                    raise ValueError("read_bgzf: `out` has room for %d bytes behind the earlier groups, this one holds %d" % (dst.numel(), rec.total_out))
-                if n > 1 and query(n, rec.ntasks, flags) > max_work_bytes:
+                    raise ValueError("%s: `out` has room for %d bytes behind the earlier groups, this one holds %d" % (what, dst.numel(), rec.total_out))
+                if n > 1 and query(n, rec.ntasks) > max_work_bytes:
                     mid = g0 + n // 2
                     todo += [(mid, g1), (g0, mid)]
                     continue
                 if out is None:
                     dst = torch.empty(rec.total_out, dtype=torch.uint8, device=dev)
-                rec, range_off = self._read_ranges(d_file, off, out_off, rg, flags, dst, dst.numel(), rec.ntasks, scratch(n, rec.ntasks))
-            _raise_unless_ok(rec, "read_bgzf", base=g0)
+                rec, range_off = call(rg, dst, rec.ntasks, scratch(n, rec.ntasks))
+            _raise_unless_ok(rec, what, base=g0)
             pieces.append(dst[:rec.total_out])
             offsets.append(range_off[:-1] + pos)
             pos += rec.total_out
@@ -538,11 +542,101 @@ class Engine(object):
             out = pieces[0] if len(pieces) == 1 else torch.cat(pieces) if pieces else torch.empty(0, dtype=torch.uint8, device=dev)
         return out[:pos], torch.cat(offsets)
 
+    @staticmethod
+    def _range_pairs(ranges, dev):
+        """R pairs (begin, end), a Python sequence or an int64 device tensor [R, 2] -> the tensor (the words are unsigned)"""
+        if not torch.is_tensor(ranges):
+            pairs = [[int(v) - (1 << 64) if int(v) >= 1 << 63 else int(v) for v in pair] for pair in ranges]
+            ranges = torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
+        assert ranges.is_cuda and ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2 and ranges.is_contiguous()
+        return ranges
+
     def read_bgzf_bytes(self, z, begin, end):
         """the bytes of a BGZF file -> (status, bytes [begin, end) of its data), clipped to the data"""
         d = self._stage(z)[:len(z)]
         try:
             out, _ = self.read_bgzf(d, [(begin, end)])
+        except HdlzStatusError as e:
+            return e.status, b""
+        return OK, bytes(out.cpu().numpy().tobytes())
+
+    # -- random access into any gzip or zlib stream (include/hdlz_seek.h): the seek index of the first read, ranges through it
+    @_on_device
+    def seek_index(self, d_file, container="gzip", span=1 << 18, point_cap=None, out=None, work=None):
+        """d_file: flat uint8 device tensor, ONE zlib stream or a gzip file (its first member) of any writer -> (out uint8[total], a
+        SeekIndex (hdl_deflate_amd/seek.py), record): the stream decoded whole and judged as inflate_checked / inflate_gzip judge one
+        stream, and the seek points it passed on the way (hdlz_seek_index_ws) -- a block boundary at or behind every multiple of `span`
+        bytes of output, each with the 32 KiB in front of it and the CRC-32 of its segment.  The record is a _lib.SeekResult; a
+        stream that fails raises HdlzStatusError.  point_cap: room for that many points, 32 KiB of window each (default: a guess --
+        the spans of `out`, or of eight times the file where that is less); when the stream holds more, the call is made once more
+        with the true count, which decodes it once more.  out: room for the data (default:
+        inflate_cap(file_len) bytes, allocated here; for gzip the ISIZE word when it does not exceed that).  One host sync per call
+        made.  `work`: the call's scratch, a uint8 device tensor at a multiple of 256 (default: allocated here)."""
+        self._is_bytes(d_file, "d_file", flat=True)
+        gzip = _container_is_gzip(container)
+        n, dev = d_file.numel(), d_file.device
+        if out is None:
+            cap = inflate_cap(n)
+            if gzip and n >= 4:
+                isize = int.from_bytes(bytes(d_file[n - 4:].cpu().numpy().tobytes()), "little")
+                cap = isize if isize <= cap else cap
+            out = torch.empty((cap + 3) & ~3, dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out", flat=True)
+        flags = _lib.SEEK_GZIP if gzip else _lib.SEEK_ZLIB
+        cap = min(out.numel() // int(span) + 2, 8 * n // int(span) + 16) if point_cap is None else int(point_cap)
+        while True:
+            bit = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            pos = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            crc = torch.empty(cap, dtype=torch.int32, device=dev)
+            win = torch.empty((cap, _lib.SEEK_WINDOW), dtype=torch.uint8, device=dev)
+            scratch = self._scratch(self.lib.hdlz_seek_index_work_bytes(n, flags, out.numel(), cap), work, torch.uint8, full=True)
+            rec = self._record("hdlz_seek_index_ws", _lib.SeekResult, scratch, d_file.data_ptr() if n else None, n, flags, int(span),
+                               out.data_ptr() if out.numel() else None, out.numel(), *[t.data_ptr() if cap else None for t in (bit, pos, crc, win)], cap)
+            if rec.status != E_OUT_CAPACITY or rec.npoints <= cap:
+                break
+            cap = rec.npoints
+        _raise_unless_ok(rec, "seek_index")
+        from .seek import SeekIndex
+        k = rec.npoints
+        return out[:rec.total_out], SeekIndex(bit[:k + 1], pos[:k + 1], crc[:k], win[:k], span, n, rec.total_out, rec.end_bit, rec.max_seg, container), rec
+
+    def _read_seek_ranges(self, d_file, index, ranges, out, out_cap, task_cap, scratch):
+        """one hdlz_seek_read_ranges_ws call and its host sync -> (record, range_off int64[R + 1])"""
+        R = ranges.shape[0]
+        range_off = torch.empty(R + 1, dtype=torch.int64, device=d_file.device)
+        rec = self._record("hdlz_seek_read_ranges_ws", _lib.SeekRangesResult, self._scratch(0, scratch, torch.uint8),
+                           d_file.data_ptr() if d_file.numel() else None, d_file.numel(), index.bit.data_ptr(), index.pos.data_ptr(),
+                           index.crc.data_ptr(), index.win.data_ptr(), index.npoints, ranges.data_ptr() if R else None, R, 0, index.max_seg,
+                           out.data_ptr() if out_cap else None, out_cap, range_off.data_ptr(), None, task_cap)
+        return rec, range_off
+
+    @_on_device
+    def read_seek(self, d_file, ranges, index, out=None, work=None, max_work_bytes=256 << 20):
+        """d_file: flat uint8 device tensor, the file `index` (a SeekIndex on this device) was taken from; ranges: R pairs (begin, end)
+        of byte offsets into the data, as read_bgzf takes them -> (out uint8[total], range_offsets int64[R + 1]), both on the device.
+        Only the segments the ranges touch are decoded (hdlz_seek_read_ranges_ws), each whole, from its seek point with its window
+        as history, and judged by its length, end bit and CRC-32.  The ranges are processed in groups as in read_bgzf: two slots of
+        max_seg bytes per range and 60 bytes per touched segment; out, work and max_work_bytes as there.  Raises HdlzStatusError with
+        .first_bad = the index of the lowest failed range over all groups."""
+        self._is_bytes(d_file, "d_file", flat=True)
+        dev = d_file.device
+        assert index.file_len == d_file.numel(), "the index was taken from a file of %d bytes, this one has %d" % (index.file_len, d_file.numel())
+        for t in (index.bit, index.pos, index.crc, index.win):
+            assert t.is_cuda and t.device == dev and t.is_contiguous(), "the index must be contiguous tensors on the file's device (SeekIndex.to)"
+        assert index.win.data_ptr() % 16 == 0
+        ranges = self._range_pairs(ranges, dev)
+        return self._ranged_read("read_seek", lambda n, ntasks: self.lib.hdlz_seek_ranges_work_bytes(n, ntasks, index.max_seg, 0),
+                                 lambda rg, dst, ntasks, scratch: self._read_seek_ranges(d_file, index, rg, dst, dst.numel(), ntasks, scratch),
+                                 2 * ((index.max_seg + 255) & ~255), 60, ranges, dev, out, work, max_work_bytes)
+
+    def read_seek_bytes(self, z, begin, end, index=None):
+        """the bytes of a .gz file (or, with a zlib index, of a zlib stream) -> (status, bytes [begin, end) of its data), clipped to the
+        data.  index: a SeekIndex of the file (default: taken here, as gzip -- which reads the whole file once)"""
+        d = self._stage(z)[:len(z)]
+        try:
+            if index is None:
+                _, index, _ = self.seek_index(d, container="gzip")
+            out, _ = self.read_seek(d, [(begin, end)], index.to(d.device))
         except HdlzStatusError as e:
             return e.status, b""
         return OK, bytes(out.cpu().numpy().tobytes())
