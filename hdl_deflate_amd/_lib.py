@@ -159,6 +159,19 @@ SEEK_CALLS = {
 }
 SEEK_EXPORTS = tuple(SEEK_CALLS)
 SEEK_ZLIB, SEEK_GZIP, SEEK_WINDOW = 1, 2, 32768      # HDLZ_SEEK_ZLIB, HDLZ_SEEK_GZIP, HDLZ_SEEK_WINDOW
+# ... and of include/hdlz_png.h: PNG images indexed, inflated and unfiltered on the device (tests/test_png_cabi.py, which also holds its
+# refusals, as tests/test_seek_cabi.py does for SEEK_CALLS)
+PNG_CALLS = {
+    "hdlz_png_index_work_bytes": (sz, [u64, u64]),                   # n, image_cap
+    # d_files, files_len, d_file_off, d_file_len, n, flags, out_align, image_cap, d_images, d_result, d_work, work_bytes, stream
+    "hdlz_png_index_ws": (ci, [vp, u64, vp, vp, u64, u32, u32, u64, vp, vp, vp, sz, vp]),
+    "hdlz_png_decode_work_bytes": (sz, [u64, u64, u64, u64]),        # count, idat_cap, z_bytes, raw_bytes
+    # d_files, files_len, d_images, first, count, flags, idat_cap, z_bytes, raw_bytes, d_out, out_cap, d_image_status, d_result, d_work,
+    # work_bytes, stream
+    "hdlz_png_decode_ws": (ci, [vp, u64, vp, u64, u64, u32, u64, u64, u64, vp, u64, vp, vp, vp, sz, vp]),
+}
+PNG_EXPORTS = tuple(PNG_CALLS)
+PNG_RAW, PNG_EXPAND, PNG_LARGE_MIN = 0, 1, 16384     # HDLZ_PNG_RAW, HDLZ_PNG_EXPAND, HDLZ_PNG_LARGE_MIN
 _lib = None
 
 
@@ -260,6 +273,24 @@ class ZipWriteResult(ctypes.Structure):
     _fields_ = [("file_len", u64), ("cd_off", u64), ("cd_size", u64), ("nstored", u64), ("status", u32), ("first_bad", u32)]
 
 
+class PngImage(ctypes.Structure):
+    """hdlz_png_image: one record of hdlz_png_index_ws (136 bytes)"""
+    _fields_ = [(f, u64) for f in ("file_off", "file_len", "idat_off", "zlen", "plte_off", "trns_off", "used", "row_bytes", "raw_len",
+                                   "out_len", "z_off", "raw_off", "out_off")] + \
+               [(f, u32) for f in ("width", "height", "nidat", "plte_n", "trns_n", "status")] + \
+               [(f, ctypes.c_uint8) for f in ("depth", "colour", "interlace", "channels_out", "sample_bytes")] + [("reserved", ctypes.c_uint8 * 3)]
+
+
+class PngIndexResult(ctypes.Structure):
+    """hdlz_png_index_result: the result record of hdlz_png_index_ws (40 bytes)"""
+    _fields_ = [("nimages", u64), ("total_z", u64), ("total_raw", u64), ("total_out", u64), ("status", u32), ("reserved", u32)]
+
+
+class PngDecodeResult(ctypes.Structure):
+    """hdlz_png_decode_result: the result record of hdlz_png_decode_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -281,7 +312,7 @@ def load():
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
             list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()) + \
-            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()):
+            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()) + list(PNG_CALLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

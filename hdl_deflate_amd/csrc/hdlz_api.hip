@@ -1157,3 +1157,93 @@ int hdlz_zip64_write_ws(const uint8_t* d_in, const uint64_t* d_ent_off, const ui
 }
 
 }  // extern "C"
+
+// ---- include/hdlz_png.h: PNG images, the chunks walked, the pixels inflated and unfiltered on the device (hdlz_png.hip)
+// The scratch of hdlz_png_decode_ws, laid out once for the size query and the call (the header states the closed form).  The one-stream
+// path takes what is left from `decode` on; `row` is what it is given of the decoded streams' room.
+static uint32_t png_bound(uint64_t z_bytes) { return z_bytes < 0x0FFFFFFFull ? (uint32_t)z_bytes : 0x0FFFFFFFu; }
+static uint64_t png_row(uint64_t raw_bytes) { return (raw_bytes & ~3ull) < 0xFFFFFE00ull ? raw_bytes & ~3ull : 0xFFFFFE00ull; }
+static Laid png_layout(hdlz::PngArgs& g, uintptr_t base) {
+    Carver c{base};
+    const size_t n = (size_t)g.count;
+    g.len = c.take<uint32_t>(n); g.status = c.take<uint32_t>(n); g.end_bit = c.take<uint32_t>(n); g.cap = c.take<uint32_t>(n);
+    g.verdict = c.take<uint32_t>(n); g.crcbad = c.take<uint32_t>(n); g.fltbad = c.take<uint32_t>(n); g.fin = c.take<uint32_t>(n); c.align256();
+    g.m_off = c.take<uint64_t>(n); g.m_end = c.take<uint64_t>(n); g.m_dst = c.take<uint8_t*>(n);
+    g.cbase = c.take<uint64_t>(n + 1u); g.tb = c.take<uint64_t>(n + 1u); g.zb = c.take<uint64_t>(n + 1u); g.sb = c.take<uint64_t>(n + 1u);
+    g.head = c.take<uint64_t>(32); c.align256();
+    g.c_src = c.take<uint64_t>((size_t)g.list_cap); g.c_dst = c.take<uint64_t>((size_t)g.list_cap);
+    g.c_len = c.take<uint32_t>((size_t)g.list_cap); g.c_img = c.take<uint32_t>((size_t)g.list_cap); c.align256();
+    g.tiles = c.take<uint2>((size_t)g.tile_cap); c.align256();
+    g.z = c.take<uint8_t>((size_t)g.z_bytes); c.align256();
+    g.raw = c.take<uint8_t>((size_t)g.raw_bytes); c.align256();
+    const size_t decode = c.bytes();
+    if (g.count == 1) c.take<uint8_t>(hdlz::round256(hdlz_inflate_work_bytes(1, png_bound(g.z_bytes), png_row(g.raw_bytes), 0, 1)));
+    return {c.bytes(), decode};
+}
+static hdlz::PngArgs png_args(uint64_t count, uint64_t idat_cap, uint64_t z_bytes, uint64_t raw_bytes) {
+    hdlz::PngArgs g{};
+    g.count = count; g.list_cap = idat_cap + 4u * count; g.tile_cap = raw_bytes / 32768u + count; g.z_bytes = z_bytes; g.raw_bytes = raw_bytes;
+    return g;
+}
+static bool png_caps_ok(uint64_t idat_cap, uint64_t z_bytes, uint64_t raw_bytes) { return idat_cap < (1ull << 40) && z_bytes < (1ull << 40) && raw_bytes < (1ull << 40); }
+
+extern "C" {
+
+size_t hdlz_png_index_work_bytes(uint64_t n, uint64_t image_cap) {
+    (void)image_cap;
+    return n == 0 || n > 0x7FFFFFFFull ? 0u : hdlz::png_index_work_bytes(n);
+}
+
+int hdlz_png_index_ws(const uint8_t* d_files, uint64_t files_len, const uint64_t* d_file_off, const uint64_t* d_file_len, uint64_t n,
+                      uint32_t flags, uint32_t out_align, uint64_t image_cap, hdlz_png_image* d_images, hdlz_png_index_result* d_result,
+                      void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || (n && any_null(d_files, d_file_off, d_file_len))) return fail_param("null device pointer");
+    if (image_cap && !d_images) return fail_param("d_images is null with image_cap > 0");
+    if (n > 0x7FFFFFFFull) return fail_param("n too large (below 2^31)");
+    if (image_cap > 0x7FFFFFFFull) return fail_param("image_cap too large (below 2^31)");
+    if (flags > HDLZ_PNG_EXPAND) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (work_too_small(hdlz_png_index_work_bytes(n, image_cap), d_work, work_bytes, "hdlz_png_index_work_bytes(n, image_cap)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_file_off, d_file_len, d_images, d_result) || misaligned(8, d_work)) return fail_align(8, "d_file_off / d_file_len / d_images / d_result / d_work");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_png_index(d_files, files_len, d_file_off, d_file_len, n, flags, out_align, image_cap, d_images, d_result, d_work,
+                                           static_cast<hipStream_t>(stream)), "launch k_png_parse");
+}
+
+size_t hdlz_png_decode_work_bytes(uint64_t count, uint64_t idat_cap, uint64_t z_bytes, uint64_t raw_bytes) {
+    if (count == 0 || count > 0x7FFFFFFFull || !png_caps_ok(idat_cap, z_bytes, raw_bytes)) return 0u;
+    hdlz::PngArgs g = png_args(count, idat_cap, z_bytes, raw_bytes);
+    return png_layout(g, 0).bytes;
+}
+
+int hdlz_png_decode_ws(const uint8_t* d_files, uint64_t files_len, const hdlz_png_image* d_images, uint64_t first, uint64_t count,
+                       uint32_t flags, uint64_t idat_cap, uint64_t z_bytes, uint64_t raw_bytes, uint8_t* d_out, uint64_t out_cap,
+                       uint32_t* d_image_status, hdlz_png_decode_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("d_result is required");
+    if (count && any_null(d_files, d_images)) return fail_param("null device pointer");
+    if (out_cap && !d_out) return fail_param("d_out is null with out_cap > 0");
+    if (first > 0x7FFFFFFFull || count > 0x7FFFFFFFull || first + count > 0x7FFFFFFFull) return fail_param("first + count too large (below 2^31)");
+    if (flags > HDLZ_PNG_EXPAND) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND");
+    if (!png_caps_ok(idat_cap, z_bytes, raw_bytes)) return fail_param("idat_cap, z_bytes or raw_bytes too large (below 2^40)");
+    if (misaligned(8, d_images, d_result)) return fail_align(8, "d_images / d_result");
+    if (misaligned(4, d_image_status)) return fail_align(4, "d_image_status");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    hdlz::PngArgs g = png_args(count, idat_cap, z_bytes, raw_bytes);
+    g.in = d_files; g.in_len = files_len; g.images = d_images ? d_images + first : nullptr; g.flags = flags;
+    g.out = d_out; g.out_cap = out_cap; g.image_status = d_image_status; g.result = d_result;
+    const Laid l = png_layout(g, address(d_work));
+    if (count && work_too_small(l.bytes, d_work, work_bytes, "hdlz_png_decode_work_bytes(count, idat_cap, z_bytes, raw_bytes)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool single = g.single = count == 1 && png_row(raw_bytes) >= 4u;
+    if (const int rc = launched(hdlz::launch_png_front(g, st), "launch k_png_plan"); rc != HDLZ_OK) return rc;
+    if (single) {                                                                                 // a large image (m_off[0], m_end[0]: its ragged index)
+        if (const int rc = inflate_one(g.z, g.m_off, png_bound(z_bytes), g.raw, png_row(raw_bytes), g.len, g.status, g.end_bit, d_work, work_bytes, l.decode, stream); rc != HDLZ_OK) return rc;
+    } else if (count) {
+        const MemberView v{g.m_off, g.m_end, nullptr, 0, 0, 0, g.m_dst, g.cap};                        // the task view
+        if (const int rc = decode_members(g.z, count, g.raw, g.len, g.status, g.end_bit, v, st); rc != HDLZ_OK) return rc;
+    }
+    return launched(hdlz::launch_png_back(g, st), "launch k_png_unfilter");
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 #include "../../include/hdlz_zip_write.h"
 #include "../../include/hdlz_zip64.h"
 #include "../../include/hdlz_seek.h"
+#include "../../include/hdlz_png.h"
 
 namespace hdlz {
 
@@ -475,6 +476,44 @@ hipError_t launch_zip_judge(const ZipArgs64& a, hipStream_t stream);
 size_t zip64_index_work_bytes(uint64_t entry_cap);
 hipError_t launch_zip64_index(const uint8_t* file, uint64_t file_len, uint64_t entry_cap, uint32_t out_align, hdlz_zip64_entry* entries,
                               hdlz_zip_index_result* result, void* work, hipStream_t stream);
+
+// hdlz_png.hip: hdlz_png_index_ws and what hdlz_png_decode_ws runs around the decode (include/hdlz_png.h)
+size_t png_index_work_bytes(uint64_t n);
+hipError_t launch_png_index(const uint8_t* files, uint64_t files_len, const uint64_t* file_off, const uint64_t* file_len, uint64_t n, uint32_t flags,
+                            uint32_t out_align, uint64_t image_cap, hdlz_png_image* images, hdlz_png_index_result* result, void* work, hipStream_t stream);
+struct PngArgs {
+    const uint8_t* in;
+    uint64_t in_len;                  // files_len
+    const hdlz_png_image* images;     // the call's d_images + first
+    uint64_t count;
+    uint32_t flags;
+    uint64_t list_cap, tile_cap;      // the chunk list's entries (idat_cap + 4 count); the Adler tile words
+    uint64_t z_bytes, raw_bytes;
+    uint8_t* out;
+    uint64_t out_cap;
+    uint32_t* image_status;           // nullable
+    hdlz_png_decode_result* result;
+    uint32_t* len;                    // scratch, per image: the decoded length
+    uint32_t* status;                 // ... the decoder's status word (a refused image: the checks' verdict, which the decoder leaves alone)
+    uint32_t* end_bit;                // ... where the final block ended: a bit (the task view) or, single, a byte
+    uint32_t* cap;                    // ... MemberArgs::m_dst_cap (raw_len)
+    uint32_t* verdict;                // ... the checks in front of the decode
+    uint32_t* crcbad;                 // ... 1: a chunk's CRC-32 did not match
+    uint32_t* fltbad;                 // ... 1: a row's filter byte was above 4
+    uint32_t* fin;                    // ... the image's status
+    uint64_t* m_off;                  // scratch, per image: MemberArgs::m_off; single: with m_end[0] the ragged index of one stream
+    uint64_t* m_end;                  // ... MemberArgs::m_end (the word behind m_off[count - 1])
+    uint8_t** m_dst;                  // ... MemberArgs::m_dst
+    uint64_t *cbase, *tb, *zb, *sb;   // scratch, count + 1 words each: where an image's chunks, Adler tiles, gather tiles and bands start
+    uint64_t* head;                   // scratch, 32 words: the four totals
+    uint64_t *c_src, *c_dst;          // scratch, the chunk list: where the chunk's type stands in `in`; an IDAT's place in its zlib stream
+    uint32_t *c_len, *c_img;          // ... its data length; NONE: the entry is not used
+    uint2* tiles;                     // scratch: (A, C) per 32 KiB tile of the decoded streams
+    uint8_t *z, *raw;                 // scratch: the gathered zlib streams, the decoded streams
+    bool single;                      // count == 1: the batch call's path
+};
+hipError_t launch_png_front(const PngArgs& a, hipStream_t stream);     // checks, chunk list, gather, chunk CRCs: in front of the decode
+hipError_t launch_png_back(const PngArgs& a, hipStream_t stream);      // Adler tiles, unfilter, expansion, verdicts, the record
 
 // hdlz_zip_write.hip: hdlz_zip_write_ws (include/hdlz_zip_write.h).  The scratch, carved by the launcher: E = nentries
 struct ZipWriteWork {

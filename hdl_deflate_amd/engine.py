@@ -760,6 +760,89 @@ class Engine(object):
                 worst = int(st[k])
         return (worst if worst != OK else index.record.status), files
 
+    # -- PNG images (include/hdlz_png.h): the chunks walked, the pixels inflated, unfiltered and expanded on the device
+    PNG_ALONE_US = 1483.0            # a hdlz_png_decode_ws call of ONE 512 x 512 RGB image, end to end: 379.7 ms for 256 (profiles/png.txt)
+    PNG_WAVE_US_PER_BYTE = 0.109     # the wave-per-image decode: 85.7 ms for 786944 bytes of scanlines (profiles/png.txt)
+
+    @_on_device
+    def png_index(self, d_files, offsets=None, lengths=None, out_align=64, expand=True):
+        """d_files: flat uint8 device tensor holding PNG files; offsets, lengths: int64 device tensors, file i is
+        d_files[offsets[i] : offsets[i] + lengths[i]] (default: one file, all of d_files) -- the out_off and usize of Engine.inflate_zip's
+        index fit as they stand -> a PngIndex (hdl_deflate_amd/png.py): the device records of hdlz_png_index_ws, its result record and a
+        host copy.  An image's status stands in its record and is not raised.  expand: plain samples (HDLZ_PNG_EXPAND: (H, W, C), uint8 or
+        little-endian uint16) or the scanlines as PNG packs them (HDLZ_PNG_RAW); out_align: every image's slot in the flat output starts
+        at a multiple of it (a power of two up to 256).  One host sync for the records."""
+        from .png import PngIndex, IMAGE_DTYPE
+        import numpy as np
+        self._is_bytes(d_files, "d_files", flat=True)
+        dev = d_files.device
+        if offsets is None:
+            offsets = torch.zeros(1, dtype=torch.int64, device=dev)
+            lengths = torch.full((1,), d_files.numel(), dtype=torch.int64, device=dev)
+        offsets, lengths = offsets.to(torch.int64).contiguous(), lengths.to(torch.int64).contiguous()
+        _is_index(offsets)
+        _is_index(lengths, offsets.numel())
+        n, flags = offsets.numel(), _lib.PNG_EXPAND if expand else _lib.PNG_RAW
+        images = torch.empty((n, ctypes.sizeof(_lib.PngImage) // 8), dtype=torch.int64, device=dev)
+        rec = self._record("hdlz_png_index_ws", _lib.PngIndexResult, self._scratch(self.lib.hdlz_png_index_work_bytes(n, n), None, full=True),
+                           d_files.data_ptr() if n else None, d_files.numel(), offsets.data_ptr() if n else None, lengths.data_ptr() if n else None,
+                           n, flags, out_align, n, images.data_ptr() if n else None)
+        host = np.frombuffer(images.cpu().numpy().tobytes(), dtype=IMAGE_DTYPE)
+        return PngIndex(images, rec, host, out_align, bool(expand))
+
+    @_on_device
+    def decode_png(self, d_files, index, first=0, count=None, out=None, work=None):
+        """d_files: the buffer the PngIndex `index` was taken of -> (out uint8[n], status int32[count]), both on the device: image
+        first + k stands at out[rel : rel + out_len], rel = out_off[first + k] - out_off[first], and has status[k] -- HDLZ_OK, or why it
+        was not read; nothing is raised for an image.  Any range [first, first + count) decodes without the rest.  The range is routed
+        here as Engine.inflate_zip routes entries: maximal runs of images below PNG_LARGE_MIN compressed bytes go in one
+        hdlz_png_decode_ws call each, a wave per image; every larger image goes in a call of its own, decoded by the whole GPU -- unless
+        the range holds so many large images that their calls would cost more than the longest of them costs a wave: then the whole
+        range is one call.  out: at
+        least the range's bytes (default: allocated here); work: the scratch of the largest call, uint8 at a multiple of 256 (default:
+        allocated here).  No host sync."""
+        self._is_bytes(d_files, "d_files", flat=True)
+        dev = d_files.device
+        host, E = index.host, len(index.host)
+        count = E - first if count is None else int(count)
+        if not 0 <= first <= first + count <= E:
+            raise ValueError("images [%d, %d) are not a range of the index's %d images" % (first, first + count, E))
+        ok = host["status"] == OK
+        end = first + count
+        rel = (host["out_off"] - (host["out_off"][first] if count else 0)).astype("int64")
+        size = host["out_len"].astype("int64") * ok
+        total = int(rel[end - 1] + size[end - 1]) if count else 0
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out", flat=True, room=total)
+        status = torch.empty(count, dtype=torch.int32, device=dev)
+        r16 = lambda x: (int(x) + 15) & ~15
+        # which images go alone: a call of its own costs PNG_ALONE_US whatever the image, a wave takes PNG_WAVE_US_PER_BYTE per decoded
+        # byte and a batch pays only its longest image -- many large images are faster together (INTEGRATION.md section 4)
+        large = ok & (host["zlen"] >= _lib.PNG_LARGE_MIN)
+        large[:first] = large[end:] = False
+        if large.any() and int(large.sum()) * self.PNG_ALONE_US > int(host["raw_len"][large].max()) * self.PNG_WAVE_US_PER_BYTE:
+            large[:] = False
+        calls, e = [], first
+        while e < end:
+            b = e
+            if large[e]:
+                e += 1
+            else:
+                while e < end and not large[e]:
+                    e += 1
+            last = e - 1
+            calls.append((b, e - b, int(host["nidat"][b:e].sum()),
+                          int(host["z_off"][last] - host["z_off"][b]) + r16(host["zlen"][last] + 8) * int(ok[last]),
+                          int(host["raw_off"][last] - host["raw_off"][b]) + r16(host["raw_len"][last]) * int(ok[last]),
+                          int(rel[last] + size[last] - rel[b])))
+        scratch = self._scratch(max([self.lib.hdlz_png_decode_work_bytes(c, ic, zb, rb) for _, c, ic, zb, rb, _ in calls] + [0]), work, torch.uint8)
+        flags = _lib.PNG_EXPAND if index.expand else _lib.PNG_RAW
+        for b, c, ic, zb, rb, cap in calls:                     # (the records are not read: every image's verdict is in `status`)
+            self._enqueue("hdlz_png_decode_ws", _lib.PngDecodeResult, scratch, d_files.data_ptr(), d_files.numel(), index.images.data_ptr(), b, c,
+                          flags, ic, zb, rb, out.data_ptr() + int(rel[b]) if out.numel() else None, cap, status.data_ptr() + 4 * (b - first))
+        return out[:total], status
+
     # -- ZIP archives written on the device (include/hdlz_zip_write.h)
     ZIP_CRC_TILED_MIN = 1 << 17   # an entry of at least this many bytes gets a hdlz_crc32_ws call of its own (INTEGRATION.md section 4)
 
