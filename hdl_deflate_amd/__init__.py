@@ -16,7 +16,7 @@ from .bgzf import virtual_offset, split_virtual, gzi_dumps, gzi_loads   # noqa: 
 from .zip import ZipIndex                                           # noqa: F401  (what Engine.zip_index returns)
 from .seek import SeekIndex                                         # noqa: F401  (what Engine.seek_index returns; seek.loads reads its file)
 from . import seek                                                  # noqa: F401
-from .png import load_png, PngIndex                                 # noqa: F401  (PNG files into device tensors)
+from .png import load_png, save_png, PngIndex                       # noqa: F401  (PNG files into device tensors, and back)
 from .npz import load_npz, save_npz                                 # noqa: F401  (.npz files into device tensors, and back)
 
 

@@ -172,6 +172,20 @@ PNG_CALLS = {
 }
 PNG_EXPORTS = tuple(PNG_CALLS)
 PNG_RAW, PNG_EXPAND, PNG_LARGE_MIN = 0, 1, 16384     # HDLZ_PNG_RAW, HDLZ_PNG_EXPAND, HDLZ_PNG_LARGE_MIN
+# ... and of include/hdlz_png_write.h: PNG files written on the device (tests/test_png_write_cabi.py, which also holds its refusals)
+PNG_WRITE_CALLS = {
+    "hdlz_png_filter_work_bytes": (sz, [u64]),                       # n
+    # d_pix, pix_len, d_specs, n, mode, total_rows, d_raw, raw_cap, d_row_filter, d_status, d_raw_off, d_work, work_bytes, stream
+    "hdlz_png_filter_ws": (ci, [vp, u64, vp, u64, u32, u64, vp, u64, vp, vp, vp, vp, sz, vp]),
+    "hdlz_png_write_bound": (sz, [u64, u64, u64, u32, u32]),         # n, total_raw, nblocks, block_len, idat_len
+    "hdlz_png_write_work_bytes": (sz, [u64, u64]),                   # n, nblocks
+    # d_specs, n, d_raw, d_raw_off, d_filter_status, d_in_off, d_rows, row_pitch, d_len, d_end_bits, d_status, nblocks, d_blk_first, idat_len,
+    # flags, out_align, d_file, file_cap, d_file_off, d_file_len, d_image_status, d_images, d_result, d_work, work_bytes, stream
+    "hdlz_png_write_ws": (ci, [vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, sz, vp]),
+}
+PNG_WRITE_EXPORTS = tuple(PNG_WRITE_CALLS)
+# HDLZ_PNG_FILTER_ADAPTIVE, HDLZ_PNGW_BAND, HDLZ_PNGW_STEP, HDLZ_PNGW_ROW_REG_MAX
+PNG_FILTER_ADAPTIVE, PNGW_BAND, PNGW_STEP, PNGW_ROW_REG_MAX = 5, 8, 1024, 4096
 _lib = None
 
 
@@ -291,6 +305,16 @@ class PngDecodeResult(ctypes.Structure):
     _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
 
 
+class PngSpec(ctypes.Structure):
+    """hdlz_png_spec: one image of hdlz_png_filter_ws and hdlz_png_write_ws (24 bytes)"""
+    _fields_ = [("pix_off", u64), ("width", u32), ("height", u32), ("depth", ctypes.c_uint8), ("colour", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+
+
+class PngWriteResult(ctypes.Structure):
+    """hdlz_png_write_result: the result record of hdlz_png_write_ws (24 bytes)"""
+    _fields_ = [("total_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -312,7 +336,7 @@ def load():
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
             list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()) + \
-            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()) + list(PNG_CALLS.items()):
+            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()) + list(PNG_CALLS.items()) + list(PNG_WRITE_CALLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

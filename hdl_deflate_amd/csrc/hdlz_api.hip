@@ -1247,3 +1247,66 @@ int hdlz_png_decode_ws(const uint8_t* d_files, uint64_t files_len, const hdlz_pn
 }
 
 }  // extern "C"
+
+// ---- include/hdlz_png_write.h: PNG files written on the device (hdlz_png_write.hip)
+extern "C" {
+
+size_t hdlz_png_filter_work_bytes(uint64_t n) { return n == 0 || n > 0x7FFFFFFFull ? 0u : hdlz::png_filter_work_bytes(n); }
+
+int hdlz_png_filter_ws(const uint8_t* d_pix, uint64_t pix_len, const hdlz_png_spec* d_specs, uint64_t n, uint32_t mode, uint64_t total_rows,
+                       uint8_t* d_raw, uint64_t raw_cap, uint8_t* d_row_filter, uint32_t* d_status, uint64_t* d_raw_off, void* d_work,
+                       size_t work_bytes, void* stream) {
+    if (n && (any_null(d_specs) || any_null(d_status) || any_null(d_raw_off))) return fail_param("null device pointer");
+    if (pix_len && !d_pix) return fail_param("d_pix is null with pix_len > 0");
+    if (raw_cap && !d_raw) return fail_param("d_raw is null with raw_cap > 0");
+    if (n > 0x7FFFFFFFull) return fail_param("n too large (below 2^31)");
+    if (mode > HDLZ_PNG_FILTER_ADAPTIVE) return fail_param("mode must be a filter 0 .. 4 or HDLZ_PNG_FILTER_ADAPTIVE");
+    if (total_rows >= (1ull << 40)) return fail_param("total_rows too large (below 2^40)");
+    if (work_too_small(hdlz_png_filter_work_bytes(n), d_work, work_bytes, "hdlz_png_filter_work_bytes(n)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_specs) || misaligned(8, d_raw_off) || misaligned(8, d_work)) return fail_align(8, "d_specs / d_raw_off / d_work");
+    if (misaligned(4, d_status)) return fail_align(4, "d_status");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hdlz::PngFilterArgs a{d_pix, pix_len, d_specs, n, mode, total_rows, d_raw, raw_cap, d_row_filter, d_status, d_raw_off, nullptr, nullptr};
+    return launched(hdlz::launch_png_filter(a, d_work, static_cast<hipStream_t>(stream)), "launch k_pngw_filter");
+}
+
+size_t hdlz_png_write_bound(uint64_t n, uint64_t total_raw, uint64_t nblocks, uint32_t block_len, uint32_t idat_len) {
+    (void)total_raw;
+    if (idat_len == 0u) return 0u;
+    const size_t Z = 15u * (size_t)n + (size_t)nblocks * (hdlz_out_bound(block_len) - 1u);
+    return Z + 12u * (Z / idat_len) + 57u * (size_t)n;
+}
+
+size_t hdlz_png_write_work_bytes(uint64_t n, uint64_t nblocks) {
+    return n == 0 || n > 0x7FFFFFFFull || nblocks > 0x7FFFFFFFull ? 0u : hdlz::png_write_work_bytes(n, nblocks);
+}
+
+int hdlz_png_write_ws(const hdlz_png_spec* d_specs, uint64_t n, const uint8_t* d_raw, const uint64_t* d_raw_off, const uint32_t* d_filter_status,
+                      const uint64_t* d_in_off, const uint8_t* d_rows, uint64_t row_pitch, const uint32_t* d_len, const uint64_t* d_end_bits,
+                      const uint32_t* d_status, uint64_t nblocks, const uint64_t* d_blk_first, uint32_t idat_len, uint32_t flags, uint32_t out_align,
+                      uint8_t* d_file, uint64_t file_cap, uint64_t* d_file_off, uint64_t* d_file_len, uint32_t* d_image_status,
+                      hdlz_png_image* d_images, hdlz_png_write_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("d_result is required");
+    if (n > 0x7FFFFFFFull) return fail_param("n too large (below 2^31)");
+    if (nblocks > 0x7FFFFFFFull || (nblocks && !n)) return fail_param("nblocks too large for one launch (2^31 - 1 rows), or rows without images");
+    if (n && (any_null(d_specs) || any_null(d_raw_off, d_blk_first, d_file_off, d_file_len))) return fail_param("null device pointer (the images)");
+    if (nblocks && (any_null(d_in_off, d_end_bits) || any_null(d_len, d_status) || !d_rows)) return fail_param("null device pointer (the rows)");
+    if (file_cap && !d_file) return fail_param("d_file is null with file_cap > 0");
+    if (idat_len == 0u || idat_len > 0x7FFFFFFFu) return fail_param("idat_len must be in [1, 2^31 - 1]");
+    if (flags > HDLZ_PNG_EXPAND) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (work_too_small(hdlz_png_write_work_bytes(n, nblocks), d_work, work_bytes, "hdlz_png_write_work_bytes(n, nblocks)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_raw_off, d_in_off, d_end_bits, d_blk_first, d_file_off, d_file_len) || misaligned(8, d_specs) || misaligned(8, d_images) ||
+        misaligned(8, d_result) || misaligned(8, d_work))
+        return fail_align(8, "d_specs / d_raw_off / d_in_off / d_end_bits / d_blk_first / d_file_off / d_file_len / d_images / d_result / d_work");
+    if (misaligned(4, d_len, d_status, d_filter_status, d_image_status)) return fail_align(4, "d_len / d_status / d_filter_status / d_image_status");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hdlz::PngWriteArgs a{};
+    a.specs = d_specs; a.n = n; a.raw = d_raw; a.raw_off = d_raw_off; a.fstatus = d_filter_status; a.in_off = d_in_off; a.rows = d_rows;
+    a.pitch = row_pitch; a.len = d_len; a.end_bits = d_end_bits; a.status = d_status; a.nblocks = nblocks; a.blk_first = d_blk_first;
+    a.idat = idat_len; a.flags = flags; a.out_align = out_align; a.file = d_file; a.cap = file_cap; a.file_off = d_file_off; a.file_len = d_file_len;
+    a.image_status = d_image_status; a.images = d_images; a.result = d_result;
+    return launched(hdlz::launch_png_write(a, d_work, static_cast<hipStream_t>(stream)), "launch k_pngw_*");
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 #include "../../include/hdlz_zip64.h"
 #include "../../include/hdlz_seek.h"
 #include "../../include/hdlz_png.h"
+#include "../../include/hdlz_png_write.h"
 
 namespace hdlz {
 
@@ -552,5 +553,51 @@ struct ZipWriteArgs {
 };
 size_t zip_write_work_bytes(uint64_t nentries, uint64_t nblocks, bool wide = false);
 hipError_t launch_zip_write(ZipWriteArgs a, void* work, hipStream_t stream, bool wide = false);
+
+// hdlz_png_write.hip: hdlz_png_filter_ws and hdlz_png_write_ws (include/hdlz_png_write.h)
+struct PngFilterArgs {
+    const uint8_t* pix;
+    uint64_t pix_len;
+    const hdlz_png_spec* specs;
+    uint64_t n;
+    uint32_t mode;
+    uint64_t total_rows;
+    uint8_t* raw;
+    uint64_t raw_cap;
+    uint8_t* row_filter;              // nullable
+    uint32_t* status;
+    uint64_t* raw_off;
+    uint64_t *row_base, *band_base;   // scratch, n + 1 words each: where an image's rows and bands start
+};
+size_t png_filter_work_bytes(uint64_t n);
+hipError_t launch_png_filter(PngFilterArgs a, void* work, hipStream_t stream);
+struct PngWriteArgs {
+    const hdlz_png_spec* specs;
+    uint64_t n;
+    const uint8_t* raw;
+    const uint64_t* raw_off;
+    const uint32_t* fstatus;          // nullable
+    const uint64_t* in_off;
+    const uint8_t* rows;
+    uint64_t pitch;
+    const uint32_t* len;
+    const uint64_t* end_bits;
+    const uint32_t* status;
+    uint64_t nblocks;
+    const uint64_t* blk_first;
+    uint32_t idat, flags, out_align;
+    uint8_t* file;
+    uint64_t cap;
+    uint64_t *file_off, *file_len;
+    uint32_t* image_status;           // nullable
+    hdlz_png_image* images;           // nullable
+    hdlz_png_write_result* result;
+    uint64_t *pre, *cnt, *pa, *pe, *ps;      // scratch, nblocks + 1 words each: the exclusive prefixes of |M_b|, the two counts, the Adler sums
+    uint64_t *zlen, *cbase;           // scratch, per image (+ 1): zlen; where its chunks (IHDR and the IDATs) start in the CRC list
+    uint32_t *adler, *ist;            // scratch, per image: the stream's Adler-32; the image's status
+    uint64_t* head;                   // scratch, 32 words: [0] are the files written, [1] the chunks of the CRC list
+};
+size_t png_write_work_bytes(uint64_t n, uint64_t nblocks);
+hipError_t launch_png_write(PngWriteArgs a, void* work, hipStream_t stream);
 
 }  // namespace hdlz

@@ -843,8 +843,142 @@ class Engine(object):
                           flags, ic, zb, rb, out.data_ptr() + int(rel[b]) if out.numel() else None, cap, status.data_ptr() + 4 * (b - first))
         return out[:total], status
 
+    # -- PNG files written on the device (include/hdlz_png_write.h)
+    PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+
+    @_on_device
+    def encode_png(self, d_pix, specs, filter="adaptive", block=1 << 16, idat=1 << 16, cwindow=32, maxmatch=10, out=None, out_align=64,
+                   expand=True, check=True):
+        """d_pix: flat uint8 device tensor holding the samples of n images in the layout decode_png delivers with expand set: C-order
+        (H, W, C), uint8 or little-endian uint16.  specs: a numpy array of png.SPEC_DTYPE (pix_off, width, height, depth, colour), or
+        a list of shapes (H, W, C, depth) of images packed in d_pix one behind the other, C = 1, 2, 3, 4 for grey, grey + alpha, RGB,
+        RGBA -> (files uint8[total], PngIndex): every image's PNG file, packed -- image i is files[file_off : file_off + file_len] of
+        its record --, and the index png_index would take of them under (out_align, expand): the files are not indexed again.
+        filter: "adaptive" (per row the filter with the smallest sum of absolute residuals, libpng's rule), a name of PNG_FILTERS
+        or 0 .. 4: that filter for every row.  hdlz_png_filter_ws filters all images into one packed buffer, every image of at least
+        5 stream bytes is cut into blocks of `block` bytes (chain.plan_blocks, from the dimensions alone), ONE ragged
+        hdlz_compress_batch_bits deflates all blocks, and hdlz_png_write_ws frames the files with IDAT chunks of `idat` bytes.  out:
+        the files' buffer (default: hdlz_png_write_bound bytes).  One host sync (the record, with the images' records, offsets and
+        lengths behind it).  check: raise HdlzStatusError -- with .first_bad, the lowest failed image -- on a status that is not OK;
+        without it the statuses stand in the index's records and index.write_record, and the sound images are written.  The index also
+        carries .row_filters (uint8 on the device: the filter of every row) and .row_base (where an image's rows start in it)."""
+        from .png import PngIndex, IMAGE_DTYPE
+        import numpy as np
+        p = self._png_plan(d_pix, specs, filter, block, idat, cwindow, maxmatch, out, out_align, expand)
+        self._png_launch(p)
+        n, nres, nrec = p.n, p.nres, p.nrec
+        back = p.res.cpu().numpy()                              # the one host sync
+        rec = _lib.PngWriteResult.from_buffer_copy(back[:nres].tobytes())
+        if check and rec.status != OK:
+            raise HdlzStatusError(rec.status, "encode_png", first_bad=None if rec.first_bad == 2 ** 64 - 1 else rec.first_bad)
+        host = np.frombuffer(back[nres:nres + nrec * n].tobytes(), dtype=IMAGE_DTYPE)
+        ok = host["status"] == OK
+        r16 = lambda x: (int(x) + 15) & ~15
+        last = int(np.nonzero(ok)[0][-1]) if ok.any() else None
+        record = _lib.PngIndexResult(n, 0 if last is None else int(host["z_off"][last]) + r16(host["zlen"][last] + 8),
+                                     0 if last is None else int(host["raw_off"][last]) + r16(host["raw_len"][last]),
+                                     int(host["out_off"][-1]) + int(host["out_len"][-1]) if n else 0, OK, 0)
+        index = PngIndex(p.images.view(n, nrec), record, host, out_align, bool(expand))
+        index.write_record, index.row_filters, index.row_base = rec, p.row_filter[:p.total_rows], p.row_base
+        total = rec.total_len if rec.total_len <= p.out.numel() else 0
+        return p.out[:total], index
+
+    def _png_plan(self, d_pix, specs, filter, block, idat, cwindow, maxmatch, out, out_align, expand):
+        """everything of encode_png in front of its launches: the specs, the block plan from the dimensions alone, one staged copy of
+        the index arrays, every buffer of the three calls -> a namespace of them"""
+        from types import SimpleNamespace
+        from .png import SPEC_DTYPE, COLOUR_OF_CHANNELS
+        from .chain import plan_blocks
+        import numpy as np
+        self._is_bytes(d_pix, "d_pix", flat=True)
+        dev, pix_len = d_pix.device, d_pix.numel()
+        mode = self.PNG_FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+        if isinstance(mode, bool) or not isinstance(mode, int) or not 0 <= mode <= 5:
+            raise ValueError("filter must be one of %s or 0 .. 4, not %r" % (sorted(self.PNG_FILTERS), filter))
+        if not 32 <= block < (1 << 31) or not 1 <= idat < (1 << 31):
+            raise ValueError("block must be in [32, 2^31) and idat in [1, 2^31)")
+        if isinstance(specs, np.ndarray) and specs.dtype == SPEC_DTYPE:
+            sp = np.ascontiguousarray(specs)
+        else:
+            sp = np.zeros(len(specs), SPEC_DTYPE)
+            at = 0
+            for k, (h, w, c, depth) in enumerate(specs):
+                if c not in COLOUR_OF_CHANNELS or depth not in (8, 16):
+                    raise ValueError("image %d: %d channels of %d bits (1 .. 4 channels of 8 or 16 bits are written)" % (k, c, depth))
+                sp[k] = (at, w, h, depth, COLOUR_OF_CHANNELS[c], 0)
+                at += h * w * c * (depth // 8)
+        n = len(sp)
+        # the block plan, from the dimensions alone: what hdlz_png_filter_ws will answer for every image is known here
+        raw_off, blk_first, in_off, row_base, runs = [0], [0], [0], [0], []
+        for r in sp:
+            w, h, depth, colour = int(r["width"]), int(r["height"]), int(r["depth"]), int(r["colour"])
+            sound = 0 < w < (1 << 31) and 0 < h < (1 << 31) and colour in (0, 2, 4, 6) and depth in (8, 16) and not r["reserved"].any()
+            raw_len = 0
+            if sound:
+                rb = w * {0: 1, 2: 3, 4: 2, 6: 4}[colour] * (depth // 8)
+                sound = h * (rb + 1) <= (1 << 32) - 512 and int(r["pix_off"]) <= pix_len and h * rb <= pix_len - int(r["pix_off"])
+                raw_len = h * (rb + 1) if sound else 0
+            if raw_len >= 5:
+                if runs and runs[-1][1] + runs[-1][2] == raw_off[-1]:
+                    runs[-1][2] += raw_len
+                else:
+                    runs.append([in_off[-1], raw_off[-1], raw_len])      # a run of blocked streams: where it goes, where it lies, its bytes
+                for _, ln in plan_blocks(raw_len, block):
+                    in_off.append(in_off[-1] + ln)
+            row_base.append(row_base[-1] + (h if sound else 0))
+            raw_off.append(raw_off[-1] + raw_len)
+            blk_first.append(len(in_off) - 1)
+        B, total_raw = len(in_off) - 1, raw_off[-1]
+        words = np.array(blk_first + in_off, dtype=np.int64)
+        staged = torch.from_numpy(np.concatenate([words.view(np.uint8), sp.view(np.uint8).reshape(-1)])).to(dev)
+        idx = staged[:8 * words.size].view(torch.int64)
+        pitch = pitch_for(block)
+        rows, out_len, status = self._results(None, (B, pitch), B, dev)
+        if out is None:
+            out = torch.empty(self.lib.hdlz_png_write_bound(n, total_raw, B, block, idat), dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out", flat=True)
+        nres, nrec = ctypes.sizeof(_lib.PngWriteResult) // 8, ctypes.sizeof(_lib.PngImage) // 8
+        res = torch.empty(nres + (nrec + 2) * n, dtype=torch.int64, device=dev)
+        # (16 bytes behind the streams: the compress kernels load whole 16-byte pieces.)  The blocks are cut from the packed streams as they
+        # lie; only when a stream under 5 bytes -- which gets no blocks -- lies between two that have some are the blocked streams copied
+        # to a buffer of their own, so that the blocks stand back to back (hdlz_png_write_ws uses only differences of d_in_off)
+        raw = torch.empty(total_raw + 32, dtype=torch.uint8, device=dev)
+        gaps = bool(runs) and (len(runs) > 1 or runs[0][1] != 0)
+        cin = torch.empty(in_off[-1] + 32, dtype=torch.uint8, device=dev) if gaps else raw
+        return SimpleNamespace(
+            n=n, B=B, mode=mode, block=block, idat=idat, cwindow=cwindow, maxmatch=maxmatch, total_rows=row_base[-1], row_base=row_base, total_raw=total_raw,
+            d_pix=d_pix, staged=staged, blk_first=idx[:n + 1], in_off=idx[n + 1:], specs=staged[8 * words.size:],
+            raw=raw, cin=cin, runs=runs if gaps else [],
+            fstatus=torch.empty(max(n, 1), dtype=torch.int32, device=dev), raw_off=torch.empty(n + 1, dtype=torch.int64, device=dev),
+            row_filter=torch.empty(max(row_base[-1], 1), dtype=torch.uint8, device=dev),
+            fwork=self._scratch(self.lib.hdlz_png_filter_work_bytes(n), None, full=True), rows=rows, pitch=pitch, len=out_len, status=status,
+            end_bits=torch.empty(B, dtype=torch.int64, device=dev), out=out, nres=nres, nrec=nrec, res=res, images=res[nres:nres + nrec * n],
+            file_off=res[nres + nrec * n:nres + (nrec + 1) * n], file_len=res[nres + (nrec + 1) * n:],
+            wwork=self._scratch(self.lib.hdlz_png_write_work_bytes(n, B), None, full=True),
+            flags=_lib.PNG_EXPAND if expand else _lib.PNG_RAW, out_align=out_align)
+
+    def _png_launch(self, p):
+        """the three calls of encode_png over a _png_plan, on the current stream: nothing is allocated, nothing crosses to the host
+        -- a linear chain that a graph captures"""
+        n, B = p.n, p.B
+        ptr = lambda t, some: t.data_ptr() if some else None
+        self._check(self.lib.hdlz_png_filter_ws(ptr(p.d_pix, p.d_pix.numel()), p.d_pix.numel(), ptr(p.specs, n), n, p.mode, p.total_rows, p.raw.data_ptr(),
+                                                p.total_raw, p.row_filter.data_ptr(), ptr(p.fstatus, n), ptr(p.raw_off, n), p.fwork[1], p.fwork[2],
+                                                self._stream()), "hdlz_png_filter_ws")
+        for dst, src, ln in p.runs:
+            p.cin[dst:dst + ln].copy_(p.raw[src:src + ln])
+        if B:
+            self._check(self.lib.hdlz_compress_batch_bits(p.cin.data_ptr(), p.in_off.data_ptr(), 0, p.block, B, p.cwindow, p.maxmatch, p.rows.data_ptr(),
+                                                          p.pitch, p.len.data_ptr(), p.status.data_ptr(), p.end_bits.data_ptr(), self._stream()),
+                        "hdlz_compress_batch_bits")
+        some = lambda t: t.data_ptr() if B else None
+        self._check(self.lib.hdlz_png_write_ws(ptr(p.specs, n), n, p.raw.data_ptr(), ptr(p.raw_off, n), ptr(p.fstatus, n), some(p.in_off), some(p.rows),
+                                               p.pitch, some(p.len), some(p.end_bits), some(p.status), B, ptr(p.blk_first, n), p.idat, p.flags, p.out_align,
+                                               ptr(p.out, p.out.numel()), p.out.numel(), ptr(p.file_off, n), ptr(p.file_len, n), None, ptr(p.images, n),
+                                               p.res.data_ptr(), p.wwork[1], p.wwork[2], self._stream()), "hdlz_png_write_ws")
+
     # -- ZIP archives written on the device (include/hdlz_zip_write.h)
-    ZIP_CRC_TILED_MIN = 1 << 17   # an entry of at least this many bytes gets a hdlz_crc32_ws call of its own
+    ZIP_CRC_TILED_MIN = 1 << 17  # an entry of at least this many bytes gets a hdlz_crc32_ws call of its own (INTEGRATION.md section 4)
 
     @_on_device
     def compress_zip(self, d_in, entry_lengths, names, block=1 << 16, cwindow=32, maxmatch=10, store=None, out=None,

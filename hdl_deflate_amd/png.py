@@ -1,5 +1,6 @@
 """PNG files read into device tensors (include/hdlz_png.h): the chunks are walked, the IDAT stream inflated, the scanlines unfiltered
-and expanded on the device; only the records of the index pass through the host, no pixel byte does."""
+and expanded on the device; only the records of the index pass through the host, no pixel byte does.  And written from device tensors
+(include/hdlz_png_write.h): filtered, deflated and framed on the device; the finished files are what crosses to the host."""
 import numpy as np
 
 from .constants import OK
@@ -11,6 +12,10 @@ IMAGE_DTYPE = np.dtype([(f, "<u8") for f in ("file_off", "file_len", "idat_off",
                        [(f, "<u4") for f in ("width", "height", "nidat", "plte_n", "trns_n", "status")] +
                        [(f, "u1") for f in ("depth", "colour", "interlace", "channels_out", "sample_bytes")] + [("reserved", "u1", (3,))])
 assert IMAGE_DTYPE.itemsize == 136
+# hdlz_png_spec, 24 bytes
+SPEC_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<u4"), ("height", "<u4"), ("depth", "u1"), ("colour", "u1"), ("reserved", "u1", (6,))])
+assert SPEC_DTYPE.itemsize == 24
+COLOUR_OF_CHANNELS = {1: 0, 2: 4, 3: 2, 4: 6}
 
 
 class PngIndex(object):
@@ -76,4 +81,29 @@ def load_png(engine, files):
     for k, r in enumerate(index.host):
         o, n = int(r["out_off"]), int(r["out_len"])
         res.append(out[o:o + n].view(index.dtypes[k]).reshape(index.shapes[k]))
+    return res[0] if one else res
+
+
+def save_png(engine, tensors, **kw):
+    """tensors: one device tensor or a list of them, (H, W) or (H, W, C) of torch.uint8 or torch.uint16, C in 1 .. 4 -- grey, grey +
+    alpha, RGB, RGBA; (H, W, 1) is grey -> the bytes of a PNG file (a list of them for a list): what load_png reads back to the same
+    tensors.  The keywords of Engine.encode_png (filter, block, idat, cwindow, maxmatch) pass through.  No pixel byte crosses to the host
+    before it is compressed: the tensors are gathered on the device, and the finished files come back in one copy.  An image that
+    fails raises HdlzStatusError with .first_bad = its index."""
+    import torch
+    one = torch.is_tensor(tensors)
+    ts = [tensors] if one else list(tensors)
+    shapes, flat = [], []
+    for k, t in enumerate(ts):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype in (torch.uint8, torch.uint16) and t.dim() in (2, 3)):
+            raise ValueError("save_png: tensor %d must be a device tensor (H, W) or (H, W, C) of uint8 or uint16" % k)
+        h, w, c = t.shape[0], t.shape[1], (t.shape[2] if t.dim() == 3 else 1)
+        if c not in COLOUR_OF_CHANNELS:
+            raise ValueError("save_png: tensor %d has %d channels (1 .. 4 are written)" % (k, c))
+        shapes.append((h, w, c, 16 if t.dtype == torch.uint16 else 8))
+        flat.append(t.contiguous().view(torch.uint8).reshape(-1))
+    d_pix = flat[0] if len(flat) == 1 else torch.cat(flat) if flat else torch.empty(0, dtype=torch.uint8, device=engine.device)
+    files, index = engine.encode_png(d_pix, shapes, **kw)
+    host = files.cpu().numpy().tobytes()
+    res = [host[int(r["file_off"]):int(r["file_off"]) + int(r["file_len"])] for r in index.host]
     return res[0] if one else res

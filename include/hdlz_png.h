@@ -63,8 +63,8 @@
  *
  * Not there: Adam7 interlace (refused per image); APNG frames (acTL / fcTL / fdAT are skipped: the default image is read); tRNS colour
  * keys of grey and RGB images; gamma and colour profiles (gAMA, iCCP, sRGB, cHRM are skipped); images past the decoders' limits (step
- * 4); writing PNG; decoding straight out of a ZIP in one call (hdlz_zip_index_ws(out_align), hdlz_zip_inflate_ws, then the two calls
- * here over (d_out, out_off, usize) do it, nothing staged in between); several large images on the whole-GPU path in one call (the
+ * 4); writing PNG (hdlz_png_write.h, the extension of this header, writes it); decoding straight out of a ZIP in one call
+ * (hdlz_zip_index_ws(out_align), hdlz_zip_inflate_ws, then the two calls here over (d_out, out_off, usize) do it, nothing staged in between); several large images on the whole-GPU path in one call (the
  * caller makes one call per large image, or one call over all of them when they are many: Engine.decode_png decides; INTEGRATION.md
  * section 4); a chunk walk that guesses ahead (the index and the chunk list follow a file's chunks one dependent load a hop); the
  * CRC-32 of one very long IDAT chunk by more than one workgroup.
