@@ -172,6 +172,7 @@ PNG_CALLS = {
 }
 PNG_EXPORTS = tuple(PNG_CALLS)
 PNG_RAW, PNG_EXPAND, PNG_LARGE_MIN = 0, 1, 16384     # HDLZ_PNG_RAW, HDLZ_PNG_EXPAND, HDLZ_PNG_LARGE_MIN
+PNG_ADAM7 = 4                                        # HDLZ_PNG_ADAM7, OR-ed into either: interlaced images are read
 # ... and of include/hdlz_png_write.h: PNG files written on the device (tests/test_png_write_cabi.py, which also holds its refusals)
 PNG_WRITE_CALLS = {
     "hdlz_png_filter_work_bytes": (sz, [u64]),                       # n

@@ -1201,7 +1201,7 @@ int hdlz_png_index_ws(const uint8_t* d_files, uint64_t files_len, const uint64_t
     if (image_cap && !d_images) return fail_param("d_images is null with image_cap > 0");
     if (n > 0x7FFFFFFFull) return fail_param("n too large (below 2^31)");
     if (image_cap > 0x7FFFFFFFull) return fail_param("image_cap too large (below 2^31)");
-    if (flags > HDLZ_PNG_EXPAND) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND");
+    if (flags & ~(HDLZ_PNG_EXPAND | HDLZ_PNG_ADAM7)) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND, with or without HDLZ_PNG_ADAM7");
     if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
     if (work_too_small(hdlz_png_index_work_bytes(n, image_cap), d_work, work_bytes, "hdlz_png_index_work_bytes(n, image_cap)")) return HDLZ_E_BAD_PARAM;
     if (misaligned(8, d_file_off, d_file_len, d_images, d_result) || misaligned(8, d_work)) return fail_align(8, "d_file_off / d_file_len / d_images / d_result / d_work");
@@ -1223,7 +1223,7 @@ int hdlz_png_decode_ws(const uint8_t* d_files, uint64_t files_len, const hdlz_pn
     if (count && any_null(d_files, d_images)) return fail_param("null device pointer");
     if (out_cap && !d_out) return fail_param("d_out is null with out_cap > 0");
     if (first > 0x7FFFFFFFull || count > 0x7FFFFFFFull || first + count > 0x7FFFFFFFull) return fail_param("first + count too large (below 2^31)");
-    if (flags > HDLZ_PNG_EXPAND) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND");
+    if (flags & ~(HDLZ_PNG_EXPAND | HDLZ_PNG_ADAM7)) return fail_param("flags must be HDLZ_PNG_RAW or HDLZ_PNG_EXPAND, with or without HDLZ_PNG_ADAM7");
     if (!png_caps_ok(idat_cap, z_bytes, raw_bytes)) return fail_param("idat_cap, z_bytes or raw_bytes too large (below 2^40)");
     if (misaligned(8, d_images, d_result)) return fail_align(8, "d_images / d_result");
     if (misaligned(4, d_image_status)) return fail_align(4, "d_image_status");

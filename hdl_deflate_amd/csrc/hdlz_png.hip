@@ -14,6 +14,7 @@
 // k_png_adler        a workgroup per 32 KiB tile of a decoded stream: (A, C) of the tile (the loop of k_adler_tiles).
 // k_png_unfilter     a WAVE per segment (see below): rows are lanes, skewed by one pixel; LDS-staged tiles of 64 rows x 128 bytes.
 // k_png_expand       the types whose samples are not the scanline's bytes: byte swap, unpack and scale, palette look-up.
+// k_png_deinterlace  (HDLZ_PNG_ADAM7 only) the interlaced images: the seven unfiltered passes scattered into the slot, expanded on the way.
 // k_png_judge / k_png_finish   the verdict per image; the lowest failed image and the record.
 // Plain stores only; no workgroup waits for another.  Loads: inside the files of the range; of the scratch only what the call wrote.
 #include <hip/hip_runtime.h>
@@ -46,16 +47,57 @@ __device__ __forceinline__ bool pair_ok(uint32_t colour, uint32_t depth) {
 }
 __device__ __forceinline__ uint32_t channels_of(uint32_t colour) { return colour == 2u ? 3u : colour == 4u ? 2u : colour == 6u ? 4u : 1u; }
 
+// Adam7 (step 4 of THE RULE for an interlaced image): pass p = 0 .. 6 takes the pixels (x0 + i dx, y0 + j dy) of the image.  The four
+// tables are nibbles of a word, pass 0 the lowest: x0 = 0 4 0 2 0 1 0, y0 = 0 0 4 0 2 0 1, log2 dx = 3 3 2 2 1 1 0, log2 dy = 3 3 3 2 2 1 1
+struct Pass { uint32_t x0, y0, ldx, ldy, pw, ph; uint64_t prb; };      // pw x ph pixels, prb bytes a row; absent: pw or ph is 0
+__host__ __device__ inline Pass adam7_pass(uint32_t p, uint32_t width, uint32_t height, uint32_t bits) {
+    Pass q;
+    q.x0 = (0x0102040u >> (4u * p)) & 15u; q.y0 = (0x1020400u >> (4u * p)) & 15u;
+    q.ldx = (0x0112233u >> (4u * p)) & 15u; q.ldy = (0x1122333u >> (4u * p)) & 15u;
+    q.pw = width > q.x0 ? (uint32_t)(((uint64_t)width - q.x0 + (1u << q.ldx) - 1u) >> q.ldx) : 0u;
+    q.ph = height > q.y0 ? (uint32_t)(((uint64_t)height - q.y0 + (1u << q.ldy) - 1u) >> q.ldy) : 0u;
+    q.prb = ((uint64_t)q.pw * bits + 7u) >> 3;
+    return q;
+}
+// the pass of pixel (x, y) by (y & 7, x & 7): a word per row, x = 0 the lowest nibble
+__constant__ uint32_t ADAM7_OF[8] = {0x53515350u, 0x66666666u, 0x54545454u, 0x66666666u, 0x53525352u, 0x66666666u, 0x54545454u, 0x66666666u};
+// the sum over the present passes of ph (prb + 1); false: past the decoders' limit (no product or sum here leaves 64 bits)
+__host__ __device__ inline bool adam7_raw_len(uint32_t width, uint32_t height, uint32_t bits, uint64_t& raw_len) {
+    uint64_t sum = 0;
+    for (uint32_t p = 0; p < 7u; p++) {
+        const Pass q = adam7_pass(p, width, height, bits);
+        if (q.pw == 0u || q.ph == 0u) continue;
+        if (q.prb + 1u > RAW_MAX / q.ph) return false;
+        sum += (uint64_t)q.ph * (q.prb + 1u);
+    }
+    if (sum > RAW_MAX) return false;
+    raw_len = sum;
+    return true;
+}
+// the bands of 64 rows that the present passes of an interlaced image take: a slot of k_png_unfilter each
+__device__ __forceinline__ uint64_t adam7_bands(uint32_t width, uint32_t height) {
+    uint64_t nb = 0;
+    for (uint32_t p = 0; p < 7u; p++) {
+        const Pass q = adam7_pass(p, width, height, 8u);
+        if (q.pw != 0u) nb += ((uint64_t)q.ph + BAND - 1u) / BAND;
+    }
+    return nb;
+}
+
 // step 4 of THE RULE for a (colour, depth) pair that pair_ok accepts and 0 < width, height < 2^31; false: raw_len is past the limit
 struct Sizes { uint64_t row_bytes, raw_len, out_len; uint32_t channels_out, sample_bytes; };
-__device__ __forceinline__ bool sizes_of(uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, bool trns, uint32_t flags, Sizes& s) {
+__device__ __forceinline__ bool sizes_of(uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, bool trns, uint32_t flags, bool lace, Sizes& s) {
     const uint32_t ch = channels_of(colour);
     s.row_bytes = ((uint64_t)width * depth * ch + 7u) >> 3;
     s.sample_bytes = depth == 16u ? 2u : 1u;
     s.channels_out = (flags & HDLZ_PNG_EXPAND) && colour == 3u ? (trns ? 4u : 3u) : ch;
     s.raw_len = 0u; s.out_len = 0u;
-    if (s.row_bytes + 1u > RAW_MAX / height) return false;
-    s.raw_len = (uint64_t)height * (s.row_bytes + 1u);
+    if (lace) {
+        if (!adam7_raw_len(width, height, depth * ch, s.raw_len)) return false;
+    } else {
+        if (s.row_bytes + 1u > RAW_MAX / height) return false;
+        s.raw_len = (uint64_t)height * (s.row_bytes + 1u);
+    }
     s.out_len = (flags & HDLZ_PNG_EXPAND) ? (uint64_t)height * width * s.channels_out * s.sample_bytes : (uint64_t)height * s.row_bytes;
     return true;
 }
@@ -121,14 +163,14 @@ __global__ __launch_bounds__(256) void k_png_parse(const uint8_t* __restrict__ f
             const uint32_t width = load_be32(f + 16), height = load_be32(f + 20), depth = f[24], colour = f[25], comp = f[26], filt = f[27], lace = f[28];
             if (width == 0u || height == 0u || width >= 0x80000000u || height >= 0x80000000u) st = HDLZ_E_BAD_HEADER;
             else if (!pair_ok(colour, depth) || comp != 0u || filt != 0u) st = HDLZ_E_BAD_HEADER;
-            else if (lace == 1u) st = HDLZ_E_BAD_BTYPE;
+            else if (lace == 1u && !(flags & HDLZ_PNG_ADAM7)) st = HDLZ_E_BAD_BTYPE;
             else if (lace > 1u) st = HDLZ_E_BAD_HEADER;
-            else if (!sizes_of(width, height, depth, colour, trns, flags, s) || zlen > Z_MAX) st = HDLZ_E_OUT_CAPACITY;
+            else if (!sizes_of(width, height, depth, colour, trns, flags, lace == 1u, s) || zlen > Z_MAX) st = HDLZ_E_OUT_CAPACITY;
             else {
                 rec.idat_off = idat_off; rec.zlen = zlen; rec.plte_off = plte_off; rec.trns_off = trns_off; rec.used = used;
                 rec.row_bytes = s.row_bytes; rec.raw_len = s.raw_len; rec.out_len = s.out_len;
                 rec.width = width; rec.height = height; rec.nidat = nidat; rec.plte_n = plte_n; rec.trns_n = trns_n;
-                rec.depth = (uint8_t)depth; rec.colour = (uint8_t)colour; rec.interlace = 0u;
+                rec.depth = (uint8_t)depth; rec.colour = (uint8_t)colour; rec.interlace = (uint8_t)lace;
                 rec.channels_out = (uint8_t)s.channels_out; rec.sample_bytes = (uint8_t)s.sample_bytes;
             }
         }
@@ -196,9 +238,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_png_offsets(uint64_t n, uint64
 __device__ __forceinline__ uint32_t check_record(const PngArgs& a, const hdlz_png_image& r, const hdlz_png_image& r0) {
     if (r.status != HDLZ_OK) return r.status;
     if (r.file_off > a.in_len || r.file_len > a.in_len - r.file_off || r.used > r.file_len) return HDLZ_E_BAD_PARAM;
-    if (r.width == 0u || r.height == 0u || r.width >= 0x80000000u || r.height >= 0x80000000u || !pair_ok(r.colour, r.depth) || r.interlace != 0u) return HDLZ_E_BAD_PARAM;
+    if (r.width == 0u || r.height == 0u || r.width >= 0x80000000u || r.height >= 0x80000000u || !pair_ok(r.colour, r.depth) ||
+        r.interlace > ((a.flags & HDLZ_PNG_ADAM7) ? 1u : 0u)) return HDLZ_E_BAD_PARAM;
     Sizes s;
-    if (!sizes_of(r.width, r.height, r.depth, r.colour, r.trns_off != 0u, a.flags, s)) return HDLZ_E_BAD_PARAM;
+    if (!sizes_of(r.width, r.height, r.depth, r.colour, r.trns_off != 0u, a.flags, r.interlace != 0u, s)) return HDLZ_E_BAD_PARAM;
     if (s.row_bytes != r.row_bytes || s.raw_len != r.raw_len || s.out_len != r.out_len || s.channels_out != r.channels_out || s.sample_bytes != r.sample_bytes) return HDLZ_E_BAD_PARAM;
     if (r.zlen > Z_MAX) return HDLZ_E_BAD_PARAM;
     if (r.nidat == 0u || r.idat_off < 8u || r.idat_off > r.used || r.used - r.idat_off < 12u) return HDLZ_E_BAD_PARAM;
@@ -229,7 +272,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_png_plan(PngArgs a) {
         a.verdict[b] = st;
         const bool ok = st == HDLZ_OK;
         const uint64_t nc = ok ? (uint64_t)r.nidat + 4u : 0u, nt = ok ? (r.raw_len + ADLER_TILE - 1u) / ADLER_TILE : 0u,
-                       nz = ok ? (r.zlen + GATHER_TILE - 1u) / GATHER_TILE : 0u, nb = ok ? ((uint64_t)r.height + BAND - 1u) / BAND : 0u;
+                       nz = ok ? (r.zlen + GATHER_TILE - 1u) / GATHER_TILE : 0u,
+                       nb = !ok ? 0u : r.interlace ? adam7_bands(r.width, r.height) : ((uint64_t)r.height + BAND - 1u) / BAND;
         a.cbase[b] = nc; a.tb[b] = nt; a.zb[b] = nz; a.sb[b] = nb;
         m1.v[0] += nc; m1.v[1] += nt; m1.v[2] += nz; m2.v[0] += nb;
     }
@@ -546,8 +590,21 @@ __global__ __launch_bounds__(64) void k_png_unfilter(PngArgs a) {
         if (a.verdict[b] != HDLZ_OK) continue;                    // (uniform)
         const hdlz_png_image r = a.images[b];
         if (decoded(a, b, r) != r.raw_len || a.len[b] != r.raw_len) continue;      // only a stream of exactly raw_len bytes has rows
-        const uint32_t rb = (uint32_t)r.row_bytes, h = r.height, k = (uint32_t)(g - a.sb[b]), nb = (h + BAND - 1u) / BAND;
+        const uint32_t bits = (uint32_t)r.depth * channels_of(r.colour), bpp = bits < 8u ? 1u : bits >> 3;
+        uint32_t rb = (uint32_t)r.row_bytes, h = r.height, k = (uint32_t)(g - a.sb[b]);
         uint8_t* raw = a.raw + (r.raw_off - a.images[0].raw_off);
+        if (r.interlace) {                                        // slot k is band k of the passes' bands, counted through the present passes:
+            bool found = false;                                   // the pass is an image of pw x ph of its own, where its rows start
+            for (uint32_t p = 0; p < 7u && !found; p++) {
+                const Pass q = adam7_pass(p, r.width, r.height, bits);
+                if (q.pw == 0u || q.ph == 0u) continue;
+                const uint32_t nbp = (q.ph + BAND - 1u) / BAND;
+                if (k < nbp) { rb = (uint32_t)q.prb; h = q.ph; found = true; }
+                else { k -= nbp; raw += (uint64_t)q.ph * (q.prb + 1u); }
+            }
+            if (!found) continue;                                 // (k_png_plan counted the same bands: every slot has its pass)
+        }
+        const uint32_t nb = (h + BAND - 1u) / BAND;
         const uint64_t spitch = (uint64_t)rb + 1u;
         // the first row of band kk that does not look up (a filter byte above 4 is read as 0), or h
         auto start_in = [&](uint32_t kk) -> uint32_t {
@@ -560,10 +617,9 @@ __global__ __launch_bounds__(64) void k_png_unfilter(PngArgs a) {
         if (k != 0u) { r0 = start_in(k); if (r0 == h) continue; }
         uint32_t r1 = h;
         for (uint32_t kk = k + 1u; kk < nb; kk++) { r1 = start_in(kk); if (r1 != h) break; }
-        const bool inplace = expands(a, r);
+        const bool inplace = r.interlace || expands(a, r);        // (a pass's rows are not the slot's: k_png_deinterlace writes it)
         uint8_t* dst = inplace ? raw + 1u : a.out + (r.out_off - a.images[0].out_off);
         const uint64_t dpitch = inplace ? spitch : rb;
-        const uint32_t bits = (uint32_t)r.depth * channels_of(r.colour), bpp = bits < 8u ? 1u : bits >> 3;
         uint32_t* bad = a.fltbad + b;
         switch (bpp) {
             case 1u: unfilter_rows<1u>(raw, dst, dpitch, rb, r0, r1, s_tile, bad); break;
@@ -581,7 +637,7 @@ __global__ __launch_bounds__(256) void k_png_expand(PngArgs a) {
     for (uint64_t b = blockIdx.y; b < a.count; b += gridDim.y) {
         if (a.verdict[b] != HDLZ_OK) continue;                    // (uniform)
         const hdlz_png_image r = a.images[b];
-        if (!expands(a, r) || decoded(a, b, r) != r.raw_len || a.len[b] != r.raw_len) continue;
+        if (r.interlace || !expands(a, r) || decoded(a, b, r) != r.raw_len || a.len[b] != r.raw_len) continue;
         const uint8_t* raw = a.raw + (r.raw_off - a.images[0].raw_off);
         uint8_t* out = a.out + (r.out_off - a.images[0].out_off);
         const uint8_t* f = a.in + r.file_off;
@@ -604,6 +660,118 @@ __global__ __launch_bounds__(256) void k_png_expand(PngArgs a) {
             const uint8_t* e = f + r.plte_off + 3u * v;
             o[0] = in ? e[0] : 0u; o[1] = in ? e[1] : 0u; o[2] = in ? e[2] : 0u;
             if (co == 4u) o[3] = v < r.trns_n ? f[r.trns_off + v] : 255u;
+        }
+    }
+}
+
+// ---- the interlaced images: the seven unfiltered sub-images -> the slot, expanded on the way (what k_png_expand does for the others).
+// Threads are OUTPUT elements -- a pixel, or in RAW mode below 8 bits a byte of a packed row --, W2 = 256 of one row a workgroup, or, where
+// a row has fewer, its elements rounded up to a power of two and 256 / W2 rows: a wave's stores are consecutive bytes of the slot.  A
+// row takes its pixels from at most four passes, by (x & 7, y & 7) (ADAM7_OF), and the lanes that read one pass read consecutive pixels
+// of one of its rows: every fetched line is used whole.  The pieces of a pixel are moved at any address: 1, 2, 4 or 8 bytes at once.
+typedef uint16_t u16u __attribute__((aligned(1), may_alias));
+typedef uint32_t u32u __attribute__((aligned(1), may_alias));
+typedef uint64_t u64u __attribute__((aligned(1), may_alias));
+template <uint32_t N> __device__ __forceinline__ void lace_move(uint8_t* o, const uint8_t* s, bool swap) {
+    uint64_t v;
+    if constexpr (N == 1u) v = s[0];
+    else if constexpr (N == 2u) v = *reinterpret_cast<const u16u*>(s);
+    else if constexpr (N == 3u) v = (uint64_t)*reinterpret_cast<const u16u*>(s) | ((uint64_t)s[2] << 16);
+    else if constexpr (N == 4u) v = *reinterpret_cast<const u32u*>(s);
+    else if constexpr (N == 6u) v = (uint64_t)*reinterpret_cast<const u32u*>(s) | ((uint64_t)*reinterpret_cast<const u16u*>(s + 4) << 32);
+    else v = *reinterpret_cast<const u64u*>(s);
+    if (swap) v = ((v & 0x00FF00FF00FF00FFull) << 8) | ((v >> 8) & 0x00FF00FF00FF00FFull);       // 16-bit samples: big-endian -> little-endian
+    if constexpr (N == 1u) o[0] = (uint8_t)v;
+    else if constexpr (N == 2u) *reinterpret_cast<u16u*>(o) = (uint16_t)v;
+    else if constexpr (N == 3u) { *reinterpret_cast<u16u*>(o) = (uint16_t)v; o[2] = (uint8_t)(v >> 16); }
+    else if constexpr (N == 4u) *reinterpret_cast<u32u*>(o) = (uint32_t)v;
+    else if constexpr (N == 6u) { *reinterpret_cast<u32u*>(o) = (uint32_t)v; *reinterpret_cast<u16u*>(o + 4) = (uint16_t)(v >> 32); }
+    else *reinterpret_cast<u64u*>(o) = v;
+}
+// sample i of d <= 8 bits in a packed row
+__device__ __forceinline__ uint32_t lace_sample(const uint8_t* line, uint32_t i, uint32_t d) {
+    const uint64_t bit = (uint64_t)i * d;
+    return (line[bit >> 3] >> (8u - d - (uint32_t)(bit & 7u))) & ((1u << d) - 1u);
+}
+
+__global__ __launch_bounds__(256) void k_png_deinterlace(PngArgs a) {
+    __shared__ uint32_t s_off[7], s_pitch[7];                     // where a pass's rows start in the image's stream; prb + 1
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t b = blockIdx.y; b < a.count; b += gridDim.y) {
+        if (a.verdict[b] != HDLZ_OK) continue;                    // (uniform, as every `continue` of this loop)
+        const hdlz_png_image r = a.images[b];
+        if (!r.interlace || decoded(a, b, r) != r.raw_len || a.len[b] != r.raw_len) continue;
+        const uint32_t d = r.depth, bits = d * channels_of(r.colour), co = r.channels_out;
+        __syncthreads();                                          // (nobody reads the table of the image before any more)
+        if (tid == 0u) {
+            uint64_t off = 0;
+            for (uint32_t p = 0; p < 7u; p++) {
+                const Pass q = adam7_pass(p, r.width, r.height, bits);
+                s_off[p] = (uint32_t)off; s_pitch[p] = (uint32_t)(q.prb + 1u);
+                if (q.pw != 0u && q.ph != 0u) off += (uint64_t)q.ph * (q.prb + 1u);
+            }
+        }
+        __syncthreads();
+        const uint8_t* raw = a.raw + (r.raw_off - a.images[0].raw_off);
+        uint8_t* out = a.out + (r.out_off - a.images[0].out_off);
+        const uint8_t* f = a.in + r.file_off;
+        // the unfiltered row of its pass that holds pixel (x, y), and which pixel of that row it is
+        auto row_of = [&](uint32_t x, uint32_t y, uint32_t& px) -> const uint8_t* {
+            const uint32_t p4 = 4u * ((ADAM7_OF[y & 7u] >> (4u * (x & 7u))) & 15u);
+            px = (x - ((0x0102040u >> p4) & 15u)) >> ((0x0112233u >> p4) & 15u);
+            const uint32_t py = (y - ((0x1020400u >> p4) & 15u)) >> ((0x1122333u >> p4) & 15u);
+            return raw + s_off[p4 >> 2] + (uint64_t)py * s_pitch[p4 >> 2] + 1u;
+        };
+        const bool ex = (a.flags & HDLZ_PNG_EXPAND) != 0u;
+        const bool packed = !ex && d < 8u;                        // the elements are the bytes of a packed row, 8 / d pixels each
+        const bool looked = ex && (d < 8u || r.colour == 3u);     // unpacked and scaled, or looked up in the palette
+        const uint64_t epr = packed ? r.row_bytes : r.width;      // elements a row
+        const uint32_t eb = looked ? co : packed ? 1u : bits >> 3;      // bytes an element
+        uint32_t lg = 0;
+        while (lg < 8u && (1ull << lg) < epr) lg++;
+        const uint32_t W2 = 1u << lg, R = 256u >> lg;
+        const uint64_t chunks = (epr + W2 - 1u) >> lg, groups = ((uint64_t)r.height + R - 1u) / R;
+        for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+            const uint64_t y64 = g * R + (tid >> lg);
+            if (y64 >= r.height) continue;
+            const uint32_t y = (uint32_t)y64;
+            for (uint64_t c = 0; c < chunks; c++) {
+                const uint64_t e = c * W2 + (tid & (W2 - 1u));
+                if (e >= epr) break;
+                uint8_t* o = out + (y64 * epr + e) * eb;
+                uint32_t px;
+                if (packed) {
+                    uint32_t v = 0;
+                    for (uint32_t j = 0; j < 8u / d; j++) {       // (pixels past the row's last: pad bits, 0)
+                        const uint64_t x = e * (8u / d) + j;
+                        if (x >= r.width) break;
+                        const uint8_t* line = row_of((uint32_t)x, y, px);
+                        v |= lace_sample(line, px, d) << (8u - d * (j + 1u));
+                    }
+                    o[0] = (uint8_t)v;
+                    continue;
+                }
+                const uint8_t* line = row_of((uint32_t)e, y, px);
+                if (looked) {
+                    const uint32_t v = lace_sample(line, px, d);
+                    if (r.colour != 3u) { o[0] = (uint8_t)(v * (255u / ((1u << d) - 1u))); continue; }
+                    const bool in = v < r.plte_n;
+                    const uint8_t* t = f + r.plte_off + 3u * v;
+                    const uint32_t rgb = in ? (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) : 0u;
+                    if (co == 4u) *reinterpret_cast<u32u*>(o) = rgb | ((v < r.trns_n ? (uint32_t)f[r.trns_off + v] : 255u) << 24);
+                    else { *reinterpret_cast<u16u*>(o) = (uint16_t)rgb; o[2] = (uint8_t)(rgb >> 16); }
+                    continue;
+                }
+                const bool swap = ex && d == 16u;
+                switch (eb) {
+                    case 1u: lace_move<1u>(o, line + px, swap); break;
+                    case 2u: lace_move<2u>(o, line + 2ull * px, swap); break;
+                    case 3u: lace_move<3u>(o, line + 3ull * px, swap); break;
+                    case 4u: lace_move<4u>(o, line + 4ull * px, swap); break;
+                    case 6u: lace_move<6u>(o, line + 6ull * px, swap); break;
+                    default: lace_move<8u>(o, line + 8ull * px, swap); break;
+                }
+            }
         }
     }
 }
@@ -694,7 +862,7 @@ hipError_t launch_png_front(const PngArgs& a, hipStream_t stream) {
     return e;
 }
 
-// behind the decode: the Adler tiles, the unfilter, the expansion, the verdicts and the record
+// behind the decode: the Adler tiles, the unfilter, the expansion, (under HDLZ_PNG_ADAM7) the deinterlace, the verdicts and the record
 hipError_t launch_png_back(const PngArgs& a, hipStream_t stream) {
     using namespace png;
     hipError_t e = hipSuccess;
@@ -703,6 +871,8 @@ hipError_t launch_png_back(const PngArgs& a, hipStream_t stream) {
         if (e == hipSuccess) e = launch(k_png_unfilter, dim3(grid_of(a.raw_bytes / (2u * BAND) + a.count, 8192u)), dim3(64), stream, a);
         if ((a.flags & HDLZ_PNG_EXPAND) && e == hipSuccess)
             e = launch(k_png_expand, dim3(grid_of(a.out_cap / a.count / 4096u, 512u), grid_of(a.count, 4096u)), dim3(256), stream, a);
+        if ((a.flags & HDLZ_PNG_ADAM7) && e == hipSuccess)
+            e = launch(k_png_deinterlace, dim3(grid_of(a.out_cap / a.count / 4096u, 512u), grid_of(a.count, 4096u)), dim3(256), stream, a);
         if (e == hipSuccess) e = launch(k_png_judge, dim3(grid_of(a.count, 65536u)), dim3(64), stream, a);
     }
     if (e == hipSuccess) e = launch(k_png_finish, dim3(1), dim3(SCAN_THREADS), stream, a);

@@ -765,13 +765,14 @@ class Engine(object):
     PNG_WAVE_US_PER_BYTE = 0.109     # the wave-per-image decode: 85.7 ms for 786944 bytes of scanlines (profiles/png.txt)
 
     @_on_device
-    def png_index(self, d_files, offsets=None, lengths=None, out_align=64, expand=True):
+    def png_index(self, d_files, offsets=None, lengths=None, out_align=64, expand=True, interlaced=False):
         """d_files: flat uint8 device tensor holding PNG files; offsets, lengths: int64 device tensors, file i is
         d_files[offsets[i] : offsets[i] + lengths[i]] (default: one file, all of d_files) -- the out_off and usize of Engine.inflate_zip's
         index fit as they stand -> a PngIndex (hdl_deflate_amd/png.py): the device records of hdlz_png_index_ws, its result record and a
         host copy.  An image's status stands in its record and is not raised.  expand: plain samples (HDLZ_PNG_EXPAND: (H, W, C), uint8 or
         little-endian uint16) or the scanlines as PNG packs them (HDLZ_PNG_RAW); out_align: every image's slot in the flat output starts
-        at a multiple of it (a power of two up to 256).  One host sync for the records."""
+        at a multiple of it (a power of two up to 256).  interlaced: HDLZ_PNG_ADAM7 -- Adam7 interlaced images are indexed (the slot
+        will hold the deinterlaced image) instead of refused.  One host sync for the records."""
         from .png import PngIndex, IMAGE_DTYPE
         import numpy as np
         self._is_bytes(d_files, "d_files", flat=True)
@@ -782,13 +783,13 @@ class Engine(object):
         offsets, lengths = offsets.to(torch.int64).contiguous(), lengths.to(torch.int64).contiguous()
         _is_index(offsets)
         _is_index(lengths, offsets.numel())
-        n, flags = offsets.numel(), _lib.PNG_EXPAND if expand else _lib.PNG_RAW
+        n, flags = offsets.numel(), (_lib.PNG_EXPAND if expand else _lib.PNG_RAW) | (_lib.PNG_ADAM7 if interlaced else 0)
         images = torch.empty((n, ctypes.sizeof(_lib.PngImage) // 8), dtype=torch.int64, device=dev)
         rec = self._record("hdlz_png_index_ws", _lib.PngIndexResult, self._scratch(self.lib.hdlz_png_index_work_bytes(n, n), None, full=True),
                            d_files.data_ptr() if n else None, d_files.numel(), offsets.data_ptr() if n else None, lengths.data_ptr() if n else None,
                            n, flags, out_align, n, images.data_ptr() if n else None)
         host = np.frombuffer(images.cpu().numpy().tobytes(), dtype=IMAGE_DTYPE)
-        return PngIndex(images, rec, host, out_align, bool(expand))
+        return PngIndex(images, rec, host, out_align, bool(expand), bool(interlaced))
 
     @_on_device
     def decode_png(self, d_files, index, first=0, count=None, out=None, work=None):
@@ -837,7 +838,7 @@ class Engine(object):
                           int(host["raw_off"][last] - host["raw_off"][b]) + r16(host["raw_len"][last]) * int(ok[last]),
                           int(rel[last] + size[last] - rel[b])))
         scratch = self._scratch(max([self.lib.hdlz_png_decode_work_bytes(c, ic, zb, rb) for _, c, ic, zb, rb, _ in calls] + [0]), work, torch.uint8)
-        flags = _lib.PNG_EXPAND if index.expand else _lib.PNG_RAW
+        flags = (_lib.PNG_EXPAND if index.expand else _lib.PNG_RAW) | (_lib.PNG_ADAM7 if index.interlaced else 0)
         for b, c, ic, zb, rb, cap in calls:                     # (the records are not read: every image's verdict is in `status`)
             self._enqueue("hdlz_png_decode_ws", _lib.PngDecodeResult, scratch, d_files.data_ptr(), d_files.numel(), index.images.data_ptr(), b, c,
                           flags, ic, zb, rb, out.data_ptr() + int(rel[b]) if out.numel() else None, cap, status.data_ptr() + 4 * (b - first))

@@ -25,12 +25,14 @@ class PngIndex(object):
     host       the records on the host, a numpy array of IMAGE_DTYPE
     out_align  what the slots' starts are multiples of
     expand     True: HDLZ_PNG_EXPAND, plain samples; False: HDLZ_PNG_RAW, the scanlines as PNG packs them
+    interlaced True: taken with HDLZ_PNG_ADAM7 (Adam7 interlaced images are read), which Engine.decode_png passes on
     shapes, dtypes   per image what its slot holds: (H, W) or (H, W, C) of torch.uint8 or torch.uint16 when expand is set, else
                (H, row_bytes) of torch.uint8; None for an image whose status is not OK"""
 
-    def __init__(self, images, record, host, out_align, expand):
+    def __init__(self, images, record, host, out_align, expand, interlaced=False):
         import torch
         self.images, self.record, self.host, self.out_align, self.expand = images, record, host, out_align, bool(expand)
+        self.interlaced = bool(interlaced)
         self.shapes, self.dtypes = [], []
         for r in host:
             if r["status"] != OK:
@@ -49,11 +51,12 @@ class PngIndex(object):
         return len(self.host)
 
 
-def load_png(engine, files):
+def load_png(engine, files, interlaced=True):
     """files: the bytes of one PNG file, a list of such, or (flat uint8 device tensor, offsets int64, lengths int64) -- file i is
     tensor[offsets[i] : offsets[i] + lengths[i]], which is what Engine.inflate_zip leaves of a ZIP of PNGs -> a list of device tensors
     (one tensor for one `bytes`), views into one flat output with slots at multiples of 64: (H, W) or (H, W, C), torch.uint8, or
-    torch.uint16 for depth 16; palette images as RGB or RGBA.  An image that fails raises HdlzStatusError with .first_bad = its index."""
+    torch.uint16 for depth 16; palette images as RGB or RGBA.  interlaced: Adam7 interlaced files are read like the others (False:
+    they are refused, E_BAD_BTYPE).  An image that fails raises HdlzStatusError with .first_bad = its index."""
     import torch
     one = isinstance(files, (bytes, bytearray, memoryview))
     if one:
@@ -68,7 +71,7 @@ def load_png(engine, files):
         lens = np.array([len(f) for f in files], np.int64)
         offsets = torch.from_numpy(np.cumsum(lens) - lens).to(d.device)
         lengths = torch.from_numpy(lens).to(d.device)
-    index = engine.png_index(d, offsets, lengths, out_align=64, expand=True)
+    index = engine.png_index(d, offsets, lengths, out_align=64, expand=True, interlaced=interlaced)
     bad = np.nonzero(index.host["status"] != OK)[0]
     if len(bad):
         raise HdlzStatusError(int(index.host["status"][bad[0]]), "load_png: image %d" % bad[0], first_bad=int(bad[0]))

@@ -36,11 +36,22 @@
  *   3  IHDR (bytes 16 .. 29: width, height, depth, colour, compression, filter, interlace)
  *        width or height is 0 or >= 2^31                             HDLZ_E_BAD_HEADER
  *        (colour, depth) not one of 0:{1,2,4,8,16} 2:{8,16} 3:{1,2,4,8} 4:{8,16} 6:{8,16}, or compression or filter not 0      HDLZ_E_BAD_HEADER
- *        interlace 1 (Adam7)                                         HDLZ_E_BAD_BTYPE ("a method this library does not read")
+ *        interlace 1 (Adam7) and flags without HDLZ_PNG_ADAM7          HDLZ_E_BAD_BTYPE ("a method this call was not asked to read")
  *        interlace above 1                                           HDLZ_E_BAD_HEADER
+ *        (with HDLZ_PNG_ADAM7 interlace 1 is accepted and the record's interlace is 1)
  *   4  sizes    channels = 1, 3, 1, 2, 4 for colour 0, 2, 3, 4, 6; row_bytes = ceil(width * depth * channels / 8);
  *        raw_len = height * (row_bytes + 1); raw_len > 2^32 - 512 or zlen > 2^28 - 7: HDLZ_E_OUT_CAPACITY (the decoders' limits, the
  *        numbers hdlz_zip.h states).
+ *        An INTERLACED image (interlace 1, under HDLZ_PNG_ADAM7) is seven reduced images, the passes, one behind the other in the
+ *        stream; pass p = 1 .. 7 takes the pixels (x0 + i dx, y0 + j dy):   p   1  2  3  4  5  6  7
+ *                                                                           x0  0  4  0  2  0  1  0
+ *                                                                           y0  0  0  4  0  2  0  1
+ *                                                                           dx  8  8  4  4  2  2  1
+ *                                                                           dy  8  8  8  4  4  2  2
+ *        pw = ceil((width - x0) / dx), 0 if width <= x0; ph the same in y; a pass with pw = 0 or ph = 0 is absent from the stream;
+ *        prb = ceil(pw * depth * channels / 8); raw_len = the sum over the present passes of ph * (prb + 1), held against the same
+ *        limit (no product or sum of the check leaves 64 bits).  row_bytes, out_len, channels_out and sample_bytes are those of the
+ *        whole image, as below: the slot holds the DEINTERLACED image under either flag.
  *        HDLZ_PNG_RAW:    channels_out = channels, sample_bytes = 2 for depth 16 else 1, out_len = height * row_bytes
  *        HDLZ_PNG_EXPAND: channels_out = channels, but 3 for colour 3 (4 when a tRNS was taken); sample_bytes as above;
  *                         out_len = height * width * channels_out * sample_bytes
@@ -60,8 +71,12 @@
  * HDLZ_PNG_EXPAND delivers C-order (height, width, channels_out): uint8 for depths up to 8, LITTLE-endian uint16 for depth 16; grey
  * below 8 bits scaled by bit replication (x255, x85, x17); palette images as RGB, or RGBA when a tRNS was taken: alpha is 255 for an
  * index at or past trns_n, and an index at or past plte_n is (0, 0, 0), opaque.
+ * An INTERLACED image: the filter rule holds inside each pass as if the pass were an image of pw x ph -- nothing is above a pass's
+ * first row, bpp is the whole image's --, and a filter byte above 4 in any pass is HDLZ_E_BAD_SYMBOL.  HDLZ_PNG_EXPAND delivers exactly
+ * what the same pixels deliver non-interlaced; HDLZ_PNG_RAW delivers height * row_bytes bytes of packed scanlines, the pixels below 8
+ * bits packed again from the high bit, the pad bits of a row's last byte 0.
  *
- * Not there: Adam7 interlace (refused per image); APNG frames (acTL / fcTL / fdAT are skipped: the default image is read); tRNS colour
+ * Not there: progressive delivery of an interlaced image (a usable image after each pass); writing interlaced files; APNG frames (acTL / fcTL / fdAT are skipped: the default image is read); tRNS colour
  * keys of grey and RGB images; gamma and colour profiles (gAMA, iCCP, sRGB, cHRM are skipped); images past the decoders' limits (step
  * 4); writing PNG (hdlz_png_write.h, the extension of this header, writes it); decoding straight out of a ZIP in one call
  * (hdlz_zip_index_ws(out_align), hdlz_zip_inflate_ws, then the two calls here over (d_out, out_off, usize) do it, nothing staged in between); several large images on the whole-GPU path in one call (the
@@ -79,6 +94,9 @@ extern "C" {
 
 #define HDLZ_PNG_RAW    0u
 #define HDLZ_PNG_EXPAND 1u
+/* OR-ed into either of them, in both calls: Adam7 interlaced images are read (steps 3 and 4).  Without it both calls do, launch and
+ * answer what they did before the flag existed. */
+#define HDLZ_PNG_ADAM7  4u
 /* an image of at least this many compressed bytes is worth a call of its own (count == 1: the whole-GPU path); below it, images are
  * read together, a wave each.  (HDLZ_ZIP_LARGE_MIN's number: INTEGRATION.md section 4.) */
 #define HDLZ_PNG_LARGE_MIN 16384u
@@ -110,7 +128,7 @@ size_t hdlz_png_index_work_bytes(uint64_t n, uint64_t image_cap);
  * result record.
  * Parameter errors (HDLZ_E_BAD_PARAM before the device is looked at), in this order: d_result NULL, or with n > 0 any of d_files,
  * d_file_off, d_file_len NULL; d_images NULL with image_cap > 0; n >= 2^31; image_cap >= 2^31; flags not HDLZ_PNG_RAW or
- * HDLZ_PNG_EXPAND; out_align not a power of two in [1, 256]; d_work NULL or work_bytes below the query; d_file_off, d_file_len,
+ * HDLZ_PNG_EXPAND, with or without HDLZ_PNG_ADAM7 (0, 1, 4, 5); out_align not a power of two in [1, 256]; d_work NULL or work_bytes below the query; d_file_off, d_file_len,
  * d_images, d_result or d_work not 8-byte aligned.
  * Nothing is allocated; every launch is capturable; only this form exists.
  * writes: d_images[0 .. min(n, image_cap)), the record, d_work[0 .. work_bytes).
@@ -148,8 +166,9 @@ typedef struct hdlz_png_decode_result {
  * is not decoded:
  *     the record's status is not HDLZ_OK                                                       that status
  *     file_off + file_len > files_len, or used > file_len                                      HDLZ_E_BAD_PARAM
- *     width, height, (colour, depth), interlace not what steps 3 and 4 accept; channels_out, sample_bytes, row_bytes, raw_len or
- *     out_len not what step 4 gives for them under `flags`                                     HDLZ_E_BAD_PARAM
+ *     width, height, (colour, depth), interlace not what steps 3 and 4 accept under `flags` (interlace 1: only with HDLZ_PNG_ADAM7);
+ *     channels_out, sample_bytes, row_bytes, raw_len (an interlaced image: the sum over its passes) or out_len not what step 4 gives
+ *     for them under `flags`                                                                   HDLZ_E_BAD_PARAM
  *     nidat = 0 or idat_off + 12 > used; colour 3: plte_n not in [1, 256] or the PLTE taken not inside [8, used); trns_n > 256 or the
  *     tRNS taken not inside [8, used)                                                          HDLZ_E_BAD_PARAM
  *     z_off, raw_off or out_off below the first image's; raw_off - raw_off[first] no multiple of 16; a slot that ends behind z_bytes
@@ -174,6 +193,10 @@ typedef struct hdlz_png_decode_result {
  *                through LDS with coalesced 16-byte loads and written back the same way.  8-bit grey, grey-alpha, RGB and RGBA (and
  *                every type in RAW mode) go straight into the slot; the other types are unfiltered in place and a second kernel
  *                (k_png_expand: byte swap, unpack and scale, palette look-up) writes the slot.
+ *                An interlaced image takes a band per 64 rows of each present pass; the segment rule holds inside a pass (a segment
+ *                starts at the pass's row 0 and never crosses a pass), every pass is unfiltered in place, and k_png_deinterlace --
+ *                launched only under HDLZ_PNG_ADAM7 -- writes the slot from the seven sub-images, a thread per output element (a
+ *                pixel; RAW below 8 bits: a byte of a packed row), expanding as k_png_expand does, which skips such images.
  *   (e) judge    behind the record's checks and HDLZ_E_BAD_CHECKSUM of (b), per image, the first that applies -- stricter than libpng,
  *                as the ZIP reader is than unzip: the decoder's own status; the zlib header's two bytes (the rule of
  *                hdlz_inflate_checked): HDLZ_E_BAD_HEADER; decoded length above raw_len: HDLZ_E_OUT_CAPACITY; below it:
@@ -181,7 +204,8 @@ typedef struct hdlz_png_decode_result {
  *                HDLZ_E_BAD_CHECKSUM; a filter byte above 4 in any row: HDLZ_E_BAD_SYMBOL.  The same on both routes.
  * d_image_status (nullable): count words, WRITTEN: every image's status.
  * Parameter errors (HDLZ_E_BAD_PARAM before the device is looked at), in this order: d_result NULL; with count > 0 any of d_files,
- * d_images NULL; d_out NULL with out_cap > 0; first + count >= 2^31; flags not HDLZ_PNG_RAW or HDLZ_PNG_EXPAND; idat_cap >= 2^40,
+ * d_images NULL; d_out NULL with out_cap > 0; first + count >= 2^31; flags not HDLZ_PNG_RAW or HDLZ_PNG_EXPAND, with or without
+ * HDLZ_PNG_ADAM7; idat_cap >= 2^40,
  * z_bytes >= 2^40 or raw_bytes >= 2^40; d_images or d_result not 8-byte aligned; d_image_status not 4-byte aligned; d_work not 256-byte
  * aligned; with count > 0, d_work NULL or work_bytes below the query.
  * Nothing is allocated; every launch is capturable; only this form exists.

@@ -10,7 +10,11 @@ gathered.
                                      five filter types occur; IDAT chunks of 64 KiB
 
 Totals: HIP events around the calls of Engine.decode_png (no host sync inside), the PNG calls and the yardstick in turn within a repeat,
-median of --repeats after --warmup, spread = max - min.  Steps: the kernels of one more repeat, profiler on (torch.profiler, device
+median of --repeats after --warmup, spread = max - min.  --adam7 (-> profiles/png_adam7.txt): on each workload decode_png over the same
+pixels stored plain and Adam7 interlaced (tests/png_adam7_ref.py's encoder, adaptive filters inside every pass), in turn within a repeat,
+and the kernel times of k_png_unfilter and k_png_deinterlace of one profiled repeat.  --retime: decode_png alone on the three plain
+workloads, every run listed, for comparing two builds of the library in one session: a process a build (HDLZ_LIB), or --against PATH,
+which loads the second build into the same process and times the two call by call in turn.  Steps: the kernels of one more repeat, profiler on (torch.profiler, device
 activity), summed by kernel name -- gather + CRC: k_png_plan, k_png_list, k_png_gather, k_png_crc; decode: every kernel that is not
 k_png_*; unfilter + expand: k_png_unfilter, k_png_expand; judge: k_png_adler, k_png_judge, k_png_finish.  The profiled pass is not timed."""
 import argparse
@@ -25,6 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import png_ref as P      # noqa: E402
+import png_adam7_ref as A      # noqa: E402
 
 
 def adaptive(rows, h, rb, bpp):
@@ -58,7 +63,7 @@ def picture(w, h, ch, seed):
     return np.clip(a, 0, 255).astype(np.uint8).tobytes()
 
 
-def workload(name):
+def workload(name, interlaced=False):
     if name == "4096 x 64x64 RGBA":
         w, h, colour, distinct, times, idat = 64, 64, 6, 64, 64, None
     elif name == "256 x 512x512 RGB":
@@ -70,6 +75,10 @@ def workload(name):
     for k in range(distinct):
         rows = picture(w, h, ch, k)
         first = first or rows
+        if interlaced:                                       # the same pixels; the adaptive choice is made inside every pass
+            fl = sum((adaptive(sub, g[5], g[6], ch) for sub, g in zip(A.interlace_rows(rows, w, h, colour, 8), A.passes_of(w, h, colour, 8))), [])
+            files.append(A.make_adam7(w, h, colour, 8, rows=rows, filters=fl, level=6, idat=idat))
+            continue
         files.append(P.make_png(w, h, colour, 8, rows=rows, filters=adaptive(rows, h, w * ch, ch), level=6, idat=idat))
     return files * times, first
 
@@ -171,21 +180,128 @@ def measure(eng, name, repeats, warmup):
     return lines
 
 
+def staged(files):
+    import torch
+    blob = b"".join(files)
+    d = torch.frombuffer(bytearray(blob + bytes(16)), dtype=torch.uint8).cuda()[:len(blob)]
+    lens = np.array([len(f) for f in files], np.int64)
+    return d, torch.from_numpy(np.cumsum(lens) - lens).cuda(), torch.from_numpy(lens).cuda()
+
+
+def timed(fns, repeats, warmup):
+    """the functions in turn within a repeat -> {name: [us]}"""
+    import torch
+    times = {k: [] for k in fns}
+    for rep in range(warmup + repeats):
+        for key, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= warmup:
+                times[key].append(e0.elapsed_time(e1) * 1e3)
+    return times
+
+
+def measure_adam7(eng, name, repeats, warmup):
+    import torch
+    from torch.profiler import profile, ProfilerActivity
+    legs = {}
+    for key, lace in (("plain", False), ("interlaced", True)):
+        files, first = workload(name, lace)
+        d, off, ln = staged(files)
+        pi = eng.png_index(d, off, ln, interlaced=lace)
+        assert (pi.host["status"] == 0).all() and (pi.host["interlace"] == int(lace)).all()
+        out, status = eng.decode_png(d, pi)
+        assert int((status != 0).sum()) == 0 and out[:len(first)].cpu().numpy().tobytes() == first
+        legs[key] = (d, pi, out, sum(len(f) for f in files))
+    assert torch.equal(legs["plain"][2], legs["interlaced"][2])           # the same pixels, slot for slot
+    fns = {key: (lambda d=d, pi=pi, out=out: eng.decode_png(d, pi, out=out)) for key, (d, pi, out, _) in legs.items()}
+    times = timed(fns, repeats, warmup)
+    lines = ["workload: %s -- %.1f MB of pixels; %.1f MB of PNG plain, %.1f MB interlaced (raw streams %.1f and %.1f MB)" %
+             (name, legs["plain"][1].record.total_out / 1e6, legs["plain"][3] / 1e6, legs["interlaced"][3] / 1e6,
+              legs["plain"][1].record.total_raw / 1e6, legs["interlaced"][1].record.total_raw / 1e6)]
+    for key, t in times.items():
+        lines.append("  decode_png %-12s median %10.1f us   min %10.1f   max %10.1f   runs %s" %
+                     (key, statistics.median(t), min(t), max(t), " ".join("%.1f" % x for x in t)))
+    lines.append("  interlaced / plain: %.2fx" % (statistics.median(times["interlaced"]) / statistics.median(times["plain"])))
+    for key, fn in fns.items():
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        per, rest = {}, 0.0
+        for ev in prof.key_averages():
+            us = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+            if not us or "Memcpy" in ev.key or "Memset" in ev.key:
+                continue
+            hit = [k for k in ("k_png_unfilter", "k_png_deinterlace", "k_png_expand") if k in ev.key]
+            if hit:
+                per[hit[0]] = per.get(hit[0], 0.0) + us
+            else:
+                rest += us
+        lines.append("  kernels, %-12s %s; every other kernel %.1f us" % (key + ":", "; ".join("%s %.1f us" % kv for kv in sorted(per.items())), rest))
+    return lines
+
+
+def retime(engines, name, repeats, warmup):
+    """engines: {label: Engine}, each over its own build of the library: decode_png of the same staged files, in turn within a repeat"""
+    import torch
+    files, first = workload(name)
+    d, off, ln = staged(files)
+    fns, outs = {}, []
+    for label, eng in engines.items():
+        pi = eng.png_index(d, off, ln)
+        out, status = eng.decode_png(d, pi)
+        assert int((status != 0).sum()) == 0 and out[:len(first)].cpu().numpy().tobytes() == first
+        outs.append(out)
+        fns[label] = lambda eng=eng, pi=pi, out=out: eng.decode_png(d, pi, out=out)
+    assert all(torch.equal(o, outs[0]) for o in outs)
+    times = timed(fns, repeats, warmup)
+    lines = ["retime %s" % name]
+    for label, t in times.items():
+        lines.append("  %-8s decode_png median %10.1f us   min %10.1f   max %10.1f   runs %s" %
+                     (label, statistics.median(t), min(t), max(t), " ".join("%.1f" % x for x in t)))
+    if len(times) == 2:
+        (la, ta), (lb, tb) = times.items()
+        lines.append("  the median of %s %s inside the min-max of %s" % (lb, "LIES" if min(ta) <= statistics.median(tb) <= max(ta) else "does NOT lie", la))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "png.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--adam7", action="store_true")
+    ap.add_argument("--retime", action="store_true")
+    ap.add_argument("--against", default=None, help="--retime: another build of the library, timed in turn with the loaded one in one process")
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default=None)
     args = ap.parse_args()
     import hdl_deflate_amd
+    from hdl_deflate_amd import _lib
     eng = hdl_deflate_amd.Engine()
-    lines = ["command: python tools/probe_png.py --repeats %d --warmup %d" % (args.repeats, args.warmup),
-             "HDLZ_PNG_LARGE_MIN is HDLZ_ZIP_LARGE_MIN's 16384: the crossover was not re-measured for PNG here.", ""]
+    mode = " --adam7" if args.adam7 else " --retime" if args.retime else ""
+    args.out = args.out or os.path.join(ROOT, "profiles", "png_adam7.txt" if args.adam7 else "png_retime.txt" if args.retime else "png.txt")
+    lines = ["command: python tools/probe_png.py%s --repeats %d --warmup %d" % (mode, args.repeats, args.warmup)]
+    lines += ["library: %s" % os.path.basename(_lib.LIB_PATH)] if mode else \
+        ["HDLZ_PNG_LARGE_MIN is HDLZ_ZIP_LARGE_MIN's 16384: the crossover was not re-measured for PNG here."]
+    lines.append("")
+    engines = {"this": eng}
+    if args.against:                                          # (a second handle: its own code object, its own Engine)
+        _lib._lib, _lib.LIB_PATH = None, os.path.abspath(args.against)
+        engines = {"against": hdl_deflate_amd.Engine(), "this": eng}
+        assert engines["against"].lib is not eng.lib
+        lines.insert(2, "against: %s, both in one process, call by call in turn" % os.path.basename(args.against))
     for name in ("4096 x 64x64 RGBA", "256 x 512x512 RGB", "1 x 4096x4096 RGBA"):
         if args.only and args.only not in name:
             continue
-        lines += measure(eng, name, args.repeats, args.warmup) + [""]
+        if args.adam7:
+            lines += measure_adam7(eng, name, args.repeats, args.warmup) + [""]
+        elif args.retime:
+            lines += retime(engines, name, args.repeats, args.warmup)
+        else:
+            lines += measure(eng, name, args.repeats, args.warmup) + [""]
         with open(args.out, "w") as f:                        # (kept as far as it got)
             f.write("\n".join(lines) + "\n")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
