@@ -105,6 +105,7 @@ __host__ __device__ __forceinline__ constexpr bool zlib_header_ok(uint32_t cmf, 
 __host__ __device__ __forceinline__ uint32_t load_be32(const uint8_t* p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
 }
+__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
 
 // Pinned against zlib.adler32 and zlib.decompressobj (values computed there, A and C from their definitions above).
 static_assert(adler32_from(0u, 0u, 0u) == 0x00000001u, "the empty input");

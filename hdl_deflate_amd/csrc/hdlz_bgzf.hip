@@ -89,8 +89,6 @@ __global__ __launch_bounds__(256) void k_bgzf_scan(const uint8_t* __restrict__ f
     const uint32_t tid = threadIdx.x;
     const uint64_t win = blockIdx.x, lo = win << WIN_LOG2;
     const uint64_t hi = file_len - lo < WIN ? file_len : lo + WIN;
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-    typedef v4 __attribute__((aligned(1))) v4u;
     if (tid == 0u) s_found = NONE;
     __syncthreads();
     for (uint32_t step = 0; step < WIN / 4096u; step++) {

@@ -143,8 +143,6 @@ __global__ __launch_bounds__(256) void k_archive(const uint8_t* __restrict__ row
         const uint32_t head = min(rn, (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u));
         if (lane < head) dst[lane] = src[lane];
         const uint32_t body = (rn - head) >> 4;
-        typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-        typedef v4 __attribute__((aligned(1))) v4u;
         for (uint32_t k = lane; k < body; k += 64u)
             *reinterpret_cast<v4*>(dst + head + 16u * k) = *reinterpret_cast<const v4u*>(src + head + 16u * k);
         const uint32_t done = head + 16u * body;

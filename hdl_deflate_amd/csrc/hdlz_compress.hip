@@ -68,7 +68,6 @@ namespace hdlz {
 
 // lsrc[0 .. words) (LDS, 16-byte aligned) -> dst (HBM, 4-byte aligned): 16-byte stores, then the one to three words that are left
 __device__ __forceinline__ void store_words(uint32_t* __restrict__ dst, const uint32_t* lsrc, uint32_t words, uint32_t lane) {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
     const uint32_t nq = words >> 2;
     for (uint32_t q0 = 0; q0 < nq; q0 += 64u) {
         const uint32_t q = q0 + lane;

@@ -1166,6 +1166,16 @@ __device__ __forceinline__ void wipe_behind(uint32_t* lout, uint32_t end_bits, u
 }
 // R8: bytes of the block up to the trailer = the tokens, EOB (7 zero bits), zero padding to a byte (32- and 64-bit bit counts)
 template <class U> __device__ __forceinline__ U block_nbytes(U end_bits) { return (end_bits + 7u + 7u) >> 3; }
+// |M_b|, the member a row of n bytes that ends at bit E becomes in a joined stream (hdlz_join.h), and in `body` the bytes of it that
+// come from the row; 0: the row's length, its end bit and the pitch contradict each other
+__device__ __forceinline__ uint32_t member_len(uint32_t n, uint64_t E, uint64_t pitch, uint32_t& body) {
+    body = 0u;
+    if (E < HEADER_BITS || block_nbytes(E) + 4u != (uint64_t)n || (uint64_t)n > pitch) return 0u;
+    const uint32_t nbytes = n - 4u;
+    const uint32_t p = (uint32_t)(8ull * nbytes - E) - 7u;       // pad bits behind the end-of-block code
+    body = nbytes - 2u;
+    return body + (p >= 3u ? 4u : 5u);
+}
 // R8: Adler-32 of the block from A = sum x_p and W = sum (N - p) x_p (any residues mod 65521, 32 or 64 bits wide)
 template <class U> __device__ __forceinline__ void adler_finish(U A, U W, uint32_t n, uint32_t& s1, uint32_t& s2) {
     s1 = (uint32_t)((A + 1u) % ADLER_MOD);

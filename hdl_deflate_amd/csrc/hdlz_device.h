@@ -120,6 +120,10 @@ __host__ __device__ inline uint32_t out_bound(uint32_t n) {
 // scratch is handed out in pieces of 256 bytes
 constexpr size_t round256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
+// 16 bytes as four words: v4 at a multiple of 16, v4u at any address
+typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+typedef v4 __attribute__((aligned(1))) v4u;
+
 // wave64 ballot straight from the compare.  (HIP's __ballot(int) takes the predicate through a 0/1 VGPR: v_cndmask + v_cmp_ne per
 // call -- 19 such pairs in a round of k_inflate_tok.)
 __device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }

@@ -4,6 +4,7 @@
 // take from here without another instruction sequence stands in that kernel and is listed in profiles/framing_shared.txt, section 3.
 #pragma once
 #include "hdlz_device.h"
+#include "hdlz_plan.h"                                   // wave_scan_add
 
 namespace hdlz {
 
@@ -42,8 +43,6 @@ __device__ __forceinline__ uint32_t lowest_word(const uint32_t* words, uint32_t 
 // ---- n bytes src -> dst by `nlanes` lanes: up to 15 bytes to dst's next 16-byte boundary, whole chunks with 16-byte stores (no load
 // leaves src[0 .. n)), at most 15 bytes behind them
 __device__ __forceinline__ void copy_to_aligned16(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane, uint32_t nlanes) {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-    typedef v4 __attribute__((aligned(1))) v4u;
     const uint32_t head = min(n, (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u));
     if (lane < head) dst[lane] = src[lane];
     const uint32_t chunks = (n - head) >> 4;
@@ -81,12 +80,7 @@ constexpr uint32_t PARTS = 4;                            // words a tile leaves 
 
 // the exclusive scan of the tile's 256 lengths m: this thread's prefix, and the tile's sum in tsum (one __syncthreads inside)
 __device__ __forceinline__ uint64_t tile_scan(uint32_t m, uint32_t lane, uint32_t wave, uint64_t (&s_wsum)[4], uint64_t& tsum) {
-    uint64_t v = m;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v += t;
-    }
+    const uint64_t v = wave_scan_add(m);
     if (lane == 63u) s_wsum[wave] = v;
     __syncthreads();
     const uint64_t w0 = s_wsum[0], w1 = s_wsum[1], w2 = s_wsum[2], w3 = s_wsum[3];

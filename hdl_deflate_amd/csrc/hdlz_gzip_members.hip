@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include "hdlz_device.h"
 #include "hdlz_frame.h"
+#include "hdlz_plan.h"
 #include "hdlz_gzip_walk.h"
 
 namespace hdlz {
@@ -63,8 +64,6 @@ __device__ __forceinline__ uint32_t load_word(const uint8_t* __restrict__ f, uin
 }
 // this lane's 16 bytes at q -> d[0 .. 4)
 __device__ __forceinline__ void load_piece(const uint8_t* __restrict__ f, uint64_t file_len, uint64_t q, uint32_t d[5]) {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-    typedef v4 __attribute__((aligned(1))) v4u;
     if (q + 16u <= file_len) {
         const v4 v = *reinterpret_cast<const v4u*>(f + q);
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
@@ -95,12 +94,7 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
 __device__ __forceinline__ uint64_t shfl_up64(uint64_t v, uint32_t d) {
     return (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)v, d, 64) | ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64) << 32);
 }
-// inclusive scans over the wave.  Positions travel as int64: -1 = none
-__device__ __forceinline__ uint64_t wave_scan_add(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) { const uint64_t t = shfl_up64(v, d); if (lane >= d) v += t; }
-    return v;
-}
+// the inclusive largest over the wave (the sum: wave_scan_add, hdlz_plan.h).  Positions travel as int64: -1 = none
 __device__ __forceinline__ int64_t wave_scan_max(int64_t v, uint32_t lane) {
 #pragma unroll
     for (uint32_t d = 1; d < 64u; d <<= 1) { const int64_t t = (int64_t)shfl_up64((uint64_t)v, d); if (lane >= d && t > v) v = t; }
@@ -148,7 +142,7 @@ __device__ __forceinline__ void kib(const uint8_t* __restrict__ f, uint64_t q, u
         }
     }
     const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-    const uint64_t icnt = wave_scan_add(cnt, lane), igl = wave_scan_add(gl, lane);
+    const uint64_t icnt = wave_scan_add(cnt), igl = wave_scan_add(gl);
     if constexpr (EMIT) {
         uint64_t k = r.idx + icnt - cnt, o = r.acc + igl - gl;
         int64_t pv = pred;
@@ -237,18 +231,7 @@ __global__ __launch_bounds__(256) void k_gzm_emit(const uint8_t* __restrict__ f,
     emit_window(f, file_len, win, w, member_cap, off, out_off);
 }
 
-// exclusive scans over the seam workgroup: every thread's v -> what the threads in front hold together; *total: all of them
-__device__ __forceinline__ uint64_t block_scan_add(uint64_t v, uint64_t* s, uint64_t* total) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t incl = wave_scan_add(v, lane);
-    __syncthreads();                                      // (s is free again)
-    if (lane == 63u) s[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t k = 0; k < SEAM_THREADS / 64u; k++) { const uint64_t t = s[k]; if (k < wave) before += t; all += t; }
-    *total = all;
-    return before + incl - v;
-}
+// the exclusive largest over the seam workgroup: what the threads in front hold; *total: all of them (block_scan's barriers)
 __device__ __forceinline__ int64_t block_scan_max(int64_t v, uint64_t* s, int64_t* total) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const int64_t incl = wave_scan_max(v, lane);
@@ -266,8 +249,9 @@ __device__ __forceinline__ int64_t block_scan_max(int64_t v, uint64_t* s, int64_
 __global__ __launch_bounds__(SEAM_THREADS) void k_gzm_seam(const uint8_t* __restrict__ f, uint64_t file_len, uint64_t W, uint64_t member_cap,
                                                            uint64_t* __restrict__ off, uint64_t* __restrict__ out_off,
                                                            hdlz_gzip_members_index_result* __restrict__ result, IndexWork w) {
-    __shared__ uint64_t s[SEAM_THREADS / 64u];
+    __shared__ uint64_t s[2][SEAM_THREADS / 64u];
     const uint32_t tid = threadIdx.x;
+    // (the strip of hdlz_plan.h, written out: tests/second_trips.py reads K from this line to place its shapes)
     const uint64_t K = (W + SEAM_THREADS - 1u) / SEAM_THREADS;
     const uint64_t w0 = tid * K < W ? tid * K : W, w1 = w0 + K < W ? w0 + K : W;
     const uint32_t* __restrict__ count = w.count;
@@ -276,19 +260,19 @@ __global__ __launch_bounds__(SEAM_THREADS) void k_gzm_seam(const uint8_t* __rest
     int64_t lm = -1;
     for (uint64_t win = w0; win < w1; win++) { const int64_t l = (int64_t)last[win]; if (l > lm) lm = l; }
     int64_t last_all;
-    const int64_t p0 = block_scan_max(lm, s, &last_all);  // the last candidate in front of window w0
+    const int64_t p0 = block_scan_max(lm, s[0], &last_all);  // the last candidate in front of window w0
     // this thread's windows twice: their sums for the scan, then -- with the threads' in front -- every window's words
-    uint64_t c = 0, g = 0;
+    uint64_t mine[2] = {0u, 0u}, base[2], all[2];                // members, guessed bytes
     int64_t p = p0;
     for (uint64_t win = w0; win < w1; win++) {
         if (count[win] == 0u) continue;
-        c += count[win];
-        g += gsum[win] + (p >= 0 ? guess(f, (uint64_t)p, first[win]) : 0u);
+        mine[0] += count[win];
+        mine[1] += gsum[win] + (p >= 0 ? guess(f, (uint64_t)p, first[win]) : 0u);
         p = (int64_t)last[win];
     }
-    uint64_t M, total;
-    c = block_scan_add(c, s, &M);
-    g = block_scan_add(g, s, &total);
+    block_scan<2, SEAM_THREADS>(mine, base, all, s);
+    uint64_t c = base[0], g = base[1], total = all[1];
+    const uint64_t M = all[0];
     p = p0;
     for (uint64_t win = w0; win < w1; win++) {
         cbase[win] = c; obase[win] = g; prev[win] = (uint64_t)p;

@@ -104,8 +104,6 @@ __global__ __launch_bounds__(256) void k_join(JoinArgs a) {
         const uint64_t o0 = s_off[r];
         const uint32_t rn = (uint32_t)((r + 1u < JT ? s_off[r + 1u] : STREAM_HEAD + s_base + tsum) - o0);      // the member's length
         if (rn == 0u || o0 + rn > a.cap) continue;            // a failed row / a member that would end beyond the capacity
-        typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-        typedef v4 __attribute__((aligned(1))) v4u;
         const uint32_t bl = s_body[r], mark0 = rn - 2u;      // [0, bl): from the row; [bl, mark0): 00; [mark0, rn): FF
         const uint8_t* src = a.rows + rb * a.pitch + STREAM_HEAD;
         uint8_t* dst = a.stream + o0;

@@ -17,6 +17,7 @@
 // k_png_deinterlace  (HDLZ_PNG_ADAM7 only) the interlaced images: the seven unfiltered passes scattered into the slot, expanded on the way.
 // k_png_judge / k_png_finish   the verdict per image; the lowest failed image and the record.
 // Plain stores only; no workgroup waits for another.  Loads: inside the files of the range; of the scratch only what the call wrote.
+// The planners' strip and scan and the owner search are hdlz_plan.h's; the format's facts shared with the writer: hdlz_png_rules.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -24,28 +25,18 @@
 #include "hdlz_crc32.h"
 #include "hdlz_frame.h"
 #include "hdlz_adler.h"
+#include "hdlz_plan.h"
+#include "hdlz_png_rules.h"
 
 namespace hdlz {
 namespace png {
 
-constexpr uint32_t T_IHDR = 0x49484452u, T_PLTE = 0x504C5445u, T_IDAT = 0x49444154u, T_IEND = 0x49454E44u, T_TRNS = 0x74524E53u;
-constexpr uint64_t RAW_MAX = 0xFFFFFE00ull, Z_MAX = 0x10000000ull - 7u;       // the decoders' limits (hdlz_zip.h)
 constexpr uint32_t SCAN_THREADS = 1024u;
 constexpr uint32_t GATHER_TILE = 16384u;
 constexpr uint32_t BAND = 64u;                                   // rows a wave unfilters together
 constexpr uint32_t CB = 128u, LPITCH = 132u;                     // bytes of a row a tile holds; its pitch in LDS (33 words: a column of 64 rows spreads over all banks)
 constexpr uint64_t NONE64 = ~0ull;
 
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef v4 __attribute__((aligned(1))) v4u;
-
-__host__ __device__ inline uint64_t r16(uint64_t x) { return (x + 15u) & ~15ull; }
-
-__device__ __forceinline__ bool pair_ok(uint32_t colour, uint32_t depth) {
-    const bool d8 = depth == 8u || depth == 16u, low = depth == 1u || depth == 2u || depth == 4u;
-    return colour == 0u ? (d8 || low) : colour == 3u ? (low || depth == 8u) : (colour == 2u || colour == 4u || colour == 6u) && d8;
-}
-__device__ __forceinline__ uint32_t channels_of(uint32_t colour) { return colour == 2u ? 3u : colour == 4u ? 2u : colour == 6u ? 4u : 1u; }
 
 // Adam7 (step 4 of THE RULE for an interlaced image): pass p = 0 .. 6 takes the pixels (x0 + i dx, y0 + j dy) of the image.  The four
 // tables are nibbles of a word, pass 0 the lowest: x0 = 0 4 0 2 0 1 0, y0 = 0 0 4 0 2 0 1, log2 dx = 3 3 2 2 1 1 0, log2 dy = 3 3 3 2 2 1 1
@@ -127,18 +118,18 @@ __global__ __launch_bounds__(256) void k_png_parse(const uint8_t* __restrict__ f
     Sizes s{};
     const uint8_t* f = files + off;
     if (off > files_len || len > files_len - off) st = HDLZ_E_BAD_PARAM;
-    else if (len < 8u || load_be32(f) != 0x89504E47u || load_be32(f + 4) != 0x0D0A1A0Au) st = HDLZ_E_BAD_HEADER;
-    else if (len >= 16u && (load_be32(f + 8) != 13u || load_be32(f + 12) != T_IHDR)) st = HDLZ_E_BAD_HEADER;
+    else if (len < 8u || load_be32(f) != SIG_HI || load_be32(f + 4) != SIG_LO) st = HDLZ_E_BAD_HEADER;
+    else if (len >= 16u && (load_be32(f + 8) != IHDR_LEN || load_be32(f + 12) != T_IHDR)) st = HDLZ_E_BAD_HEADER;
     else {
         uint64_t p = 8;
         bool seen = false, gap = false, plte = false, trns = false;
         for (;;) {
-            if (p + 12u > len) { st = HDLZ_E_NO_EOF; break; }
+            if (p + CHUNK > len) { st = HDLZ_E_NO_EOF; break; }
             const uint64_t L = load_be32(f + p);
             if (L >= 0x80000000ull) { st = HDLZ_E_BAD_HEADER; break; }
-            if (p + 12u + L > len) { st = HDLZ_E_NO_EOF; break; }
+            if (p + CHUNK + L > len) { st = HDLZ_E_NO_EOF; break; }
             const uint32_t type = load_be32(f + p + 4);
-            if (type == T_IEND) { used = p + 12u + L; break; }
+            if (type == T_IEND) { used = p + CHUNK + L; break; }
             if (type == T_IHDR) {
                 if (p != 8u) { st = HDLZ_E_BAD_HEADER; break; }
             } else if (type == T_IDAT) {
@@ -156,7 +147,7 @@ __global__ __launch_bounds__(256) void k_png_parse(const uint8_t* __restrict__ f
                     trns = true; trns_off = p + 8u; trns_n = (uint32_t)L;
                 }
             }
-            p += 12u + L;
+            p += CHUNK + L;
         }
         if (st == HDLZ_OK && (!seen || (f[25] == 3u && !plte))) st = HDLZ_E_BAD_HEADER;
         if (st == HDLZ_OK) {
@@ -181,54 +172,32 @@ __global__ __launch_bounds__(256) void k_png_parse(const uint8_t* __restrict__ f
     if (i < image_cap) images[i] = rec;
 }
 
-// an exclusive scan over the workgroup's 1024 threads of three 64-bit values at once; tot: the sums (one __syncthreads pair inside)
-struct Scan3 { uint64_t v[3]; };
-__device__ __forceinline__ Scan3 block_scan3(Scan3 mine, uint64_t (&s_wave)[3][SCAN_THREADS / 64u], Scan3& tot) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    Scan3 r;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        uint64_t v = mine.v[k];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(v, o, 64);
-            if (lane >= (uint32_t)o) v += t;
-        }
-        if (lane == 63u) s_wave[k][wave] = v;
-        r.v[k] = v - mine.v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        uint64_t base = 0, all = 0;
-        for (uint32_t j = 0; j < SCAN_THREADS / 64u; j++) { const uint64_t x = s_wave[k][j]; if (j < wave) base += x; all += x; }
-        r.v[k] += base; tot.v[k] = all;
-    }
-    __syncthreads();
-    return r;
-}
-
-// ---- step 5 and the record: thread t takes the images [per t, per (t + 1))
+// ---- step 5 and the record: a strip of the images a thread (hdlz_plan.h)
 __global__ __launch_bounds__(SCAN_THREADS) void k_png_offsets(uint64_t n, uint64_t image_cap, uint32_t out_align, hdlz_png_image* __restrict__ images,
                                                               hdlz_png_index_result* __restrict__ result, IndexWork w) {
     __shared__ uint64_t s_wave[3][SCAN_THREADS / 64u];
     __shared__ uint64_t s_end;
     const uint32_t tid = threadIdx.x;
     const uint64_t mask = (uint64_t)out_align - 1u;
-    const uint64_t per = (n + SCAN_THREADS - 1u) / SCAN_THREADS, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-    Scan3 mine{{0, 0, 0}}, tot;
-    for (uint64_t e = lo; e < hi; e++) { mine.v[0] += r16(w.wz[e]); mine.v[1] += r16(w.wr[e]); mine.v[2] += (w.wo[e] + mask) & ~mask; }
-    if (tid == 0u) s_end = 0u;
-    Scan3 base = block_scan3(mine, s_wave, tot);
+    uint64_t lo, hi;
+    strip(n, SCAN_THREADS, tid, lo, hi);
+    uint64_t mine[3] = {0u, 0u, 0u}, base[3], tot[3];
     for (uint64_t e = lo; e < hi; e++) {
-        if (e < image_cap) { images[e].z_off = base.v[0]; images[e].raw_off = base.v[1]; images[e].out_off = base.v[2]; }
-        if (e + 1u == n) s_end = base.v[2] + w.wo[e];             // the end of the last slot
-        base.v[0] += r16(w.wz[e]); base.v[1] += r16(w.wr[e]); base.v[2] += (w.wo[e] + mask) & ~mask;
+        const Slots s = slots_of(w.wz[e], w.wr[e], w.wo[e], mask);
+        mine[0] += s.z; mine[1] += s.raw; mine[2] += s.out;
+    }
+    if (tid == 0u) s_end = 0u;
+    block_scan<3, SCAN_THREADS>(mine, base, tot, s_wave);
+    for (uint64_t e = lo; e < hi; e++) {
+        if (e < image_cap) { images[e].z_off = base[0]; images[e].raw_off = base[1]; images[e].out_off = base[2]; }
+        if (e + 1u == n) s_end = base[2] + w.wo[e];               // the end of the last slot
+        const Slots s = slots_of(w.wz[e], w.wr[e], w.wo[e], mask);
+        base[0] += s.z; base[1] += s.raw; base[2] += s.out;
     }
     __syncthreads();
     if (tid != 0u) return;
     hdlz_png_index_result res;
-    res.nimages = n; res.total_z = tot.v[0]; res.total_raw = tot.v[1]; res.total_out = s_end;
+    res.nimages = n; res.total_z = tot[0]; res.total_raw = tot[1]; res.total_out = s_end;
     res.status = n > image_cap ? (uint32_t)HDLZ_E_OUT_CAPACITY : (uint32_t)HDLZ_OK;
     res.reserved = 0u;
     *result = res;
@@ -244,7 +213,7 @@ __device__ __forceinline__ uint32_t check_record(const PngArgs& a, const hdlz_pn
     if (!sizes_of(r.width, r.height, r.depth, r.colour, r.trns_off != 0u, a.flags, r.interlace != 0u, s)) return HDLZ_E_BAD_PARAM;
     if (s.row_bytes != r.row_bytes || s.raw_len != r.raw_len || s.out_len != r.out_len || s.channels_out != r.channels_out || s.sample_bytes != r.sample_bytes) return HDLZ_E_BAD_PARAM;
     if (r.zlen > Z_MAX) return HDLZ_E_BAD_PARAM;
-    if (r.nidat == 0u || r.idat_off < 8u || r.idat_off > r.used || r.used - r.idat_off < 12u) return HDLZ_E_BAD_PARAM;
+    if (r.nidat == 0u || r.idat_off < 8u || r.idat_off > r.used || r.used - r.idat_off < CHUNK) return HDLZ_E_BAD_PARAM;
     if (r.colour == 3u && (r.plte_n == 0u || r.plte_n > 256u || r.plte_off < 16u || r.plte_off > r.used || r.used - r.plte_off < 3u * r.plte_n + 4u)) return HDLZ_E_BAD_PARAM;
     if (r.trns_off != 0u && (r.trns_n > 256u || r.trns_off < 16u || r.trns_off > r.used || r.used - r.trns_off < r.trns_n + 4u)) return HDLZ_E_BAD_PARAM;
     if (r.plte_off != 0u && (r.plte_n == 0u || r.plte_n > 256u || r.plte_off < 16u || r.plte_off > r.used || r.used - r.plte_off < 3u * r.plte_n + 4u)) return HDLZ_E_BAD_PARAM;
@@ -260,12 +229,13 @@ __device__ __forceinline__ bool expands(const PngArgs& a, const hdlz_png_image& 
 
 // ---- the checks and the four scans.  head: [0] chunks, [1] Adler tiles, [2] gather tiles, [3] bands
 __global__ __launch_bounds__(SCAN_THREADS) void k_png_plan(PngArgs a) {
-    __shared__ uint64_t s_wave[3][SCAN_THREADS / 64u];
+    __shared__ uint64_t s_wave[4][SCAN_THREADS / 64u];
     const uint32_t tid = threadIdx.x;
     const uint64_t n = a.count;
-    const uint64_t per = (n + SCAN_THREADS - 1u) / SCAN_THREADS, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+    uint64_t lo, hi;
+    strip(n, SCAN_THREADS, tid, lo, hi);
     const hdlz_png_image r0 = a.images[0];
-    Scan3 m1{{0, 0, 0}}, m2{{0, 0, 0}}, tot1, tot2;
+    uint64_t mine[4] = {0u, 0u, 0u, 0u}, base[4], tot[4];
     for (uint64_t b = lo; b < hi; b++) {
         const hdlz_png_image r = a.images[b];
         const uint32_t st = check_record(a, r, r0);
@@ -275,20 +245,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_png_plan(PngArgs a) {
                        nz = ok ? (r.zlen + GATHER_TILE - 1u) / GATHER_TILE : 0u,
                        nb = !ok ? 0u : r.interlace ? adam7_bands(r.width, r.height) : ((uint64_t)r.height + BAND - 1u) / BAND;
         a.cbase[b] = nc; a.tb[b] = nt; a.zb[b] = nz; a.sb[b] = nb;
-        m1.v[0] += nc; m1.v[1] += nt; m1.v[2] += nz; m2.v[0] += nb;
+        mine[0] += nc; mine[1] += nt; mine[2] += nz; mine[3] += nb;
     }
-    Scan3 b1 = block_scan3(m1, s_wave, tot1), b2 = block_scan3(m2, s_wave, tot2);
+    block_scan<4, SCAN_THREADS>(mine, base, tot, s_wave);
     for (uint64_t b = lo; b < hi; b++) {
         const uint64_t nc = a.cbase[b], nt = a.tb[b], nz = a.zb[b], nb = a.sb[b];
-        a.cbase[b] = b1.v[0]; a.tb[b] = b1.v[1]; a.zb[b] = b1.v[2]; a.sb[b] = b2.v[0];
+        a.cbase[b] = base[0]; a.tb[b] = base[1]; a.zb[b] = base[2]; a.sb[b] = base[3];
         // (an image whose share does not fit the lists the query sized -- records of overlapping slots, an idat_cap too small -- is refused:
         //  no kernel behind this one writes a list entry or a tile word of a refused image)
-        if (a.verdict[b] == HDLZ_OK && (b1.v[0] + nc > a.list_cap || b1.v[1] + nt > a.tile_cap)) a.verdict[b] = HDLZ_E_BAD_PARAM;
-        b1.v[0] += nc; b1.v[1] += nt; b1.v[2] += nz; b2.v[0] += nb;
+        if (a.verdict[b] == HDLZ_OK && (base[0] + nc > a.list_cap || base[1] + nt > a.tile_cap)) a.verdict[b] = HDLZ_E_BAD_PARAM;
+        base[0] += nc; base[1] += nt; base[2] += nz; base[3] += nb;
     }
     if (tid == 0u) {
-        a.cbase[n] = tot1.v[0]; a.tb[n] = tot1.v[1]; a.zb[n] = tot1.v[2]; a.sb[n] = tot2.v[0];
-        a.head[0] = tot1.v[0] < a.list_cap ? tot1.v[0] : a.list_cap; a.head[1] = tot1.v[1]; a.head[2] = tot1.v[2]; a.head[3] = tot2.v[0];
+        a.cbase[n] = tot[0]; a.tb[n] = tot[1]; a.zb[n] = tot[2]; a.sb[n] = tot[3];
+        a.head[0] = tot[0] < a.list_cap ? tot[0] : a.list_cap; a.head[1] = tot[1]; a.head[2] = tot[2]; a.head[3] = tot[3];
     }
 }
 
@@ -305,31 +275,31 @@ __global__ __launch_bounds__(JT) void k_png_list(PngArgs a) {
         bool good = true;
         uint32_t k = 0;
         for (; k < r.nidat; k++) {
-            if (p > r.used || r.used - p < 12u) { good = false; break; }
+            if (p > r.used || r.used - p < CHUNK) { good = false; break; }
             const uint64_t L = load_be32(f + p);
-            if (L > r.used - p - 12u || load_be32(f + p + 4) != T_IDAT || L > r.zlen - z) { good = false; break; }
+            if (L > r.used - p - CHUNK || load_be32(f + p + 4) != T_IDAT || L > r.zlen - z) { good = false; break; }
             a.c_src[c0 + k] = abs0 + p + 4u; a.c_dst[c0 + k] = z; a.c_len[c0 + k] = (uint32_t)L; a.c_img[c0 + k] = (uint32_t)b;
-            z += L; p += 12u + L;
+            z += L; p += CHUNK + L;
         }
         if (good && z != r.zlen) good = false;
         uint64_t iend = 0;
         while (good) {                                            // the chunks behind the IDATs, up to the IEND that ends at `used`
-            if (p > r.used || r.used - p < 12u) { good = false; break; }
+            if (p > r.used || r.used - p < CHUNK) { good = false; break; }
             const uint64_t L = load_be32(f + p);
-            if (L > r.used - p - 12u) { good = false; break; }
-            if (load_be32(f + p + 4) == T_IEND) { if (p + 12u + L != r.used) good = false; iend = p; break; }
-            p += 12u + L;
+            if (L > r.used - p - CHUNK) { good = false; break; }
+            if (load_be32(f + p + 4) == T_IEND) { if (p + CHUNK + L != r.used) good = false; iend = p; break; }
+            p += CHUNK + L;
         }
         // IHDR (the rule's step 1 is checked again: the chunk at 8), PLTE, tRNS: type and length in front of the data
-        if (good && (r.used < 33u || load_be32(f + 8) != 13u || load_be32(f + 12) != T_IHDR)) good = false;
+        if (good && (r.used < SIG_IHDR_END || load_be32(f + 8) != IHDR_LEN || load_be32(f + 12) != T_IHDR)) good = false;
         if (good && r.plte_off && (load_be32(f + r.plte_off - 8u) != 3u * r.plte_n || load_be32(f + r.plte_off - 4u) != T_PLTE)) good = false;
         if (good && r.trns_off && (load_be32(f + r.trns_off - 8u) != r.trns_n || load_be32(f + r.trns_off - 4u) != T_TRNS)) good = false;
         const uint64_t x = c0 + r.nidat;
         if (good) {
-            a.c_src[x] = abs0 + 12u; a.c_len[x] = 13u; a.c_img[x] = (uint32_t)b;
+            a.c_src[x] = abs0 + 12u; a.c_len[x] = IHDR_LEN; a.c_img[x] = (uint32_t)b;
             a.c_src[x + 1u] = abs0 + r.plte_off - 4u; a.c_len[x + 1u] = 3u * r.plte_n; a.c_img[x + 1u] = r.plte_off ? (uint32_t)b : NONE;
             a.c_src[x + 2u] = abs0 + r.trns_off - 4u; a.c_len[x + 2u] = r.trns_n; a.c_img[x + 2u] = r.trns_off ? (uint32_t)b : NONE;
-            a.c_src[x + 3u] = abs0 + iend + 4u; a.c_len[x + 3u] = (uint32_t)(r.used - iend - 12u); a.c_img[x + 3u] = (uint32_t)b;
+            a.c_src[x + 3u] = abs0 + iend + 4u; a.c_len[x + 3u] = (uint32_t)(r.used - iend - CHUNK); a.c_img[x + 3u] = (uint32_t)b;
             for (uint32_t j = 0; j < 4u; j++) a.c_dst[x + j] = NONE64;
         } else {
             st = HDLZ_E_BAD_PARAM;
@@ -349,16 +319,6 @@ __global__ __launch_bounds__(JT) void k_png_list(PngArgs a) {
     a.m_end[b] = decode ? zo + r.zlen : 2u;                       // (the Adler-32 supplies the four bytes the end-of-input rules want)
     a.m_dst[b] = a.raw + (decode ? ro : 0u);
     a.cap[b] = decode ? (uint32_t)r.raw_len : 0u;
-}
-
-// the largest b < count with base[b] <= g (base[count] > g)
-__device__ __forceinline__ uint64_t owner(const uint64_t* __restrict__ base, uint64_t count, uint64_t g) {
-    uint64_t lo = 0, hi = count;
-    while (hi - lo > 1u) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (base[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // ---- (a) the gather: gather tile g is 16 KiB of one image's zlib stream

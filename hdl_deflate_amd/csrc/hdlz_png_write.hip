@@ -26,33 +26,33 @@
 //                 stream's tail (or the whole stored stream), IEND.
 // k_pngw_crc      a workgroup per IHDR / IDAT chunk: crc_block over type and data, the word stored behind them.
 // Plain stores only; no workgroup waits for another.
+// The planners' strip and scan, the searches and the rows' verdict are hdlz_plan.h's; the format's facts shared with the reader:
+// hdlz_png_rules.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
-#include "hdlz_compress_common.h"                        // HEADER_BITS, block_nbytes
+#include "hdlz_compress_common.h"                        // member_len
 #include "hdlz_crc32.h"
 #include "hdlz_frame.h"
 #include "hdlz_adler.h"
+#include "hdlz_plan.h"
+#include "hdlz_png_rules.h"
 
 namespace hdlz {
 namespace pngw {
 
 constexpr uint32_t BAND = HDLZ_PNGW_BAND, STEP = HDLZ_PNGW_STEP, KREG = HDLZ_PNGW_ROW_REG_MAX / HDLZ_PNGW_STEP;
-constexpr uint64_t RAW_MAX = 0xFFFFFE00ull, Z_MAX = 0x10000000ull - 7u;
+using namespace png;                                     // hdlz_png_rules.h
 constexpr uint32_t PLAN_THREADS = 1024u, PLAN_WAVES = PLAN_THREADS / 64u;
-constexpr uint32_t COUNT_BITS = 31u;
-constexpr uint64_t COUNT_MASK = (1ull << COUNT_BITS) - 1u;
 constexpr uint64_t NONE64 = ~0ull;
-constexpr uint32_t SIG_IHDR_END = 33u, CHUNK = 12u, FIRST_DATA = SIG_IHDR_END + 8u;      // signature + IHDR chunk; a chunk's frame; the first IDAT's data
+constexpr uint32_t FIRST_DATA = SIG_IHDR_END + 8u;      // the first IDAT's data
 constexpr uint32_t STORED_HEAD = 7u, Z_TAIL = 6u;        // 78 9C 01 LEN NLEN; 03 00 + Adler-32
 constexpr uint32_t CRC_GROUPS_MAX = 4096u, FILTER_GRID_MAX = 1u << 20;
 
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef v4 __attribute__((aligned(1))) v4u;
 
-__host__ __device__ inline uint64_t r16(uint64_t x) { return (x + 15u) & ~15ull; }
-
-// the first three lines of the per-image refusals; rb = row_bytes, bpp as the header states them
+// the first three lines of the per-image refusals; rb = row_bytes, bpp as the header states them.  The pairs that are written are
+// those of pair_ok (hdlz_png_rules.h) with whole bytes a sample and without a palette, spelled out here: the filter kernel calls this
+// for rb and bpp, and the test's text is part of its instruction sequence (profiles/planner_shared.txt, section 3)
 __device__ __forceinline__ uint32_t check_spec(const hdlz_png_spec& s, uint64_t& rb, uint64_t& raw_len, uint32_t& bpp) {
     rb = 0u; raw_len = 0u; bpp = 1u;
     if (s.width == 0u || s.height == 0u || s.width >= 0x80000000u || s.height >= 0x80000000u) return HDLZ_E_BAD_HEADER;
@@ -60,61 +60,20 @@ __device__ __forceinline__ uint32_t check_spec(const hdlz_png_spec& s, uint64_t&
     bool res = false;
     for (int k = 0; k < 6; k++) res = res || s.reserved[k] != 0u;
     if (!pair || res) return HDLZ_E_BAD_HEADER;
-    const uint32_t ch = s.colour == 2u ? 3u : s.colour == 4u ? 2u : s.colour == 6u ? 4u : 1u;
-    bpp = ch * (s.depth >> 3);
+    bpp = channels_of(s.colour) * (s.depth >> 3);
     rb = (uint64_t)s.width * bpp;
     if (rb + 1u > RAW_MAX / s.height) return HDLZ_E_OUT_CAPACITY;
     raw_len = (uint64_t)s.height * (rb + 1u);
     return HDLZ_OK;
 }
 
-// the exclusive prefix of every thread's mine[0 .. Q) over the plan's workgroup -> base; total: the sums (two barriers inside)
-template <int Q>
-__device__ __forceinline__ void plan_scan(const uint64_t (&mine)[Q], uint64_t (&base)[Q], uint64_t (&total)[Q], uint64_t (*s)[PLAN_WAVES]) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t v[Q];
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        v[q] = mine[q];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(v[q], o, 64);
-            if (lane >= (uint32_t)o) v[q] += t;
-        }
-    }
-    __syncthreads();                                              // (a scan in front of this one has been read)
-    if (lane == 63u) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) s[q][wave] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        base[q] = v[q] - mine[q];
-        total[q] = 0u;
-        for (uint32_t k = 0; k < PLAN_WAVES; k++) {
-            if (k < wave) base[q] += s[q][k];
-            total[q] += s[q][k];
-        }
-    }
-}
-
-// the largest i < count with base[i] <= g (base ascending, base[0] <= g)
-__device__ __forceinline__ uint64_t owner(const uint64_t* __restrict__ base, uint64_t count, uint64_t g) {
-    uint64_t lo = 0, hi = count;
-    while (hi - lo > 1u) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (base[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// ---- hdlz_png_filter_ws: the plan.  Thread t takes the images [per t, per (t + 1))
+// ---- hdlz_png_filter_ws: the plan.  A strip of the images a thread (hdlz_plan.h)
 __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_plan(PngFilterArgs a) {
     __shared__ uint64_t s_wave[3][PLAN_WAVES];
     const uint32_t tid = threadIdx.x;
     const uint64_t n = a.n;
-    const uint64_t per = (n + PLAN_THREADS - 1u) / PLAN_THREADS, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+    uint64_t lo, hi;
+    strip(n, PLAN_THREADS, tid, lo, hi);
     uint64_t mine[3] = {0u, 0u, 0u}, base[3], total[3];           // raw_len, rows, bands
     for (uint64_t i = lo; i < hi; i++) {
         const hdlz_png_spec s = a.specs[i];
@@ -125,7 +84,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_plan(PngFilterArgs a) {
         a.status[i] = st;
         if (st == HDLZ_OK) { mine[0] += raw_len; mine[1] += s.height; mine[2] += ((uint64_t)s.height + BAND - 1u) / BAND; }
     }
-    plan_scan(mine, base, total, s_wave);
+    block_scan<3, PLAN_THREADS>(mine, base, total, s_wave);
     for (uint64_t i = lo; i < hi; i++) {
         a.raw_off[i] = base[0]; a.row_base[i] = base[1]; a.band_base[i] = base[2];
         if (a.status[i] != HDLZ_OK) continue;
@@ -429,24 +388,13 @@ __global__ __launch_bounds__(256) void k_pngw_filter(PngFilterArgs a) {
     }
 }
 
-// ---- hdlz_png_write_ws.  |M_b| and the bytes of it that come from the row; 0: the row's three words contradict each other
-__device__ __forceinline__ uint32_t member_len(const PngWriteArgs& a, uint64_t b, uint32_t& body) {
-    const uint32_t n = a.len[b];
-    const uint64_t E = a.end_bits[b];
-    body = 0u;
-    if (E < HEADER_BITS || block_nbytes(E) + 4u != (uint64_t)n || (uint64_t)n > a.pitch) return 0u;
-    const uint32_t nbytes = n - 4u;
-    const uint32_t p = (uint32_t)(8ull * nbytes - E) - 7u;       // pad bits behind the end-of-block code
-    body = nbytes - 2u;
-    return body + (p >= 3u ? 4u : 5u);
-}
-
-// the prefixes over the rows: thread t takes the blocks [per t, per (t + 1))
+// ---- hdlz_png_write_ws.  The prefixes over the rows: a strip of the blocks a thread
 __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_scan(PngWriteArgs a) {
     __shared__ uint64_t s_wave[5][PLAN_WAVES];
     const uint32_t tid = threadIdx.x;
     const uint64_t B = a.nblocks;
-    const uint64_t per = (B + PLAN_THREADS - 1u) / PLAN_THREADS, lo = tid * per < B ? tid * per : B, hi = lo + per < B ? lo + per : B;
+    uint64_t lo, hi;
+    strip(B, PLAN_THREADS, tid, lo, hi);
     uint64_t mine[5] = {0u, 0u, 0u, 0u, 0u}, base[5], total[5];
     const uint64_t in0 = a.in_off[0];
     for (uint64_t b = lo; b < hi; b++) {
@@ -454,7 +402,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_scan(PngWriteArgs a) {
         if (a.status[b] != HDLZ_OK) k = 1u;
         else {
             uint32_t body;
-            m = member_len(a, b, body);
+            m = member_len(a.len[b], a.end_bits[b], a.pitch, body);
             const uint64_t i0 = a.in_off[b], i1 = a.in_off[b + 1u];
             if (i1 < i0 || i0 < in0) m = 0u;
             if (m == 0u) k = 1ull << COUNT_BITS;
@@ -469,7 +417,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_scan(PngWriteArgs a) {
         a.pre[b] = m; a.cnt[b] = k; a.pa[b] = pa; a.pe[b] = pe; a.ps[b] = ps;
         mine[0] += m; mine[1] += k; mine[2] += pa; mine[3] += pe; mine[4] += ps;
     }
-    plan_scan(mine, base, total, s_wave);
+    block_scan<5, PLAN_THREADS>(mine, base, total, s_wave);
     for (uint64_t b = lo; b < hi; b++) {
         const uint64_t m = a.pre[b], k = a.cnt[b], pa = a.pa[b], pe = a.pe[b], ps = a.ps[b];
         a.pre[b] = base[0]; a.cnt[b] = base[1]; a.pa[b] = base[2]; a.pe[b] = base[3]; a.ps[b] = base[4];
@@ -488,12 +436,8 @@ __device__ __forceinline__ uint32_t check_image(const PngWriteArgs& a, uint64_t 
     const uint64_t F0 = a.blk_first[i], F1 = a.blk_first[i + 1u];
     if (F0 > F1 || F1 > a.nblocks) return HDLZ_E_BAD_PARAM;
     if (F1 > F0) {
-        const uint64_t k = a.cnt[F1] - a.cnt[F0];                 // (both counts ascend: the halves subtract without a borrow)
-        if (k & COUNT_MASK) {
-            for (uint64_t b = F0; b < F1; b++) st = max(st, a.status[b]);
-            return st;
-        }
-        if (k >> COUNT_BITS) return HDLZ_E_BAD_PARAM;
+        st = rows_verdict(a.cnt, a.status, F0, F1);
+        if (st != HDLZ_OK) return st;
         if (a.in_off[F1] - a.in_off[F0] != raw_len) return HDLZ_E_BAD_PARAM;
     } else if (raw_len >= 5u || !a.raw) return HDLZ_E_BAD_PARAM;
     if (a.raw_off[i + 1u] - a.raw_off[i] != raw_len) return HDLZ_E_BAD_PARAM;
@@ -523,7 +467,8 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_layout(PngWriteArgs a) {
     __shared__ uint64_t s_first[PLAN_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t n = a.n, amask = (uint64_t)a.out_align - 1u;
-    const uint64_t per = (n + PLAN_THREADS - 1u) / PLAN_THREADS, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+    uint64_t lo, hi;
+    strip(n, PLAN_THREADS, tid, lo, hi);
     uint64_t mine[5] = {0u, 0u, 0u, 0u, 0u}, base[5], total[5];  // file_len, the index's z / raw / out slots, chunks of the CRC list
     uint32_t worst = HDLZ_OK;
     uint64_t first = NONE64;
@@ -538,7 +483,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_layout(PngWriteArgs a) {
         if (st == HDLZ_OK) {
             const uint64_t nidat = (zlen + a.idat - 1u) / a.idat;
             mine[0] += SIG_IHDR_END + zlen + CHUNK * nidat + CHUNK;
-            if (zlen <= Z_MAX) { mine[1] += r16(zlen + 8u); mine[2] += r16(raw_len); mine[3] += (out_len_of(s, rb) + amask) & ~amask; }
+            if (zlen <= Z_MAX) { const Slots t = slots_of(zlen + 8u, raw_len, out_len_of(s, rb), amask); mine[1] += t.z; mine[2] += t.raw; mine[3] += t.out; }
             mine[4] += 1u + nidat;
         } else {
             worst = max(worst, st);
@@ -552,7 +497,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_layout(PngWriteArgs a) {
         for (int o = 32; o > 0; o >>= 1) { const uint64_t t = __shfl_xor(rf, o, 64); rf = rf < t ? rf : t; }
         if (lane == 0u) { s_worst[wave] = rw; s_first[wave] = rf; }
     }
-    plan_scan(mine, base, total, s_wave);                         // (its barriers stand behind the stores of s_worst and s_first, too)
+    block_scan<5, PLAN_THREADS>(mine, base, total, s_wave);      // (its barriers stand behind the stores of s_worst and s_first, too)
     worst = HDLZ_OK; first = NONE64;
     for (uint32_t k = 0; k < PLAN_WAVES; k++) { worst = max(worst, s_worst[k]); first = first < s_first[k] ? first : s_first[k]; }
     const bool write = total[0] <= a.cap;
@@ -582,7 +527,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_pngw_layout(PngWriteArgs a) {
         }
         if (st == HDLZ_OK) {
             base[0] += flen; base[4] += 1u + nidat;
-            if (indexed) { base[1] += r16(zlen + 8u); base[2] += r16(raw_len); base[3] += (out_len_of(s, rb) + amask) & ~amask; }
+            if (indexed) { const Slots t = slots_of(zlen + 8u, raw_len, out_len_of(s, rb), amask); base[1] += t.z; base[2] += t.raw; base[3] += t.out; }
         }
     }
     if (tid != 0u) return;
@@ -603,7 +548,6 @@ __device__ __forceinline__ uint8_t member_byte(const uint8_t* src, uint32_t i, u
     if (i < bl) return i == 0u ? (uint8_t)(src[0] & 0xFEu) : src[i];
     return i < m - 2u ? (uint8_t)0u : (uint8_t)0xFFu;
 }
-__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
 
 __global__ __launch_bounds__(256) void k_pngw_gather(PngWriteArgs a, uint32_t row_groups) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -612,13 +556,12 @@ __global__ __launch_bounds__(256) void k_pngw_gather(PngWriteArgs a, uint32_t ro
         // ---- a wave per block
         const uint64_t b = (uint64_t)blockIdx.x * 4u + wave;
         if (b >= a.nblocks) return;
-        uint64_t lo = 0, hi = a.n + 1u;                           // the first index with blk_first > b
-        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (a.blk_first[mid] > b) hi = mid; else lo = mid + 1u; }
-        if (lo == 0u || lo > a.n) return;                         // (a row that no image owns)
-        const uint64_t i = lo - 1u;
+        const uint64_t ub = upper(a.blk_first, a.n + 1u, b);
+        if (ub == 0u || ub > a.n) return;                         // (a row that no image owns)
+        const uint64_t i = ub - 1u;
         if (a.ist[i] != HDLZ_OK) return;
         uint32_t bl;
-        const uint32_t m = member_len(a, b, bl);
+        const uint32_t m = member_len(a.len[b], a.end_bits[b], a.pitch, bl);
         const uint8_t* __restrict__ src = a.rows + b * a.pitch + 2u;
         uint8_t* const file = a.file + a.file_off[i];
         const uint64_t o = 2u + (a.pre[b] - a.pre[a.blk_first[i]]);      // where M_b starts in the image's stream
@@ -648,7 +591,7 @@ __global__ __launch_bounds__(256) void k_pngw_gather(PngWriteArgs a, uint32_t ro
     const uint64_t zlen = a.zlen[i], nidat = (zlen + a.idat - 1u) / a.idat;
     const uint32_t adler = a.adler[i];
     if (lane < SIG_IHDR_END - 4u) {                               // the signature and IHDR up to its CRC-32
-        const uint8_t fixed[16] = {0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A, 0, 0, 0, 13, 0x49, 0x48, 0x44, 0x52};
+        const uint8_t fixed[16] = {HDLZ_BE32_BYTES(SIG_HI), HDLZ_BE32_BYTES(SIG_LO), HDLZ_BE32_BYTES(IHDR_LEN), HDLZ_BE32_BYTES(T_IHDR)};
         uint8_t v = 0u;
         if (lane < 16u) { for (uint32_t k = 0; k < 16u; k++) if (k == lane) v = fixed[k]; }
         else if (lane < 20u) v = (uint8_t)(s.width >> (8u * (19u - lane)));
@@ -661,7 +604,7 @@ __global__ __launch_bounds__(256) void k_pngw_gather(PngWriteArgs a, uint32_t ro
         uint8_t* h = file + SIG_IHDR_END + k * ((uint64_t)a.idat + CHUNK);
         const uint64_t left = zlen - k * a.idat;
         put_be32(h, (uint32_t)(left < a.idat ? left : a.idat));
-        h[4] = 0x49; h[5] = 0x44; h[6] = 0x41; h[7] = 0x54;
+        put_be32(h + 4, T_IDAT);
     }
     const bool stored = a.blk_first[i] == a.blk_first[i + 1u];
     const uint32_t raw_len = stored ? (uint32_t)(zlen - STORED_HEAD - 4u) : 0u;
@@ -685,7 +628,7 @@ __global__ __launch_bounds__(256) void k_pngw_gather(PngWriteArgs a, uint32_t ro
         file[file_pos(sp, a.idat)] = v;
     }
     if (lane < CHUNK) {                                           // IEND, its CRC-32 a constant
-        const uint8_t iend[CHUNK] = {0, 0, 0, 0, 0x49, 0x45, 0x4E, 0x44, 0xAE, 0x42, 0x60, 0x82};
+        const uint8_t iend[CHUNK] = {0, 0, 0, 0, HDLZ_BE32_BYTES(T_IEND), 0xAE, 0x42, 0x60, 0x82};
         uint8_t v = 0u;
         for (uint32_t k = 0; k < CHUNK; k++) if (k == lane) v = iend[k];
         file[SIG_IHDR_END + zlen + CHUNK * nidat + lane] = v;
@@ -703,7 +646,7 @@ __global__ __launch_bounds__(CRC_THREADS) void k_pngw_crc(PngWriteArgs a) {
         uint8_t* const file = a.file + a.file_off[i];
         uint8_t* p;
         uint32_t L;
-        if (k == 0u) { p = file + 12u; L = 17u; }
+        if (k == 0u) { p = file + 12u; L = 4u + IHDR_LEN; }
         else {
             const uint64_t left = a.zlen[i] - (k - 1u) * a.idat;
             p = file + SIG_IHDR_END + (k - 1u) * ((uint64_t)a.idat + CHUNK) + 4u;

@@ -60,7 +60,6 @@ __global__ __launch_bounds__(RT) void k_seek_points(SeekIndexArgs a) {
 }
 
 __global__ __launch_bounds__(RT) void k_seek_windows(SeekIndexArgs a) {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
     const uint32_t tid = threadIdx.x;
     const uint64_t n = a.head[0];                  // (at most point_cap)
     for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {

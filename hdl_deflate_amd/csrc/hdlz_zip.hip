@@ -24,6 +24,7 @@
 #include "hdlz_device.h"
 #include "hdlz_crc32.h"
 #include "hdlz_frame.h"
+#include "hdlz_plan.h"
 
 namespace hdlz {
 namespace zip {
@@ -31,12 +32,10 @@ namespace zip {
 constexpr uint32_t EOCD = 22u, CDREC = 46u, LOCREC = 30u, COMMENT_MAX = 65535u, ENTRIES_MAX = 65536u;      // (a directory holds at most 65535)
 constexpr uint32_t SIG_EOCD = 0x06054B50u, SIG_CD = 0x02014B50u, SIG_LOCAL = 0x04034B50u, SIG_LOCATOR = 0x07064B50u;
 constexpr uint32_t PIECE = 16384u, WALK_THREADS = 256u;          // a staging piece: four 16-byte loads a thread
-constexpr uint32_t SCAN_THREADS = 1024u, SCAN_PER = ENTRIES_MAX / SCAN_THREADS;
+constexpr uint32_t SCAN_THREADS = 1024u;
 constexpr uint32_t SKIP = 0xFFFFFFFFu;                           // the decoder's status word of a stored entry: it is left alone
 constexpr uint32_t DST_CAP_MAX = 0xFFFFFE00u;                    // the task view's room (member_view: o + 258 never wraps)
 
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef v4 __attribute__((aligned(1))) v4u;
 
 // the summary at the front of the index scratch (64-bit words), then cdoff[65536] and size[65536] (32-bit words)
 struct IndexWork {
@@ -186,33 +185,25 @@ __global__ __launch_bounds__(256) void k_zip_entries(const uint8_t* __restrict__
     entries[e] = rec;
 }
 
-// ---- step 4 and the record: thread t takes the entries [SCAN_PER t, SCAN_PER (t + 1))
+// ---- step 4 and the record: a strip of the entries a thread (hdlz_plan.h)
 __global__ __launch_bounds__(SCAN_THREADS) void k_zip_offsets(uint64_t entry_cap, uint32_t out_align, hdlz_zip_entry* __restrict__ entries,
                                                               hdlz_zip_index_result* __restrict__ result, IndexWork w) {
-    __shared__ uint64_t s_wave[SCAN_THREADS / 64u];
+    __shared__ uint64_t s_wave[1][SCAN_THREADS / 64u];
     __shared__ uint64_t s_total;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t n = (uint32_t)w.head[5];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = (uint32_t)w.head[5];                       // (at most ENTRIES_MAX)
     const uint64_t mask = (uint64_t)out_align - 1u;
-    const uint32_t lo = tid * SCAN_PER, hi = lo + SCAN_PER < n ? lo + SCAN_PER : n;
-    uint64_t mine = 0;
-    for (uint32_t e = lo; e < hi; e++) mine += ((uint64_t)w.size[e] + mask) & ~mask;
-    uint64_t v = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v += t;
-    }
-    if (lane == 63u) s_wave[wave] = v;
+    uint64_t lo, hi;
+    strip(n, SCAN_THREADS, tid, lo, hi);
+    uint64_t mine[1] = {0u}, base[1], total[1];
+    for (uint64_t e = lo; e < hi; e++) mine[0] += ((uint64_t)w.size[e] + mask) & ~mask;
     if (tid == 0u) s_total = 0u;                                  // (no entries)
-    __syncthreads();
-    uint64_t base = v - mine;
-    for (uint32_t k = 0; k < wave; k++) base += s_wave[k];
-    for (uint32_t e = lo; e < hi; e++) {
+    block_scan<1, SCAN_THREADS>(mine, base, total, s_wave);
+    for (uint64_t e = lo; e < hi; e++) {
         const uint64_t s = w.size[e];
-        if (e < entry_cap) entries[e].out_off = base;
-        if (e + 1u == n) s_total = base + s;                      // the end of the last slot
-        base += (s + mask) & ~mask;
+        if (e < entry_cap) entries[e].out_off = base[0];
+        if (e + 1u == n) s_total = base[0] + s;                   // the end of the last slot
+        base[0] += (s + mask) & ~mask;
     }
     __syncthreads();
     if (tid != 0u) return;
@@ -417,34 +408,25 @@ __global__ __launch_bounds__(256) void k_zip64_entries(const uint8_t* __restrict
     entries[e] = rec;
 }
 
-// step 4 and the record: k_zip_offsets over the n = min(entries passed, entry_cap) entries that have a record, thread t the run
-// [per t, per (t + 1)) with per = ceil(n / 1024)
+// step 4 and the record: k_zip_offsets over the n = min(entries passed, entry_cap) entries that have a record
 __global__ __launch_bounds__(SCAN_THREADS) void k_zip64_offsets(uint64_t entry_cap, uint32_t out_align, hdlz_zip64_entry* __restrict__ entries,
                                                                 hdlz_zip_index_result* __restrict__ result, Index64Work w) {
-    __shared__ uint64_t s_wave[SCAN_THREADS / 64u];
+    __shared__ uint64_t s_wave[1][SCAN_THREADS / 64u];
     __shared__ uint64_t s_total;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint64_t passed = w.head[5], n = passed < entry_cap ? passed : entry_cap;
     const uint64_t mask = (uint64_t)out_align - 1u;
-    const uint64_t per = (n + SCAN_THREADS - 1u) / SCAN_THREADS, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-    uint64_t mine = 0;
-    for (uint64_t e = lo; e < hi; e++) mine += (w.size[e] + mask) & ~mask;
-    uint64_t v = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v += t;
-    }
-    if (lane == 63u) s_wave[wave] = v;
+    uint64_t lo, hi;
+    strip(n, SCAN_THREADS, tid, lo, hi);
+    uint64_t mine[1] = {0u}, base[1], total[1];
+    for (uint64_t e = lo; e < hi; e++) mine[0] += (w.size[e] + mask) & ~mask;
     if (tid == 0u) s_total = 0u;                                  // (no entries)
-    __syncthreads();
-    uint64_t base = v - mine;
-    for (uint32_t k = 0; k < wave; k++) base += s_wave[k];
+    block_scan<1, SCAN_THREADS>(mine, base, total, s_wave);
     for (uint64_t e = lo; e < hi; e++) {
         const uint64_t s = w.size[e];
-        entries[e].out_off = base;
-        if (e + 1u == n) s_total = base + s;                      // the end of the last slot
-        base += (s + mask) & ~mask;
+        entries[e].out_off = base[0];
+        if (e + 1u == n) s_total = base[0] + s;                   // the end of the last slot
+        base[0] += (s + mask) & ~mask;
     }
     __syncthreads();
     if (tid != 0u) return;

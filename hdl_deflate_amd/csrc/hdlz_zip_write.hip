@@ -8,7 +8,8 @@
 //                whose status is not HDLZ_OK (bits 0 .. 30) and rows whose length, end bit and pitch contradict each other (bits
 //                31 .. 61; a block of negative length counts among them) --, so that an entry's payload length and "does a block of
 //                mine fail" are each two loads.  The two look-backs run side by side, a wave each.
-// k_zipw_plan    ONE workgroup of 1024 threads, 64 entries each at most: the checks of step 1, c_e and the form, the scans of the record
+// k_zipw_plan    ONE workgroup of 1024 threads, 64 entries each at most (strip, block_scan: hdlz_plan.h): the checks of step 1
+//                (entry_check, shared with k_zipw64_plan), c_e and the form, the scans of the record
 //                sizes (local offsets, directory offsets, out_off, the tiles of the stored copy) -> the plan in the scratch; thread 0
 //                writes the end record and the result record.  An entry with a failed row walks its rows for the largest status:
 //                the one serial loop, on the failing path only.
@@ -30,8 +31,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdlz_device.h"
-#include "hdlz_compress_common.h"                        // the framing constants: HEADER_BITS, block_nbytes
+#include "hdlz_compress_common.h"                        // member_len
 #include "hdlz_frame.h"                                  // the tile's scan and look-back, the wave reductions, copy_to_aligned16
+#include "hdlz_plan.h"                                   // strip, block_scan, upper, rows_verdict
 
 namespace hdlz {
 namespace zipw {
@@ -44,36 +46,9 @@ constexpr uint64_t NO_ZIP64 = 0xFFFFFFFFull;                     // a size or of
 constexpr uint32_t PLAN_THREADS = 1024u, PLAN_WAVES = PLAN_THREADS / 64u;      // 65535 entries: 64 a thread
 constexpr uint32_t STORE_TILE = 65536u;                          // 16 stores of 16 bytes a thread
 constexpr uint32_t ROWS_MAX = 256u, ROWS_FEW = 16u, ROWS_MANY_MIN = 1u << 16;      // rows a workgroup of the gather takes: 16, or 256 from 65536 rows on (not measured: between the profile's two shapes)
-constexpr uint32_t COUNT_BITS = 31u;                             // nblocks < 2^31: two counts fit under the look-back word's state bits
-constexpr uint64_t COUNT_MASK = (1ull << COUNT_BITS) - 1u;
 // the summary at w.head
 enum { H_WRITE = 0, H_TILES = 1, H_FAILED = 2 };
 
-typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-typedef v4 __attribute__((aligned(1))) v4u;
-
-// |M_b| and the bytes of it that come from the row; 0: the row's three words contradict each other (hdlz_join.h)
-__device__ __forceinline__ uint32_t member_len(const ZipWriteArgs& a, uint64_t b, uint32_t& body) {
-    const uint32_t n = a.len[b];
-    const uint64_t E = a.end_bits[b];
-    body = 0u;
-    if (E < HEADER_BITS || block_nbytes(E) + 4u != (uint64_t)n || (uint64_t)n > a.pitch) return 0u;
-    const uint32_t nbytes = n - 4u;
-    const uint32_t p = (uint32_t)(8ull * nbytes - E) - 7u;       // pad bits behind the end-of-block code
-    body = nbytes - 2u;
-    return body + (p >= 3u ? 4u : 5u);
-}
-
-// the first index i of v[0 .. n) with v[i] > x (n: none) -- v ascending
-template <class T>
-__device__ __forceinline__ uint32_t upper_bound(const T* __restrict__ v, uint32_t n, uint64_t x) {
-    uint32_t lo = 0u, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((uint64_t)v[mid] > x) hi = mid; else lo = mid + 1u;
-    }
-    return lo;
-}
 
 // ---- (a) the prefixes over the rows
 __global__ __launch_bounds__(JT) void k_zipw_scan(ZipWriteArgs a) {
@@ -89,7 +64,7 @@ __global__ __launch_bounds__(JT) void k_zipw_scan(ZipWriteArgs a) {
         if (a.status[b] != HDLZ_OK) k = 1u;
         else {
             uint32_t body;
-            m = member_len(a, b, body);
+            m = member_len(a.len[b], a.end_bits[b], a.pitch, body);
             if (a.in_off[b + 1u] < a.in_off[b]) m = 0u;           // (a block of negative length: the copy of a stored entry's rows trusts these)
             if (m == 0u) k = 1u << 16;
         }
@@ -129,80 +104,65 @@ __device__ __forceinline__ uint8_t record_byte(const uint32_t (&w)[N], uint32_t 
     return (uint8_t)(x >> (8u * (i & 3u)));
 }
 
-// ---- (b) the plan: thread t takes the entries [per t, per (t + 1)), per = ceil(E / 1024)
+// the checks of step 1 for entry e of u bytes with a name of n bytes (but the classic format's size limit), and its form: stored with
+// c = u, or deflated -- the members and 03 00 -- where that is shorter
+__device__ __forceinline__ uint32_t entry_check(const ZipWriteArgs& a, uint64_t e, uint64_t u, uint64_t n, uint32_t& method, uint64_t& c) {
+    const uint64_t F0 = a.blk_first[e], F1 = a.blk_first[e + 1u];
+    uint32_t st = HDLZ_OK;
+    method = 0u; c = u;
+    if (F0 > F1 || F1 > a.nblocks) st = HDLZ_E_BAD_PARAM;
+    else if (F1 > F0) {
+        st = rows_verdict(a.w.cnt, a.status, F0, F1);
+        if (st == HDLZ_OK && a.in_off[F1] - a.in_off[F0] != u) st = HDLZ_E_BAD_PARAM;
+    }
+    if (st == HDLZ_OK && n > NAME_LEN_MAX) st = HDLZ_E_BAD_PARAM;
+    if (st == HDLZ_OK && F1 > F0) {
+        const uint64_t cd = a.w.pre[F1] - a.w.pre[F0] + 2u;
+        if (cd < u) { method = METHOD_DEFLATED; c = cd; }
+    }
+    return st;
+}
+
+// ---- (b) the plan: a strip of the entries a thread (hdlz_plan.h)
 __global__ __launch_bounds__(PLAN_THREADS) void k_zipw_plan(ZipWriteArgs a) {
-    __shared__ uint64_t s_wave[PLAN_WAVES][4];
+    __shared__ uint64_t s_wave[4][PLAN_WAVES];
     __shared__ uint32_t s_worst[PLAN_WAVES], s_first[PLAN_WAVES], s_nst[PLAN_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t E = (uint32_t)a.nentries;
     const uint64_t amask = (uint64_t)a.out_align - 1u;
-    const uint32_t per = (E + PLAN_THREADS - 1u) / PLAN_THREADS;        // at most 64
-    const uint32_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
-    uint64_t mine[4] = {0u, 0u, 0u, 0u};                          // local records, central records, output slots, tiles of the stored copy
+    uint64_t lo, hi;
+    strip(E, PLAN_THREADS, tid, lo, hi);                          // at most 64 entries
+    uint64_t mine[4] = {0u, 0u, 0u, 0u}, base[4], total[4];      // local records, central records, output slots, tiles of the stored copy
     uint32_t worst = HDLZ_OK, first = NONE, nst = 0u;
-    for (uint32_t e = lo; e < hi; e++) {
+    for (uint64_t e = lo; e < hi; e++) {
         const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e];
-        const uint64_t F0 = a.blk_first[e], F1 = a.blk_first[e + 1u];
-        uint32_t st = HDLZ_OK, method = 0u;
-        uint64_t c = u;
-        if (F0 > F1 || F1 > a.nblocks) st = HDLZ_E_BAD_PARAM;
-        else if (F1 > F0) {
-            const uint64_t k = a.w.cnt[F1] - a.w.cnt[F0];         // (both counts ascend: the halves subtract without a borrow)
-            if (k & COUNT_MASK) {
-                for (uint64_t b = F0; b < F1; b++) st = max(st, a.status[b]);
-            } else if (k >> COUNT_BITS) st = HDLZ_E_BAD_PARAM;
-            else if (a.in_off[F1] - a.in_off[F0] != u) st = HDLZ_E_BAD_PARAM;
-        }
-        if (st == HDLZ_OK && n > NAME_LEN_MAX) st = HDLZ_E_BAD_PARAM;
-        if (st == HDLZ_OK && u >= NO_ZIP64) st = HDLZ_E_OUT_CAPACITY;
-        if (st == HDLZ_OK && F1 > F0) {
-            const uint64_t cd = a.w.pre[F1] - a.w.pre[F0] + 2u;   // the members and 03 00
-            if (cd < u) { method = METHOD_DEFLATED; c = cd; }
-        }
+        uint32_t method;
+        uint64_t c;
+        uint32_t st = entry_check(a, e, u, n, method, c);
+        if (st == HDLZ_OK && u >= NO_ZIP64) { st = HDLZ_E_OUT_CAPACITY; method = 0u; c = u; }
         a.w.csize[e] = (uint32_t)c;
         a.w.form[e] = method | (st << 8);
         if (st == HDLZ_OK) {
             mine[0] += LOCREC + n + c; mine[1] += CDREC + n; mine[2] += (u + amask) & ~amask;
-            if (F0 == F1) mine[3] += (u + STORE_TILE - 1u) / STORE_TILE;
+            if (a.blk_first[e] == a.blk_first[e + 1u]) mine[3] += (u + STORE_TILE - 1u) / STORE_TILE;
             nst += method == 0u ? 1u : 0u;
         } else {
             worst = max(worst, st);
-            first = min(first, e);
+            first = min(first, (uint32_t)e);
         }
-    }
-    uint64_t v[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        v[q] = mine[q];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(v[q], o, 64);
-            if (lane >= (uint32_t)o) v[q] += t;
-        }
-        if (lane == 63u) s_wave[wave][q] = v[q];
     }
     {
         const uint32_t rw = wave_max(worst), rf = wave_min(first), rn = wave_add(nst);
         if (lane == 0u) { s_worst[wave] = rw; s_first[wave] = rf; s_nst[wave] = rn; }
     }
-    __syncthreads();
-    uint64_t base[4], total[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        base[q] = v[q] - mine[q];
-        total[q] = 0u;
-        for (uint32_t k = 0; k < PLAN_WAVES; k++) {
-            if (k < wave) base[q] += s_wave[k][q];
-            total[q] += s_wave[k][q];
-        }
-    }
+    block_scan<4, PLAN_THREADS>(mine, base, total, s_wave);      // (its barriers stand behind the stores of s_worst, s_first and s_nst, too)
     worst = HDLZ_OK; first = NONE; nst = 0u;
     for (uint32_t k = 0; k < PLAN_WAVES; k++) { worst = max(worst, s_worst[k]); first = min(first, s_first[k]); nst += s_nst[k]; }
     const bool failed = worst != HDLZ_OK;
     const uint64_t cd_off = total[0], cd_size = total[1], file_len = cd_off + cd_size + EOCD;
     const bool limit = cd_off >= NO_ZIP64 || file_len > NO_ZIP64;       // (the local offsets ascend to cd_off)
     const bool write = !failed && !limit && file_len <= a.cap;
-    for (uint32_t e = lo; e < hi; e++) {
+    for (uint64_t e = lo; e < hi; e++) {
         const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e];
         const bool none = a.blk_first[e] == a.blk_first[e + 1u];
         a.w.pay[e] = base[0] + LOCREC + n; a.w.cdrec[e] = cd_off + base[1]; a.w.out_off[e] = base[2]; a.w.tile0[e] = (uint32_t)base[3];
@@ -236,73 +196,30 @@ __device__ __forceinline__ uint32_t central_extra(uint64_t u, uint64_t c, uint64
     return k ? 4u + 8u * k : 0u;
 }
 
-// the exclusive prefix of every thread's v[0 .. Q) over the workgroup of the plan -> base; total: the sums.  (s: PLAN_WAVES x Q words)
-template <int Q>
-__device__ __forceinline__ void plan_scan(const uint64_t (&mine)[Q], uint64_t (&base)[Q], uint64_t (&total)[Q], uint64_t (*s)[4], uint32_t lane, uint32_t wave) {
-    uint64_t v[Q];
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        v[q] = mine[q];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(v[q], o, 64);
-            if (lane >= (uint32_t)o) v[q] += t;
-        }
-    }
-    __syncthreads();                                              // (the scan in front of this one has been read)
-    if (lane == 63u) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) s[wave][q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        base[q] = v[q] - mine[q];
-        total[q] = 0u;
-        for (uint32_t k = 0; k < PLAN_WAVES; k++) {
-            if (k < wave) base[q] += s[k][q];
-            total[q] += s[k][q];
-        }
-    }
-}
-
-// ONE workgroup, thread t the entries [per t, per (t + 1)), per = ceil(E / 1024) without a limit.  A local record's size hangs on u_e and
+// ONE workgroup, a strip of the entries a thread, E without a limit.  A local record's size hangs on u_e and
 // c_e alone, a central record's on the local offset L_e too: so two scans one behind the other -- the local records (with the slots and
 // the tiles), then, L_e known, the central records -- and a coalesced sweep that makes the central offsets, run-relative until then, absolute.
 __global__ __launch_bounds__(PLAN_THREADS) void k_zipw64_plan(ZipWriteArgs a) {
-    __shared__ uint64_t s_wave[PLAN_WAVES][4];
+    __shared__ uint64_t s_wave[4][PLAN_WAVES];
     __shared__ uint32_t s_worst[PLAN_WAVES], s_first[PLAN_WAVES];
     __shared__ uint64_t s_cbase[PLAN_THREADS];                    // where each thread's run of central records starts
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t E = a.nentries, from = a.zip64_from;
     const uint64_t amask = (uint64_t)a.out_align - 1u;
-    const uint64_t per = (E + PLAN_THREADS - 1u) / PLAN_THREADS;
-    const uint64_t lo = tid * per < E ? tid * per : E, hi = lo + per < E ? lo + per : E;
+    uint64_t lo, hi;
+    const uint64_t per = strip(E, PLAN_THREADS, tid, lo, hi);
     uint64_t mine[4] = {0u, 0u, 0u, 0u};                          // local records, entries stored, output slots, tiles of the stored copy
     uint32_t worst = HDLZ_OK, first = NONE;
     for (uint64_t e = lo; e < hi; e++) {
         const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], n = a.name_off[e + 1u] - a.name_off[e];
-        const uint64_t F0 = a.blk_first[e], F1 = a.blk_first[e + 1u];
-        uint32_t st = HDLZ_OK, method = 0u;
-        uint64_t c = u;
-        if (F0 > F1 || F1 > a.nblocks) st = HDLZ_E_BAD_PARAM;
-        else if (F1 > F0) {
-            const uint64_t k = a.w.cnt[F1] - a.w.cnt[F0];
-            if (k & COUNT_MASK) {
-                for (uint64_t b = F0; b < F1; b++) st = max(st, a.status[b]);
-            } else if (k >> COUNT_BITS) st = HDLZ_E_BAD_PARAM;
-            else if (a.in_off[F1] - a.in_off[F0] != u) st = HDLZ_E_BAD_PARAM;
-        }
-        if (st == HDLZ_OK && n > NAME_LEN_MAX) st = HDLZ_E_BAD_PARAM;
-        if (st == HDLZ_OK && F1 > F0) {
-            const uint64_t cd = a.w.pre[F1] - a.w.pre[F0] + 2u;   // the members and 03 00
-            if (cd < u) { method = METHOD_DEFLATED; c = cd; }
-        }
+        uint32_t method;
+        uint64_t c;
+        const uint32_t st = entry_check(a, e, u, n, method, c);
         a.w.csize64[e] = c;
         a.w.form[e] = method | (st << 8);
         if (st == HDLZ_OK) {
             mine[0] += LOCREC + n + local_extra(u, c, from) + c; mine[1] += method == 0u ? 1u : 0u; mine[2] += (u + amask) & ~amask;
-            if (F0 == F1) mine[3] += (u + STORE_TILE - 1u) / STORE_TILE;
+            if (a.blk_first[e] == a.blk_first[e + 1u]) mine[3] += (u + STORE_TILE - 1u) / STORE_TILE;
         } else {
             worst = max(worst, st);
             first = min(first, (uint32_t)e);
@@ -313,7 +230,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_zipw64_plan(ZipWriteArgs a) {
         if (lane == 0u) { s_worst[wave] = rw; s_first[wave] = rf; }
     }
     uint64_t base[4], total[4];
-    plan_scan(mine, base, total, s_wave, lane, wave);             // (its barriers stand behind the stores of s_worst and s_first, too)
+    block_scan<4, PLAN_THREADS>(mine, base, total, s_wave);      // (its barriers stand behind the stores of s_worst and s_first, too)
     worst = HDLZ_OK; first = NONE;
     for (uint32_t k = 0; k < PLAN_WAVES; k++) { worst = max(worst, s_worst[k]); first = min(first, s_first[k]); }
     const bool failed = worst != HDLZ_OK;
@@ -332,7 +249,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_zipw64_plan(ZipWriteArgs a) {
             if (none) base[3] += (u + STORE_TILE - 1u) / STORE_TILE;
         }
     }
-    plan_scan(cmine, cbase, ctotal, s_wave, lane, wave);
+    block_scan<1, PLAN_THREADS>(cmine, cbase, ctotal, s_wave);
     const uint64_t cd_size = ctotal[0];
     // pass 2 left every central offset relative to its thread's run: the runs' starts go through LDS and the third pass is one
     // coalesced sweep -- a load, an add and a store an entry, independent of each other, where a third walk of the runs would cost
@@ -457,7 +374,7 @@ __global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t ro
             const uint64_t b = b0 + lane;
             uint32_t kind = ROW_SKIP;
             if (lane < per && b < a.nblocks) {
-                if (ub == ub0 + 64u) ub = upper_bound(a.blk_first, E + 1u, b);
+                if (ub == ub0 + 64u) ub = upper(a.blk_first, E + 1u, b);
                 if (ub >= 1u && ub <= E) {                        // (else: a row that no entry owns)
                     const uint32_t e = ub - 1u;
                     const uint64_t F0 = a.blk_first[e], skip = a.in_off[b] - a.in_off[F0];      // skip: the entry's bytes in front of this block
@@ -467,7 +384,7 @@ __global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t ro
                         s_len[w0 + lane] = (uint32_t)(a.in_off[b + 1u] - a.in_off[b]); s_m[w0 + lane] = 0u;
                     } else {
                         uint32_t bl;
-                        const uint32_t m = member_len(a, b, bl);
+                        const uint32_t m = member_len(a.len[b], a.end_bits[b], a.pitch, bl);
                         kind = b + 1u == a.blk_first[ub] ? ROW_LAST_MEMBER : ROW_MEMBER;
                         s_dst[w0 + lane] = a.w.pay[e] + (a.w.pre[b] - a.w.pre[F0]); s_src[w0 + lane] = b * a.pitch + 2u;
                         s_len[w0 + lane] = bl; s_m[w0 + lane] = m;
@@ -518,7 +435,7 @@ __global__ __launch_bounds__(256) void k_zipw_gather(ZipWriteArgs a, uint32_t ro
         __shared__ uint32_t s_e;
         const uint64_t ntiles = a.w.head[H_TILES];                // (0 unless the file is written)
         for (uint64_t t = blockIdx.x - row_groups; t < ntiles; t += tile_groups) {
-            if (tid == 0u) s_e = upper_bound(a.w.tile0, E + 1u, t) - 1u;      // tile0[e] <= t < tile0[e + 1]
+            if (tid == 0u) s_e = upper(a.w.tile0, E + 1u, t) - 1u;            // tile0[e] <= t < tile0[e + 1]
             __syncthreads();
             const uint32_t e = s_e;
             const uint64_t u = a.ent_off[e + 1u] - a.ent_off[e], at = (t - a.w.tile0[e]) * STORE_TILE;

@@ -29,11 +29,13 @@ def stage(files):
     return d, torch.from_numpy(np.cumsum(lens) - lens).cuda(), torch.from_numpy(lens).cuda()
 
 
-def run_decode(engine, d, pi, first, count, out_fill=0):
-    """ONE hdlz_png_decode_ws call over images [first, first + count) -> (out, status, record)"""
+def run_decode(engine, d, pi, first, count, out_fill=0, flags=None):
+    """ONE hdlz_png_decode_ws call over images [first, first + count) -> (out, status, record).  flags: default, the index's expand"""
     import torch
     from hdl_deflate_amd import _lib
     L, h = engine.lib, pi.host
+    if flags is None:
+        flags = _lib.PNG_EXPAND if pi.expand else _lib.PNG_RAW
     last = first + count - 1
     ok = int(h["status"][last] == 0)
     zb = int(h["z_off"][last] - h["z_off"][first]) + P.r16(int(h["zlen"][last]) + 8) * ok
@@ -44,8 +46,7 @@ def run_decode(engine, d, pi, first, count, out_fill=0):
     status = torch.full((count,), 77, dtype=torch.int32, device="cuda")
     work = torch.empty(L.hdlz_png_decode_work_bytes(count, idat, zb, rb), dtype=torch.uint8, device="cuda")
     rec = engine._record("hdlz_png_decode_ws", _lib.PngDecodeResult, (work, work.data_ptr(), work.numel()), d.data_ptr(), d.numel(),
-                         pi.images.data_ptr(), first, count, _lib.PNG_EXPAND if pi.expand else _lib.PNG_RAW, idat, zb, rb,
-                         out.data_ptr() if total else None, total, status.data_ptr())
+                         pi.images.data_ptr(), first, count, flags, idat, zb, rb, out.data_ptr() if total else None, total, status.data_ptr())
     return out, status, rec
 
 
@@ -309,6 +310,73 @@ def test_a_batch_of_200_mixed_small_images(engine):
         assert rec.first_bad == (bad[0] if bad else 2 ** 64 - 1) and rec.status == (expect[first + bad[0]][0] if bad else P.OK)
         out2, status2 = engine.decode_png(d, pi, first, count)
         check_slots(("routed range", first, count), pi, first, count, expect, out2, status2)
+
+
+def _tiny_batch(n, flags):
+    """n images of 1 .. 5 x 1 .. 5 pixels: every pair of P.PAIRS in turn, a filter a row at random, every eleventh image interlaced; a
+    damaged file at every 97th image, at 191 and 192 and at the last -> (files, png_adam7_ref's index at out_align 64, its decode of each)"""
+    import png_adam7_ref as A
+    rng = np.random.default_rng(97)
+    damaged = [c for c in _damaged() if c[2] != P.OK and not c[0].startswith("interlace")]      # (under ADAM7 interlace 1 is no damage)
+    files = []
+    for k in range(n):
+        if k % 97 == 50 or k in (191, 192, n - 1):
+            files.append(damaged[(k // 97 + k) % len(damaged)][1])
+            continue
+        colour, depth = P.PAIRS[k % len(P.PAIRS)]
+        w, h = int(rng.integers(1, 6)), int(rng.integers(1, 6))
+        kw = dict(seed=k, level=1, trns=bytes([k & 255, 7]) if colour == 3 and k % 2 else None)
+        if k % 11 == 7:
+            files.append(A.make_adam7(w, h, colour, depth, filters=[int(x) for x in rng.integers(0, 5, A.total_rows(w, h))], **kw))
+        else:
+            files.append(P.make_png(w, h, colour, depth, filters=[int(x) for x in rng.integers(0, 5, h)], idat=None if k % 3 else 3, **kw))
+    ix = A.index(files, flags, 64)
+    return files, ix, [A.decode(f, rec, flags) for f, rec in zip(files, ix["images"])]
+
+
+def test_a_batch_of_2051_tiny_images_three_a_thread_of_the_planners(engine):
+    """2051 images: k_png_offsets and k_png_plan take them three a thread (1024 threads), so a thread's strip holds images of several
+    kinds, eleven waves have work, wave 10 a partial strip and the threads behind it none; failed images on both sides of a wave
+    seam (191 | 192 at three a thread), in many waves and at the very end.  Records and totals for out_align 64 and 1, every slot and
+    status, first_bad, sub-ranges that start and end inside strips, and an index call with room for 1500 records"""
+    import torch
+    import png_adam7_ref as A
+    from hdl_deflate_amd import _lib
+    n, flags = 2051, P.EXPAND | A.ADAM7
+    files, ix, expect = _tiny_batch(n, flags)
+    bad = [k for k, (s, _) in enumerate(expect) if s != P.OK]
+    assert {191, 192, n - 1} <= set(bad) and len(bad) >= 24 and sum(r["interlace"] for r in ix["images"]) > 150
+    assert {r["colour"] * 100 + r["depth"] for r in ix["images"] if r["status"] == P.OK} == {c * 100 + d for c, d in P.PAIRS}
+    d, off, ln = stage(files)
+    for align in (64, 1):
+        pi = engine.png_index(d, off, ln, out_align=align, expand=True, interlaced=True)
+        want = ix if align == 64 else A.index(files, flags, align)
+        names = list(P.FIELDS)
+        got = np.stack([pi.host[f].astype(np.int64) for f in names], 1)
+        ref = np.array([[rec[f] for f in names] for rec in want["images"]], np.int64)
+        rows = np.nonzero((got != ref).any(1))[0]
+        assert rows.size == 0, (align, int(rows[0]), got[rows[0]].tolist(), ref[rows[0]].tolist())
+        assert (pi.host["reserved"] == 0).all()
+        r = pi.record
+        assert (r.nimages, r.total_z, r.total_raw, r.total_out, r.status, r.reserved) == \
+            (n, want["total_z"], want["total_raw"], want["total_out"], P.OK, 0), align
+    pi = engine.png_index(d, off, ln, out_align=64, expand=True, interlaced=True)
+    out, status, rec = run_decode(engine, d, pi, 0, n, flags=flags)
+    check_slots("one call", pi, 0, n, expect, out, status)
+    assert (rec.status, rec.first_bad, rec.out_len, rec.reserved) == (expect[bad[0]][0], bad[0], 0, 0)
+    for first, count in ((3, 2048), (1500, 551), (2050, 1)):
+        out, status, rec = run_decode(engine, d, pi, first, count, out_fill=first & 255, flags=flags)
+        check_slots(("range", first, count), pi, first, count, expect, out, status)
+        fb = [k for k in range(count) if expect[first + k][0] != P.OK]
+        assert rec.first_bad == fb[0] and rec.status == expect[first + fb[0]][0], (first, count)
+    # room for 1500 records: those are written, no word behind them, and the totals are those of all 2051
+    cap, nrec = 1500, pi.images.shape[1]
+    images = torch.full((n, nrec), -1, dtype=torch.int64, device="cuda")
+    work = torch.empty(engine.lib.hdlz_png_index_work_bytes(n, cap), dtype=torch.uint8, device="cuda")
+    r = engine._record("hdlz_png_index_ws", _lib.PngIndexResult, (work, work.data_ptr(), work.numel()), d.data_ptr(), d.numel(), off.data_ptr(),
+                       ln.data_ptr(), n, flags, 64, cap, images.data_ptr())
+    assert (r.nimages, r.total_z, r.total_raw, r.total_out, r.status) == (n, ix["total_z"], ix["total_raw"], ix["total_out"], P.E_OUT_CAPACITY)
+    assert torch.equal(images[:cap], pi.images[:cap]) and bool((images[cap:] == -1).all())
 
 
 def test_palette_images(engine):

@@ -120,21 +120,22 @@ def test_the_filter_waves_stride_when_total_rows_understated_the_rows(engine):
     assert int(p.row_filter[0]) == W.expected(arrays[0]).filters[0]
 
 
-def _mixed_batch(n, seed):
-    """n small images of every pair, every tenth one failing in one of three ways -> (flat pixels, specs, [pixels or the status])"""
+def _mixed_batch(n, seed, widths=(1, 40), heights=(1, 20), failing=()):
+    """n small images of every pair, widths and heights drawn from [lo, hi), every tenth one -- and those of `failing` -- failing in one
+    of three ways -> (flat pixels, specs, [pixels or the status])"""
     from hdl_deflate_amd.png import SPEC_DTYPE
     rng = np.random.default_rng(seed)
     sp = np.zeros(n, SPEC_DTYPE)
     arrays, blobs, at = [], [], 0
     for k in range(n):
         colour, depth = W.PAIRS[int(rng.integers(0, 8))]
-        w, h = int(rng.integers(1, 40)), int(rng.integers(1, 20))
+        w, h = int(rng.integers(*widths)), int(rng.integers(*heights))
         a = pixels(colour, depth, w, h, seed + k)
         sp[k] = (at, w, h, depth, colour, 0)
         blobs.append(a.tobytes())
         at += len(blobs[-1])
         arrays.append(a)
-        if k % 10 == 3:
+        if k % 10 == 3 or k in failing:
             bad = (k // 10) % 3
             if bad == 0:
                 sp[k]["width"] = 0
@@ -166,6 +167,44 @@ def test_a_batch_of_mixed_images_some_of_them_failing(engine):
     with pytest.raises(HdlzStatusError) as e:
         engine.encode_png(flat, sp)
     assert e.value.first_bad == 3
+
+
+def test_a_batch_of_2051_tiny_images_three_a_thread_of_the_planners(engine):
+    """2051 images of 1 .. 5 x 1 .. 5 pixels in blocks of 32 bytes: k_pngw_plan and k_pngw_layout take the images three a thread (1024
+    threads), k_pngw_scan the blocks -- more than 2048, asserted -- at least three a thread; failing specs every tenth image, on both
+    sides of a wave seam (191 | 192 at three a thread) and at the very end; images under 5 stream bytes, which are stored, among them.
+    (Of 2051 such images about 70 are under 5 bytes and a tenth fail, so it is the blocks that are counted, not the images of at
+    least 5 bytes: the block size makes most images bring two or more.)"""
+    from hdl_deflate_amd.chain import plan_blocks
+    n, block = 2051, 32
+    flat, sp, arrays = _mixed_batch(n, 70, widths=(1, 6), heights=(1, 6), failing=(191, 192, 2050))
+    failed = np.array([isinstance(a, int) for a in arrays])
+    raw_len = [0 if isinstance(a, int) else a.nbytes + a.shape[0] for a in arrays]      # the scanlines and a filter byte a row
+    assert sum(len(plan_blocks(r, block)) for r in raw_len if r >= 5) > 2048 and sum(1 for r in raw_len if 0 < r < 5) >= 20
+    files, index = engine.encode_png(flat, sp, block=block, check=False)
+    host = files.cpu().numpy().tobytes()
+    off, ln = index.host["file_off"].astype(np.int64), index.host["file_len"].astype(np.int64)
+    assert (off == np.cumsum(ln) - ln).all() and (ln[failed] == 0).all() and len(host) == int(ln.sum())
+    assert index.host["status"].tolist() == [a if isinstance(a, int) else W.OK for a in arrays]
+    near = {k + j for k in np.nonzero(failed)[0] for j in (-1, 1)}
+    for k, a in enumerate(arrays):
+        if isinstance(a, int):
+            continue
+        f = host[int(off[k]):int(off[k]) + int(ln[k])]
+        if k % 8 == 0 or k in near:
+            assert f == W.expected(a, block=block).file, k
+        rec = P.index([f])["images"][0]
+        st, back = P.decode(f, rec)
+        assert (st, rec["used"]) == (P.OK, len(f)) and back == a.tobytes(), (k, st)
+    rec = index.write_record
+    assert (rec.status, rec.first_bad, rec.total_len) == (max(a for a in arrays if isinstance(a, int)), 3, len(host))
+    # the records are the index of the written files, byte for byte; of a refused image -- an empty file -- all but the reason
+    again = engine.png_index(files, torch.from_numpy(off).cuda(), torch.from_numpy(ln).cuda(), out_align=64, expand=True)
+    theirs = again.host.copy()
+    assert (theirs["status"][failed] != W.OK).all()
+    theirs["status"][failed] = index.host["status"][failed]
+    assert theirs.tobytes() == index.host.tobytes(), [f for f in theirs.dtype.names if (theirs[f] != index.host[f]).any()]
+    assert (again.record.total_z, again.record.total_raw, again.record.total_out) == (index.record.total_z, index.record.total_raw, index.record.total_out)
 
 
 def test_the_sizing_call_and_a_capacity_one_byte_short_write_nothing(engine):

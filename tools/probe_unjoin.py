@@ -4,7 +4,9 @@
   codeobj --parent OBJDIR   (no GPU) the code-object metadata of every kernel in hdlz_inflate_tok / _grp / _dyn / hdlz_checksum (or of
                             --sources A,B,...) of a build of the parent commit (its csrc/_obj) beside this build's: the existing
                             instantiations must be the same, the member twins are listed next to them.  Each kernel's instructions
-                            (llvm-objdump -d) are compared too: identical / same opcodes, registers renamed / differs.  With
+                            (llvm-objdump -d) are compared too: identical / same opcodes, registers renamed / identical but for
+                            the offsets of scalar loads, for the pc-relative distance to a constant table, or for the exchanged
+                            sources of commutative instructions (each named as such) / differs.  With
                             hdlz_join and hdlz_bgzf_stored among the sources, the kernels of MOVED are listed against the parent's
                             kernels they took the place of; a pair that differs there is settled by its timing and not counted.
   time                      (a) hdlz_inflate_checked of the per-block rows as a ragged archive, forced to the mapping (b) chooses,
@@ -80,6 +82,21 @@ def code_tag(old, new):
     args = lambda seq: [re.sub(r"^(s_load_dword\w* .*), 0x[0-9a-f]+$", r"\1, #", i) for i in seq]
     if args(old) == args(new):
         return "identical but for the offsets of scalar loads: the argument record changed (%d instructions)" % len(new)
+    if len(old) == len(new):
+        # a table's address is pc-relative (s_getpc_b64, then s_add_u32 with the distance): it moves with the size of the kernels that
+        # stand between; and a commutative scalar op may come out with its two sources exchanged
+        pcrel = lambda k: k > 0 and old[k - 1].startswith("s_getpc_b64") and old[k].startswith("s_add_u32") and new[k].startswith("s_add_u32")
+        def swapped(a, b):
+            m, n = re.match(r"^(s_and_b64|s_or_b64|v_lshl_add_u64) (\S+), (\S+), (.*)$", a), re.match(r"^(s_and_b64|s_or_b64|v_lshl_add_u64) (\S+), (\S+), (.*)$", b)
+            if not m or not n or m.group(1, 2) != n.group(1, 2):
+                return False
+            x, y = [m.group(3)] + m.group(4).split(", "), [n.group(3)] + n.group(4).split(", ")
+            return sorted(x) == sorted(y)
+        bad = [k for k in range(len(new)) if old[k] != new[k]]
+        if all(pcrel(k) for k in bad):
+            return "identical but for the pc-relative distance to a constant table (%d instructions)" % len(new)
+        if all(pcrel(k) or swapped(old[k], new[k]) for k in bad):
+            return "identical but for the sources of %d commutative instructions exchanged (%d instructions)" % (sum(not pcrel(k) for k in bad), len(new))
     return "differs (%d -> %d instructions)" % (len(old), len(new))
 
 
