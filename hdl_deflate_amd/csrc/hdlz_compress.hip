@@ -91,6 +91,7 @@ template <int NCH, bool FULLWIN, bool ONE_TILE, bool ENDBITS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH>(), waves_eu<NCH>()))) void k_compress(CompressArgs a) {
     constexpr bool HASH = wide_hash<NCH>();         // windows > 32: the window-independent finder
     constexpr bool BITS = ONE_TILE && NCH == 1 && search_bits();     // bit-sliced search whose mismatch words are the extension (WaveLdsBits)
+    constexpr bool LIT_EMIT = BITS && literal_emit();                // a match-free tile emits its literals' codes itself (literal_codes)
     __shared__ typename std::conditional<HASH, WaveLdsNoOut, typename std::conditional<BITS, WaveLdsBits, WaveLds>::type>::type lds;
     __shared__ typename std::conditional<HASH, HashLds<NCH>, uint32_t>::type hl;
     // the bit buffer of a tile: HASH kernels keep it in the finder's transposition buffer, which is dead once best[] is in registers
@@ -194,8 +195,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
         uint32_t skip_in = 0;       // positions at the tile start covered by the previous tile's last match
         // per-lane Adler partials: ad_a = sum x (plain: reduced once per GiB and at the end), ad_w = sum (N-p) x mod 65521 with
         // ONE modulo per tile -- the weight N - p_run is carried mod 65521 from tile to tile instead of being reduced every time
+        // (ONE_TILE: N <= 2048 -- the weight is below 65521 as it is and the one tile's terms are summed plainly, see adler_finish)
+        constexpr bool ADLER_PLAIN = ONE_TILE && adler_plain_one_tile();
         uint32_t ad_a = 0, ad_w = 0;
-        uint32_t wm = (n - min(lane * (uint32_t)RUN, n)) % ADLER_MOD;
+        uint32_t wm = n - min(lane * (uint32_t)RUN, n);
+        if constexpr (!ADLER_PLAIN) wm %= ADLER_MOD;
 
         for (uint32_t t0 = 0; t0 < n; t0 += TILE) {       // (ONE_TILE: one iteration; left as a loop -- hipcc spills when it is peeled)
             // -------------------------------------------------------------- 1. stage the tile
@@ -227,7 +231,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
             const uint32_t p_run = t0 + lane * RUN;                   // first position of this run
             const uint32_t nrem = n - min(p_run, n);                  // positions of the block from p_run on
             uint32_t best[RUN], tok[RUN], code[RUN];
-            [[maybe_unused]] uint32_t oww[12];                    // BITS: the own bytes, in registers from here to the extension
+            [[maybe_unused]] uint32_t oww[12];                    // BITS: the own bytes, in registers from here to the extension (a match-free tile: to its codes)
             // BITS: false = no position of the tile has a match candidate (match_search_bits): every token is a literal, whatever the
             // extension, the parse and the skip chain would compute -- they do not run (wave-uniform; every other kernel: constant true)
             [[maybe_unused]] bool any = true;
@@ -255,10 +259,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 any = match_search_bits<true>(oww[0], oww[1], oww[2], oww[3], oww[4], oww[5], oww[6], oww[7], planes, lds.neq + lane, end_cap_word((int32_t)(n - t0) - 2, lane * (uint32_t)RUN));
 #endif
             else match_search<NCH, ONE_TILE && NCH == 1>(lds.in, run_dw, best);                    // 2. R3/R4 (a one-tile block: candidate keys by DPP)
+            uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (BITS: still in registers; else reloaded: see match_search)
             {
                 TT(2);
                 HDLZ_MARK("adler");
-                uint32_t ow[12];                                      // own 32 bytes + 16 look-ahead (BITS: still in registers; else reloaded: see match_search)
                 if constexpr (BITS) {
 #pragma unroll
                     for (int k = 0; k < 12; k++) ow[k] = oww[k];
@@ -268,18 +272,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                     adler_run(ow, sa, sc);
                     // sum (N - p) x_p over the run = (N - p_run) * sa - sc ; bytes at p >= N are zero (then the weight does not matter);
                     // wm * sa <= 65520 * 8160, sc <= 252960 < 4 * 65521: the sum stays below 2^31
+                    if constexpr (ADLER_PLAIN) {
+                        // the one tile: wm = N - p_run <= 2048, and sc <= wm * sa (a byte at p >= N is zero): no wrap, no modulo, no carried weight
+                        ad_a = sa;
+                        ad_w = __umul24(wm, sa) - sc;
+                        asm volatile("" : "+v"(ad_a), "+v"(ad_w));                        // computed HERE, while the bytes are in registers
+                    } else {
                     ad_a += sa;
                     ad_w = (ad_w + __umul24(wm, sa) + (4u * ADLER_MOD - sc)) % ADLER_MOD;
                     wm = wm >= (uint32_t)(TILE % ADLER_MOD) ? wm - (uint32_t)(TILE % ADLER_MOD) : wm + (ADLER_MOD - (uint32_t)(TILE % ADLER_MOD));
                     if (((t0 >> 11) & 0x3FFFFu) == 0x3FFFFu) ad_a %= ADLER_MOD;      // (every 2^18 tiles: ad_a grows by <= 8160 per tile)
                     asm volatile("" : "+v"(ad_a), "+v"(ad_w), "+v"(wm));              // computed HERE, while the bytes are in registers
+                    }
                 }
                 TT(3);
                 if constexpr (!HASH) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(HDLZ_HP_EXTEND);
+            }
+            uint32_t lane_bits;
+            // ONE wave-uniform branch around everything a match-free tile does differently: with the two arms apart the own bytes are live
+            // to the codes in the literal arm only, and no token word exists there (as a value live across both arms: spills, see
+            // search_result_bytes)
+            if (LIT_EMIT && !any) {
+                // 3..5 of a MATCH-FREE tile: no extension, no parse, no chain -- entry skip 0 in every lane.  Nothing here reads NEQ, so
+                // nothing waits for the search's row stores: they must have been performed before the LUT's LDS-DMA and the zeroing of
+                // the bit buffer reuse that memory (normal path: implied by the reads)
+                HDLZ_MARK("litcodes");
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wave_lds_order();
+                request_lut();
+                zero_bit_buffer(lout, lane, carry_word);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the LUT has landed
+                wave_lds_order();
+                if constexpr (LIT_EMIT) lane_bits = literal_codes(lut8, oww, code);                // 5. R6/R7, one literal per position
+            } else {
                 HDLZ_MARK("extend");
                 if constexpr (BITS) {
-                    if (any) {
+                    if (LIT_EMIT || any) {
 #if HDLZ_EXT_SDWA
                         uint32_t Q[8];                            // the result bytes, four to a register: read in place (sub-dword operands)
                         search_result_packed(planes, Q);
@@ -290,43 +319,41 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                         wave_lds_order();                         // (every lane's rows are written)
                         make_tokens_bits<FULLWIN>(lds.neq, lane, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), tok, (int32_t)(n - t0));   // 3. R5, from NEQ
 #endif
-                    } else {
+                    } else {                                      // (-DHDLZ_LITERAL_TOKENS: a match-free tile as literal tokens through the common code)
                         literal_tokens(ow, tok);
-                        // nothing here reads NEQ, so nothing waits for the search's row stores: they must have been performed before
-                        // the LUT's LDS-DMA and the zeroing of the bit buffer reuse that memory (normal path: implied by the reads)
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the row stores: see the literal arm above)
                         wave_lds_order();
                     }
                 } else
                 make_tokens<NCH, FULLWIN, true>(lds.in, HALO + lane * RUN, ow, best, cw4, kmax, 4u * min(p_run, 32u * NCH), nrem, tok, (int32_t)(n - t0));   // 3. R5
+                pin(tok);
+                PHASE_FENCE();
+                TT(4);
+                if constexpr (BITS) {                             // NEQ is dead (every read has returned: tok is pinned): the LUT and the bit buffer
+                    HDLZ_MARK("zero");                            // take its place, ordered before codes / the scatter by the wait and the fences below
+                    wave_lds_order();
+                    request_lut();
+                    zero_bit_buffer(lout, lane, carry_word);
+                }
+                if constexpr (HASH) __builtin_amdgcn_s_setprio(HDLZ_HP_REST);
+                HDLZ_MARK("parse");
+                uint32_t myskip = 0;                              // (a match-free tile as literal tokens: every run function is "-> 0", every entry skip 0)
+                if (!BITS || LIT_EMIT || any) {
+                    const uint64_t P = run_transfer(tok);                                          // 4. greedy parse
+                    TT(5);
+                    HDLZ_MARK("chain");
+                    myskip = chain_skips(P, lane, skip_in);       // (skip_in: carried into the next tile)
+                }
+                pin(tok); asm volatile("" : "+v"(myskip));
+                PHASE_FENCE();
+                TT(6);
+                HDLZ_MARK("codes");
+                if constexpr (BITS) {                             // the LUT has landed (its latency ran under zero, parse and chain)
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    wave_lds_order();
+                }
+                lane_bits = token_codes<NCH, false>(lut8, tok, myskip, 0u, code);                  // 5. R6/R7
             }
-            pin(tok);
-            PHASE_FENCE();
-            TT(4);
-            if constexpr (BITS) {                                 // NEQ is dead (every read has returned: tok is pinned): the LUT and the bit buffer
-                HDLZ_MARK("zero");                                // take its place, ordered before codes / the scatter by the wait and the fences below
-                wave_lds_order();
-                request_lut();
-                zero_bit_buffer(lout, lane, carry_word);
-            }
-            if constexpr (HASH) __builtin_amdgcn_s_setprio(HDLZ_HP_REST);
-            HDLZ_MARK("parse");
-            uint32_t myskip = 0;                                  // (a match-free tile: every run function is "-> 0", every entry skip 0)
-            if (!BITS || any) {
-                const uint64_t P = run_transfer(tok);                                              // 4. greedy parse
-                TT(5);
-                HDLZ_MARK("chain");
-                myskip = chain_skips(P, lane, skip_in);           // (skip_in: carried into the next tile)
-            }
-            pin(tok); asm volatile("" : "+v"(myskip));
-            PHASE_FENCE();
-            TT(6);
-            HDLZ_MARK("codes");
-            if constexpr (BITS) {                                 // the LUT has landed (its latency ran under zero, parse and chain)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                wave_lds_order();
-            }
-            uint32_t lane_bits = token_codes<NCH, false>(lut8, tok, myskip, 0u, code);             // 5. R6/R7
             pin(code);
             PHASE_FENCE();
             TT(7);
@@ -362,7 +389,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(waves_eu<NCH
                 if (lane < 4u) wipe_behind(lout, end_bits, lane);
                 // R8: EOB, zero pad to a byte, Adler-32
                 uint32_t s1, s2;
-                adler_finish(wave_sum(ad_a % ADLER_MOD), wave_sum(ad_w), n, s1, s2);
+                if constexpr (ADLER_PLAIN) adler_finish(wave_sum(ad_a), wave_sum(ad_w), n, s1, s2);      // (the one reduction)
+                else adler_finish(wave_sum(ad_a % ADLER_MOD), wave_sum(ad_w), n, s1, s2);
                 const uint32_t nbytes = block_nbytes(end_bits);
                 wave_lds_order();
                 if (lane == 0) put_adler(out8, nbytes, s1, s2);

@@ -365,8 +365,9 @@ __device__ __forceinline__ void transpose4x4_bytes(uint32_t r0, uint32_t r1, uin
 //           v_readfirstlane, one compare + ballot) and its 31 v_alignbit + 32 v_bitop3 jumped over; P_b is fetched inside the live
 //           branch.  A second pass over the distances does what follows neq: row store, n3, D, G.  (-DHDLZ_PLANES_ALL_LIVE: no test.)
 //   a MATCH-FREE TILE  G is all ones in every lane (random, compressed or encrypted bytes): every result byte would be 0xFF and every
-//           token a literal.  The function returns false; the kernel then does not transpose the result, forms the literal tokens
-//           itself and runs neither the extension nor the parse nor the skip chain.  Lane 0's false history and lane 63's zero bits
+//           token a literal.  The function returns false; the kernel then does not transpose the result, runs neither the extension
+//           nor the parse nor the skip chain and emits the literals' codes straight from the own bytes (literal_codes; the token form,
+//           literal_tokens + token_codes: -DHDLZ_LITERAL_TOKENS).  Lane 0's false history and lane 63's zero bits
 //           32, 33 can only CLEAR bits of G: such a tile takes the normal path, which rejects them.  A short block is no exception: the
 //           end cap (below) keeps the zero bytes behind its end from matching each other.  (-DHDLZ_NO_LITERAL_TILE: always true.)
 constexpr bool skip_dead_planes() {
@@ -378,6 +379,36 @@ constexpr bool skip_dead_planes() {
 }
 constexpr bool literal_tiles() {
 #ifdef HDLZ_NO_LITERAL_TILE
+    return false;
+#else
+    return true;
+#endif
+}
+// THE DISTANCE PLANES BY GROUPS OF FOUR.  Inside an aligned group of four distances (d >> 2 fixed: 1..3, 4..7, .. 28..31, 32) only bits 0
+// and 1 of d change, so only D_0 and D_1 are updated distance by distance.  The positions that took a distance of the group are the bits G
+// lost inside it: D_k |= G_at_group_start & ~G_at_group_end for the set bits k >= 2 of d, ONCE per group -- 13 v_bitop3 where the per-
+// distance form has 49 (32 + 32 + 13 = 77 against 113 for D and G together).  G itself is still narrowed distance by distance: nearest
+// first is untouched.  One more live register (G at the group's start).  (-DHDLZ_PLANES_PER_DISTANCE: every plane at every distance.)
+constexpr bool grouped_planes() {
+#ifdef HDLZ_PLANES_PER_DISTANCE
+    return false;
+#else
+    return true;
+#endif
+}
+// A MATCH-FREE TILE EMITS ITS LITERALS ITSELF (literal_codes, next to token_codes) instead of forming literal tokens for the generic
+// token_codes to read back.  (-DHDLZ_LITERAL_TOKENS: the token form.)
+constexpr bool literal_emit() {
+#ifdef HDLZ_LITERAL_TOKENS
+    return false;
+#else
+    return literal_tiles();
+#endif
+}
+// ONE-TILE BLOCKS SUM THEIR ADLER WEIGHTS PLAINLY: see the static_assert next to adler_finish.  (-DHDLZ_ADLER_TILE_MOD: one modulo per
+// tile and the carried weight, as the multi-tile kernels need them.)
+constexpr bool adler_plain_one_tile() {
+#ifdef HDLZ_ADLER_TILE_MOD
     return false;
 #else
     return true;
@@ -429,18 +460,27 @@ __device__ __forceinline__ bool match_search_bits(uint32_t x0, uint32_t x1, uint
         PHASE_FENCE();
     });
     uint32_t G = 0xFFFFFFFFu, D[6] = {0, 0, 0, 0, 0, 0};
+    [[maybe_unused]] uint32_t Gs = 0xFFFFFFFFu;              // G in front of the aligned group of four distances that d lies in
+    constexpr int KD = grouped_planes() ? 2 : 6;             // planes updated distance by distance
     static_for<1, RUN + 1>([&](auto Dd) {
         constexpr int d = decltype(Dd)::value;
         const uint32_t neq = nq[d - 1];
         if constexpr (KEEP) neq_col[(d & (NEQ_ROWS - 1)) * 64] = neq;
         const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)neq, 0x130, 0xF, 0xF, true);                      // wave_shl:1 (lane 63: 0)
         const uint32_t n3 = bitop3<B3_OR3>(neq, __builtin_amdgcn_alignbit(nx, neq, 1u), __builtin_amdgcn_alignbit(nx, neq, 2u));
-        static_for<0, 6>([&](auto K) {
+        static_for<0, KD>([&](auto K) {
             constexpr int k = decltype(K)::value;
             if constexpr ((d >> k) & 1) D[k] = bitop3<B3_OR_ANDN>(D[k], G, n3);
         });
         G &= n3;
-        if constexpr ((d & 3) == 0) { pin(D); asm volatile("" : "+v"(G)); PHASE_FENCE(); }
+        if constexpr (grouped_planes() && ((d & 3) == 3 || d == RUN)) {      // the group's last distance: what G lost inside it took d >> 2
+            static_for<2, 6>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                if constexpr ((d >> k) & 1) D[k] = bitop3<B3_OR_ANDN>(D[k], Gs, G);
+            });
+            Gs = G;
+        }
+        if constexpr ((d & 3) == 0) { pin(D); asm volatile("" : "+v"(G)); if constexpr (grouped_planes()) asm volatile("" : "+v"(Gs)); PHASE_FENCE(); }
     });
     R[0] = G;
 #pragma unroll
@@ -841,7 +881,8 @@ __device__ __forceinline__ uint32_t literal_token(const uint32_t (&ow)[12]) {
     if constexpr (bsh == 0) return (ow[I >> 2] << 2) & 0x3FCu;
     else return (ow[I >> 2] >> (bsh - 2)) & 0x3FCu;
 }
-// a match-free tile (match_search_bits returned false): every token is its literal
+// a match-free tile (match_search_bits returned false): every token is its literal.  The -DHDLZ_LITERAL_TOKENS form only: two
+// instructions per position that token_codes then reads back; literal_codes (below token_codes) needs no token at all
 __device__ __forceinline__ void literal_tokens(const uint32_t (&ow)[12], uint32_t (&tok)[RUN]) {
     static_for<0, RUN>([&](auto I) { tok[decltype(I)::value] = literal_token<decltype(I)::value>(ow); });
 }
@@ -1073,6 +1114,7 @@ __device__ __forceinline__ uint32_t chain_skips_serial(uint64_t P, uint32_t lane
 // (Measured and dropped, profiles/tile_diet.txt: the start flag as a mask in a register -- (c - 4) >> 31, v_bitop3 select, v_and: 5.5
 // instructions per position, all of the 1.96-cycle class, where hipcc turns the selects below into a v_cmp and an exec-masked region
 // with five scalar instructions per position -- was 0.03 ms SLOWER on the headline, three runs against three.)
+// (A match-free tile of the one-tile bit-search kernels does not come here: every position starts a literal, literal_codes below.)
 template <int NCH, bool LIMIT>
 __device__ __forceinline__ uint32_t token_codes(const uint8_t* lut8, uint32_t (&tok)[RUN], uint32_t c0, uint32_t nlimit,
                                                 uint32_t (&code)[RUN]) {
@@ -1092,6 +1134,24 @@ __device__ __forceinline__ uint32_t token_codes(const uint8_t* lut8, uint32_t (&
         acc += code[i];
         constexpr int CG = HDLZ_CODE_GROUP;
         if constexpr ((i & (CG - 1)) == CG - 1) { pin_range<(i & ~(CG - 1)), (i & ~(CG - 1)) + CG>(code); asm volatile("" : "+v"(c), "+v"(acc)); PHASE_FENCE(); }
+    });
+    return (acc & NB_SUM_MASK) >> NB_SHIFT;
+}
+// ... of a MATCH-FREE tile: every position starts a one-byte token (entry skip 0, padding positions behind a short block's end
+// included: 8-bit literals that wipe_behind removes), so there is no start flag, no count and no token word -- code[i] is the LUT entry
+// at 4 * byte, the address one sub-dword shift of the own bytes (as the extension forms its literal), the bit count the sum of the
+// entries masked once.  Two VALU instructions per position where literal_tokens + token_codes had about eight, and the 32 LUT reads
+// run under no exec mask.
+__device__ __forceinline__ uint32_t literal_codes(const uint8_t* lut8, const uint32_t (&ow)[12], uint32_t (&code)[RUN]) {
+    static_assert(4u * 255u + 4u <= 4u * (uint32_t)LUT_LIT, "every byte's offset inside the literal LUT");
+    uint32_t acc = 0;
+    const uint32_t two = sconst(2u);
+    static_for<0, RUN>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        code[i] = *reinterpret_cast<const uint32_t*>(lut8 + shl_byte<(i & 3)>(two, ow[i >> 2]));
+        acc += code[i];
+        constexpr int CG = HDLZ_CODE_GROUP;
+        if constexpr ((i & (CG - 1)) == CG - 1) { pin_range<(i & ~(CG - 1)), (i & ~(CG - 1)) + CG>(code); asm volatile("" : "+v"(acc)); PHASE_FENCE(); }
     });
     return (acc & NB_SUM_MASK) >> NB_SHIFT;
 }
@@ -1177,6 +1237,11 @@ __device__ __forceinline__ uint32_t member_len(uint32_t n, uint64_t E, uint64_t 
     return body + (p >= 3u ? 4u : 5u);
 }
 // R8: Adler-32 of the block from A = sum x_p and W = sum (N - p) x_p (any residues mod 65521, 32 or 64 bits wide)
+// (A ONE-TILE block needs no reduction in front of this one: a lane's weight N - p_run is at most TILE, its run sums to at most 32 * 255, so
+// its term sum (N - p) x_p = (N - p_run) * sa - sc is at most TILE * 8160, and the wave's 64 terms stay below 2^31 -- k_compress sums
+// them plainly, without the modulo per tile and the carried weight of the multi-tile kernels.)
+static_assert(64ull * TILE * (RUN * 255ull) < (1ull << 31) && 64ull * (RUN * 255ull) + 1ull < (1ull << 31) && (uint64_t)TILE < (uint64_t)ADLER_MOD,
+              "one-tile blocks: the plain Adler sums of a wave fit 31 bits");
 template <class U> __device__ __forceinline__ void adler_finish(U A, U W, uint32_t n, uint32_t& s1, uint32_t& s2) {
     s1 = (uint32_t)((A + 1u) % ADLER_MOD);
     s2 = (uint32_t)((W + n % ADLER_MOD) % ADLER_MOD);
