@@ -17,6 +17,7 @@ from .zip import ZipIndex                                           # noqa: F401
 from .seek import SeekIndex                                         # noqa: F401  (what Engine.seek_index returns; seek.loads reads its file)
 from . import seek                                                  # noqa: F401
 from .png import load_png, save_png, PngIndex                       # noqa: F401  (PNG files into device tensors, and back)
+from .tiff import load_tiff, TiffIndex                              # noqa: F401  (TIFF files into device tensors)
 from .npz import load_npz, save_npz                                 # noqa: F401  (.npz files into device tensors, and back)
 
 

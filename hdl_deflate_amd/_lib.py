@@ -187,6 +187,18 @@ PNG_WRITE_CALLS = {
 PNG_WRITE_EXPORTS = tuple(PNG_WRITE_CALLS)
 # HDLZ_PNG_FILTER_ADAPTIVE, HDLZ_PNGW_BAND, HDLZ_PNGW_STEP, HDLZ_PNGW_ROW_REG_MAX
 PNG_FILTER_ADAPTIVE, PNGW_BAND, PNGW_STEP, PNGW_ROW_REG_MAX = 5, 8, 1024, 4096
+# ... and of include/hdlz_tiff.h: TIFF images indexed, their strips and tiles inflated and unpredicted on the device (tests/test_tiff_cabi.py,
+# which also holds its refusals)
+TIFF_CALLS = {
+    "hdlz_tiff_index_work_bytes": (sz, [u64, u64]),                  # n, image_cap
+    # d_files, files_len, d_file_off, d_file_len, d_page, n, out_align, image_cap, d_images, d_result, d_work, work_bytes, stream
+    "hdlz_tiff_index_ws": (ci, [vp, u64, vp, vp, vp, u64, u32, u64, vp, vp, vp, sz, vp]),
+    "hdlz_tiff_decode_work_bytes": (sz, [u64, u64, u64]),            # count, chunk_cap, raw_bytes
+    # d_files, files_len, d_images, first, count, chunk_cap, raw_bytes, d_out, out_cap, d_image_status, d_result, d_work, work_bytes, stream
+    "hdlz_tiff_decode_ws": (ci, [vp, u64, vp, u64, u64, u64, u64, vp, u64, vp, vp, vp, sz, vp]),
+}
+TIFF_EXPORTS = tuple(TIFF_CALLS)
+TIFF_LARGE_MIN = 16384                               # HDLZ_TIFF_LARGE_MIN (HDLZ_PNG_LARGE_MIN's number, not measured again for TIFF)
 _lib = None
 
 
@@ -316,6 +328,25 @@ class PngWriteResult(ctypes.Structure):
     _fields_ = [("total_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
 
 
+class TiffImage(ctypes.Structure):
+    """hdlz_tiff_image: one record of hdlz_tiff_index_ws (136 bytes)"""
+    _fields_ = [(f, u64) for f in ("file_off", "file_len", "ifd_off", "next_ifd", "off_arr", "cnt_arr", "raw_len", "out_len", "chunk_off",
+                                   "raw_off", "out_off")] + \
+               [(f, u32) for f in ("width", "height", "tile_w", "tile_h", "nchunks", "compression", "photometric", "status")] + \
+               [(f, ctypes.c_uint8) for f in ("off_type", "cnt_type", "bits", "samples", "format", "predictor", "big_endian", "tiled")] + \
+               [("reserved", ctypes.c_uint8 * 8)]
+
+
+class TiffIndexResult(ctypes.Structure):
+    """hdlz_tiff_index_result: the result record of hdlz_tiff_index_ws (40 bytes)"""
+    _fields_ = [("nimages", u64), ("total_chunks", u64), ("total_raw", u64), ("total_out", u64), ("status", u32), ("reserved", u32)]
+
+
+class TiffDecodeResult(ctypes.Structure):
+    """hdlz_tiff_decode_result: the result record of hdlz_tiff_decode_ws (24 bytes)"""
+    _fields_ = [("out_len", u64), ("first_bad", u64), ("status", u32), ("reserved", u32)]
+
+
 class IState(ctypes.Structure):
     """hdlz_istate: the session of hdlz_inflate_chunk (384 bytes)"""
     _fields_ = [(f, u32) for f in ("bitpos", "out_pos", "phase", "final_", "hm", "srem", "nlen", "ndist", "started",
@@ -337,7 +368,8 @@ def load():
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JOIN_SIGNATURES.items()) + list(UNJOIN_SIGNATURES.items()) + \
             list(GZIP_SIGNATURES.items()) + list(BGZF_SIGNATURES.items()) + list(BGZF_RANGE_SIGNATURES.items()) + list(BGZF_STORED_SIGNATURES.items()) + \
             list(GUNZIP_SIGNATURES.items()) + list(ZIP_SIGNATURES.items()) + list(ZIP_WRITE_SIGNATURES.items()) + list(ZIP64_SIGNATURES.items()) + \
-            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()) + list(PNG_CALLS.items()) + list(PNG_WRITE_CALLS.items()):
+            list(GZIP_MEMBERS_SIGNATURES.items()) + list(SEEK_CALLS.items()) + list(PNG_CALLS.items()) + list(PNG_WRITE_CALLS.items()) + \
+            list(TIFF_CALLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

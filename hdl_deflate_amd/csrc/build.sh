@@ -46,7 +46,7 @@ lib="$out/libhdlz${var:+_$var}.so"
 mkdir -p "$out" "$objdir"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function ${HDLZ_DEFS:-}"
-srcs="hdlz_compress hdlz_compress_small hdlz_compress_stream hdlz_compress_chunk hdlz_inflate_tok hdlz_inflate_grp hdlz_inflate_par hdlz_inflate_any hdlz_inflate_dyn hdlz_checksum hdlz_compact hdlz_join hdlz_unjoin hdlz_crc32 hdlz_bgzf hdlz_bgzf_range hdlz_bgzf_stored hdlz_gunzip hdlz_gzip_members hdlz_zip hdlz_zip_write hdlz_seek hdlz_png hdlz_png_write hdlz_api"
+srcs="hdlz_compress hdlz_compress_small hdlz_compress_stream hdlz_compress_chunk hdlz_inflate_tok hdlz_inflate_grp hdlz_inflate_par hdlz_inflate_any hdlz_inflate_dyn hdlz_checksum hdlz_compact hdlz_join hdlz_unjoin hdlz_crc32 hdlz_bgzf hdlz_bgzf_range hdlz_bgzf_stored hdlz_gunzip hdlz_gzip_members hdlz_zip hdlz_zip_write hdlz_seek hdlz_png hdlz_png_write hdlz_tiff hdlz_api"
 only="${HDLZ_ONLY:-$srcs}"
 pids=()
 for f in $only; do

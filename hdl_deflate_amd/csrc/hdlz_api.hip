@@ -1310,3 +1310,89 @@ int hdlz_png_write_ws(const hdlz_png_spec* d_specs, uint64_t n, const uint8_t* d
 }
 
 }  // extern "C"
+
+// ---- include/hdlz_tiff.h: TIFF images, the directory walked, the strips and tiles inflated and the predictor undone on the device (hdlz_tiff.hip)
+// The scratch of hdlz_tiff_decode_ws, laid out once for the size query and the call (the header states the closed form).  The one-chunk
+// route takes what is left from `decode` on; `row` is what it is given of the decoded chunks' room, `bound` what it sizes itself from.
+static uint32_t tiff_bound(uint64_t raw_bytes) { return 2u * raw_bytes + 64u < 0x0FFFFFFFull ? (uint32_t)(2u * raw_bytes + 64u) : 0x0FFFFFFFu; }
+static bool tiff_one(const hdlz::TiffArgs& g) { return g.count == 1 && g.chunk_cap == 1; }
+static Laid tiff_layout(hdlz::TiffArgs& g, uintptr_t base) {
+    Carver c{base};
+    const size_t n = (size_t)g.count, k = (size_t)g.chunk_cap;
+    g.verdict = c.take<uint32_t>(n); g.fin = c.take<uint32_t>(n); c.align256();
+    g.cb = c.take<uint64_t>(n + 1u); g.tb = c.take<uint64_t>(n + 1u); g.head = c.take<uint64_t>(32); c.align256();
+    g.m_off = c.take<uint64_t>(k); g.m_end = c.take<uint64_t>(k); g.m_dst = c.take<uint8_t*>(k); c.align256();
+    g.cap = c.take<uint32_t>(k); g.len = c.take<uint32_t>(k); g.status = c.take<uint32_t>(k); g.end_bit = c.take<uint32_t>(k); g.cst = c.take<uint32_t>(k); c.align256();
+    g.tiles = c.take<uint2>((size_t)g.tile_cap); c.align256();
+    g.raw = c.take<uint8_t>((size_t)g.raw_bytes); c.align256();
+    const size_t decode = c.bytes();
+    if (tiff_one(g)) c.take<uint8_t>(hdlz::round256(hdlz_inflate_work_bytes(1, tiff_bound(g.raw_bytes), png_row(g.raw_bytes), 0, 1)));
+    return {c.bytes(), decode};
+}
+static hdlz::TiffArgs tiff_args(uint64_t count, uint64_t chunk_cap, uint64_t raw_bytes) {
+    hdlz::TiffArgs g{};
+    g.count = count; g.chunk_cap = chunk_cap; g.tile_cap = raw_bytes / 32768u + chunk_cap; g.raw_bytes = raw_bytes;
+    return g;
+}
+static bool tiff_caps_ok(uint64_t chunk_cap, uint64_t raw_bytes) { return chunk_cap <= 0x7FFFFFFFull && raw_bytes < (1ull << 40); }
+
+extern "C" {
+
+size_t hdlz_tiff_index_work_bytes(uint64_t n, uint64_t image_cap) {
+    (void)image_cap;
+    return n == 0 || n > 0x7FFFFFFFull ? 0u : hdlz::tiff_index_work_bytes(n);
+}
+
+int hdlz_tiff_index_ws(const uint8_t* d_files, uint64_t files_len, const uint64_t* d_file_off, const uint64_t* d_file_len, const uint32_t* d_page,
+                       uint64_t n, uint32_t out_align, uint64_t image_cap, hdlz_tiff_image* d_images, hdlz_tiff_index_result* d_result,
+                       void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result || (n && any_null(d_files, d_file_off, d_file_len))) return fail_param("null device pointer");
+    if (image_cap && !d_images) return fail_param("d_images is null with image_cap > 0");
+    if (n > 0x7FFFFFFFull) return fail_param("n too large (below 2^31)");
+    if (image_cap > 0x7FFFFFFFull) return fail_param("image_cap too large (below 2^31)");
+    if (out_align == 0u || out_align > 256u || (out_align & (out_align - 1u))) return fail_param("out_align must be a power of two in [1, 256]");
+    if (work_too_small(hdlz_tiff_index_work_bytes(n, image_cap), d_work, work_bytes, "hdlz_tiff_index_work_bytes(n, image_cap)")) return HDLZ_E_BAD_PARAM;
+    if (misaligned(8, d_file_off, d_file_len, d_images, d_result) || misaligned(8, d_work)) return fail_align(8, "d_file_off / d_file_len / d_images / d_result / d_work");
+    if (misaligned(4, d_page)) return fail_align(4, "d_page");
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    return launched(hdlz::launch_tiff_index(d_files, files_len, d_file_off, d_file_len, d_page, n, out_align, image_cap, d_images, d_result, d_work,
+                                            static_cast<hipStream_t>(stream)), "launch k_tiff_parse");
+}
+
+size_t hdlz_tiff_decode_work_bytes(uint64_t count, uint64_t chunk_cap, uint64_t raw_bytes) {
+    if (count == 0 || count > 0x7FFFFFFFull || !tiff_caps_ok(chunk_cap, raw_bytes)) return 0u;
+    hdlz::TiffArgs g = tiff_args(count, chunk_cap, raw_bytes);
+    return tiff_layout(g, 0).bytes;
+}
+
+int hdlz_tiff_decode_ws(const uint8_t* d_files, uint64_t files_len, const hdlz_tiff_image* d_images, uint64_t first, uint64_t count,
+                        uint64_t chunk_cap, uint64_t raw_bytes, uint8_t* d_out, uint64_t out_cap, uint32_t* d_image_status,
+                        hdlz_tiff_decode_result* d_result, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_result) return fail_param("d_result is required");
+    if (count && any_null(d_files, d_images)) return fail_param("null device pointer");
+    if (out_cap && !d_out) return fail_param("d_out is null with out_cap > 0");
+    if (first > 0x7FFFFFFFull || count > 0x7FFFFFFFull || first + count > 0x7FFFFFFFull) return fail_param("first + count too large (below 2^31)");
+    if (!tiff_caps_ok(chunk_cap, raw_bytes)) return fail_param("chunk_cap (below 2^31) or raw_bytes (below 2^40) too large");
+    if (misaligned(8, d_images, d_result)) return fail_align(8, "d_images / d_result");
+    if (misaligned(4, d_image_status)) return fail_align(4, "d_image_status");
+    if (misaligned(256, d_work)) return fail_align(256, "d_work");
+    hdlz::TiffArgs g = tiff_args(count, chunk_cap, raw_bytes);
+    g.in = d_files; g.in_len = files_len; g.images = d_images ? d_images + first : nullptr;
+    g.out = d_out; g.out_cap = out_cap; g.image_status = d_image_status; g.result = d_result;
+    const Laid l = tiff_layout(g, address(d_work));
+    if (count && work_too_small(l.bytes, d_work, work_bytes, "hdlz_tiff_decode_work_bytes(count, chunk_cap, raw_bytes)")) return HDLZ_E_BAD_PARAM;
+    if (const int rc = check_device(); rc != HDLZ_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool single = g.single = tiff_one(g) && png_row(raw_bytes) >= 4u;
+    g.bound = tiff_bound(raw_bytes);
+    if (const int rc = launched(hdlz::launch_tiff_front(g, st), "launch k_tiff_plan"); rc != HDLZ_OK) return rc;
+    if (single) {                                                                                 // a single-strip image (m_off[0], m_end[0]: its ragged index)
+        if (const int rc = inflate_one(d_files, g.m_off, g.bound, g.raw, png_row(raw_bytes), g.len, g.status, g.end_bit, d_work, work_bytes, l.decode, stream); rc != HDLZ_OK) return rc;
+    } else if (count && chunk_cap) {
+        const MemberView v{g.m_off, g.m_end, nullptr, 0, 0, 0, g.m_dst, g.cap};                        // the task view: a task a chunk
+        if (const int rc = decode_members(d_files, chunk_cap, g.raw, g.len, g.status, g.end_bit, v, st); rc != HDLZ_OK) return rc;
+    }
+    return launched(hdlz::launch_tiff_back(g, st), "launch k_tiff_unpredict");
+}
+
+}  // extern "C"

@@ -14,6 +14,7 @@
 #include "../../include/hdlz_seek.h"
 #include "../../include/hdlz_png.h"
 #include "../../include/hdlz_png_write.h"
+#include "../../include/hdlz_tiff.h"
 
 namespace hdlz {
 
@@ -519,6 +520,41 @@ struct PngArgs {
 };
 hipError_t launch_png_front(const PngArgs& a, hipStream_t stream);     // checks, chunk list, gather, chunk CRCs: in front of the decode
 hipError_t launch_png_back(const PngArgs& a, hipStream_t stream);      // Adler tiles, unfilter, expansion, verdicts, the record
+
+// hdlz_tiff.hip: hdlz_tiff_index_ws and what hdlz_tiff_decode_ws runs around the decode (include/hdlz_tiff.h)
+size_t tiff_index_work_bytes(uint64_t n);
+hipError_t launch_tiff_index(const uint8_t* files, uint64_t files_len, const uint64_t* file_off, const uint64_t* file_len, const uint32_t* pages, uint64_t n,
+                             uint32_t out_align, uint64_t image_cap, hdlz_tiff_image* images, hdlz_tiff_index_result* result, void* work, hipStream_t stream);
+struct TiffArgs {
+    const uint8_t* in;
+    uint64_t in_len;                  // files_len
+    const hdlz_tiff_image* images;    // the call's d_images + first
+    uint64_t count;
+    uint64_t chunk_cap, tile_cap;     // the slots of the chunk list; the Adler tile words (raw_bytes / 32768 + chunk_cap)
+    uint64_t raw_bytes;
+    uint8_t* out;
+    uint64_t out_cap;
+    uint32_t* image_status;           // nullable
+    hdlz_tiff_decode_result* result;
+    uint32_t* verdict;                // scratch, per image: the checks in front of the decode
+    uint32_t* fin;                    // ... the image's status
+    uint64_t *cb, *tb;                // scratch, count + 1 words each: where an image's chunks and Adler tiles start
+    uint64_t* head;                   // scratch, 32 words: the two totals
+    uint64_t* m_off;                  // scratch, per chunk: MemberArgs::m_off; single: with m_end[0] the ragged index of one stream
+    uint64_t* m_end;                  // ... MemberArgs::m_end (the word behind m_off[chunk_cap - 1])
+    uint8_t** m_dst;                  // ... MemberArgs::m_dst: the chunk's place among the decoded chunks
+    uint32_t* cap;                    // ... MemberArgs::m_dst_cap (the chunk's decoded bytes)
+    uint32_t* len;                    // ... the decoded length
+    uint32_t* status;                 // ... the decoder's status word (FFFFFFFF: a chunk it is not to touch)
+    uint32_t* end_bit;                // ... where the final block ended: a bit (the task view) or, single, a byte
+    uint32_t* cst;                    // ... the planner's verdict on the chunk
+    uint2* tiles;                     // scratch: (A, C) per 32 KiB tile of the decoded chunks
+    uint8_t* raw;                     // scratch: the decoded chunks
+    uint32_t bound;                   // single: the bound the batch call's path is given on the stream's length
+    bool single;                      // count == 1 and chunk_cap == 1: the batch call's path
+};
+hipError_t launch_tiff_front(const TiffArgs& a, hipStream_t stream);    // checks, chunk list: in front of the decode
+hipError_t launch_tiff_back(const TiffArgs& a, hipStream_t stream);     // Adler tiles, unpredict, verdicts, the record
 
 // hdlz_zip_write.hip: hdlz_zip_write_ws (include/hdlz_zip_write.h).  The scratch, carved by the launcher: E = nentries
 struct ZipWriteWork {

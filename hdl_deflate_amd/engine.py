@@ -844,8 +844,95 @@ class Engine(object):
                           flags, ic, zb, rb, out.data_ptr() + int(rel[b]) if out.numel() else None, cap, status.data_ptr() + 4 * (b - first))
         return out[:total], status
 
+    # -- TIFF images (include/hdlz_tiff.h): the directory walked, the strips and tiles inflated, the predictor undone on the device
+    @_on_device
+    def tiff_index(self, d_files, offsets=None, lengths=None, pages=None, out_align=64):
+        """d_files: flat uint8 device tensor holding TIFF files; offsets, lengths: int64 device tensors, file i is
+        d_files[offsets[i] : offsets[i] + lengths[i]] (default: one file, all of d_files) -- the out_off and usize of Engine.inflate_zip's
+        index fit as they stand; pages: per image the directory (IFD) read of its file, a sequence of ints or a tensor (default: the
+        first of every file; a pyramid or a stack is read by naming its file once per page) -> a TiffIndex (hdl_deflate_amd/tiff.py):
+        the device records of hdlz_tiff_index_ws, its result record and a host copy.  An image's status stands in its record and is not
+        raised.  out_align: every image's slot in the flat output starts at a multiple of it (a power of two up to 256).  One host sync
+        for the records."""
+        from .tiff import TiffIndex, IMAGE_DTYPE
+        import numpy as np
+        self._is_bytes(d_files, "d_files", flat=True)
+        dev = d_files.device
+        if offsets is None:
+            offsets = torch.zeros(1, dtype=torch.int64, device=dev)
+            lengths = torch.full((1,), d_files.numel(), dtype=torch.int64, device=dev)
+        offsets, lengths = offsets.to(torch.int64).contiguous(), lengths.to(torch.int64).contiguous()
+        _is_index(offsets)
+        _is_index(lengths, offsets.numel())
+        n = offsets.numel()
+        if pages is not None:
+            pages = np.asarray(pages.cpu().numpy() if isinstance(pages, torch.Tensor) else pages, dtype=np.int64).reshape(-1)
+            if pages.size != n or (n and (pages.min() < 0 or pages.max() > 0xFFFFFFFF)):
+                raise ValueError("pages must hold one page number in [0, 2^32) per image (%d)" % n)
+            pages = torch.from_numpy(pages.astype(np.uint32).view(np.int32).copy()).to(dev)
+        images = torch.empty((n, ctypes.sizeof(_lib.TiffImage) // 8), dtype=torch.int64, device=dev)
+        rec = self._record("hdlz_tiff_index_ws", _lib.TiffIndexResult, self._scratch(self.lib.hdlz_tiff_index_work_bytes(n, n), None, full=True),
+                           d_files.data_ptr() if n else None, d_files.numel(), offsets.data_ptr() if n else None, lengths.data_ptr() if n else None,
+                           pages.data_ptr() if pages is not None and n else None, n, out_align, n, images.data_ptr() if n else None)
+        host = np.frombuffer(images.cpu().numpy().tobytes(), dtype=IMAGE_DTYPE)
+        return TiffIndex(images, rec, host, out_align)
+
+    @_on_device
+    def decode_tiff(self, d_files, index, first=0, count=None, out=None, work=None):
+        """d_files: the buffer the TiffIndex `index` was taken of -> (out uint8[n], status int32[count]), both on the device: image
+        first + k stands at out[rel : rel + out_len], rel = out_off[first + k] - out_off[first], and has status[k] -- HDLZ_OK, or why it
+        was not read; nothing is raised for an image.  Any range [first, first + count) decodes without the rest.  The range is routed
+        here as Engine.decode_png routes: maximal runs of images go in one hdlz_tiff_decode_ws call each, a wave per strip or tile of
+        all of them; an image of ONE deflate chunk in a file of at least TIFF_LARGE_MIN bytes goes in a call of its own, decoded by the
+        whole GPU.  out: at least the range's bytes (default: allocated here); work: the scratch of the largest call, uint8 at a
+        multiple of 256 (default: allocated here).  No host sync."""
+        self._is_bytes(d_files, "d_files", flat=True)
+        dev = d_files.device
+        host, E = index.host, len(index.host)
+        count = E - first if count is None else int(count)
+        if not 0 <= first <= first + count <= E:
+            raise ValueError("images [%d, %d) are not a range of the index's %d images" % (first, first + count, E))
+        ok = host["status"] == OK
+        end = first + count
+        rel = (host["out_off"] - (host["out_off"][first] if count else 0)).astype("int64")
+        size = host["out_len"].astype("int64") * ok
+        total = int(rel[end - 1] + size[end - 1]) if count else 0
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        self._is_bytes(out, "out", flat=True, room=total)
+        status = torch.empty(count, dtype=torch.int32, device=dev)
+        # what an image takes of the decoded chunks: every chunk's bytes rounded up to 16 (step 7 of the header's rule)
+        r16 = lambda x: (x + 15) & ~15
+        nch = host["nchunks"].astype("int64")
+        full = host["tile_w"].astype("int64") * host["tile_h"] * host["samples"] * (host["bits"] // 8)
+        raw16 = ((nch - 1) * r16(full) + r16(host["raw_len"].astype("int64") - (nch - 1) * full)) * ok
+        # which images go alone: a single-strip deflate image whose file -- all but the strip is a directory -- says the stream is a large
+        # one (the strip's byte count stands in the file, on the device, and is not fetched for this)
+        large = ok & (host["nchunks"] == 1) & (host["compression"] != 1) & (host["file_len"] >= _lib.TIFF_LARGE_MIN)
+        large[:first] = large[end:] = False
+        # ... unless they are so many that their calls would cost more than the longest of them costs a wave (decode_png's weighing, with
+        # its two numbers: not measured again for TIFF)
+        if large.any() and int(large.sum()) * self.PNG_ALONE_US > int(host["raw_len"][large].max()) * self.PNG_WAVE_US_PER_BYTE:
+            large[:] = False
+        calls, e = [], first
+        while e < end:
+            b = e
+            if large[e]:
+                e += 1
+            else:
+                while e < end and not large[e]:
+                    e += 1
+            last = e - 1
+            calls.append((b, e - b, int(host["nchunks"][b:e][ok[b:e]].sum()), int(host["raw_off"][last] - host["raw_off"][b]) + int(raw16[last]),
+                          int(rel[last] + size[last] - rel[b])))
+        scratch = self._scratch(max([self.lib.hdlz_tiff_decode_work_bytes(c, cc, rb) for _, c, cc, rb, _ in calls] + [0]), work, torch.uint8)
+        for b, c, cc, rb, cap in calls:                         # (the records are not read: every image's verdict is in `status`)
+            self._enqueue("hdlz_tiff_decode_ws", _lib.TiffDecodeResult, scratch, d_files.data_ptr(), d_files.numel(), index.images.data_ptr(), b, c,
+                          cc, rb, out.data_ptr() + int(rel[b]) if out.numel() else None, cap, status.data_ptr() + 4 * (b - first))
+        return out[:total], status
+
     # -- PNG files written on the device (include/hdlz_png_write.h)
-    PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+    PNG_FILTERS ={"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
 
     @_on_device
     def encode_png(self, d_pix, specs, filter="adaptive", block=1 << 16, idat=1 << 16, cwindow=32, maxmatch=10, out=None, out_align=64,
